@@ -10,17 +10,22 @@ angular-velocities -- the WHOLE population on one GPU, in the reference's arithm
 BASELINE.json; configs[1] / configs[2] (10^4 / 10^5 targets, launch-bound) and everything else are reported under
 `extra`.  With N > 1 every rank owns its own 10^6-target shard (weak scaling, no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--reps R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--reps R] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, before this process touches the GPU); under the driver's own
 torch.distributed.run launch the ranks are already there.  Either way the line reports the number of ranks the
 process group actually had and the run fails if that differs from --gpus.
 
-Timing: W untimed warm-up steps, then R repetitions of EXACTLY K steps, every repetition bracketed by a barrier +
-torch.cuda.synchronize() on both sides, MAX over ranks per repetition; `ms_per_step` is the median repetition / K
-(R is chosen so that the repetitions add up to >= 30 ms: a 20-step region of a 10^4-target batch is 0.1 ms).
+Timing: W untimed warm-up steps, then R repetitions (default 1) of EXACTLY K steps, every repetition bracketed by a
+barrier + torch.cuda.synchronize() on both sides, MAX over ranks per repetition; `ms_per_step` is the median repetition / K.
 Prints ONE JSON line on rank 0.
+
+A plain run does only that (and writes the headline's side file).  `--dump-outputs DIR` writes what the timed steps
+computed (dump_outputs()): the inputs are seeded and the number of steps is fixed, so two builds can be compared output
+for output.  `--full` adds everything else after the line: CPU baseline, parity sample, configs[0], copy bandwidth, the
+`--extra` workloads (per-workload rows that repeat short regions until they add up to >= 30 ms), the pose gather and the
+slow-down check against the committed record.
 """
 import argparse
 import json
@@ -249,12 +254,52 @@ def summarize(name, desc, models, dtype, batches, kernels, n_total, world, steps
 
 
 # ------------------------------------------------------------------------------------------------ workloads
+DUMP_EST_SAMPLE = 65536     # targets per batch whose pose / twist / acceleration estimates --dump-outputs writes
+DUMP_STATE_SAMPLE = 2048    # targets per batch whose state x and covariance P it writes
+DUMP_SEED = 20241016
+DUMP_LIMIT = 64 << 20       # bytes of all dumped arrays together
+
+
+def dump_outputs(out_dir, mgr, parts):
+    """--dump-outputs: what a caller of the timed path receives after its last step, for a fixed seeded sample of every batch's
+    targets (the same ids from run to run): the estimates (pose [S,7], twist [S,6], acceleration [S,6]) and the filter state
+    (x [s,n], P [s,n,n]) read back by id, and the sphere query's outputs (delta [S], pose [S,7]) where the tick runs one.
+    parts: [(model, batch, ids of the batch, (delta, pose) CUDA tensors in slot order or None)].  float64 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for j, (model, b, ids, query_out) in enumerate(parts):
+        rng = np.random.default_rng(DUMP_SEED + j)
+        est_ids = ids[np.sort(rng.choice(len(ids), size=min(len(ids), DUMP_EST_SAMPLE), replace=False))]
+        state_ids = ids[np.sort(rng.choice(len(ids), size=min(len(ids), DUMP_STATE_SAMPLE), replace=False))]
+        pose, twist, acc, found = mgr.get_est_batch(est_ids)
+        assert found.all(), "dump: ids missing from the manager"
+        x, P = mgr.get_state_batch(state_ids)
+        tag = "b%d_%s" % (j, model)
+        arrays.update({tag + "_pose": pose, tag + "_twist": twist, tag + "_acc": acc, tag + "_x": x, tag + "_P": P})
+        if query_out is not None:
+            import torch
+            slot_ids = b.slot_ids()
+            order = np.argsort(slot_ids, kind="stable")    # id -> slot of the batch's device arrays
+            slots = order[np.searchsorted(slot_ids[order], est_ids)]
+            assert (slot_ids[slots] == est_ids).all()
+            sl = torch.from_numpy(slots.astype(np.int64)).to(query_out[0].device)
+            arrays[tag + "_query_delta"] = query_out[0][sl].cpu().numpy()
+            arrays[tag + "_query_pose"] = query_out[1][sl].cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "dump: %d bytes > %d" % (total, DUMP_LIMIT)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return total
+
+
 def run_workload(te, torch, name, steps, warmup, lanes=0, targets=None, dist=None, rank=0, world=1, stream_ticks=64,
-                 launch_mode="auto", reps=3, keep=False):
+                 launch_mode="auto", reps=3, keep=False, min_total_s=0.03, dump=None):
     """One motion model, one batch.  One launch of the step kernel per tick in every launch mode: "python" = one C-ABI
     call per tick; "sequence" = the launches of K ticks enqueued by one C call; "graph" = recorded hipGraph blocks
     replayed; "auto" = graph for launch-bound batches (<= SMALL targets), sequence otherwise; "fused" = K ticks in ONE
-    launch (an "effective" figure, never `value`)."""
+    launch (an "effective" figure, never `value`).  min_total_s = 0: exactly `reps` regions of `steps` steps are timed;
+    dump = a directory: dump_outputs() right after them."""
     import numpy as np
     from target_estimation_amd.streams import make_stream
     desc, model, dtype, n_targets, seed = WORKLOADS[name]
@@ -339,7 +384,9 @@ def run_workload(te, torch, name, steps, warmup, lanes=0, targets=None, dist=Non
     run_ticks(warmup)
     done[0] = 0          # the timed region starts on a block boundary of the ring
     clock = Clock(torch, dist)
-    wall, dev = clock.measure(run_ticks, steps, reps)
+    wall, dev = clock.measure(run_ticks, steps, reps, min_total_s=min_total_s)
+    if dump:
+        dump_outputs(dump, mgr, [(model, b, ids, None)])
     x, P = mgr.get_state_batch(ids[:64])
     assert np.isfinite(x).all() and np.isfinite(P).all()
     res = summarize(name, desc, [model], dtype, [b], [kernel_name(b, model)], n_targets, world, steps, wall, dev, launch_mode)
@@ -467,12 +514,13 @@ def run_live_mixed(te, torch, name, desc, parts, dtype, mgr, batches, meas, dt, 
     return res
 
 
-def run_mixed(te, torch, name, steps, warmup, dist=None, rank=0, world=1, stream_ticks=64, launch_mode="auto", reps=3, split=1):
+def run_mixed(te, torch, name, steps, warmup, dist=None, rank=0, world=1, stream_ticks=64, launch_mode="auto", reps=3, split=1,
+              min_total_s=0.03, dump=None):
     """Several motion models (batches) in one manager, one step launch per batch per tick; the sphere query of
     configs[4] runs inside the step kernels.  Launch-bound populations: the batches are concurrent branches of ONE
     recorded hipGraph (target_manager_step_sequence_all).  Large populations: plain launches in tick order on the
     manager's stream (AR tick s, AV tick s, AR tick s+1, ...) -- the kernels are tens of microseconds long, and a
-    serial chain is what rocprofv3's per-kernel durations can be compared with."""
+    serial chain is what rocprofv3's per-kernel durations can be compared with.  min_total_s, dump: as run_workload."""
     import numpy as np
     from target_estimation_amd.streams import make_stream
     desc, parts, dtype, seed, intersect = MIXED[name]
@@ -490,11 +538,12 @@ def run_mixed(te, torch, name, steps, warmup, dist=None, rank=0, world=1, stream
         ticks = gb
     else:
         ticks = max(2, min(stream_ticks, steps + warmup, RING_BYTES // (7 * es * n_all)))
-    streams, base = [], 0
+    streams, base, all_ids = [], 0, []
     for k, (model, n) in enumerate(parts):
         mt = te.MODEL_TYPES[model]
         st = make_stream(mt, n, ticks, dt, seed + 17 * k, dtype=dtype, first_target=rank * n)
         ids = np.arange(n, dtype=np.uint32) + base + rank * 16_000_000
+        all_ids.append(ids)
         base += n
         params = _model_params(model)
         mgr.init_batch(ids, dt, 0.0, st["p0"].cpu().numpy(), None, None, type=mt, Q=params["Q"], R=params["R"], P0=params["P"])
@@ -541,8 +590,10 @@ def run_mixed(te, torch, name, steps, warmup, dist=None, rank=0, world=1, stream
             mgr.step_sequence_all(dt, meas, query=query, use_graph=2, n_ticks=gb * passes)
     run(warmup)
     clock = Clock(torch, dist)
-    wall, dev = clock.measure(run, steps, reps)
+    wall, dev = clock.measure(run, steps, reps, min_total_s=min_total_s)
     models = [m for m, _ in parts]
+    if dump:
+        dump_outputs(dump, mgr, [(m, b, i, outs[j] if intersect else None) for j, (m, b, i) in enumerate(zip(models, batches, all_ids))])
     kernels = [kernel_name(b, m) + ("+query" if intersect else "") for b, m in zip(batches, models)]
     extra_alg = sum(8 * 8 * b.size for b in batches) if intersect else 0   # the query writes delta + pose7 (doubles)
     res = summarize(name, desc, models, dtype, batches, kernels, n_all, world, steps, wall, dev, launch_mode, extra_alg)
@@ -1097,14 +1148,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region (median reported); more are taken "
-                    "until they add up to 30 ms")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the K-step timed region of the headline (median reported); "
+                    "the default times exactly --steps steps")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline line: CPU baseline, parity "
+                    "sample, configs[0], copy bandwidth, the --extra workloads, the pose gather and the slow-down check")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what they computed (a fixed seeded "
+                    "sample of every batch: estimates, state, query outputs) as DIR/<name>.npy, float64, at most 64 MB")
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS) + sorted(MIXED))
     ap.add_argument("--lanes", type=int, default=0, help="lanes per target / layout code (0 = the workload's default)")
     ap.add_argument("--targets", type=int, default=0, help="override targets per GPU (single-model workloads)")
-    ap.add_argument("--extra", default=DEFAULT_EXTRA, help="comma list of extra workloads reported under 'extra' (N=1; '' = none)")
+    ap.add_argument("--extra", default=DEFAULT_EXTRA, help="comma list of extra workloads reported under 'extra' (--full, N=1; '' = none)")
     ap.add_argument("--extra-multi", default=DEFAULT_EXTRA_MULTI,
-                    help="extra workloads when --gpus > 1 (per-GPU sizes, every rank in lockstep; NAME_strong = the workload's targets split over the ranks)")
+                    help="extra workloads when --gpus > 1 (--full; per-GPU sizes, every rank in lockstep; NAME_strong = the workload's targets split over the ranks)")
     ap.add_argument("--extra-steps", type=int, default=24)
     ap.add_argument("--stream-ticks", type=int, default=0, help="ticks of synthetic measurements kept in HBM and cycled through; 0 = default")
     ap.add_argument("--no-cpu", action="store_true")
@@ -1119,6 +1174,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="no device work: rank start-up, rendezvous, barriers, timing protocol and "
                     "the JSON line only (value is null); what the CPU tests exercise")
     args = ap.parse_args()
+    if args.dump_outputs and args.launch_mode == "live":
+        ap.error("--dump-outputs needs a per-tick launch mode (not live)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -1154,6 +1211,9 @@ def main():
 
     import target_estimation_amd as te
     st_kw = {"stream_ticks": args.stream_ticks} if args.stream_ticks else {}
+    # the headline times exactly --reps x --steps steps (no repetitions added for short regions), so that --steps sets the timed
+    # steps and a run's outputs do not depend on its timing; rank 0 dumps its shard's outputs
+    st_kw.update(min_total_s=0.0, dump=args.dump_outputs if rank == 0 else None)
     if args.workload in MIXED:
         res = run_mixed(te, torch, args.workload, args.steps, args.warmup, dist, rank, world,
                         launch_mode="auto" if args.launch_mode in ("fused", "live") else args.launch_mode, reps=args.reps, **st_kw)
@@ -1187,7 +1247,7 @@ def main():
                               "note": "all kernels of the tick over the timed region itself (events on the launch stream)"},
                      "kernels": res["kernels"]},
     }
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu:
         try:
             cb = cpu_baseline(parts, res["dtype"])
             out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample")}
@@ -1203,7 +1263,7 @@ def main():
             side["configs0"] = configs0_report(te, torch)
         except Exception as exc:
             side["configs0"] = {"error": str(exc)[:300]}
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         try:
             bw = copy_bandwidth(torch)
             side["roofline"]["measured_copy_gbs"] = bw["copy"]
@@ -1225,6 +1285,11 @@ def main():
     if rank == 0:
         emit(compact_line(out))
         write_side(args, dict(side, line=out))
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the outputs and the line; the rest is --full
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # Everything below is optional and the line is out: a rank that falls out of step in an extra (an exception between two
     # barriers on one rank only) must not leave the job hanging at the others' barrier.  After --post-deadline seconds every
     # rank says so and leaves (exit 0: the record stands; the side file says what is missing).

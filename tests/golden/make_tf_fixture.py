@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Extract the /tf stream of the reference's recorded bag (test/test_multiple_targets.bag) into
 tests/golden/multiple_targets_tf.npz with target_estimation_amd/rosbag_tf.py.  The fixture is data
-(stamps, frame names, poses); the bag itself is not copied.  Run where /root/reference exists."""
+(stamps, frame names, poses); the bag itself is not copied.
+
+    python tests/golden/make_tf_fixture.py <reference checkout>/test/test_multiple_targets.bag"""
 import os
 import sys
 
@@ -11,9 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from target_estimation_amd import rosbag_tf  # noqa: E402
 
-BAG = "/root/reference/test/test_multiple_targets.bag"
-
 if __name__ == "__main__":
+    BAG = sys.argv[1]
     stats = {}
     tr = rosbag_tf.read_tf(BAG, stats=stats)
     # what the bag's own index section says (written by the ROS recorder; a second path through the file)

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -174,12 +175,96 @@ def test_dry_run_lines_are_short():
         assert all(len(ln) < 4096 for ln in p.stdout.splitlines())
 
 
+class _FakeBatch:
+    def __init__(self, ids):
+        self._slots = ids[::-1].copy()     # slots in another order than the ids
+
+    def slot_ids(self):
+        return self._slots
+
+
+class _FakeManager:
+    """get_est_batch / get_state_batch of a manager whose every value is a function of the target id."""
+    def get_est_batch(self, ids):
+        f = ids.astype(float)[:, None]
+        return f + np.arange(7), f + 10 + np.arange(6), f + 20 + np.arange(6), np.ones(len(ids), bool)
+
+    def get_state_batch(self, ids):
+        f = ids.astype(float)
+        return f[:, None] + np.arange(18), f[:, None, None] + np.zeros((18, 18))
+
+
+def test_dump_outputs_writes_a_fixed_sample_in_float64_within_64_mb(tmp_path):
+    """--dump-outputs: the same ids every run, by id (not slot), float64 .npy, the query outputs mapped from slots to ids,
+    and a bounded total even for the largest populations."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = [np.arange(500_000, dtype=np.uint32), np.arange(500_000, dtype=np.uint32) + 500_000]
+    batches = [_FakeBatch(i) for i in ids]
+    query = [(torch.from_numpy(b.slot_ids().astype(np.float64)), torch.from_numpy(b.slot_ids().astype(np.float64))[:, None].repeat(1, 7))
+             for b in batches]
+    parts = [("angular_rates", batches[0], ids[0], query[0]), ("angular_velocities", batches[1], ids[1], query[1])]
+    total = bench.dump_outputs(str(tmp_path / "a"), _FakeManager(), parts)
+    bench.dump_outputs(str(tmp_path / "b"), _FakeManager(), parts)
+    assert 0 < total <= bench.DUMP_LIMIT
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert names == sorted("b%d_%s_%s.npy" % (j, m, k) for j, m in enumerate(["angular_rates", "angular_velocities"])
+                           for k in ("pose", "twist", "acc", "x", "P", "query_delta", "query_pose"))
+    size = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        size += a.nbytes
+    assert size == total
+    pose = np.load(tmp_path / "a" / "b1_angular_velocities_pose.npy")
+    assert pose.shape == (bench.DUMP_EST_SAMPLE, 7) and len(np.unique(pose[:, 0])) == bench.DUMP_EST_SAMPLE
+    assert pose[:, 0].min() >= 500_000
+    # the query's slot-ordered outputs come out in the same (id) order as the estimates
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "b1_angular_velocities_query_delta.npy"), pose[:, 0])
+    assert np.load(tmp_path / "a" / "b0_angular_rates_P.npy").shape == (bench.DUMP_STATE_SAMPLE, 18, 18)
+
+
+def test_full_and_dump_outputs_are_options():
+    p = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+@pytest.mark.gpu
+def test_a_plain_run_is_lean_and_its_outputs_repeat(tmp_path):
+    """The plain command times exactly --steps steps and measures nothing else (no CPU baseline, parity or extras); two runs
+    with the same arguments dump the same outputs, bit for bit."""
+    lines = []
+    for k in ("a", "b"):
+        p, line = _run(["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / k),
+                        "--side-file", str(tmp_path / (k + ".json"))], timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(line)
+    for line in lines:
+        assert line["config"]["name"] == "cfg4_1gpu" and line["steps"] == 7 and line["warmup"] == 3 and line["value"] > 1e7
+        assert line["ms_per_step"] > 0 and line["unit"] == "cycles/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert "cpu_baseline" not in line and "parity" not in line
+    side = json.load(open(tmp_path / "a.json"))
+    assert "extra" not in side and "configs0" not in side and "measured_copy_gbs" not in side["roofline"]
+    assert "1 repetitions of 7 steps" in side["config"]["timing"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "b0_angular_rates_x.npy" in names and "b1_angular_velocities_pose.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+
+
 @pytest.mark.gpu
 def test_two_ranks_end_to_end_on_one_gpu(tmp_path):
     """The literal `bench.py --gpus 2` (it starts its two ranks itself), gloo between them, both on the box's one GPU:
     every rank steps its own shard, rank 0 prints the one line (first) and writes the side file."""
     side = str(tmp_path / "side.json")
-    p, line = _run(["--gpus", "2", "--steps", "8", "--warmup", "2", "--reps", "2", "--workload", "cfg4_64", "--extra-multi", "cfg4_1gpu_strong,uv1m_strong",
+    p, line = _run(["--gpus", "2", "--steps", "8", "--warmup", "2", "--reps", "2", "--full", "--workload", "cfg4_64", "--extra-multi", "cfg4_1gpu_strong,uv1m_strong",
                     "--extra-steps", "4", "--side-file", side], env={"TE_BENCH_BACKEND": "gloo"}, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["config"]["targets_total"] == 2 * line["config"]["targets_per_gpu"]
@@ -194,9 +279,9 @@ def test_two_ranks_end_to_end_on_one_gpu(tmp_path):
 
 @pytest.mark.gpu
 def test_single_gpu_line_parses_and_carries_roofline_and_cpu_baseline(tmp_path):
-    """The driver's command shape at N = 1 (fewer extras, to keep the test short): the last stdout line is the record."""
+    """The driver's command shape at N = 1 with --full (fewer extras, to keep the test short): the last stdout line is the record."""
     side = str(tmp_path / "side.json")
-    p, line = _run(["--steps", "6", "--warmup", "2", "--reps", "2", "--extra", "cfg2,ar4m64", "--extra-steps", "4", "--side-file", side], timeout=900)
+    p, line = _run(["--steps", "6", "--warmup", "2", "--reps", "2", "--full", "--extra", "cfg2,ar4m64", "--extra-steps", "4", "--side-file", side], timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     last = p.stdout.strip().splitlines()[-1]
     assert len(last) < 4096 and json.loads(last) == line
@@ -217,7 +302,7 @@ def test_extras_that_overrun_their_deadline_do_not_cost_the_line(tmp_path):
     the process says which extra it was in, marks the side file, and leaves with status 4 -- a stalled extra (a hang, a resident
     session that never ends) must not be recorded as a clean run."""
     side = str(tmp_path / "side.json")
-    p, line = _run(["--workload", "cfg2", "--steps", "8", "--warmup", "2", "--reps", "2", "--no-cpu", "--extra", "ar4m64,av4m64,uv10m,ua10m", "--extra-steps", "64",
+    p, line = _run(["--workload", "cfg2", "--steps", "8", "--warmup", "2", "--reps", "2", "--full", "--no-cpu", "--extra", "ar4m64,av4m64,uv10m,ua10m", "--extra-steps", "64",
                     "--post-deadline", "0.05", "--side-file", side], timeout=600)
     assert p.returncode == 4, p.stderr[-3000:]
     assert line is not None and line["value"] > 0 and json.loads(p.stdout.strip().splitlines()[-1]) == line

@@ -1,7 +1,9 @@
 """Recorded multi-target data (the reference's test/test_multiple_targets.bag, extracted to
 tests/golden/multiple_targets_tf.npz) replayed through the ingest policy: on CPU with the policy
-restatement + oracle, on the GPU with the product, compared tick by tick."""
+restatement + oracle, on the GPU with the product, compared tick by tick.  The bag reader is checked
+on a rosbag v2 file written from the fixture (the bag itself is not part of the repository)."""
 import os
+import struct
 
 import numpy as np
 import pytest
@@ -12,7 +14,6 @@ from target_estimation_amd import rosbag_tf
 from conftest import ROOT, model_path
 
 FIX = os.path.join(ROOT, "tests", "golden", "multiple_targets_tf.npz")
-BAG = "/root/reference/test/test_multiple_targets.bag"
 
 
 def load_fixture():
@@ -21,10 +22,70 @@ def load_fixture():
                  child_frame_id=a["child_frame_id"][i].decode(), pose=a["pose"][i].copy()) for i in range(len(a["stamp"]))]
 
 
-def test_reader_reproduces_the_fixture():
-    if not os.path.exists(BAG):
-        pytest.skip("reference tree not present (GPU box)")
-    tr = rosbag_tf.read_tf(BAG)
+def _time(t):
+    """(sec, nsec) that the reader turns back into exactly the float t."""
+    sec = int(t)
+    base = int(round((t - sec) * 1e9))
+    for d in range(1000):
+        for nsec in (base - d, base + d):
+            if float(sec) + 1e-9 * float(nsec) == t:
+                return sec, nsec
+    raise ValueError(t)
+
+
+def write_bag(path, fx):
+    """A rosbag v2 file as the ROS recorder lays it out: bag header record (padded to 4 KB), one uncompressed chunk holding the
+    /tf connection and one TFMessage per transform, the chunk's index record, then the index section (connection record and
+    chunk-info record) that the bag header points to."""
+    def field(name, value):
+        return struct.pack("<I", len(name) + 1 + len(value)) + name.encode() + b"=" + value
+
+    def record(fields, data):
+        header = b"".join(field(k, v) for k, v in fields)
+        return struct.pack("<I", len(header)) + header + struct.pack("<I", len(data)) + data
+
+    def text(s):
+        b = s.encode()
+        return struct.pack("<I", len(b)) + b
+
+    conn_data = b"".join(field(k, v.encode()) for k, v in (("topic", "/tf"), ("type", "tf2_msgs/TFMessage"), ("md5sum", "94810edda583a504dfda3829e70d7eec"),
+                                                            ("message_definition", "geometry_msgs/TransformStamped[] transforms\n")))
+    conn = record([("op", b"\x07"), ("conn", struct.pack("<I", 0)), ("topic", b"/tf")], conn_data)
+    chunk, offsets, times = conn, [], []
+    for seq, t in enumerate(fx):
+        sec, nsec = _time(t["recv_time"])
+        ssec, snsec = _time(t["stamp"])
+        msg = struct.pack("<IIII", 1, seq, ssec, snsec) + text(t["frame_id"]) + text(t["child_frame_id"]) + struct.pack("<7d", *t["pose"])
+        offsets.append(len(chunk))
+        times.append((sec, nsec))
+        chunk += record([("op", b"\x02"), ("conn", struct.pack("<I", 0)), ("time", struct.pack("<II", sec, nsec))], msg)
+    magic = b"#ROSBAG V2.0\n"
+    header_len = 4096
+    chunk_pos = len(magic) + header_len
+    chunk_rec = record([("op", b"\x05"), ("compression", b"none"), ("size", struct.pack("<I", len(chunk)))], chunk)
+    index = record([("op", b"\x04"), ("ver", struct.pack("<I", 1)), ("conn", struct.pack("<I", 0)), ("count", struct.pack("<I", len(fx)))],
+                   b"".join(struct.pack("<IIi", s, n, o) for (s, n), o in zip(times, offsets)))
+    index_pos = chunk_pos + len(chunk_rec) + len(index)
+    info = record([("op", b"\x06"), ("ver", struct.pack("<I", 1)), ("chunk_pos", struct.pack("<Q", chunk_pos)),
+                   ("start_time", struct.pack("<II", *min(times))), ("end_time", struct.pack("<II", *max(times))), ("count", struct.pack("<I", 1))],
+                  struct.pack("<II", 0, len(fx)))
+    fields = [("op", b"\x03"), ("index_pos", struct.pack("<Q", index_pos)), ("conn_count", struct.pack("<I", 1)), ("chunk_count", struct.pack("<I", 1))]
+    head = record(fields, b"")
+    head = record(fields, b" " * (header_len - len(head)))
+    assert len(head) == header_len
+    with open(path, "wb") as f:
+        f.write(magic + head + chunk_rec + index + conn + info)
+
+
+@pytest.fixture(scope="module")
+def bag(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("bag") / "test_multiple_targets.bag")
+    write_bag(path, load_fixture())
+    return path
+
+
+def test_reader_reproduces_the_fixture(bag):
+    tr = rosbag_tf.read_tf(bag)
     fx = load_fixture()
     assert len(tr) == len(fx) == 572
     for a, b in zip(tr, fx):
@@ -33,19 +94,19 @@ def test_reader_reproduces_the_fixture():
         np.testing.assert_array_equal(a["pose"], b["pose"])
 
 
-def test_reader_agrees_with_the_bags_own_index():
+def test_reader_agrees_with_the_bags_own_index(bag):
     """Independent of the reader's walk over the chunks: the bag's INDEX section (written by the ROS recorder) declares how
     many messages the /tf connection holds; the reader must have decoded exactly that many, each TFMessage consumed to its
-    last byte (parse_tf_message raises otherwise).  Stored in the fixture when it was made; re-derived here when the
-    reference tree is present."""
+    last byte (parse_tf_message raises otherwise).  Stored in the fixture when it was made; re-derived here on the bag
+    written from the fixture."""
     a = np.load(FIX)
     assert int(a["tf_messages_declared_by_the_bag_index"]) == int(a["tf_messages_decoded"]) == 572
     assert int(a["bag_conn_count"]) == 1 and int(a["bag_chunk_count"]) == 1
-    if os.path.exists(BAG):
-        declared, conns, chunks = rosbag_tf.declared_counts(BAG)
-        stats = {}
-        rosbag_tf.read_tf(BAG, stats=stats)
-        assert declared == {"/tf": stats["messages"]} and (conns, chunks) == (1, 1)
+    declared, conns, chunks = rosbag_tf.declared_counts(bag)
+    stats = {}
+    rosbag_tf.read_tf(bag, stats=stats)
+    assert declared == {"/tf": stats["messages"]} and (conns, chunks) == (1, 1)
+    assert stats["messages"] == int(a["tf_messages_decoded"])
 
 
 def test_fixture_contents_and_cpu_replay(models):

@@ -8,7 +8,8 @@ DESIGN.md holds blocks of the form
     <!-- GENERATED:<name> END -->
 
 and this tool fills them from the committed records of the round:
-    profiles/r04_bench_extra.json      the side file of `python bench.py --gpus 1 --steps 20 --warmup 5` (every workload of the run)
+    profiles/r04_bench_extra.json      the side file of `python bench.py --gpus 1 --steps 20 --warmup 5` (every workload of the run;
+                                       today that command needs --full)
     profiles/hbm_traffic.json          rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes per workload (tools/pmc_traffic.py)
     profiles/r04_live_capacity.txt     tools/live_capacity.py
     profiles/r04_kernel_resources.txt  tools/kres_all.sh

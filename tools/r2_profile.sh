@@ -6,7 +6,7 @@ OUT=$PWD/gpurun_out/r2prof
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== kernel trace of the default bench command" | tee $OUT/progress.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace rc=$?" | tee -a $OUT/progress.txt
 python3 tools/summarize_trace.py $OUT/trace $OUT/bench_trace.json > $OUT/bench_default_rocprofv3.txt 2>> $OUT/progress.txt
 cp $OUT/trace/*kernel_stats.csv $OUT/bench_default_kernel_stats.csv 2>/dev/null || find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/bench_default_kernel_stats.csv \;

@@ -8,14 +8,14 @@ OUT=$PWD/gpurun_out/r3prof
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== kernel trace of the default bench command" | tee $OUT/progress.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra_trace.json > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra_trace.json > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace rc=$?" | tee -a $OUT/progress.txt
 python3 tools/summarize_trace.py $OUT/trace $OUT/bench_trace.json > $OUT/bench_default_rocprofv3.txt 2>> $OUT/progress.txt
 find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/bench_default_kernel_stats.csv \;
 rm -rf $OUT/trace
 head -40 $OUT/bench_default_rocprofv3.txt
 echo "== all-in-one PMC pass (once)" | tee -a $OUT/progress.txt
-TE_BENCH_MAPS=$OUT/allinone_maps.txt timeout -k 10 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/allinone -o allinone -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra_allinone.json > $OUT/allinone.json 2> $OUT/allinone.err
+TE_BENCH_MAPS=$OUT/allinone_maps.txt timeout -k 10 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/allinone -o allinone -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra_allinone.json > $OUT/allinone.json 2> $OUT/allinone.err
 echo "all-in-one rc=$?" | tee -a $OUT/progress.txt
 cat $OUT/allinone_maps.txt.progress 2>/dev/null | tail -3
 grep -v "^W20\|^I20" $OUT/allinone.err | tail -60 > $OUT/allinone_stderr_tail.txt

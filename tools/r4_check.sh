@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1; rc=$?; echo "tests rc=$rc"
 tail -15 $OUT/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra.json > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --side-file $OUT/bench_extra.json > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc=$?"
 tail -c 600 $OUT/bench.err
 python - $OUT/bench_extra.json <<'PY'
 import json, sys

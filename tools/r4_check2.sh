@@ -8,7 +8,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_live.py tests/test_highprec_ka
 tail -8 $OUT/tests.log
 [ $rc -eq 0 ] || exit $rc
 bash tools/r4_pop_grid.sh
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --extra cfg2_live,cfg3_live,cfg4_live,cfg4_64_live,cfg5_live --side-file $OUT/live.json > $OUT/live.line 2> $OUT/live.err
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --extra cfg2_live,cfg3_live,cfg4_live,cfg4_64_live,cfg5_live --side-file $OUT/live.json > $OUT/live.line 2> $OUT/live.err
 python - $OUT/live.json <<'PY'
 import json, sys
 for e in json.load(open(sys.argv[1])).get("extra", []):

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests/test_gpu_live.py tests/test_gpu_c_abi_program.py -m gpu -x -q > $OUT/tests.log 2>&1; rc=$?; echo "tests rc=$rc"; tail -4 $OUT/tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 5 120 tools/_build/bar_doorbell | tee $OUT/echo.txt
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 for mode in bar host bar host; do
   TE_LIVE_DOORBELL=$mode timeout -k 10 300 python3 bench.py $COMMON --extra cfg2_live,cfg3_live,cfg4_live,cfg4_64_live,cfg5_live --side-file $OUT/$mode.json > $OUT/$mode.line 2> $OUT/$mode.err
   python3 - $OUT/$mode.json $mode <<'PY' | tee -a $OUT/summary.txt

@@ -5,7 +5,7 @@ set -o pipefail
 OUT=$PWD/gpurun_out/r4liveord
 mkdir -p $OUT
 export TMPDIR=/tmp
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 printf "%-8s %-58s %10s %10s %10s\n" flags "edges in force" cfg2_live cfg3_live cfg4_live | tee $OUT/summary.txt
 run() {
   TE_LIVE_FLAGS=$1 timeout -k 10 300 python3 bench.py $COMMON --extra cfg2_live,cfg3_live,cfg4_live --side-file $OUT/f$1.json > $OUT/f$1.line 2> $OUT/f$1.err

@@ -4,7 +4,7 @@ set -o pipefail
 OUT=$PWD/gpurun_out/r4popgrid
 mkdir -p $OUT
 export TMPDIR=/tmp
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 printf "%-44s %8s %8s %8s\n" "variant" cfg4 cfg4_64 cfg5 | tee $OUT/summary.txt
 run() {
   env $2 timeout -k 10 300 python3 bench.py $COMMON --extra cfg4,cfg4_64,cfg5 --side-file $OUT/$1.json > $OUT/$1.line 2> $OUT/$1.err

@@ -17,7 +17,7 @@ for e in d.get("extra", []):
     else: print("  %-12s %8.2f us/tick  frac %.3f  %s" % (e["name"], 1e3 * e["ms_per_step"], e["roofline_frac"], e["launch_mode"]))
 EOF
 }
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2"
 echo "== A: mixed shares alone" | tee $OUT/progress.txt
 timeout -k 10 300 python3 bench.py $COMMON --extra cfg4,cfg4_64,cfg5 --side-file $OUT/A.json > $OUT/A.line 2> $OUT/A.err; echo "rc=$?" | tee -a $OUT/progress.txt
 show $OUT/A.json | tee -a $OUT/progress.txt

@@ -15,7 +15,7 @@ for e in d.get("extra", []):
     else: print("  %-12s %8.2f us/tick  %s" % (e["name"], 1e3 * e["ms_per_step"], e["launch_mode"][:40]))
 PY
 }
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2"
 echo "== F: a high-priority stream exists (never used), no resident session" | tee $OUT/progress.txt
 timeout -k 10 300 python3 -c "
 import sys, torch

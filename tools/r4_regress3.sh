@@ -5,7 +5,7 @@ set -o pipefail
 OUT=$PWD/gpurun_out/r4regress3
 mkdir -p $OUT
 export TMPDIR=/tmp
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 for tag in bad good; do
   if [ $tag = bad ]; then EX=cfg2_live,cfg4_64; else EX=cfg4_64; fi
   AMD_LOG_LEVEL=4 AMD_LOG_MASK=24 timeout -k 10 300 python3 bench.py $COMMON --extra $EX --side-file $OUT/$tag.json > $OUT/$tag.line 2> /tmp/$tag.log

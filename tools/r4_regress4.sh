@@ -5,7 +5,7 @@ set -o pipefail
 OUT=$PWD/gpurun_out/r4regress4
 mkdir -p $OUT
 export TMPDIR=/tmp
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 for q in 8 4 2; do
   tag=q$q
   GPU_MAX_HW_QUEUES=$q AMD_LOG_LEVEL=4 AMD_LOG_MASK=24 timeout -k 10 300 python3 bench.py $COMMON --extra cfg4,cfg4_64,cfg5 --side-file $OUT/$tag.json > $OUT/$tag.line 2> /tmp/$tag.log

@@ -5,7 +5,7 @@ set -o pipefail
 OUT=$PWD/gpurun_out/r4smallgrid
 mkdir -p $OUT
 export TMPDIR=/tmp
-COMMON="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
+COMMON="--full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-gather --workload cfg2 --reps 1"
 printf "%-28s %8s %12s %14s %10s\n" "TE_SMALL_GRID_WAVES" cfg3 cfg3_stream ar100k64_1kcls cfg4_64 | tee $OUT/summary.txt
 for g in 1024 2048 4096 8192 1024; do
   TE_SMALL_GRID_WAVES=$g timeout -k 10 300 python3 bench.py $COMMON --extra cfg3,cfg3_stream,ar100k64_1kcls,cfg4_64 --side-file $OUT/g$g.json > $OUT/g$g.line 2> $OUT/g$g.err
