@@ -33,7 +33,7 @@ def load(fast=False):
     strict_p, fast_p = build()
     lib = C.CDLL(fast_p if fast else strict_p)
     dp = C.POINTER(C.c_double)
-    for sfx, real in (("f64", C.c_double), ("f32", C.c_float)):
+    for sfx, real in (("f64", C.c_double), ("f32", C.c_float), ("f80", C.c_longdouble)):
         rp = C.POINTER(real)
         g = lambda name: getattr(lib, "%s_%s" % (name, sfx))  # noqa: E731
         g("orc_target_sizeof").restype = C.c_int
@@ -85,6 +85,7 @@ def load(fast=False):
     lib.orc_poly_roots.restype = C.c_int
     lib.orc_poly_roots.argtypes = [dp, C.c_int, dp]
     lib.orc_max_threads.restype = C.c_int
+    lib.orc_long_double_mant_dig.restype = C.c_int
     lib.orc_ref_test_stream.argtypes = [dp, C.c_int, C.c_int, C.c_double, dp, dp]
     lib.orc_harness_run_f64.argtypes = [C.c_int, dp, dp, dp, dp, C.c_long, C.c_double, dp, dp]
     lib.orc_stream_fill.argtypes = [C.c_int, C.c_ulonglong, C.c_long, C.c_long, C.c_long, C.c_long, C.c_double, C.c_double,

@@ -6,6 +6,7 @@
 #include "te_oracle.h"
 
 #include <complex.h>
+#include <float.h>
 #include <math.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -189,6 +190,30 @@ int orc_gate_update(orc_gate* g, int exists, const double* pose7, double pos_th,
 #define RFMOD fmodf
 #define RFABS fabsf
 #include "te_oracle_impl.h"
+#undef REAL
+#undef SFX
+#undef RSIN
+#undef RCOS
+#undef RATAN2
+#undef RASIN
+#undef RSQRT
+#undef RFMOD
+#undef RFABS
+
+/* Extended precision (x87 80-bit on x86-64: a 64-bit mantissa): the yardstick the f64 and f32 paths are measured against, not
+ * a restatement of the reference's precision.  R_PI stays the double pi, as in the reference and in the 50-digit generator. */
+#define REAL long double
+#define SFX f80
+#define RSIN sinl
+#define RCOS cosl
+#define RATAN2 atan2l
+#define RASIN asinl
+#define RSQRT sqrtl
+#define RFMOD fmodl
+#define RFABS fabsl
+#include "te_oracle_impl.h"
+
+int orc_long_double_mant_dig(void) { return LDBL_MANT_DIG; }
 
 /* ------------------------------------------------------------------------- */
 /* The reference's integration-test loop for ONE target, in C (for timing configs[0] without a Python loop around it):

@@ -20,7 +20,8 @@
  * (I - K*C)*P, inverse by partial-pivot LU (what Eigen's dynamic .inverse() does),
  * accumulation k-ascending, no FMA contraction (build with -ffp-contract=off).
  *
- * Two instantiations: _f64 (the reference's precision) and _f32.
+ * Three instantiations: _f64 (the reference's precision), _f32, and _f80 (long double: the extended-precision yardstick
+ * the other two and the HIP kernels are measured against; entry points still take and return double).
  * Matrices are row-major here; Eigen's column-major storage does not change the
  * arithmetic.
  */
@@ -105,6 +106,10 @@ enum {
 
 ORC_DECLARE(double, f64)
 ORC_DECLARE(float, f32)
+ORC_DECLARE(long double, f80)
+
+/* LDBL_MANT_DIG of the compiler that built the oracle (64 for the x87 format the _f80 instantiation needs) */
+int orc_long_double_mant_dig(void);
 
 /* MovingAvgFilter (include/target_estimation/utils.hpp:206-265) and the convergence gate of
  * IntersectionSolver::getIntersectionPoseWithSphere (src/intersection_solver.cpp:105-120): one gate per

@@ -1,6 +1,6 @@
 /*
  * te_oracle_impl.h -- body of the CPU oracle, instantiated once per precision by
- * te_oracle.c (REAL = double / float, SFX = f64 / f32).  TEST INFRASTRUCTURE ONLY,
+ * te_oracle.c (REAL = double / float / long double, SFX = f64 / f32 / f80).  TEST INFRASTRUCTURE ONLY,
  * see te_oracle.h for the parity status and the rules on who may use it.
  *
  * All citations are file:line under /root/reference.

@@ -1,10 +1,10 @@
 """GPU parity: the HIP path, called through the C ABI, against the CPU oracle on the same seeded
 inputs.  Run on the MI355X box with `pytest -m gpu`.
 
-Tolerances (stated here, measured margins in DESIGN.md):
-  f64 HIP vs f64 oracle : |dx| <= 1e-10 + 1e-10|x| ; |dP| <= 1e-9 * max|P|   (fma + unpivoted
-                          Gauss-Jordan vs mul/add + pivoted LU; (1-K) cancellation ~1e3 on step 1)
-  f32 HIP vs f32 oracle : |dx| <= 2e-3 + 1e-4|x| ; |dP| <= 2e-3 * max|P|
+Tolerances (stated here; tests/test_gpu_precision.py holds every path to a multiple of what a faithful implementation errs
+by against an extended-precision oracle, which is where these figures come from):
+  f64 HIP vs f64 oracle : |dx| <= 1e-12 + 1e-12|x| ; |dP| <= 1e-10 * max|P| ; outputs 1e-11   
+  f32 HIP vs f32 oracle : |dx| <= 5e-4 + 2e-5|x| ; |dP| <= 2e-4 * max|P| ; outputs 1e-3
   target ids / slot order: exact.
 """
 import numpy as np
@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 te = pytest.importorskip("target_estimation_amd")
 
-TOL = {"f64": dict(x_atol=1e-10, x_rtol=1e-10, P_rel=1e-9, out_atol=1e-9),
-       "f32": dict(x_atol=2e-3, x_rtol=1e-4, P_rel=2e-3, out_atol=5e-3)}
+TOL = {"f64": dict(x_atol=1e-12, x_rtol=1e-12, P_rel=1e-10, out_atol=1e-11),
+       "f32": dict(x_atol=5e-4, x_rtol=2e-5, P_rel=2e-4, out_atol=1e-3)}
 
 # 101 = thread per target with symmetric-packed P in HBM (1 + TARGET_LAYOUT_SYMMETRIC_PACKED);
 # 201 = axis-separable layout (1 + TARGET_LAYOUT_AXIS_SEPARABLE); 0 = automatic (separable here,

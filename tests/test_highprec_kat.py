@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
+from conftest import synth_stream
 from oracle import np_twin as tw
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,6 +23,23 @@ MODELS = ["uniform_velocity", "uniform_acceleration", "angular_rates", "angular_
 @pytest.fixture(scope="module")
 def kat():
     return np.load(os.path.join(HERE, "golden", "highprec_kat.npz"))
+
+
+def x_err(x, xr):
+    """|dx|_inf / max(1, |x|_inf) per target (x [N, n] or one vector), maximum over the batch (as `check` below)"""
+    x, xr = np.asarray(x).reshape(-1, xr.shape[-1]), xr.reshape(-1, xr.shape[-1])
+    return float((np.abs(x - xr).max(axis=1) / np.maximum(1.0, np.abs(xr).max(axis=1))).max())
+
+
+def P_err(P, Pr):
+    """|dP| / max|P| per target (P [N, n, n]), maximum over the batch"""
+    P, Pr = np.asarray(P).reshape(-1, *Pr.shape[-2:]), Pr.reshape(-1, *Pr.shape[-2:])
+    return float((np.abs(P - Pr).max(axis=(1, 2)) / np.abs(Pr).max(axis=(1, 2))).max())
+
+
+def f32r(a):
+    """the values an f32 holds, as doubles"""
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
 
 
 def check(tag, x, P, xk, Pk):
@@ -217,3 +235,72 @@ def test_hip_through_the_gimbal_branches(kat):
         p1, t1w, _, _ = mgr.get_est_batch([3], t1=(s + 1) * dt + ahead)
         _out_check("hip gimbal tick %d ahead" % (s + 1), (p1[0], t1w[0]), want[19:])
     mgr.close()
+
+
+# ---- the extended-precision (f80, long double) oracle: the yardstick of tests/test_gpu_precision.py --------------------------------
+def test_long_double_has_a_64_bit_mantissa():
+    """The f80 instantiation is only a yardstick if long double is wider than double (x87 extended: 64 bits)."""
+    dig = oracle.load().orc_long_double_mant_dig()
+    assert dig >= 64, ("long double has a %d-bit mantissa on this platform: the f80 oracle would be no more precise than the "
+                       "f64 one, and tests/test_gpu_precision.py would measure nothing" % dig)
+
+
+@pytest.mark.parametrize("name", MODELS)
+def test_f80_oracle_matches_the_high_precision_answers(models, kat, name):
+    """Measured: 0 to 1.3e-21 (x and P, relative)."""
+    m = models[name]
+    t = oracle.OracleTarget(m["model"], m["Q"], m["R"], m["P"], kat["p0"], float(kat["dt"]), dtype="f80")
+    for s in drive(t, kat):
+        x, P = t.state()
+        xk, Pk = kat["x_" + name][s], kat["P_" + name][s]
+        ex, eP = x_err(x[0], xk), P_err(P[0], Pk)
+        print("f80 oracle %-22s tick %d  x %.2e  P %.2e" % (name, s + 1, ex, eP))
+        assert ex <= 1e-18 and eP <= 1e-18, (name, s + 1, ex, eP)
+        assert np.all(P[0][Pk == 0] == 0), name
+
+
+def test_f80_oracle_intersections_match_the_high_precision_roots(models, kat):
+    m = models["uniform_acceleration"]
+    n = len(kat["ix_delta"])
+    p0 = np.concatenate([kat["ix_p0"], np.tile([0, 0, 0, 1.0], (n, 1))], 1)
+    v0 = np.concatenate([kat["ix_v0"], np.zeros((n, 3))], 1)
+    a0 = np.concatenate([kat["ix_a0"], np.zeros((n, 3))], 1)
+    orc = oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], p0, float(kat["dt"]), 0.0, v0, a0, dtype="f80")
+    ok, pose, delta = orc.intersection_pose(0.0, kat["ix_origin"], float(kat["ix_radius"]))
+    _ix_check("f80 oracle", kat, delta, pose)
+
+
+# What a faithful implementation errs by against the f80 oracle on synth_stream (200 targets), measured: f64 at tick 100,
+# f32 (f32-rounded inputs on both sides) at tick 300.  x: |dx| / max(1, |x|); P: |dP| / max|P|; per target, batch maxima.
+FAITHFUL = {"uniform_velocity": dict(f64=(6e-14, 1e-15), f32=(2e-5, 3e-6)),
+            "uniform_acceleration": dict(f64=(7e-14, 8e-15), f32=(1.7e-4, 7e-6)),
+            "angular_rates": dict(f64=(1.7e-13, 5e-15), f32=(1.7e-4, 4e-6)),
+            "angular_velocities": dict(f64=(6e-14, 5e-15), f32=(2e-5, 1e-5))}
+
+
+@pytest.mark.parametrize("name", MODELS)
+def test_f64_and_f32_oracles_stay_near_the_f80_oracle(models, name):
+    """Pins the 'faithful error' the GPU precision matrix holds every kernel to a small multiple of: over 300 ticks the f64
+    and f32 oracles stay within 4x the figures above (f64 at tick 100, f32 at tick 300) of the f80 oracle, and not absurdly far inside them either (a yardstick
+    that agreed with f64 to the last bit would be no yardstick)."""
+    m = models[name]
+    N, steps, dt = 200, 300, 0.004
+    p0, meas = synth_stream(name, N, steps, seed=23)
+    p032, meas32 = f32r(p0), f32r(meas)
+    mk = lambda d, p: oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], p, dt, dtype=d)  # noqa: E731
+    o64, o80, o32, o80r = mk("f64", p0), mk("f80", p0), mk("f32", p032), mk("f80", p032)
+    for s in range(steps):
+        for o, mm in ((o64, meas), (o80, meas), (o32, meas32), (o80r, meas32)):
+            o.step(dt, mm[s], nthreads=8)
+        if s + 1 in (100, steps):
+            (x64, P64), (x80, P80) = o64.state(), o80.state()
+            (x32, P32), (x80r, P80r) = o32.state(), o80r.state()
+            e64, e32 = (x_err(x64, x80), P_err(P64, P80)), (x_err(x32, x80r), P_err(P32, P80r))
+            print("faithful %-22s tick %3d  f64 x %.2e P %.2e   f32 x %.2e P %.2e" % (name, s + 1, *e64, *e32))
+            if s + 1 == 100:
+                fx, fP = FAITHFUL[name]["f64"]
+                assert e64[0] <= 4 * fx and e64[1] <= 4 * fP, (name, s + 1, e64)
+                assert e64[0] >= 1e-17 and e64[1] >= 1e-18, (name, s + 1, e64)
+    fx, fP = FAITHFUL[name]["f32"]
+    assert e32[0] <= 4 * fx and e32[1] <= 4 * fP, (name, e32)
+    assert e32[0] >= 1e-9 and e32[1] >= 1e-10, (name, e32)
