@@ -48,6 +48,9 @@ def load(fast=False):
             g(nm).argtypes = [C.c_void_p, dp]
         g("orc_target_get_period_estimate").restype = C.c_double
         g("orc_target_get_period_estimate").argtypes = [C.c_void_p]
+        g("orc_target_get_time").restype = C.c_double
+        g("orc_target_get_time").argtypes = [C.c_void_p]
+        g("orc_target_set_time").argtypes = [C.c_void_p, C.c_double]
         for nm in ("orc_target_get_pose_at", "orc_target_get_twist_at",
                    "orc_target_get_acceleration_at"):
             g(nm).argtypes = [C.c_void_p, C.c_double, dp]
@@ -199,6 +202,18 @@ class OracleBatch:
     def period_estimate(self):
         f = self._f("orc_target_get_period_estimate")
         return np.array([f(self._at(i)) for i in range(self.N)])
+
+    def times(self):
+        """every target's clock t_ (the reference's sequential sum from t0)"""
+        f = self._f("orc_target_get_time")
+        return np.array([f(self._at(i)) for i in range(self.N)])
+
+    def set_times(self, t):
+        """put every target's clock at t [N] (or one value for all)"""
+        t = np.broadcast_to(np.asarray(t, dtype=np.float64), (self.N,))
+        f = self._f("orc_target_set_time")
+        for i in range(self.N):
+            f(self._at(i), float(t[i]))
 
     def pose_at(self, t1):
         return self._get("orc_target_get_pose_at", 7, float(t1))

@@ -541,6 +541,13 @@ void FN(orc_target_get_transform)(const TGT* tg, double* T16) {
   T16[12] = 0; T16[13] = 0; T16[14] = 0; T16[15] = 1;
 }
 
+/* getTime, target_interface.hpp (the sequential t_ = t_ + dt clock) */
+double FN(orc_target_get_time)(const TGT* tg) { return tg->t; }
+
+/* not in the reference: lets a test put the clock where it wants the getters at t1 to measure from
+ * (t = 0 and t1 = an exact offset rounded once) */
+void FN(orc_target_set_time)(TGT* tg, double t) { tg->t = t; }
+
 /* TargetInterface::getPeriodEstimate target_interface.cpp:80-87 */
 double FN(orc_target_get_period_estimate)(const TGT* tg) {
   const double wx = (double)tg->twist[3], wy = (double)tg->twist[4], wz = (double)tg->twist[5];

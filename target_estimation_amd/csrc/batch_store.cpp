@@ -292,20 +292,20 @@ void Batch::reserve(long n) {
   want = (want + tpw - 1) / tpw * tpw;
   const size_t new_bytes = (size_t)(want / tpw) * (size_t)ops_->L.tile_bytes;
   char* rec = nullptr;
-  double* tb = nullptr;
+  TClock* tb = nullptr;
   int* nm = nullptr;
   int* cl = nullptr;
   TE_HIP_CHECK(hipMalloc((void**)&rec, new_bytes));
-  TE_HIP_CHECK(hipMalloc((void**)&tb, sizeof(double) * want));
+  TE_HIP_CHECK(hipMalloc((void**)&tb, sizeof(TClock) * want));
   TE_HIP_CHECK(hipMalloc((void**)&nm, sizeof(int) * want));
   TE_HIP_CHECK(hipMalloc((void**)&cl, sizeof(int) * want));
   TE_HIP_CHECK(hipMemsetAsync(rec, 0, new_bytes, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(tb, 0, sizeof(double) * want, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(tb, 0, sizeof(TClock) * want, stream_));
   TE_HIP_CHECK(hipMemsetAsync(nm, 0, sizeof(int) * want, stream_));
   TE_HIP_CHECK(hipMemsetAsync(cl, 0, sizeof(int) * want, stream_));
   if (cap_ > 0) {
     TE_HIP_CHECK(hipMemcpyAsync(rec, d_rec_, (size_t)(cap_ / tpw) * (size_t)ops_->L.tile_bytes, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(tb, d_tbase_, sizeof(double) * cap_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(tb, d_tbase_, sizeof(TClock) * cap_, hipMemcpyDeviceToDevice, stream_));
     TE_HIP_CHECK(hipMemcpyAsync(nm, d_nmbase_, sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
     TE_HIP_CHECK(hipMemcpyAsync(cl, d_cls_, sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
   }
@@ -410,7 +410,7 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
     if (cls_of) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + count, cls_of, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.cls_of = d_idx_ + count; }
     if (P0_index) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + 2 * count, P0_index, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.P0_index = d_idx_ + 2 * count; }
   }
-  a.t_off = t0 - t_acc_; a.nm_off = (int)(-nm_acc_);
+  a.t_off = te_clock_sub(t0, t_acc_); a.nm_off = (int)(-nm_acc_);
   a.t_base = d_tbase_; a.nm_base = d_nmbase_;
   ops_->init(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -510,7 +510,7 @@ void Batch::step_dense(double dt, const void* meas_dev, long ld, const unsigned 
   if (pingpong()) p.rec_out = alt_records();
   launch_step(p, stream_, host_meas_rows_);
   if (p.rec_out) std::swap(d_rec_, d_rec_alt_);   // later launches on the stream see the finished tick in the new current buffer
-  t_acc_ += dt;
+  t_acc_ = te_clock_add(t_acc_, dt);
   if (meas_dev && !has_dev) nm_acc_ += 1;
 }
 
@@ -590,7 +590,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
-  t_acc_ += dt * (double)n_ticks;
+  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (meas_base && !has_base) nm_acc_ += n_ticks;
 }
 
@@ -617,7 +617,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
     IntersectArgs a;
     a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
     a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-    a.t_acc = 0.0; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
+    a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
     ops_->intersect(a, st);
   }
 }
@@ -643,7 +643,7 @@ StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, c
 }
 
 void Batch::account_sequence(long n_ticks, double dt, bool all_measured) {
-  t_acc_ += dt * (double)n_ticks;
+  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (all_measured) nm_acc_ += n_ticks;
 }
 
@@ -656,7 +656,7 @@ void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick
   p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
-  t_acc_ += dt * (double)n_ticks;
+  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (meas_base && !has_base) nm_acc_ += n_ticks;
 }
 
@@ -854,7 +854,7 @@ long Batch::live_stop() {
   // the relay's last word: the ticks EVERY wavefront served.  The host's stop, or the relay's own after a silent host, reaches
   // all workers through one device word, so they all stop at the same tick.
   const long mn = std::max(0L, (long)__atomic_load_n(live_.h_done, __ATOMIC_ACQUIRE));
-  t_acc_ += live_.dt * (double)mn;
+  t_acc_ = te_clock_add_ticks(t_acc_, live_.dt, (double)mn);
   if (live_.all_measured) nm_acc_ += mn;
   if (mn != live_.posted)
     throw std::runtime_error("target_estimation_amd: live session ended after " + std::to_string(mn) + " of " + std::to_string(live_.posted) +
@@ -1339,17 +1339,18 @@ long long Batch::n_measurements(long slot) {
 void Batch::times(double* out) {
   flush();
   if (n_ == 0) return;
-  TE_HIP_CHECK(hipMemcpyAsync(out, d_tbase_, sizeof(double) * n_, hipMemcpyDeviceToHost, stream_));
+  std::vector<TClock> tb((size_t)n_);
+  TE_HIP_CHECK(hipMemcpyAsync(tb.data(), d_tbase_, sizeof(TClock) * n_, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  for (long i = 0; i < n_; ++i) out[i] += t_acc_;
+  for (long i = 0; i < n_; ++i) out[i] = te_clock_time(tb[(size_t)i], t_acc_);
 }
 
 double Batch::time(long slot) {
   flush();
-  double v = 0;
-  TE_HIP_CHECK(hipMemcpyAsync(&v, d_tbase_ + slot, sizeof(double), hipMemcpyDeviceToHost, stream_));
+  TClock v{0.0, 0.0};
+  TE_HIP_CHECK(hipMemcpyAsync(&v, d_tbase_ + slot, sizeof(TClock), hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  return v + t_acc_;
+  return te_clock_time(v, t_acc_);
 }
 
 }  // namespace te

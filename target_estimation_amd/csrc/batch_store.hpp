@@ -46,7 +46,7 @@ class Batch {
   hipStream_t stream() const { return stream_; }
   unsigned slot_id(long slot) const { return slot_ids_[slot]; }
   const std::vector<unsigned>& slot_ids() const { return slot_ids_; }
-  double clock() const { return t_acc_; }
+  double clock() const { return t_acc_.hi + t_acc_.lo; }
 
   // Construct `count` new targets in slots [size(), size()+count).  Host arrays.
   // cls: the class of every new target, or cls_of [count] one class each; P0_index [count] (with P0 = a table of
@@ -242,12 +242,12 @@ class Batch {
   char* d_rec_alt_ = nullptr;      // second record buffer of the same capacity, allocated on the first A -> B tick
   char* alt_records();             // null if the device has no room for it (the batch then stays in place)
   bool alt_failed_ = false;
-  double* d_tbase_ = nullptr;
+  TClock* d_tbase_ = nullptr;
   int* d_nmbase_ = nullptr;
   long cap_ = 0;  // slots
   long n_ = 0;
   std::vector<unsigned> slot_ids_;
-  double t_acc_ = 0.0;      // batch clock: target time = t_base[slot] + t_acc_
+  TClock t_acc_{0.0, 0.0};  // batch clock: target time = t_base[slot] + t_acc_, both compensated pairs (te_clock.hpp)
   long long nm_acc_ = 0;    // batch measurement counter
   // staging for the host-array paths
   long stage_cap_ = 0;

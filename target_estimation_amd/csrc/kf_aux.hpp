@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "te_clock.hpp"
 #include "te_device_math.hpp"
 #include "te_layout.hpp"
 #include "te_quartic.hpp"
@@ -61,9 +62,9 @@ struct InitArgs {
   int* cls = nullptr;              // per-slot parameter class array of the batch
   const int* cls_of = nullptr;     // [n] class of entry e, or null: every entry gets cls_value
   int cls_value = 0;
-  double t_off;            // t0 - batch clock
+  TClock t_off;            // t0 - batch clock
   int nm_off;              // - batch measurement counter
-  double* t_base;
+  TClock* t_base;
   int* nm_base;
 };
 
@@ -150,7 +151,7 @@ __global__ void set_state_kernel(char* rec, const int* idx, long n, const double
 
 // copy the whole record of slot `src` over slot `dst` (erase = swap-with-last compaction)
 template <class M, typename T, int G, int LAYOUT>
-__global__ void move_record_kernel(char* rec, long src, long dst, double* t_base, int* nm_base, int* cls) {
+__global__ void move_record_kernel(char* rec, long src, long dst, TClock* t_base, int* nm_base, int* cls) {
   using C = Cfg<M, T, G, LAYOUT>;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= C::G * C::RW) return;
@@ -164,7 +165,7 @@ __global__ void move_record_kernel(char* rec, long src, long dst, double* t_base
 
 // m independent moves at once (batched erase: survivors from the tail fill the holes); blockIdx.y = move
 template <class M, typename T, int G, int LAYOUT>
-__global__ void move_records_kernel(char* rec, const int* src, const int* dst, long m, double* t_base, int* nm_base, int* cls) {
+__global__ void move_records_kernel(char* rec, const int* src, const int* dst, long m, TClock* t_base, int* nm_base, int* cls) {
   using C = Cfg<M, T, G, LAYOUT>;
   const long mv = blockIdx.y;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -194,8 +195,8 @@ struct OutArgs {
   double* acc;      // [n][6] or null
   int at_time;      // 0: current outputs; 1: extrapolated to t1 (getEstimated*(t1))
   double t1;        // absolute query time (at_time); NaN = each target's own time
-  double t_acc;     // batch clock; target time = t_base[slot] + t_acc
-  const double* t_base;
+  TClock t_acc;     // batch clock; target time = t_base[slot] + t_acc (te_clock.hpp)
+  const TClock* t_base;
   int by_slot = 0;  // 1: output row = slot (scatter into a per-slot table) instead of the entry index
   // One-workgroup launches only (n <= kOutputsBlock): after every row has been written, store done_seq to *done_flag
   // (host-mapped memory).  A host thread that spins on the flag sees the rows without a stream synchronisation: the
@@ -294,7 +295,7 @@ __global__ void outputs_kernel(const OutArgs a) {
 #pragma unroll
     for (int r = 0; r < N; ++r) x[r] = state_get<C, T>(a.rec, slot, r, N);
     T d = 0;
-    if (a.at_time) d = (a.t1 != a.t1) ? (T)0 : (T)(a.t1 - (a.t_base[slot] + a.t_acc));
+    if (a.at_time) d = (a.t1 != a.t1) ? (T)0 : (T)te_clock_offset(a.t1, a.t_base[slot], a.t_acc);
     T pose7[7], twist6[6], acc6[6];
     derive_outputs<M, T>(x, a.at_time != 0, d, pose7, twist6, acc6);
     const long row = a.by_slot ? slot : e;
@@ -316,8 +317,8 @@ struct IntersectArgs {
   double t1;          // absolute query time; NaN = each target's own time (t1 = t_)
   double origin[3];
   double radius;
-  double t_acc;
-  const double* t_base;
+  TClock t_acc;
+  const TClock* t_base;
   double* delta;      // [n]: time to the first intersection after t1, or -1
   double* pose;       // [n][7] pose at t1 + delta (initPose if none), or null
 };
@@ -325,10 +326,11 @@ struct IntersectArgs {
 // IntersectionSolver::getIntersectionTimeWithSphere / getIntersectionPoseWithSphere without the
 // moving-average convergence gate (src/intersection_solver.cpp:42-104) for one target with state x:
 // quartic in delta from the (p, v, a) extrapolated by dq = t1 - t_, smallest real root, pose at
-// t1 + delta.  own = the query is at the target's own time (dq = 0, pose offset = delta itself).
+// t1 + delta, i.e. at the offset delta + dq (the reference's (delta + t1) - t_, with the clock's
+// offset taken before t1's rounding).  own = the query is at the target's own time (dq = 0).
 // The values: delta (the reference's intersection time, -1 if none) and, if wanted, the pose at that time (identity if none).
 template <class M, typename T>
-__device__ __forceinline__ void sphere_query_values(const T* x, bool own, double t1, double t, const double* origin, double radius,
+__device__ __forceinline__ void sphere_query_values(const T* x, bool own, double dq, const double* origin, double radius,
                                                     double& delta, double (&pose)[7], const bool want_pose
 #ifdef TE_QUERY_PHASE_CLOCK
                                                     , long long* ts = nullptr
@@ -341,7 +343,7 @@ __device__ __forceinline__ void sphere_query_values(const T* x, bool own, double
 #define TE_TS(i) do {} while (0)
 #endif
   T pose7[7], twist6[6], acc6[6];
-  derive_outputs<M, T>(x, true, own ? (T)0 : (T)(t1 - t), pose7, twist6, acc6);
+  derive_outputs<M, T>(x, true, own ? (T)0 : (T)dq, pose7, twist6, acc6);
   const double px = (double)pose7[0] - origin[0], py = (double)pose7[1] - origin[1], pz = (double)pose7[2] - origin[2];
   const double vx = (double)twist6[0], vy = (double)twist6[1], vz = (double)twist6[2];
   const double ax = (double)acc6[0], ay = (double)acc6[1], az = (double)acc6[2];
@@ -360,7 +362,7 @@ __device__ __forceinline__ void sphere_query_values(const T* x, bool own, double
   if (want_pose) {
     pose[0] = pose[1] = pose[2] = pose[3] = pose[4] = pose[5] = 0; pose[6] = 1;
     if (d > -1) {
-      derive_outputs<M, T>(x, true, own ? (T)d : (T)((d + t1) - t), pose7, twist6, acc6);
+      derive_outputs<M, T>(x, true, own ? (T)d : (T)(d + dq), pose7, twist6, acc6);
 #pragma unroll
       for (int k = 0; k < 7; ++k) pose[k] = (double)pose7[k];
     }
@@ -369,10 +371,10 @@ __device__ __forceinline__ void sphere_query_values(const T* x, bool own, double
 }
 
 template <class M, typename T>
-__device__ __forceinline__ void sphere_query(const T* x, bool own, double t1, double t, const double* origin, double radius,
+__device__ __forceinline__ void sphere_query(const T* x, bool own, double dq, const double* origin, double radius,
                                              double* delta_out, double* pose_out /* [7] or null */) {
   double d, out[7];
-  sphere_query_values<M, T>(x, own, t1, t, origin, radius, d, out, pose_out != nullptr);
+  sphere_query_values<M, T>(x, own, dq, origin, radius, d, out, pose_out != nullptr);
   *delta_out = d;
   if (pose_out)
     for (int k = 0; k < 7; ++k) pose_out[k] = out[k];
@@ -391,8 +393,8 @@ __global__ void intersect_kernel(const IntersectArgs a) {
   // own-time query (t1 = NaN): the offsets are 0 and delta themselves, so a recorded launch (hipGraph)
   // does not depend on the batch clock; the reference's (delta + t1) - t_ differs by at most ulp(t_)
   const bool own = a.t1 != a.t1;
-  const double t = own ? 0.0 : a.t_base[slot] + a.t_acc;
-  sphere_query<M, T>(x, own, a.t1, t, a.origin, a.radius, &a.delta[e], a.pose ? &a.pose[e * 7] : nullptr);
+  const double dq = own ? 0.0 : te_clock_offset(a.t1, a.t_base[slot], a.t_acc);
+  sphere_query<M, T>(x, own, dq, a.origin, a.radius, &a.delta[e], a.pose ? &a.pose[e * 7] : nullptr);
 }
 
 }  // namespace te

@@ -21,7 +21,7 @@ struct StepParams {
   const unsigned char* has_meas;
   const double* dt_per;
   double dt;
-  double* t_base;
+  TClock* t_base;
   int* nm_base;
   int n_ticks = 1;        // > 1: temporally fused launch (state stays in registers for n_ticks ticks)
   long tick_stride = 0;   // elements between the measurement blocks of consecutive ticks
@@ -64,8 +64,8 @@ struct Ops {
   void (*init)(const InitArgs&, hipStream_t);
   void (*get_state)(char* rec, const int* idx, long n, double* x, double* P, hipStream_t);
   void (*set_state)(char* rec, const int* idx, long n, const double* x, const double* P, const double* uw, hipStream_t);
-  void (*move_record)(char* rec, long src, long dst, double* t_base, int* nm_base, int* cls, hipStream_t);
-  void (*move_records)(char* rec, const int* src_dev, const int* dst_dev, long m, double* t_base, int* nm_base, int* cls, hipStream_t);
+  void (*move_record)(char* rec, long src, long dst, TClock* t_base, int* nm_base, int* cls, hipStream_t);
+  void (*move_records)(char* rec, const int* src_dev, const int* dst_dev, long m, TClock* t_base, int* nm_base, int* cls, hipStream_t);
   void (*outputs)(const OutArgs&, hipStream_t);
   void (*pack_meas)(const double* aos, long n, void* soa, long ld, hipStream_t);
   void (*intersect)(const IntersectArgs&, hipStream_t);

@@ -160,7 +160,7 @@ struct OpsImpl {
     const long th = n * C::N;
     hipLaunchKernelGGL((set_state_kernel<M, T, G, LAYOUT>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, rec, idx, n, x, P, uw);
   }
-  static void move_records(char* rec, const int* src, const int* dst, long m, double* t_base, int* nm_base, int* cls, hipStream_t s) {
+  static void move_records(char* rec, const int* src, const int* dst, long m, TClock* t_base, int* nm_base, int* cls, hipStream_t s) {
     const int th = C::G * C::RW;
     for (long done = 0; done < m; done += 65535) {   // grid.y limit
       const long part = std::min<long>(65535, m - done);
@@ -168,7 +168,7 @@ struct OpsImpl {
                          dst + done, part, t_base, nm_base, cls);
     }
   }
-  static void move_record(char* rec, long src, long dst, double* t_base, int* nm_base, int* cls, hipStream_t s) {
+  static void move_record(char* rec, long src, long dst, TClock* t_base, int* nm_base, int* cls, hipStream_t s) {
     const int th = C::G * C::RW;
     hipLaunchKernelGGL((move_record_kernel<M, T, G, LAYOUT>), dim3((th + 255) / 256), dim3(256), 0, s, rec, src, dst, t_base, nm_base, cls);
   }

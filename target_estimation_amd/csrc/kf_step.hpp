@@ -49,7 +49,7 @@ struct StepArgs {
   const unsigned char* has_meas;  // per entry; null = every entry has a measurement (if meas != null)
   const double* dt_per;      // indexed only, optional per-entry dt
   double dt;
-  double* t_base;            // per-slot time offset       (touched by the indexed path only)
+  TClock* t_base;            // per-slot time offset       (touched by the indexed path only)
   int* nm_base;              // per-slot measurement count (touched when a mask is given or indexed)
   // temporal fusion: n_ticks > 1 runs that many consecutive ticks in ONE launch with the state
   // kept in registers; tick s reads meas + s * tick_stride and has_meas + s * has_stride
@@ -957,7 +957,7 @@ kf_step_kernel(const StepArgs<T> a) {
     if (i == 0) {
       if constexpr (INDEXED) {
         const long slot = slot_of;
-        a.t_base[slot] += dtd * n_ticks;
+        a.t_base[slot] = te_clock_add_ticks(a.t_base[slot], dtd, (double)n_ticks);
         a.nm_base[slot] += n_has;
       } else {
         if (a.has_meas != nullptr) a.nm_base[entry] += n_has;
@@ -986,7 +986,7 @@ kf_step_kernel(const StepArgs<T> a) {
       }
       if constexpr (QUERY) {
         if (valid && i == 0)
-          sphere_query<M, T>(xq, true, 0.0, 0.0, a.q_origin, a.q_radius, &a.q_delta[entry], a.q_pose ? &a.q_pose[entry * 7] : nullptr);
+          sphere_query<M, T>(xq, true, 0.0, a.q_origin, a.q_radius, &a.q_delta[entry], a.q_pose ? &a.q_pose[entry * 7] : nullptr);
       } else {
         if (valid && i == 0) write_outputs_row<M, T>(xq, slot_of, a.o_pose, a.o_twist, a.o_acc);
         signal_done(a.done_flag, a.done_seq, lane, a.done_count, a.n, TPW);

@@ -613,7 +613,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       // straight to memory (configs[4]'s share: 4.9 -> 10.5 us per tick).  The wavefront's 64 rows are one contiguous run of
       // 3584 bytes, so they go through its LDS and leave as seven full 512-byte stores.
       double qd, qp[7];
-      sphere_query_values<M, T>(xq, true, 0.0, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr);
+      sphere_query_values<M, T>(xq, true, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr);
       __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.q_delta[entry]), (unsigned long long)__double_as_longlong(qd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       if (a.q_pose != nullptr) {
 #pragma unroll
@@ -684,11 +684,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #ifdef TE_QUERY_PHASE_CLOCK
       long long ts[8];
       __builtin_amdgcn_sched_barrier(0); ts[0] = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);
-      sphere_query_values<M, T>(xq, true, 0.0, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr, ts);
+      sphere_query_values<M, T>(xq, true, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr, ts);
       // lanes 0..4 of every wavefront report: cycles from the wavefront's first instruction to the head of the query, then the query's phases
       qd = lane == 0 ? (double)(ts[0] - ts_begin) : lane == 1 ? (double)(ts[1] - ts[0]) : lane == 2 ? (double)(ts[2] - ts[1]) : lane == 3 ? (double)(ts[3] - ts[2]) : qd;
 #else
-      sphere_query_values<M, T>(xq, true, 0.0, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr);
+      sphere_query_values<M, T>(xq, true, 0.0, a.q_origin, a.q_radius, qd, qp, a.q_pose != nullptr);
 #endif
       a.q_delta[entry] = qd;
       if (a.q_pose != nullptr) {
@@ -698,7 +698,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
     if constexpr (INDEXED) {
       const long slot = slot_of;
-      a.t_base[slot] += dtd * n_ticks;
+      a.t_base[slot] = te_clock_add_ticks(a.t_base[slot], dtd, (double)n_ticks);
       a.nm_base[slot] += n_has;
     } else {
       if (a.has_meas != nullptr) a.nm_base[entry] += n_has;

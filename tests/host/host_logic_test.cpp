@@ -1,7 +1,8 @@
-// host_logic_test.cpp -- CPU-only checks of the host logic that needs no GPU: the model-file reader
-// and the record layout tables.  Built and run by tests/test_host_logic.py with g++.
+// host_logic_test.cpp -- CPU-only checks of the host logic that needs no GPU: the model-file reader,
+// the record layout tables and the compensated target clock.  Built and run by tests/test_host_logic.py with g++.
 #define __host__
 #define __device__
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <set>
@@ -11,6 +12,7 @@
 #include <random>
 
 #include "../../target_estimation_amd/csrc/id_table.hpp"
+#include "../../target_estimation_amd/csrc/te_clock.hpp"
 #include "../../target_estimation_amd/csrc/te_layout.hpp"
 #include "../../target_estimation_amd/csrc/yaml_mini.hpp"
 
@@ -152,8 +154,73 @@ static void check_qr_rows(const char* name) {
   std::printf("qr rows ok: %s (%d dense words, %d separable)\n", name, qr_words(M::TYPE, false), qr_words(M::TYPE, true));
 }
 
+// exact value of a double in units of 2^-90: every time, dt and error term below lies on that grid (|t| < 2^31 s)
+static __int128 grid(double v) {
+  if (v == 0) return 0;
+  int e = 0;
+  const double f = std::frexp(v, &e);
+  long long m = (long long)std::ldexp(f, 53);   // exact: 53-bit significand
+  int sh = e - 53 + 90;
+  while (sh < 0 && m % 2 == 0) { m /= 2; ++sh; }
+  CHECK(sh >= 0 && sh < 72);
+  if (sh < 0) return 0;
+  return (__int128)m * ((__int128)1 << sh);
+}
+static __int128 grid(TClock c) { return grid(c.hi) + grid(c.lo); }
+static double ulp_of(double v) { return std::nextafter(std::fabs(v), INFINITY) - std::fabs(v); }
+static bool within(__int128 err, double bound) { return (double)(err < 0 ? -err : err) <= std::ldexp(bound, 90); }
+
+// te_clock.hpp: the batch clock and the per-slot offsets stay exact over a day of uptime and 1e5 updates of 4 ms; the time
+// read back is rounded once (half an ulp of the target's own time), the offset of a query at t1 is within an ulp of exact
+static void check_clock() {
+  const double dt = 0.004, day_dt = 8640.0123;
+  TClock a{0.0, 0.0};                                     // batch clock: ten ticks of day_dt, then batch ticks of dt
+  for (int k = 0; k < 10; ++k) a = te_clock_add(a, day_dt);
+  CHECK(grid(a) == 10 * grid(day_dt));
+  const TClock a2 = te_clock_add_ticks(TClock{0.0, 0.0}, day_dt, 10.0);   // the same as one step of 10 ticks
+  CHECK(grid(a2) == grid(a));
+  const double t0s[3] = {0.0, a.hi + a.lo, 1.7e9};
+  for (const double t0 : t0s) {
+    TClock b = te_clock_sub(t0, a), acc = a;             // a target born now at t0
+    CHECK(grid(b) + grid(acc) == grid(t0));
+    CHECK(te_clock_time(b, acc) == t0);
+    double seq = t0;                                      // the reference's clock: t_ = t_ + dt
+    long n = 0;
+    for (long s = 0; s < 100000; ++s) {
+      b = te_clock_add_ticks(b, dt, 1.0);                 // by id (the indexed kernels)
+      seq += dt; ++n;
+      if (s % 1000 == 999) { acc = te_clock_add(acc, dt); seq += dt; ++n; }   // a batch-wide tick
+      CHECK(std::fabs(b.lo) <= ulp_of(b.hi) / 2 && std::fabs(acc.lo) <= ulp_of(acc.hi) / 2);
+    }
+    acc = te_clock_add_ticks(acc, dt, 2500.0);            // a 2500-tick sequence
+    seq += 2500 * dt;  // (the reference's sum differs: only the exact time matters here)
+    n += 2500;
+    const __int128 exact = grid(t0) + n * grid(dt);
+    CHECK(grid(b) + grid(acc) == exact);                  // no rounding error anywhere
+    const double t = te_clock_time(b, acc);
+    CHECK(within(grid(t) - exact, ulp_of(t) / 2));
+    for (const double off : {0.0, 0.1, -2.5, 1e3}) {
+      const double t1 = t + off;
+      const double q = te_clock_offset(t1, b, acc);
+      CHECK(within(grid(q) - (grid(t1) - exact), ulp_of(q) + ulp_of(t1) * 1e-9));
+    }
+    // the single-double clock this replaces: t_base = t0 - clock, t_base += dt per update, time = t_base + clock
+    double tb = t0 - (a.hi + a.lo), ta = a.hi + a.lo;
+    for (long s = 0; s < 100000; ++s) { tb += dt; if (s % 1000 == 999) ta += dt; }
+    ta += dt * 2500;
+    std::printf("clock t0 = %.10g: compensated %.2e s, single doubles %.2e s from exact\n", t0,
+                (double)(grid(t) - exact) / std::ldexp(1.0, 90), (double)(grid(tb + ta) - exact) / std::ldexp(1.0, 90));
+  }
+  const TClock c = te_clock_add_ticks(te_clock_add(TClock{0.0, 0.0}, 1e5), 1.0 / 60.0, 123457.0);
+  CHECK(grid(c) == grid(1e5) + 123457 * grid(1.0 / 60.0));
+  const TClock z = te_clock_sub(-0.75, TClock{-0.75, 0.0});   // cancellation to an exact zero
+  CHECK(z.hi == 0.0 && z.lo == 0.0);
+  std::printf("clock ok\n");
+}
+
 int main(int argc, char** argv) {
   check_id_table();
+  check_clock();
   check_qr_rows<ModelUV>("UV");
   check_qr_rows<ModelUA>("UA");
   check_qr_rows<ModelAV>("AV");
