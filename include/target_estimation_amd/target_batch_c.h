@@ -316,6 +316,42 @@ int target_manager_step_sequence_all(target_manager_c* m, long n_ticks, double d
 /* 1 if target_manager_step_sequence_all currently steps all batches with one launch per tick, 0 if with a launch per
  * batch, -1 on error (semantics served: every target of every model each tick, src/target_manager.cpp:190-225) */
 int target_manager_population_tick(target_manager_c* m);
+/* Per-tick poses from launched ticks.  The reference's node steps every target and then publishes every target's pose, every
+ * tick (src/target_manager.cpp:190-225, src/target_manager_ros.cpp:78-87).  The ..._poses forms of the launched calls below do
+ * both: after tick s of the call the estimated pose of every target at its own time -- getEstimatedPose(), the value
+ * target_batch_get_est_dev returns, bit for bit -- is in the caller's device buffer:
+ *   pose_dev + b * tick_stride,  b = (ring_ticks > 0 ? s % ring_ticks : s),  doubles SoA [7][ld]: row c = component c of
+ *   [x y z qx qy qz qw], column j = slot j (target_batch_slot_ids order; columns >= the batch size are never written).
+ * tick_stride 0: every tick overwrites the one block.  Poses are written for EVERY target on every tick, masked and predict-only
+ * ticks included.  fp32 batches derive the pose in fp32 and store it as double, as target_batch_get_est_dev does.
+ * Who writes them: the kernel that did the step, from the posterior still in registers, for the axis-separable layouts of
+ * one-class batches (the automatic layout of the shipped models) -- single ticks, temporally fused ticks, the fused query, A -> B
+ * ticks, and the one-launch population tick: one launch per tick, as without poses.  TWO launches per tick (the step as without
+ * poses, then a pose-writer launch that reads the records back) for: the dense layouts (coupled Q / R / P0, or an explicit
+ * lanes_per_target outside 201 / 301), batches with several (Q, R) classes, and a target_batch_step_fused_poses of those
+ * layouts (served tick by tick).  target_batch_step_fused_poses is one launch for the whole call except on fp32 angular_rates and
+ * uniform_acceleration batches with packed groups (the automatic fp32 layout of those models), whose temporally fused POSE kernels
+ * would spill: those are served tick by tick, one POSE launch per tick (profiles/r05_pose_kernel_resources.txt).
+ * A NULL `poses` (or per_batch_poses), or a NULL pose_dev, gives the existing call: same results, same kernels.  Bad arguments
+ * (ld < batch size, tick_stride in (0, 7 * ld) or negative, ring_ticks < 0) return a negative code with target_manager_last_error
+ * set, and nothing is launched.  The measurements, masks, rings, use_graph (0 / 1 / 2: a recorded graph is keyed by the pose
+ * stream too), the fused query and the return codes are those of target_batch_step_sequence[_ring], target_batch_step_fused and
+ * target_manager_step_sequence_all; ring_ticks of ..._step_sequence_poses is the measurement ring (0: linear). */
+typedef struct target_pose_stream_c {
+  double* pose_dev;   /* device memory; NULL = no poses for this batch */
+  long ld;            /* >= batch size */
+  long tick_stride;   /* doubles between the blocks of consecutive ticks (>= 7 * ld); 0 = every tick overwrites one block */
+  long ring_ticks;    /* > 0: tick s writes block s % ring_ticks; 0: block s */
+} target_pose_stream_c;
+int target_batch_step_sequence_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, int use_graph);
+int target_batch_step_fused_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
+                                  const unsigned char* has_meas_dev, long has_stride, const target_pose_stream_c* poses);
+/* per_batch_poses[i]: the pose stream of batch i (NULL: none for any batch) */
+int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           long n_batches, int query, const double* origin, double radius, int use_graph);
 /* Resident ("live") mode (target_batch_live_* above) for EVERY batch of a manager at once (BASELINE.json configs[3] / configs[4]: two motion models per GPU, whose per-GPU
  * share is launch-bound): one resident kernel per batch, each on a stream of its own so that they are on the device together;
  * per_batch[i] describes batch i's ring as for target_manager_step_sequence_all (ring_ticks > 0); with query != 0 the own-time

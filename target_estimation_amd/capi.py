@@ -21,6 +21,11 @@ class BatchSequence(C.Structure):
                 ("delta_dev", C.c_void_p), ("pose_dev", C.c_void_p), ("ring_ticks", C.c_long)]
 
 
+class PoseStream(C.Structure):
+    """target_pose_stream_c of target_batch_c.h: the per-tick pose stream of a launched tick"""
+    _fields_ = [("pose_dev", C.c_void_p), ("ld", C.c_long), ("tick_stride", C.c_long), ("ring_ticks", C.c_long)]
+
+
 class StreamSpec(C.Structure):
     """target_stream_c of target_batch_c.h"""
     _fields_ = [("model", C.c_int), ("seed", C.c_ulonglong), ("first_target", C.c_long), ("dt", C.c_double),
@@ -126,6 +131,12 @@ SIGNATURES = {
     "target_manager_population_tick": (C.c_int, [C.c_void_p]),
     "target_manager_step_sequence_all": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_int, c_double_p, C.c_double, C.c_int]),
     "target_batch_step_fused": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long]),
+    "target_batch_step_sequence_poses": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                   C.c_long, C.POINTER(PoseStream), C.c_int]),
+    "target_batch_step_fused_poses": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                C.POINTER(PoseStream)]),
+    "target_manager_step_sequence_all_poses": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream), C.c_long,
+                                                         C.c_int, c_double_p, C.c_double, C.c_int]),
     "target_batch_live_start": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long,
                                           C.c_long, C.c_double]),
     "target_batch_live_set_pose_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -519,8 +519,17 @@ void Batch::drop_graphs() {
   graphs_.clear();
 }
 
+void Batch::check_pose_stream(const PoseStream& q) const {
+  if (!q.dev) return;
+  if (q.ld < n_) throw std::invalid_argument("target_estimation_amd: pose stream: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
+  if (q.tick_stride < 0 || (q.tick_stride > 0 && q.tick_stride < 7 * q.ld))
+    throw std::invalid_argument("target_estimation_amd: pose stream: tick_stride must be 0 or >= 7 * ld");
+  if (q.ring < 0) throw std::invalid_argument("target_estimation_amd: pose stream: negative ring_ticks");
+}
+
 void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                          const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks) {
+                          const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks, const PoseStream& poses) {
+  check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
   const size_t es = elem_size();
@@ -532,6 +541,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     p.has_meas = has_base ? has_base + s * has_stride : nullptr;
     p.dt = dt;
     p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
+    p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
     return p;
   };
   if (!use_graph) {
@@ -548,7 +558,8 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     GraphEntry* hit = nullptr;
     for (auto& g : graphs_)
       if (g.n_ticks == n_ticks && g.tick_stride == tick_stride && g.ld == ld && g.has_stride == has_stride && g.n == n_ &&
-          g.dt == dt && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks) hit = &g;
+          g.dt == dt && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks &&
+          g.poses.dev == poses.dev && g.poses.ld == poses.ld && g.poses.tick_stride == poses.tick_stride && g.poses.ring == poses.ring) hit = &g;
     if (!hit) {
       if (graphs_.size() >= 64) {   // e.g. a ring of 4096 ticks replayed in 64-tick blocks: evict the least recently used one
         size_t victim = 0;
@@ -561,6 +572,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
       }
       if (!cap_stream_) TE_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
       GraphEntry e{n_ticks, tick_stride, ld, has_stride, n_, dt, meas_base, has_base, d_rec_, nullptr, nullptr, ring_ticks};
+      e.poses = poses;
       TE_HIP_CHECK(hipStreamBeginCapture(cap_stream_, hipStreamCaptureModeThreadLocal));
       try {
         for (long s = 0; s < n_ticks; ++s) {
@@ -597,10 +609,12 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
 void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius,
                          bool reverse, bool ab) {
   if (n_ == 0) return;
+  double* pose_block = q.poses.block(s);   // (tick s of the call: the pose stream's own ring)
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   const bool fused_q = ops_->fused_query && n_classes_ == 1;
   StepParams p = base_params();
+  p.pose = pose_block; p.pose_ld = q.poses.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
@@ -627,9 +641,11 @@ bool Batch::population_ready() const {
 }
 
 StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius, bool ab) {
+  double* pose_block = q.poses.block(s);
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   StepParams p = base_params();
+  p.pose = pose_block; p.pose_ld = q.poses.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
@@ -648,12 +664,14 @@ void Batch::account_sequence(long n_ticks, double dt, bool all_measured) {
 }
 
 void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                       const unsigned char* has_base, long has_stride) {
+                       const unsigned char* has_base, long has_stride, const PoseStream& poses) {
+  check_pose_stream(poses);
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
   StepParams p = base_params();
   p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
   p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
+  p.pose = poses.dev; p.pose_ld = poses.ld; p.pose_tick_stride = poses.tick_stride; p.pose_ring = poses.ring;
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
   t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);

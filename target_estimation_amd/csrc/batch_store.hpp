@@ -17,6 +17,17 @@
 
 namespace te {
 
+// A per-tick pose stream (target_pose_stream_c): after tick s of a call, the estimated pose of every slot (getEstimatedPose, as
+// outputs_dev derives it), doubles SoA [7][ld] with column = slot, in block b = (ring > 0 ? s % ring : s) at dev + b * tick_stride
+// (tick_stride 0: every tick overwrites one block).  dev == null: no poses.
+struct PoseStream {
+  double* dev = nullptr;
+  long ld = 0;
+  long tick_stride = 0;
+  long ring = 0;
+  double* block(long s) const { return dev ? dev + (ring > 0 ? s % ring : s) * tick_stride : nullptr; }
+};
+
 class Batch {
  public:
   // `owner_lock`: the mutex of the manager that owns the batch (TargetManager::target_lock_); the C boundary takes it
@@ -69,13 +80,19 @@ class Batch {
   // batch precision) and has_base + s * has_stride: exactly n_ticks launches of the step kernel,
   // enqueued from C++ (use_graph 1: recorded once into a hipGraph and replayed, which removes the
   // per-launch host cost when a recorded stream is replayed; 2: record only, launch nothing).
+  // poses: the per-tick pose stream of the call (PoseStream; by default none), written by the step kernel where the layout has a
+  // POSE variant, by a pose-writer launch behind every tick otherwise (OpsImpl::step)
   void step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                     const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks = 0);
+                     const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks = 0,
+                     const PoseStream& poses = PoseStream{});
   // n_ticks ticks in ONE launch: every target's state stays in registers across the ticks and only
   // the measurements are read per tick.  Same results as n_ticks single ticks; a different
   // ("effective", temporally fused) cost model -- for replaying recorded streams.
   void step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                  const unsigned char* has_base, long has_stride);
+                  const unsigned char* has_base, long has_stride, const PoseStream& poses = PoseStream{});
+  // throws std::invalid_argument unless `poses` is none or a valid stream for this batch (ld >= size, tick_stride 0 or >= 7 ld,
+  // ring >= 0): checked before a call enqueues anything
+  void check_pose_stream(const PoseStream& poses) const;
   // RESIDENT ("live") mode for small batches: ONE launch stays on the device with the batch's state in registers and serves
   // tick after tick as the host posts them -- no per-tick dispatch (a dependent launch costs 1.5-2 us, more than the tick of a
   // 10^4-target batch itself).  Protocol:
@@ -162,6 +179,7 @@ class Batch {
     const unsigned char* has_base; long has_stride;     // optional masks
     double* delta_dev; double* pose_dev;                // query outputs [size] / [size][7] (overwritten every tick)
     long ring_ticks;                                    // > 0: the measurements are a ring, tick s reads entry s % ring_ticks
+    PoseStream poses{};                                 // the per-tick pose stream of the batch (tick s: poses.block(s)), or none
   };
   // tick s of the spec on `st`, without touching the batch clock.  With query: the own-time sphere
   // query of every slot runs inside the step kernel (one launch).
@@ -277,6 +295,7 @@ class Batch {
     hipGraph_t graph;
     long ring_ticks;
     unsigned long last_use = 0;
+    PoseStream poses{};   // (recorded graphs write into the pose buffers they were recorded with)
   };
   std::vector<GraphEntry> graphs_;
   unsigned long graph_clock_ = 0;   // recorded sequences are evicted least-recently-used first (64 kept)

@@ -203,6 +203,10 @@ struct OutArgs {
   // one-target ABI's round trip is a launch and a PCIe write instead of a launch and the runtime's completion path.
   int* done_flag = nullptr;
   int done_seq = 0;
+  // pose_soa (or null): the poses once more, SoA [7][pose_ld] (column = output row) -- one block of a per-tick pose stream,
+  // written by this kernel for the layouts whose step kernel has no pose output of its own (kf_ops_impl.hpp, OpsImpl::step)
+  double* pose_soa = nullptr;
+  long pose_ld = 0;
 };
 constexpr int kOutputsBlock = 128;
 
@@ -300,6 +304,7 @@ __global__ void outputs_kernel(const OutArgs a) {
     derive_outputs<M, T>(x, a.at_time != 0, d, pose7, twist6, acc6);
     const long row = a.by_slot ? slot : e;
     if (a.pose) for (int c = 0; c < 7; ++c) a.pose[row * 7 + c] = (double)pose7[c];
+    if (a.pose_soa) for (int c = 0; c < 7; ++c) a.pose_soa[(long)c * a.pose_ld + row] = (double)pose7[c];
     if (a.twist) for (int c = 0; c < 6; ++c) a.twist[row * 6 + c] = (double)twist6[c];
     if (a.acc) for (int c = 0; c < 6; ++c) a.acc[row * 6 + c] = (double)acc6[c];
   }

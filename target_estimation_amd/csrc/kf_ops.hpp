@@ -52,6 +52,13 @@ struct StepParams {
   int live_flags = 0;
   double* live_pose = nullptr;   // SoA [7][live_pose_ld] per-tick pose output of a live launch, or null
   long live_pose_ld = 0;
+  // per-tick pose stream of a dense launch (StepArgs::pose): tick s of the launch writes SoA [7][pose_ld] doubles at
+  // pose + (pose_ring > 0 ? s % pose_ring : s) * pose_tick_stride; null = none.  Layouts without a POSE kernel get a pose-writer
+  // launch (outputs_kernel, OutArgs::pose_soa) behind every tick instead (OpsImpl::step).
+  double* pose = nullptr;
+  long pose_ld = 0;
+  long pose_tick_stride = 0;
+  long pose_ring = 0;
 };
 
 struct Ops {

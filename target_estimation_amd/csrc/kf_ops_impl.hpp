@@ -26,6 +26,7 @@ inline StepArgs<T> make_step_args(const StepParams& p) {
   a.live_posted = p.live_posted; a.live_mirror = p.live_mirror; a.live_progress = p.live_progress; a.live_done = p.live_done;
   a.live_ring = p.live_ring; a.live_first = p.live_first;
   a.live_spin_limit = p.live_spin_limit; a.live_idle_ticks = p.live_idle_ticks; a.live_flags = p.live_flags; a.live_pose = p.live_pose; a.live_pose_ld = p.live_pose_ld;
+  a.pose = p.pose; a.pose_ld = p.pose_ld; a.pose_tick_stride = p.pose_tick_stride; a.pose_ring = p.pose_ring;
   return a;
 }
 
@@ -53,6 +54,12 @@ struct OpsImpl {
       return 0;
     }
   }
+  // The temporally fused POSE kernels that would cost a wavefront per SIMD or spill (profiles/r05_pose_kernel_resources.txt):
+  // angular_rates fp32 on packed groups (97 registers, 4 waves per SIMD against the twin's 91 / 5; held to 5: 12 B of scratch) and
+  // uniform_acceleration fp32 on packed groups (66 / 7 against 62 / 8; held to 8: 12 B of scratch).  Not instantiated: a fused
+  // request with poses is served tick by tick by the single-tick POSE kernel -- same results, one launch per tick.
+  static constexpr bool kFusedPoseTickByTick = sizeof(T) == 4 && LAYOUT == LAYOUT_SEPARABLE_PACKED &&
+                                               (M::TYPE == ANGULAR_RATES || M::TYPE == UNIFORM_ACCELERATION);
   static void step(const StepParams& p, hipStream_t s) {
     if (p.n <= 0) return;
     StepArgs<T> a = make_step_args<T>(p);
@@ -73,6 +80,40 @@ struct OpsImpl {
     }
     if (p.o_pose && (!p.idx || (p.n > C::TPW && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))
       throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
+    if (p.pose) {
+      // The pose stream.  The separable layouts of one-class batches write it from the step kernel itself (POSE variants); a
+      // temporally fused request is one launch where that variant fits the register file, tick by tick where it does not
+      // (kFusedPoseTickByTick).
+      // Every other layout -- the dense kf_step_kernel ones, several (Q, R) classes -- steps as without poses and then runs one
+      // pose-writer launch per tick (outputs_kernel into the tick's block: the same derive_outputs, the same bits).
+      if (p.idx || p.o_pose) throw std::runtime_error("target_estimation_amd: the pose stream is an output of dense launches");
+      const bool pose_kernel = C::SEP && !p.cls;
+      if (p.n_ticks > 1 && (!pose_kernel || kFusedPoseTickByTick)) {
+        StepParams q = p;
+        q.n_ticks = 1;
+        q.pose_tick_stride = 0;
+        q.pose_ring = 0;
+        for (int t = 0; t < p.n_ticks; ++t) {
+          q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
+          q.has_meas = p.has_meas ? p.has_meas + (long)t * p.has_stride : nullptr;
+          q.pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
+          step(q, s);
+        }
+        return;
+      }
+      if (!pose_kernel) {
+        StepParams q = p;
+        q.pose = nullptr;
+        step(q, s);
+        OutArgs o;
+        o.rec = p.rec_out ? p.rec_out : p.rec;   // (an A -> B tick has written the new records there)
+        o.idx = nullptr; o.n = p.n; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
+        o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = p.t_base;
+        o.pose_soa = p.pose; o.pose_ld = p.pose_ld;
+        outputs(o, s);
+        return;
+      }
+    }
     static const int nt_env = [] { const char* e = std::getenv("TE_NT_MEAS"); return e ? std::atoi(e) : -1; }();
     a.nt_meas = nt_env >= 0 ? nt_env : p.nt_meas;
     if (p.q_delta && (p.idx || p.n_ticks > 1))
@@ -115,6 +156,16 @@ struct OpsImpl {
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true, false, true>), dim3(b4), blk, 0, s, a);
       else if (p.cls)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true>), dim3(b4), blk, 0, s, a);
+      else if (p.pose && p.rec_out)
+        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, true, true>), dim3(b4), blk, 0, s, a);
+      else if (p.pose && p.n_ticks > 1) {
+        if constexpr (!kFusedPoseTickByTick)
+          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
+      }
+      else if (p.pose && p.q_delta)
+        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, true, false, 0, false, true>), dim3(b4), blk, 0, s, a);
+      else if (p.pose)
+        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
       else if (p.rec_out)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, false, true>), dim3(b4), blk, 0, s, a);
       else if (p.n_ticks > 1)

@@ -12,6 +12,8 @@ namespace te {
 // model.  Every present batch: axis-separable layout with packed groups, one (Q, R) class, no slot list, one tick, the same
 // precision `dtype`.  query: the fused own-time sphere query (q_delta set in every present part).  ab: A -> B tick (rec_out set
 // in every present part; not together with the query).  reverse: walk the whole population last to first (zig-zag).
+// A part with StepParams::pose set also writes the tick's poses (one block, pose_ring / pose_tick_stride unused); other parts may
+// have none.
 void launch_population_step(int dtype, const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s);
 
 }  // namespace te

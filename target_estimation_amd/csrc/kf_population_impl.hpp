@@ -6,13 +6,27 @@
 
 namespace te {
 
+// the grid of a population tick, POSE or not (the POSE variants are instantiated in kf_population_f{64,32}_pose.hip: one
+// population translation unit already takes a minute to compile, so the pose stream's three kernels per precision get their own)
+template <typename T, bool POSE>
+void launch_population_grid(const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s) {
+  const dim3 blk(64 * wpb);
+  if (query) hipLaunchKernelGGL((kf_step_population_kernel<T, true, false, POSE>), dim3(blocks), blk, 0, s, p);
+  else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true, POSE>), dim3(blocks), blk, 0, s, p);
+  else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, POSE>), dim3(blocks), blk, 0, s, p);
+}
+void launch_population_grid_pose(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
+void launch_population_grid_pose(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
+
 template <typename T>
 void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s) {
   constexpr int TPW = 64;   // thread per target in every separable layout
   PopulationArgs<T> p;
   long waves_max = 0;
+  bool pose = false;   // some part writes the pose stream (StepParams::pose, one block: a population launch is one tick)
   for (int k = 0; k < 4; ++k) {
     const StepParams& q = parts[k];
+    if (q.n > 0 && q.pose) pose = true;
     if (q.n > 0 && (q.idx || q.cls || q.n_ticks != 1 || q.live_posted || q.o_pose || (query && !q.q_delta) || (ab && !q.rec_out) || (query && ab)))
       throw std::runtime_error("target_estimation_amd: a population launch takes dense single ticks of one-class batches");
     waves_max = std::max(waves_max, (q.n + TPW - 1) / TPW);
@@ -33,10 +47,8 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   }
   if (end == 0) return;
   p.reverse_blocks = reverse ? 1 : 0;
-  const dim3 blk(64 * wpb);
-  if (query) hipLaunchKernelGGL((kf_step_population_kernel<T, true, false>), dim3(end), blk, 0, s, p);
-  else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true>), dim3(end), blk, 0, s, p);
-  else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false>), dim3(end), blk, 0, s, p);
+  if (pose) launch_population_grid_pose(p, end, (unsigned)wpb, query, ab, s);
+  else launch_population_grid<T, false>(p, end, (unsigned)wpb, query, ab, s);
 }
 
 }  // namespace te

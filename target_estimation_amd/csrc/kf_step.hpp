@@ -109,6 +109,14 @@ struct StepArgs {
   // before the tick's progress word, so that a copy engine that reads it after `done` reached the tick sees that tick's poses
   double* live_pose;
   long live_pose_ld;
+  // pose (or null): the per-tick pose stream of a launched tick (POSE variants of the separable kernels): after tick s of the
+  // launch the estimated pose of every target (getEstimatedPose, what outputs_kernel derives) is stored, SoA [7][pose_ld]
+  // doubles, column = entry, in block b = (pose_ring > 0 ? s % pose_ring : s) at pose + b * pose_tick_stride.  Plain stores:
+  // the end of the kernel orders them for a consumer on a stream (unlike live_pose, nothing reads them while it runs).
+  double* pose;
+  long pose_ld;
+  long pose_tick_stride;
+  long pose_ring;
 };
 
 __device__ __forceinline__ long long wave_uniform_ll(long long v) {

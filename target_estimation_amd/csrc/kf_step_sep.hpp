@@ -139,10 +139,15 @@ template <class C, class M, typename T> struct LivePark {
 // and a progress word behind it (1), optionally with the per-tick sphere query and pose output (2: more registers, so fewer
 // resident targets).  Same arithmetic per tick, same results as single ticks.
 // AB: an A -> B tick (StepArgs::rec_out), its own instantiation (see kf_step_kernel).
+// POSE: the per-tick pose stream (StepArgs::pose): after each tick, derive_outputs on the posterior still in registers, the 7
+// components stored as SoA rows -- a wavefront's 64 lanes write 64 consecutive doubles per row, i.e. whole 512-byte lines.  A
+// single tick writes its block behind store_record (most of P is dead by then); FUSED writes tick s's block inside the tick loop.
 // The step of one wavefront's targets: `wg` = index of the wavefront among those of the launch (of the BATCH, in a population
 // launch: kf_step_population_kernel below), lane = its lane.
-template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false>
+template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
+          bool POSE = false>
 __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane) {
+  static_assert(!POSE || (!INDEXED && !PERQR && !LIVE), "the pose stream is an output of dense launches of one-class batches");
   static_assert(!AB || (!INDEXED && !FUSED && !QUERY && !LIVE), "A -> B ticks are dense single-tick launches without the fused query");
   static_assert(!(QUERY && (INDEXED || FUSED)), "the fused query is for dense single-tick launches");
   static_assert(!(PERQR && (FUSED || QUERY)), "per-class Q/R: single-tick launches without the fused query");
@@ -226,6 +231,18 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     if (NPARK > 0 && Park::SLOT.v[w] >= 0) park_lds[Park::SLOT.v[w] * 64 + lane] = v;
     else mem[w] = v;
   };
+  // POSE: tick `tick`'s block of the pose stream from the state words in registers (uniform branch: a population part may have none)
+  auto write_pose = [&](int tick) {
+    if (a.pose == nullptr || !valid) return;
+    T xq[N], pose7[7], twist6[6], acc6[6];
+#pragma unroll
+    for (int r = 0; r < N; ++r) xq[r] = mem[C::X_OFF + r];
+    derive_outputs<M, T>(xq, false, (T)0, pose7, twist6, acc6);
+    double* dst = a.pose + (a.pose_ring > 0 ? (long)tick % a.pose_ring : (long)tick) * a.pose_tick_stride + entry;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) dst[(long)c * a.pose_ld] = (double)pose7[c];
+  };
+  if constexpr (!POSE) (void)write_pose;
   double dtd = a.dt;
   if constexpr (INDEXED) {
     if (a.dt_per && valid) dtd = a.dt_per[entry];
@@ -646,6 +663,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tick's outputs have left before the progress word says so
   }
+  if constexpr (POSE && FUSED) write_pose(tick);
   if constexpr (LIVE) {
     // tick `tick` is done (state in registers): a word in device memory for the relay
     if (lane == 0) {
@@ -676,6 +694,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
     else if constexpr (AB) store_record<C, T, false, true>(a.rec_out + tile * C::TILE_BYTES, lt, mem);   // A -> B tick (StepArgs::rec_out)
     else store_record<C, T>(tb, lt, mem);
+    if constexpr (POSE && !FUSED) write_pose(0);
     if constexpr (QUERY) {
       T xq[N];
 #pragma unroll
@@ -721,9 +740,10 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #undef XS_
 }
 
-template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false>
+template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
+          bool POSE = false>
 __global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, PERQR, LIVE>())) kf_step_sep_kernel(const StepArgs<T> a) {
-  sep_step_wave<M, T, LAYOUT, INDEXED, FUSED, QUERY, PERQR, LIVE, AB>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
+  sep_step_wave<M, T, LAYOUT, INDEXED, FUSED, QUERY, PERQR, LIVE, AB, POSE>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------
@@ -735,6 +755,8 @@ __global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, PERQR, LIVE>
 // reference's enum (target_manager.hpp:38) -- the heaviest model first (measured at configs[4]'s share: light parts first 13.6 -> 15.2 us
 // per tick, the two parts' workgroups alternating 14.9; gpurun_out/r4popgrid).  Each part is exactly kf_step_sep_kernel's arithmetic
 // (sep_step_wave) on its own StepArgs; an absent model has end[k] == end[k - 1].
+// POSE: every part with a non-null StepArgs::pose also writes the tick's poses (sep_step_wave, POSE); a part without one (null)
+// skips that on a wavefront-uniform branch.  The POSE instantiations live in kf_population_f{64,32}_pose.hip.
 template <typename T>
 struct PopulationArgs {
   StepArgs<T> part[4];     // indexed by ModelType
@@ -742,17 +764,17 @@ struct PopulationArgs {
   int reverse_blocks;      // zig-zag over the whole population: walk the workgroups (parts and their tiles) last to first
 };
 
-template <typename T, bool QUERY, bool AB>
+template <typename T, bool QUERY, bool AB, bool POSE = false>
 __global__ void __launch_bounds__(256) kf_step_population_kernel(const PopulationArgs<T> p) {
   const int lane = (int)(threadIdx.x & 63);
   const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
   unsigned b = blockIdx.x;
   if (p.reverse_blocks) b = gridDim.x - 1 - b;
   constexpr int L = LAYOUT_SEPARABLE_PACKED;
-  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB>(p.part[0], (long)b * wpb + wave, lane);
-  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
-  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
-  else sep_step_wave<ModelUV, T, L, false, false, QUERY, false, 0, AB>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
+  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[0], (long)b * wpb + wave, lane);
+  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
+  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
+  else sep_step_wave<ModelUV, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
 }
 
 }  // namespace te

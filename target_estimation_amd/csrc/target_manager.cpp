@@ -1178,11 +1178,23 @@ void TargetManager::enqueuePopulationTick(hipStream_t st, long s, double dt, con
   if (ab_all) for (auto* b : swap) if (b) b->swap_records();
 }
 
+void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
+                                    const double* origin, double radius, int use_graph) {
+  if (n_specs < 0) throw std::invalid_argument("target_estimation_amd: stepSequenceAll: negative number of batches");
+  std::vector<Batch::SeqSpec> with((size_t)n_specs);
+  for (long b = 0; b < n_specs; ++b) {
+    with[(size_t)b] = specs[b];
+    with[(size_t)b].poses = poses ? poses[b] : PoseStream{};
+  }
+  stepSequenceAll(n_ticks, dt, with.data(), n_specs, query, origin, radius, use_graph);
+}
+
 void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
                                     const double* origin, double radius, int use_graph) {
   lock_guard<mutex> lg(target_lock_);
   const size_t nb = batches_.size();
   if ((size_t)n_specs != nb) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
+  for (size_t b = 0; b < nb; ++b) batches_[b]->check_pose_stream(specs[b].poses);   // (before anything is enqueued)
   if (n_ticks <= 0 || nb == 0) return;
   if (query && !origin) throw std::runtime_error("target_estimation_amd: stepSequenceAll: query without an origin");
   for (size_t b = 0; b < nb; ++b) {
@@ -1218,7 +1230,8 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
   } else {
     auto same_spec = [](const Batch::SeqSpec& x, const Batch::SeqSpec& y) {
       return x.meas_base == y.meas_base && x.tick_stride == y.tick_stride && x.ld == y.ld && x.has_base == y.has_base &&
-             x.has_stride == y.has_stride && x.delta_dev == y.delta_dev && x.pose_dev == y.pose_dev && x.ring_ticks == y.ring_ticks;
+             x.has_stride == y.has_stride && x.delta_dev == y.delta_dev && x.pose_dev == y.pose_dev && x.ring_ticks == y.ring_ticks &&
+             x.poses.dev == y.poses.dev && x.poses.ld == y.poses.ld && x.poses.tick_stride == y.poses.tick_stride && x.poses.ring == y.poses.ring;
     };
     auto same_id = [](const Batch::DevIdentity& x, const Batch::DevIdentity& y) {
       return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n;

@@ -149,6 +149,11 @@ class TargetManager {
   bool populationTickNow() { std::lock_guard<std::mutex> lg(target_lock_); return populationTick(); }
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
                        const double* origin, double radius, int use_graph);
+  // The same with a per-tick pose stream per batch (poses[b], PoseStream; one with a null dev writes nothing for that batch):
+  // written by the step kernels -- the population kernel's POSE variant where the tick is one launch -- or by a pose-writer
+  // launch behind each tick of a batch whose layout has no POSE kernel.  Every stream is checked before anything is enqueued.
+  void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
+                       const double* origin, double radius, int use_graph);
 
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and

@@ -70,6 +70,12 @@ inline te::MeasurementIngest* I(target_ingest_c* i) {
   if (!i) throw std::invalid_argument("NULL ingest handle");
   return (te::MeasurementIngest*)i;
 }
+// the pose stream of a ..._poses call (target_pose_stream_c; NULL or a NULL pose_dev: none)
+te::PoseStream pose_stream(const target_pose_stream_c* p) {
+  te::PoseStream q;
+  if (p && p->pose_dev) { q.dev = p->pose_dev; q.ld = p->ld; q.tick_stride = p->tick_stride; q.ring = p->ring_ticks; }
+  return q;
+}
 }  // namespace
 
 extern "C" {
@@ -419,6 +425,39 @@ int target_batch_step_fused(target_batch_c* b, long n_ticks, double dt, const vo
                             const unsigned char* has_meas_dev, long has_stride) {
   return guarded("target_batch_step_fused", [&] { BatchLock lk(B(b));
     B(b)->step_fused(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride);
+  });
+}
+
+// ---- per-tick pose streams of launched ticks
+int target_batch_step_sequence_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, int use_graph) {
+  return guarded("target_batch_step_sequence_poses", [&] { BatchLock lk(B(b));
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses));
+  });
+}
+
+int target_batch_step_fused_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
+                                  const unsigned char* has_meas_dev, long has_stride, const target_pose_stream_c* poses) {
+  return guarded("target_batch_step_fused_poses", [&] { BatchLock lk(B(b));
+    B(b)->step_fused(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, pose_stream(poses));
+  });
+}
+
+int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           long n_batches, int query, const double* origin, double radius, int use_graph) {
+  return guarded("target_manager_step_sequence_all_poses", [&] {
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+    }
+    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph);
   });
 }
 

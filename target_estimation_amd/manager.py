@@ -40,6 +40,23 @@ def _check(rc, what):
     return rc
 
 
+def _pose_stream(poses, size, n_ticks):
+    """A float64 CUDA tensor [blocks, 7, ld] (or [7, ld]: one block every tick overwrites) -> capi.PoseStream.  ld and
+    tick_stride come from its strides; fewer blocks than ticks make it a ring (tick s writes block s % blocks)."""
+    import torch
+    assert poses.is_cuda and poses.dtype == torch.float64, "poses: a float64 CUDA tensor"
+    if poses.dim() == 2:
+        poses = poses.unsqueeze(0)
+    assert poses.dim() == 3 and poses.shape[1] == 7 and poses.stride(2) == 1, "poses: [ticks_or_ring, 7, ld] with unit stride along the slots"
+    if poses.shape[2] < size:
+        raise RuntimeError("pose stream: %d columns for a batch of %d targets" % (poses.shape[2], size))
+    ps = capi.PoseStream()
+    ps.pose_dev, ps.ld = poses.data_ptr(), poses.stride(1)
+    ps.tick_stride = poses.stride(0) if poses.shape[0] > 1 else 0
+    ps.ring_ticks = poses.shape[0] if poses.shape[0] < n_ticks else 0
+    return ps
+
+
 class Batch:
     """All targets of one (model, Q, R) of a manager: the device-resident dense path."""
 
@@ -97,15 +114,24 @@ class Batch:
             hp = h.data_ptr()
         _check(self._lib.target_batch_step_host(self._h, float(dt), t.data_ptr(), t.stride(0), hp), "target_batch_step_host")
 
-    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None):
+    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None):
         """meas: CUDA tensor [ticks, 7, ld]: one launch per tick, all enqueued by one C call.  n_ticks > ticks
-        treats meas (and has_meas) as a ring: tick s reads entry s % ticks."""
+        treats meas (and has_meas) as a ring: tick s reads entry s % ticks.  poses: float64 CUDA tensor
+        [ticks_or_ring, 7, ld] (or [7, ld]) that receives every target's pose after every tick (column = slot;
+        target_batch_step_sequence_poses); fewer blocks than ticks make it a ring."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if poses is not None:
+            ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
+            ps = _pose_stream(poses, self.size, ticks)
+            _check(self._lib.target_batch_step_sequence_poses(self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1),
+                                                               hp, hs, meas.shape[0] if ticks != meas.shape[0] else 0, C.byref(ps),
+                                                               int(use_graph)), "target_batch_step_sequence_poses")
+            return
         if n_ticks is None or n_ticks == meas.shape[0]:
             _check(self._lib.target_batch_step_sequence(self._h, meas.shape[0], float(dt), meas.data_ptr(), meas.stride(0),
                                                          meas.stride(1), hp, hs, int(use_graph)),
@@ -115,14 +141,20 @@ class Batch:
                                                               meas.stride(1), hp, hs, meas.shape[0], int(use_graph)),
                    "target_batch_step_sequence_ring")
 
-    def step_fused(self, dt, meas, has_meas=None):
-        """meas: CUDA tensor [ticks, 7, ld]: all ticks in ONE launch (state stays in registers)."""
+    def step_fused(self, dt, meas, has_meas=None, poses=None):
+        """meas: CUDA tensor [ticks, 7, ld]: all ticks in ONE launch (state stays in registers).  poses: as for
+        step_sequence (target_batch_step_fused_poses)."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if poses is not None:
+            ps = _pose_stream(poses, self.size, meas.shape[0])
+            _check(self._lib.target_batch_step_fused_poses(self._h, meas.shape[0], float(dt), meas.data_ptr(), meas.stride(0),
+                                                            meas.stride(1), hp, hs, C.byref(ps)), "target_batch_step_fused_poses")
+            return
         _check(self._lib.target_batch_step_fused(self._h, meas.shape[0], float(dt), meas.data_ptr(), meas.stride(0),
                                                   meas.stride(1), hp, hs), "target_batch_step_fused")
 
@@ -502,12 +534,14 @@ class TargetManager:
             "target_manager_intersect_sphere_converged_batch")
         return conv.astype(bool), pose, delta, filt
 
-    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None):
+    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None):
         """meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order): `ticks` ticks of every batch -- ONE launch per
         tick for all of them where population_tick() holds, otherwise a launch per batch (recorded: one graph branch per
         batch) -- replayed from a recorded hipGraph (use_graph) or eagerly.  query =
         (origin[3], radius, deltas, poses) adds the own-time sphere query of every target after every step;
-        deltas[i] [size] and poses[i] [size, 7] (or None) are CUDA double tensors, overwritten every tick."""
+        deltas[i] [size] and poses[i] [size, 7] (or None) are CUDA double tensors, overwritten every tick.
+        poses: one pose stream per batch (a tensor as for Batch.step_sequence, or None for a batch without one): every
+        target's pose after every tick (target_manager_step_sequence_all_poses)."""
         nb = len(meas)          # the library checks it against the number of batches
         ring = meas[0].shape[0] if nb else 0
         ticks = ring if n_ticks is None else int(n_ticks)      # n_ticks > ring: the tensors are rings (tick s reads s % ring)
@@ -522,11 +556,22 @@ class TargetManager:
                 specs[i].has_meas_dev, specs[i].has_stride = h.data_ptr(), h.stride(0)
         origin, radius = None, 0.0
         if query is not None:
-            origin, radius, deltas, poses = query
+            origin, radius, deltas, qposes = query
             origin = _d(origin, (3,))
             for i in range(nb):
                 specs[i].delta_dev = deltas[i].data_ptr()
-                specs[i].pose_dev = None if poses is None or poses[i] is None else poses[i].data_ptr()
+                specs[i].pose_dev = None if qposes is None or qposes[i] is None else qposes[i].data_ptr()
+        if poses is not None:
+            assert len(poses) == nb, "one pose stream (or None) per batch"
+            bs = self.batches()
+            pss = (capi.PoseStream * max(nb, 1))()
+            for i, p in enumerate(poses):
+                if p is not None:
+                    pss[i] = _pose_stream(p, bs[i].size if i < len(bs) else 0, ticks)
+            _check(self._lib.target_manager_step_sequence_all_poses(
+                self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, nb, 0 if query is None else 1,
+                None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all_poses")
+            return
         _check(self._lib.target_manager_step_sequence_all(
             self._h, ticks, float(dt), C.cast(specs, C.c_void_p), nb, 0 if query is None else 1,
             None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all")
