@@ -415,6 +415,49 @@ int target_stream_fill_dev(const target_stream_c* spec, long n_targets, long fir
  * truth_dev [n][12]: p, v, a, omega of the generating motion.  Either may be NULL.  Device doubles. */
 int target_stream_truth_dev(const target_stream_c* spec, long n_targets, double* pose0_dev, double* truth_dev, void* hip_stream);
 
+/* ---- one manager over several devices ------------------------------------ */
+/* target_manager_set_devices: give the manager n shards, shard k on HIP device devices[k] (repeats allowed: {0,0,0} is three
+ * shards on device 0).  Call it after target_manager_new[_ex] and before the first target is created.  Every shard is a
+ * complete manager on its device; the handle reaches all of them and every manager-level call above and below keeps its
+ * signature and meaning (the ten reference symbols, init / update / erase / getters by id, the intersection calls and the
+ * solver object, ingest, target_manager_population_tick, target_manager_step_sequence_all[_poses], synchronize).
+ * Placement: a single creation goes to the shard with the fewest targets of its model (ties: lowest index); a batched
+ * creation is cut into contiguous runs, in the caller's order, that fill the shards towards equal per-model counts; an
+ * erased id created again is placed by the rule as it stands then.  n == 1 on the creation device: an unsharded manager.
+ * Returns -1 (target_manager_last_error set, manager unchanged) if the manager already holds targets, n < 1, a device
+ * index is out of range, or a stream was set with target_manager_set_stream (a stream belongs to one device: set the shards'
+ * streams with target_manager_set_shard_stream).  target_manager_log decides its selection once for the whole manager (an
+ * explicit list, or every target while the MANAGER holds at most 64) and writes the files an unsharded manager writes.  Where the shards span distinct devices, peer access between them is enabled here.
+ * target_manager_num_batches / target_manager_get_batch enumerate the batches of every shard, shard-major, and the
+ * per-batch specs of target_manager_step_sequence_all[_poses] follow that order: each spec's device pointers live on that
+ * batch's device (target_manager_batch_shard, target_manager_shard_device).  Host-array calls split their ids by shard
+ * and return the results in the caller's order; target_manager_get_available_targets stays ascending across shards.
+ * REFUSED on a manager with more than one shard (-1 / NULL and a message, nothing launched): resident mode
+ * (target_manager_live_*_all), the RCCL gather (target_manager_gather_pose_*), target_manager_set_stream (use
+ * target_manager_set_shard_stream) and target_manager_get_batch_of_type (a model has one batch per shard, none of which holds
+ * all its targets: use target_manager_get_batch with target_manager_batch_shard).  By default every shard launches on its
+ * device's default stream. */
+int target_manager_set_devices(target_manager_c* m, const int* devices, int n);
+/* 1 for an unsharded manager */
+int target_manager_num_shards(target_manager_c* m);
+/* HIP device of shard k, -1 if there is no such shard */
+int target_manager_shard_device(target_manager_c* m, int k);
+/* shard that holds id, -1 for an unknown id */
+int target_manager_shard_of(target_manager_c* m, unsigned int id);
+/* shard of batch i (target_manager_get_batch order), -1 if there is no such batch */
+int target_manager_batch_shard(target_manager_c* m, int index);
+/* the stream (hipStream_t on shard k's device; NULL = that device's default stream) of shard k's launches */
+int target_manager_set_shard_stream(target_manager_c* m, int k, void* hip_stream);
+/* pose7 of every target in ascending id order -- the order of target_manager_get_available_targets -- into pose_out
+ * [size][7] doubles: what the reference's node publishes every tick (src/target_manager_ros.cpp:78-87), for the whole
+ * manager, without an id list.  pose_out is pinned host memory (hipHostMalloc or registered) or device memory that every
+ * shard's device can reach.  One launch per batch (each target's pose by the getters' arithmetic, stored at its row);
+ * asynchronous: the rows are complete when target_manager_synchronize returns.  The first call after a change of membership
+ * (init, erase) rebuilds the per-batch row maps on the host, O(size log size), and uploads them stream-ordered through pinned
+ * staging; it waits on the host only where a map has to grow (for the work still queued on that batch's stream).  pose_out == NULL only counts.  Works on
+ * unsharded managers too.  Returns the number of rows (size), or -1 (capacity < size). */
+long target_manager_get_est_all_by_id(target_manager_c* m, double* pose_out, long capacity);
+
 /* ---- multi-GPU: gather of the estimated poses to one rank over xGMI (RCCL) ---------------------------- */
 /* One process per GPU, every rank owns a shard of the targets (no collective in the predict/update path).  What the
  * reference's node does with the filtered poses every tick is publish them (src/target_manager_ros.cpp:78-87); across

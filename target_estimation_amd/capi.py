@@ -129,6 +129,14 @@ SIGNATURES = {
     "target_batch_step_sequence": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_int]),
     "target_batch_step_sequence_ring": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int]),
     "target_manager_population_tick": (C.c_int, [C.c_void_p]),
+    # one manager over several devices
+    "target_manager_set_devices": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "target_manager_num_shards": (C.c_int, [C.c_void_p]),
+    "target_manager_shard_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "target_manager_shard_of": (C.c_int, [C.c_void_p, C.c_uint]),
+    "target_manager_batch_shard": (C.c_int, [C.c_void_p, C.c_int]),
+    "target_manager_set_shard_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "target_manager_get_est_all_by_id": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
     "target_manager_step_sequence_all": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_int, c_double_p, C.c_double, C.c_int]),
     "target_batch_step_fused": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long]),
     "target_batch_step_sequence_poses": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,

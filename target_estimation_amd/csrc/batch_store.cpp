@@ -1136,6 +1136,16 @@ void Batch::outputs_dev(double* pose_dev, double* twist_dev, double* acc_dev, bo
   TE_HIP_CHECK(hipGetLastError());
 }
 
+void Batch::outputs_rows_dev(double* pose_dev, const int* row_of_slot_dev) {
+  flush();
+  if (n_ == 0) return;
+  OutArgs a;
+  a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = nullptr; a.acc = nullptr;
+  a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_; a.row_of_slot = row_of_slot_dev;
+  ops_->outputs_rows(a, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+}
+
 void Batch::outputs_one(long slot, double* pose, double* twist, double* acc, bool at_time, double t1) {
   flush();
   const int one = (int)slot;

@@ -149,6 +149,8 @@ class Batch {
   void outputs(const int* slots, long n, double* pose, double* twist, double* acc, bool at_time, double t1);
   // Dense, to device arrays [size()][7] / [size()][6] / [size()][6] (doubles).
   void outputs_dev(double* pose_dev, double* twist_dev, double* acc_dev, bool at_time, double t1);
+  // pose7 of every slot into row row_of_slot_dev[slot] of pose_dev (outputs_rows_kernel; rows < 0 are skipped)
+  void outputs_rows_dev(double* pose_dev, const int* row_of_slot_dev);
   void outputs_one(long slot, double* pose, double* twist, double* acc, bool at_time, double t1);
   // AoS doubles [n][7] on device -> SoA [7][ld] in the batch precision on device
   void pack_meas_dev(const double* aos_dev, long n, void* soa_dev, long ld);

@@ -207,6 +207,8 @@ struct OutArgs {
   // written by this kernel for the layouts whose step kernel has no pose output of its own (kf_ops_impl.hpp, OpsImpl::step)
   double* pose_soa = nullptr;
   long pose_ld = 0;
+  // outputs_rows_kernel only (outputs_kernel never reads it): the destination row of every slot, -1 = none
+  const int* row_of_slot = nullptr;
 };
 constexpr int kOutputsBlock = 128;
 
@@ -312,6 +314,42 @@ __global__ void outputs_kernel(const OutArgs a) {
     __threadfence_system();       // this thread's rows are visible to the host ...
     __syncthreads();              // ... for every thread of the workgroup ...
     if (threadIdx.x == 0) __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // ... before the flag is
+  }
+}
+
+// getEstimatedPose() of every slot 0..n-1 (derive_outputs, as outputs_kernel) into row a.row_of_slot[slot] of a.pose [rows][7]:
+// the ascending-id rows of a whole manager (target_manager_get_est_all_by_id).  A workgroup's rows are staged in LDS and leave
+// as one sweep over its 7 * kOutputsBlock doubles, consecutive threads on consecutive doubles of a row, so that a run of
+// consecutive ranks is stored as whole 128-byte lines.  A slot whose row is negative stores nothing.
+template <class M, typename T, int G, int LAYOUT>
+__global__ __launch_bounds__(kOutputsBlock) void outputs_rows_kernel(const OutArgs a) {
+  using C = Cfg<M, T, G, LAYOUT>;
+  constexpr int N = C::N;
+  __shared__ double s_pose[kOutputsBlock * 7];
+  __shared__ int s_row[kOutputsBlock];
+  const long e0 = (long)blockIdx.x * kOutputsBlock;
+  const long e = e0 + threadIdx.x;
+  int row = -1;
+  if (e < a.n) {
+    row = a.row_of_slot[e];
+    if (row >= 0) {
+      T x[N];
+#pragma unroll
+      for (int r = 0; r < N; ++r) x[r] = state_get<C, T>(a.rec, e, r, N);
+      T pose7[7], twist6[6], acc6[6];
+      derive_outputs<M, T>(x, false, (T)0, pose7, twist6, acc6);
+#pragma unroll
+      for (int c = 0; c < 7; ++c) s_pose[threadIdx.x * 7 + c] = (double)pose7[c];
+    }
+  }
+  s_row[threadIdx.x] = row;
+  __syncthreads();
+  const long left = a.n - e0;
+  const int cnt = left < kOutputsBlock ? (int)left : kOutputsBlock;
+  for (int i = threadIdx.x; i < cnt * 7; i += kOutputsBlock) {
+    const int r = i / 7, c = i - r * 7;
+    const int dst = s_row[r];
+    if (dst >= 0) a.pose[(long)dst * 7 + c] = s_pose[i];
   }
 }
 

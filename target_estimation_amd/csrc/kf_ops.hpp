@@ -76,6 +76,7 @@ struct Ops {
   void (*outputs)(const OutArgs&, hipStream_t);
   void (*pack_meas)(const double* aos, long n, void* soa, long ld, hipStream_t);
   void (*intersect)(const IntersectArgs&, hipStream_t);
+  void (*outputs_rows)(const OutArgs&, hipStream_t);   // outputs_rows_kernel: poses at OutArgs::row_of_slot
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported

@@ -227,6 +227,10 @@ struct OpsImpl {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((outputs_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
   }
+  static void outputs_rows(const OutArgs& a, hipStream_t s) {
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL((outputs_rows_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
+  }
   static void pack_meas(const double* aos, long n, void* soa, long ld, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL((pack_meas_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, aos, n, static_cast<T*>(soa), ld);
@@ -238,7 +242,7 @@ struct OpsImpl {
   static const Ops* get() {
     static const Ops ops = {
         LayoutInfo{C::N, C::K, G, LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD},
-        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect};
+        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows};
     return &ops;
   }
 };

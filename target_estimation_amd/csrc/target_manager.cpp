@@ -27,6 +27,7 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) : dtype_(dtype), l
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
     throw std::runtime_error("target_estimation_amd: no HIP device available; this library has no CPU path");
+  TE_HIP_CHECK(hipGetDevice(&home_dev_));
 }
 
 TargetManager::TargetManager(const std::string& file, int dtype, int lanes_per_target)
@@ -120,6 +121,14 @@ bool TargetManager::resolveOnDevice(const unsigned* ids, long n, ResolveCounters
 }
 
 TargetManager::~TargetManager() {
+  for (size_t k = 0; k < shards_.size(); ++k) {
+    try { DeviceGuard g(shard_dev_[k]); shards_[k].reset(); } catch (...) { shards_[k].reset(); }
+  }
+  for (auto& r : rank_maps_) {
+    device_free(r.dev);
+    if (r.host) (void)hipHostFree(r.host);
+    if (r.copied) (void)hipEventDestroy(r.copied);
+  }
   closeLogFiles();
   devIdsFree();
   dropSeqGraphs();
@@ -306,19 +315,15 @@ void TargetManager::setLogTargets(const unsigned* ids, long n) {
 
 void TargetManager::setKeepMeasurement(bool on) {
   lock_guard<mutex> lg(target_lock_);
+  for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(shard_dev_[k]); shards_[k]->setKeepMeasurement(on); }
   keep_meas_ = on;
   for (auto& b : batches_) b->set_keep_measurement(on);
   dropSeqGraphs();
 }
 
-void TargetManager::log() {
-  if (log_dir_.empty()) return;
-  lock_guard<mutex> lg(target_lock_);
-  // what to log: the explicit selection, or everything while the population is small
-  std::vector<unsigned> ids = log_ids_;
-  const bool per_target = !ids.empty() || (long)targets_.size() <= kLogAutoSelect;
-  if (ids.empty()) ids = targets_.sorted_ids();
-  // group the ids by batch (slot lists), keep the id order inside a batch
+// The rows of the selected ids that this manager holds, grouped by batch (batch order), in the order of `ids` inside a batch;
+// LogRow::batch = the batch index.  Caller holds target_lock_.
+void TargetManager::logCollect(const std::vector<unsigned>& ids, std::vector<LogRow>& rows) {
   std::vector<std::vector<int>> slots(batches_.size());
   std::vector<std::vector<unsigned>> who(batches_.size());
   for (unsigned id : ids) {
@@ -327,7 +332,6 @@ void TargetManager::log() {
     slots[(size_t)loc.batch].push_back(loc.slot);
     who[(size_t)loc.batch].push_back(id);
   }
-  std::string all[7];
   for (size_t bi = 0; bi < batches_.size(); ++bi) {
     Batch& b = *batches_[bi];
     const long n = (long)slots[bi].size();
@@ -339,7 +343,9 @@ void TargetManager::log() {
     if (b.keep_measurement()) b.measured_poses(slots[bi].data(), n, meas.data());
     else for (long s = 0; s < n; ++s) for (int c = 0; c < 7; ++c) meas[(size_t)s * 7 + c] = c == 6 ? 1.0 : 0.0;
     for (long s = 0; s < n; ++s) {
-      const unsigned id = who[bi][(size_t)s];
+      LogRow r;
+      r.id = who[bi][(size_t)s];
+      r.batch = (int)bi;
       const double t = b.time(slots[bi][(size_t)s]);
       double R[9], pose6[6];
       host_quat_to_rot(&pose[(size_t)s * 7 + 3], R);
@@ -348,42 +354,88 @@ void TargetManager::log() {
       const double* row[7] = {&t, &meas[(size_t)s * 7], &pose[(size_t)s * 7], &twist[(size_t)s * 6], pose6, &acc[(size_t)s * 6],
                               &P[(size_t)s * N * N]};
       const long width[7] = {1, 7, 7, 6, 6, 6, (long)N * N};
-      if (per_target) {
-        LogFiles& lf = log_files_[id];
-        for (int ch = 0; ch < 7; ++ch) {
-          if (!lf.f[ch]) {
-            lf.f[ch] = std::fopen((log_dir_ + "/" + kLogChannel[ch] + "_" + std::to_string(id)).c_str(), "a");
-            if (!lf.f[ch]) { std::cerr << "Unable to open file : [" << log_dir_ << "/" << kLogChannel[ch] << "_" << id << "]" << std::endl; continue; }
-          }
-          std::string line;
-          append_row(line, row[ch], width[ch]);
-          std::fwrite(line.data(), 1, line.size(), lf.f[ch]);   // one buffered write per channel per call ...
-        }
-      } else {
-        const double idd = (double)id;
-        for (int ch = 0; ch < 7; ++ch) {
-          char buf[24];
-          std::snprintf(buf, sizeof buf, "%g ", idd);
-          all[ch] += buf;
-          append_row(all[ch], row[ch], width[ch]);
-        }
-      }
-    }
-  }
-  if (per_target) {
-    for (auto& kv : log_files_)
-      for (std::FILE* f : kv.second.f) if (f) std::fflush(f);   // ... made visible to readers at the end of the call
-  } else {
-    for (int ch = 0; ch < 7; ++ch) {
-      if (!log_all_[ch]) log_all_[ch] = std::fopen((log_dir_ + "/" + kLogChannel[ch] + "_all").c_str(), "a");
-      if (!log_all_[ch]) continue;
-      std::fwrite(all[ch].data(), 1, all[ch].size(), log_all_[ch]);
-      std::fflush(log_all_[ch]);
+      for (int ch = 0; ch < 7; ++ch) append_row(r.ch[ch], row[ch], width[ch]);
+      rows.push_back(std::move(r));
     }
   }
 }
 
+// rows into this manager's files: per target (one file per channel and id, kept open) or one <channel>_all file per channel with
+// the id in front of every row.  Caller holds target_lock_.
+void TargetManager::logWrite(const std::vector<LogRow>& rows, bool per_target) {
+  if (per_target) {
+    for (const LogRow& r : rows) {
+      LogFiles& lf = log_files_[r.id];
+      for (int ch = 0; ch < 7; ++ch) {
+        if (!lf.f[ch]) {
+          lf.f[ch] = std::fopen((log_dir_ + "/" + kLogChannel[ch] + "_" + std::to_string(r.id)).c_str(), "a");
+          if (!lf.f[ch]) { std::cerr << "Unable to open file : [" << log_dir_ << "/" << kLogChannel[ch] << "_" << r.id << "]" << std::endl; continue; }
+        }
+        std::fwrite(r.ch[ch].data(), 1, r.ch[ch].size(), lf.f[ch]);   // one buffered write per channel per call ...
+      }
+    }
+    for (auto& kv : log_files_)
+      for (std::FILE* f : kv.second.f) if (f) std::fflush(f);   // ... made visible to readers at the end of the call
+    return;
+  }
+  std::string all[7];
+  for (const LogRow& r : rows) {
+    char buf[24];
+    std::snprintf(buf, sizeof buf, "%g ", (double)r.id);
+    for (int ch = 0; ch < 7; ++ch) { all[ch] += buf; all[ch] += r.ch[ch]; }
+  }
+  for (int ch = 0; ch < 7; ++ch) {
+    if (!log_all_[ch]) log_all_[ch] = std::fopen((log_dir_ + "/" + kLogChannel[ch] + "_all").c_str(), "a");
+    if (!log_all_[ch]) continue;
+    std::fwrite(all[ch].data(), 1, all[ch].size(), log_all_[ch]);
+    std::fflush(log_all_[ch]);
+  }
+}
+
+void TargetManager::log() {
+  if (log_dir_.empty()) return;
+  lock_guard<mutex> lg(target_lock_);
+  // what to log: the explicit selection, or everything while the population is small -- decided once, for the whole manager
+  std::vector<unsigned> ids = log_ids_;
+  const size_t total = sharded() ? shard_map_.size() : targets_.size();
+  const bool per_target = !ids.empty() || (long)total <= kLogAutoSelect;
+  std::vector<LogRow> rows;
+  if (!sharded()) {
+    if (ids.empty()) ids = targets_.sorted_ids();
+    logCollect(ids, rows);
+    logWrite(rows, per_target);
+    return;
+  }
+  // Sharded: every shard reads the rows of its selected targets on its device; this manager writes them all, in the order an
+  // unsharded manager would (batches of one (model, layout) are one group, in order of first creation; ids ascending inside).
+  if (ids.empty()) {
+    std::vector<std::vector<unsigned>> lists;
+    for (auto& s : shards_) { lock_guard<mutex> sl(s->target_lock_); lists.push_back(s->targets_.sorted_ids()); }
+    ids = merge_sorted_ids(lists);
+  }
+  std::vector<std::vector<unsigned>> per(shards_.size());
+  for (unsigned id : ids) {
+    const int k = shard_map_.shard_of(id);
+    if (k >= 0) per[(size_t)k].push_back(id);
+  }
+  for (size_t k = 0; k < shards_.size(); ++k) {
+    if (per[k].empty()) continue;
+    DeviceGuard g(shard_dev_[k]);
+    lock_guard<mutex> sl(shards_[k]->target_lock_);
+    const size_t first = rows.size();
+    shards_[k]->logCollect(per[k], rows);
+    for (size_t i = first; i < rows.size(); ++i) {   // a shard's batch index -> the manager-wide (model, layout) group
+      const Batch& b = *shards_[k]->batches_[(size_t)rows[i].batch];
+      const auto key = std::make_pair(b.type(), b.lanes_code());
+      rows[i].batch = (int)(std::find(batch_keys_.begin(), batch_keys_.end(), key) - batch_keys_.begin());
+    }
+  }
+  std::stable_sort(rows.begin(), rows.end(), [](const LogRow& a, const LogRow& b) { return a.batch != b.batch ? a.batch < b.batch : a.id < b.id; });
+  logWrite(rows, per_target);
+}
+
 bool TargetManager::getTargetMeasuredPose(unsigned id, double* pose7) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetMeasuredPose(id, pose7); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc) || !batches_[(size_t)loc.batch]->keep_measurement()) return false;
@@ -414,6 +466,7 @@ bool TargetManager::getTargetTransform(unsigned id, double* T) {
 }
 
 bool TargetManager::getTargetDims(unsigned id, int& n, int& m) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetDims(id, n, m); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -423,6 +476,7 @@ bool TargetManager::getTargetDims(unsigned id, int& n, int& m) {
 }
 
 bool TargetManager::getTargetModelMatrices(unsigned id, double* Q, double* R, double* P0) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetModelMatrices(id, Q, R, P0); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -435,17 +489,24 @@ bool TargetManager::getTargetModelMatrices(unsigned id, double* Q, double* R, do
 std::vector<unsigned> TargetManager::getAvailableTargets() {
   std::vector<unsigned> ids;
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {   // each shard's list is ascending: merged, the whole list is
+    std::vector<std::vector<unsigned>> lists;
+    for (auto& s : shards_) lists.push_back(s->getAvailableTargets());
+    return merge_sorted_ids(lists);
+  }
   ids = targets_.sorted_ids();   // ascending, as the reference's std::map iteration
   return ids;
 }
 
 size_t TargetManager::size() {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) return shard_map_.size();
   return targets_.size();
 }
 
 bool TargetManager::hasTarget(unsigned id) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) return shard_map_.contains(id);
   return targets_.contains(id);
 }
 
@@ -460,12 +521,21 @@ void TargetManager::init(target_t type, unsigned id, double dt0, double t0, cons
                          const double* P0, const double* p0, const double* v0, const double* a0) {
   (void)dt0;  // only shapes the constructor's A, which every step rebuilds (uniform_velocity.cpp:40,67)
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {   // an existing id goes to its shard (which says so); a new one to the placement rule's shard
+    const int known = shard_map_.shard_of(id);
+    const int k = known >= 0 ? known : shard_map_.place_one((int)type);
+    DeviceGuard g(shard_dev_[(size_t)k]);
+    shards_[(size_t)k]->init(type, id, dt0, t0, Q, R, P0, p0, v0, a0);
+    if (known < 0) { shard_map_.insert(id, k, (int)type); ranks_dirty_ = true; noteBatchKeys(); }
+    return;
+  }
   if (!targets_.contains(id)) {
     int cls = 0;
     const int b = findOrCreateBatch((int)type, Q, R, chooseLayout((int)type, Q, R, P0, 1), cls);
     const long slot = batches_[(size_t)b]->append(1, &id, t0, P0, false, p0, v0 ? v0 : kZero6, a0 ? a0 : kZero6, cls);
     targets_.set(id, Loc{b, (int)slot});
     dev_ids_.dirty = true;
+    ranks_dirty_ = true;
     if (verbose_) {
       switch (type) {
         case ANGULAR_RATES: std::cout << "Using angular rates for the orientation" << std::endl; break;
@@ -496,6 +566,7 @@ long TargetManager::initBatch(target_t type, const unsigned* ids, long n, double
                               const double* R, const double* P0, bool per_target_P0, const double* p0,
                               const double* v0, const double* a0) {
   (void)dt0;
+  if (sharded()) return initBatchSharded(type, ids, n, dt0, t0, Q, R, P0, per_target_P0, p0, v0, a0, 0, nullptr);
   lock_guard<mutex> lg(target_lock_);
   const int N = model_n((int)type);
   // keep only ids that do not exist yet (existing ones are left untouched, as in init())
@@ -540,6 +611,7 @@ long TargetManager::initBatch(target_t type, const unsigned* ids, long n, double
   targets_.reserve(targets_.size() + (size_t)k);
   for (long j = 0; j < k; ++j) targets_.set(ids[keep[(size_t)j]], Loc{b, (int)(first + j)});
   dev_ids_.dirty = true;
+  ranks_dirty_ = true;
   return k;
 }
 
@@ -547,6 +619,11 @@ long TargetManager::initBatchClasses(target_t type, const unsigned* ids, long n,
                                      const double* Q, const double* R, const double* P0, const unsigned* class_of,
                                      const double* p0, const double* v0, const double* a0) {
   (void)dt0;
+  if (sharded()) {
+    if (n <= 0) return 0;
+    if (n_classes <= 0) throw std::invalid_argument("target_estimation_amd: initBatchClasses needs at least one class");
+    return initBatchSharded(type, ids, n, dt0, t0, Q, R, P0, false, p0, v0, a0, n_classes, class_of);
+  }
   lock_guard<mutex> lg(target_lock_);
   if (n <= 0) return 0;
   if (n_classes <= 0) throw std::invalid_argument("target_estimation_amd: initBatchClasses needs at least one class");
@@ -597,10 +674,12 @@ long TargetManager::initBatchClasses(target_t type, const unsigned* ids, long n,
     created += k;
   }
   dev_ids_.dirty = true;
+  ranks_dirty_ = true;
   return created;
 }
 
 bool TargetManager::update(unsigned id, double dt, const double* meas) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.update(id, dt, meas); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) {
@@ -612,6 +691,7 @@ bool TargetManager::update(unsigned id, double dt, const double* meas) {
 }
 
 bool TargetManager::update(unsigned id, double dt) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.update(id, dt); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) {
@@ -624,11 +704,19 @@ bool TargetManager::update(unsigned id, double dt) {
 
 void TargetManager::update(double dt) {
   lock_guard<mutex> lg(target_lock_);
+  for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(shard_dev_[k]); shards_[k]->update(dt); }
   for (auto& b : batches_) b->step_dense(dt, nullptr, 0, nullptr);
 }
 
 bool TargetManager::erase(unsigned id) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {
+    const int k = shard_map_.shard_of(id);
+    DeviceGuard g(shard_dev_[k < 0 ? 0 : (size_t)k]);
+    const bool ok = shards_[k < 0 ? 0 : (size_t)k]->erase(id);   // (an unknown id: shard 0 says so)
+    if (ok) { shard_map_.erase(id); ranks_dirty_ = true; closeLogFilesOf(id); }
+    return ok;
+  }
   Loc loc;
   if (!find(id, loc)) {
     std::cout << "Target(" << id << ") does not exist!" << std::endl;
@@ -639,6 +727,7 @@ bool TargetManager::erase(unsigned id) {
   const unsigned moved = b->erase_slot(loc.slot);
   targets_.erase(id);
   dev_ids_.dirty = true;
+  ranks_dirty_ = true;
   if (!was_last) targets_.set(moved, Loc{loc.batch, loc.slot});
   auto lf = log_files_.find(id);   // a logged target that goes away closes its files (a later target of that id appends)
   if (lf != log_files_.end()) {
@@ -650,6 +739,29 @@ bool TargetManager::erase(unsigned id) {
 
 long TargetManager::eraseBatch(const unsigned* ids, long n) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {
+    std::vector<std::vector<unsigned>> per(shards_.size());
+    long erased = 0;
+    for (long i = 0; i < n; ++i) {
+      const int k = shard_map_.shard_of(ids[i]);
+      if (k < 0) {   // unknown, or already taken by an earlier entry of this call
+        std::cout << "Target(" << ids[i] << ") does not exist!" << std::endl;
+        continue;
+      }
+      per[(size_t)k].push_back(ids[i]);
+      shard_map_.erase(ids[i]);
+      closeLogFilesOf(ids[i]);
+      ++erased;
+    }
+    ranks_dirty_ = true;
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      if (per[k].empty()) continue;
+      DeviceGuard g(shard_dev_[k]);
+      shards_[k]->eraseBatch(per[k].data(), (long)per[k].size());
+    }
+    return erased;
+  }
+  ranks_dirty_ = true;
   std::vector<std::vector<int>> slots(batches_.size());
   std::vector<unsigned> erased;
   for (long i = 0; i < n; ++i) {
@@ -680,6 +792,7 @@ long TargetManager::eraseBatch(const unsigned* ids, long n) {
 }
 
 bool TargetManager::getTargetPose(unsigned id, double* pose7) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetPose(id, pose7); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -688,6 +801,7 @@ bool TargetManager::getTargetPose(unsigned id, double* pose7) {
 }
 
 bool TargetManager::getTargetTwist(unsigned id, double* twist6) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetTwist(id, twist6); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -696,6 +810,7 @@ bool TargetManager::getTargetTwist(unsigned id, double* twist6) {
 }
 
 bool TargetManager::getTargetAcceleration(unsigned id, double* acc6) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetAcceleration(id, acc6); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -704,6 +819,7 @@ bool TargetManager::getTargetAcceleration(unsigned id, double* acc6) {
 }
 
 bool TargetManager::getTargetPoseAt(unsigned id, double t1, double* pose7) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetPoseAt(id, t1, pose7); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -712,6 +828,7 @@ bool TargetManager::getTargetPoseAt(unsigned id, double t1, double* pose7) {
 }
 
 bool TargetManager::getTargetTwistAt(unsigned id, double t1, double* twist6) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetTwistAt(id, t1, twist6); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -720,6 +837,7 @@ bool TargetManager::getTargetTwistAt(unsigned id, double t1, double* twist6) {
 }
 
 bool TargetManager::getTargetAccelerationAt(unsigned id, double t1, double* a6) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetAccelerationAt(id, t1, a6); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -728,6 +846,7 @@ bool TargetManager::getTargetAccelerationAt(unsigned id, double t1, double* a6) 
 }
 
 bool TargetManager::getTargetTime(unsigned id, double& t) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetTime(id, t); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return false;
@@ -736,6 +855,7 @@ bool TargetManager::getTargetTime(unsigned id, double& t) {
 }
 
 int TargetManager::getTargetState(unsigned id, double* x, double* P) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getTargetState(id, x, P); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return 0;
@@ -745,6 +865,7 @@ int TargetManager::getTargetState(unsigned id, double* x, double* P) {
 }
 
 long long TargetManager::getNumberMeasurements(unsigned id) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getNumberMeasurements(id); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (find(id, loc)) return batches_[(size_t)loc.batch]->n_measurements(loc.slot);
@@ -769,6 +890,18 @@ bool TargetManager::smallBatchPath(const unsigned* ids, long n) const {
 
 long TargetManager::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {   // each shard's ids in the caller's order (a repeated id stays two steps in a row)
+    const Split sp = splitIds(ids, n);
+    if (verbose_) for (long i : sp.unknown) std::cout << "Target(" << ids[i] << ") does not exist!" << std::endl;
+    long done = 0;
+    forShards(sp, ids, [&](TargetManager& sh, const std::vector<unsigned>& ids2, const std::vector<long>& src) {
+      std::vector<double> m2 = gatherRows(meas, src, 7);
+      std::vector<unsigned char> h2;
+      if (has_meas) for (long i : src) h2.push_back(has_meas[i]);
+      done += sh.updateBatch(ids2.data(), (long)ids2.size(), dt, meas ? m2.data() : nullptr, has_meas ? h2.data() : nullptr);
+    });
+    return done;
+  }
   const size_t nb = batches_.size();
   if (smallBatchPath(ids, n)) {
     long done = 0;
@@ -879,6 +1012,23 @@ long TargetManager::updateBatch(const unsigned* ids, long n, double dt, const do
 long TargetManager::getPoseBatch(const unsigned* ids, long n, double* pose, double* twist, double* acc,
                                  unsigned char* found, bool at_time, double t1) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {
+    const Split sp = splitIds(ids, n);
+    if (found) for (long i : sp.unknown) found[i] = 0;
+    long done = 0;
+    forShards(sp, ids, [&](TargetManager& sh, const std::vector<unsigned>& ids2, const std::vector<long>& src) {
+      const long m = (long)ids2.size();
+      std::vector<double> p2(pose ? (size_t)m * 7 : 0), t2(twist ? (size_t)m * 6 : 0), a2(acc ? (size_t)m * 6 : 0);
+      std::vector<unsigned char> f2((size_t)m);
+      done += sh.getPoseBatch(ids2.data(), m, pose ? p2.data() : nullptr, twist ? t2.data() : nullptr, acc ? a2.data() : nullptr, f2.data(),
+                              at_time, t1);
+      scatterRows(found, f2, src, 1);
+      scatterRows(pose, p2, src, 7);
+      scatterRows(twist, t2, src, 6);
+      scatterRows(acc, a2, src, 6);
+    });
+    return done;
+  }
   const size_t nb = batches_.size();
   if (!at_time && smallBatchPath(ids, n)) {   // rows from the host-resident getter table (filled by the flush's own launch)
     long done = 0;
@@ -976,6 +1126,33 @@ long TargetManager::getPoseBatch(const unsigned* ids, long n, double* pose, doub
 long TargetManager::getStateBatch(const unsigned* ids, long n, double* x, double* P) {
   lock_guard<mutex> lg(target_lock_);
   if (n <= 0) return 0;
+  if (sharded()) {
+    const Split sp = splitIds(ids, n);
+    if (!sp.unknown.empty()) return -1;
+    // one batch as an unsharded manager requires: every id of one (model, layout), so one state size
+    long ns = -1;
+    int key_type = -1, key_lanes = -1;
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      lock_guard<mutex> sl(shards_[k]->target_lock_);
+      for (long i : sp.src[k]) {
+        Loc loc;
+        shards_[k]->find(ids[i], loc);
+        const Batch& b = *shards_[k]->batches_[(size_t)loc.batch];
+        if (key_type < 0) { key_type = b.type(); key_lanes = b.lanes_code(); ns = b.n_state(); }
+        if (b.type() != key_type || b.lanes_code() != key_lanes) return -2;
+      }
+    }
+    long rc = ns;
+    forShards(sp, ids, [&](TargetManager& sh, const std::vector<unsigned>& ids2, const std::vector<long>& src) {
+      const long m = (long)ids2.size();
+      std::vector<double> x2(x ? (size_t)(m * ns) : 0), P2(P ? (size_t)(m * ns * ns) : 0);
+      const long r = sh.getStateBatch(ids2.data(), m, x ? x2.data() : nullptr, P ? P2.data() : nullptr);
+      if (r < 0) { rc = r; return; }
+      scatterRows(x, x2, src, ns);
+      scatterRows(P, P2, src, ns * ns);
+    });
+    return rc;
+  }
   std::vector<int> slots((size_t)n);
   int b0 = -1;
   for (long i = 0; i < n; ++i) {
@@ -990,6 +1167,7 @@ long TargetManager::getStateBatch(const unsigned* ids, long n, double* x, double
 }
 
 double TargetManager::getIntersectionTimeWithSphere(unsigned id, double t1, const double* origin, double radius) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getIntersectionTimeWithSphere(id, t1, origin, radius); });
   lock_guard<mutex> lg(target_lock_);
   Loc loc;
   if (!find(id, loc)) return -1;
@@ -1000,6 +1178,7 @@ double TargetManager::getIntersectionTimeWithSphere(unsigned id, double t1, cons
 
 bool TargetManager::getIntersectionPoseWithSphere(unsigned id, double t1, const double* origin, double radius,
                                                   double* pose7, double* delta) {
+  if (sharded()) return routeId(id, [&](TargetManager& s) { return s.getIntersectionPoseWithSphere(id, t1, origin, radius, pose7, delta); });
   lock_guard<mutex> lg(target_lock_);
   pose7[0] = pose7[1] = pose7[2] = pose7[3] = pose7[4] = pose7[5] = 0.0;
   pose7[6] = 1.0;  // initPose, intersection_solver.cpp:99
@@ -1024,6 +1203,30 @@ long TargetManager::intersectGatedBatch(const unsigned* ids, long n, double t1, 
                                         const double* origin, double radius, double* delta, double* pose,
                                         unsigned char* converged, unsigned char* found, double* filt) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {
+    const Split sp = splitIds(ids, n);
+    for (long i : sp.unknown) {   // what the unsharded path reports for an unknown id
+      if (found) found[i] = 0;
+      if (delta) delta[i] = -1;
+      if (converged) converged[i] = 0;
+      if (pose) { for (int c = 0; c < 6; ++c) pose[i * 7 + c] = 0.0; pose[i * 7 + 6] = 1.0; }
+      if (filt) { filt[i * 2] = 0.0; filt[i * 2 + 1] = 0.0; }
+    }
+    long done = 0;
+    forShards(sp, ids, [&](TargetManager& sh, const std::vector<unsigned>& ids2, const std::vector<long>& src) {
+      const long m = (long)ids2.size();
+      std::vector<double> d2((size_t)m), p2((size_t)m * 7), f2((size_t)m * 2);
+      std::vector<unsigned char> c2((size_t)m), fd2((size_t)m);
+      sh.setIntersectionFiltersLength(filters_length_);
+      done += sh.intersectGatedBatch(ids2.data(), m, t1, pos_th, ang_th, origin, radius, d2.data(), p2.data(), c2.data(), fd2.data(), f2.data());
+      scatterRows(found, fd2, src, 1);
+      scatterRows(delta, d2, src, 1);
+      scatterRows(converged, c2, src, 1);
+      scatterRows(pose, p2, src, 7);
+      scatterRows(filt, f2, src, 2);
+    });
+    return done;
+  }
   const size_t nb = batches_.size();
   std::vector<std::vector<int>> slots(nb);
   std::vector<std::vector<long>> src(nb);
@@ -1062,6 +1265,25 @@ long TargetManager::intersectGatedBatch(const unsigned* ids, long n, double t1, 
 long TargetManager::intersectBatch(const unsigned* ids, long n, double t1, const double* origin, double radius,
                                    double* delta, double* pose, unsigned char* found) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {
+    const Split sp = splitIds(ids, n);
+    for (long i : sp.unknown) {
+      if (found) found[i] = 0;
+      delta[i] = -1;
+      if (pose) { for (int c = 0; c < 6; ++c) pose[i * 7 + c] = 0.0; pose[i * 7 + 6] = 1.0; }
+    }
+    long done = 0;
+    forShards(sp, ids, [&](TargetManager& sh, const std::vector<unsigned>& ids2, const std::vector<long>& src) {
+      const long m = (long)ids2.size();
+      std::vector<double> d2((size_t)m), p2(pose ? (size_t)m * 7 : 0);
+      std::vector<unsigned char> fd2((size_t)m);
+      done += sh.intersectBatch(ids2.data(), m, t1, origin, radius, d2.data(), pose ? p2.data() : nullptr, fd2.data());
+      scatterRows(found, fd2, src, 1);
+      scatterRows(delta, d2, src, 1);
+      scatterRows(pose, p2, src, 7);
+    });
+    return done;
+  }
   const size_t nb = batches_.size();
   std::vector<std::vector<int>> slots(nb);
   std::vector<std::vector<long>> src(nb);
@@ -1092,12 +1314,15 @@ long TargetManager::intersectBatch(const unsigned* ids, long n, double t1, const
 }
 
 Batch* TargetManager::batchOfType(int type) {
+  // with several shards a model has one batch per shard, none of which holds all its targets: refused
+  if (sharded()) return onlyShard("target_manager_get_batch_of_type (use target_manager_get_batch / target_manager_batch_shard)").batchOfType(type);
   for (auto& b : batches_)
     if (b->type() == type) return b.get();
   return nullptr;
 }
 
 long TargetManager::posesToDevice(double* out_dev, long capacity, hipStream_t st) {
+  if (sharded()) { TargetManager& s = onlyShard("posesToDevice"); DeviceGuard g(shard_dev_[0]); return s.posesToDevice(out_dev, capacity, st); }
   lock_guard<mutex> lg(target_lock_);
   long rows = 0;
   for (auto& b : batches_) rows += b->size();
@@ -1114,6 +1339,7 @@ long TargetManager::posesToDevice(double* out_dev, long capacity, hipStream_t st
 }
 
 long TargetManager::posesForGather(long expect_rows, const std::function<double*(long, hipStream_t)>& prepare) {
+  if (sharded()) { TargetManager& s = onlyShard("the RCCL gather"); DeviceGuard g(shard_dev_[0]); return s.posesForGather(expect_rows, prepare); }
   lock_guard<mutex> lg(target_lock_);   // count, stream and the outputs launches in ONE critical section
   long rows = 0;
   for (auto& b : batches_) rows += b->size();
@@ -1130,6 +1356,7 @@ long TargetManager::posesForGather(long expect_rows, const std::function<double*
 }
 
 void TargetManager::setStream(hipStream_t s) {
+  if (sharded()) { TargetManager& one = onlyShard("target_manager_set_stream (use target_manager_set_shard_stream)"); DeviceGuard g(shard_dev_[0]); one.setStream(s); return; }
   lock_guard<mutex> lg(target_lock_);
   for (auto& b : batches_) { b->synchronize(); b->set_stream(s); }
   stream_ = s;
@@ -1146,6 +1373,15 @@ void TargetManager::dropSeqGraphs() {
 bool TargetManager::populationTick() const {
   static const bool on = [] { const char* e = std::getenv("TE_POPULATION_TICK"); return !(e && e[0] == '0'); }();
   if (!on) return false;
+  if (sharded()) {   // every shard that holds targets ticks them in one launch
+    bool any = false;
+    for (const auto& s : shards_) {
+      if (s->targets_.size() == 0) continue;
+      if (!s->populationTick()) return false;
+      any = true;
+    }
+    return any;
+  }
   int present = 0;
   bool seen[4] = {false, false, false, false};
   for (const auto& b : batches_) {
@@ -1192,6 +1428,25 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
 void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
                                     const double* origin, double radius, int use_graph) {
   lock_guard<mutex> lg(target_lock_);
+  if (sharded()) {   // specs shard-major (numBatches order); each shard takes its slice; every check before any launch
+    if (n_specs != (long)numBatches()) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
+    long off = 0;
+    for (auto& s : shards_)
+      for (auto& b : s->batches_) {
+        b->check_pose_stream(specs[off].poses);
+        if (n_ticks > 0 && query && b->size() > 0 && (!origin || !specs[off].delta_dev))
+          throw std::runtime_error("target_estimation_amd: stepSequenceAll: query without an origin or a delta output");
+        ++off;
+      }
+    off = 0;
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      const long nk = (long)shards_[k]->batches_.size();
+      DeviceGuard g(shard_dev_[k]);
+      shards_[k]->stepSequenceAll(n_ticks, dt, specs + off, nk, query, origin, radius, use_graph);
+      off += nk;
+    }
+    return;
+  }
   const size_t nb = batches_.size();
   if ((size_t)n_specs != nb) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
   for (size_t b = 0; b < nb; ++b) batches_[b]->check_pose_stream(specs[b].poses);   // (before anything is enqueued)
@@ -1318,6 +1573,12 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
 
 void TargetManager::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s,
                                  bool query, const double* origin, double radius) {
+  if (sharded()) {
+    TargetManager& s = onlyShard("resident mode (target_manager_live_*_all)");
+    DeviceGuard g(shard_dev_[0]);
+    s.liveStartAll(dt, specs, n_specs, first_entry, max_ticks, idle_limit_s, query, origin, radius);
+    return;
+  }
   lock_guard<mutex> lg(target_lock_);
   const size_t nb = batches_.size();
   if ((size_t)n_specs != nb || nb == 0) throw std::runtime_error("target_estimation_amd: liveStartAll needs one spec per batch");
@@ -1355,6 +1616,7 @@ void TargetManager::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_
 }
 
 void TargetManager::livePostAll(long n_ticks, bool one_doorbell_per_tick) {
+  if (sharded()) { TargetManager& s = onlyShard("resident mode (target_manager_live_*_all)"); DeviceGuard g(shard_dev_[0]); s.livePostAll(n_ticks, one_doorbell_per_tick); return; }
   lock_guard<mutex> lg(target_lock_);
   if (one_doorbell_per_tick) {
     for (long i = 0; i < n_ticks; ++i)
@@ -1365,6 +1627,7 @@ void TargetManager::livePostAll(long n_ticks, bool one_doorbell_per_tick) {
 }
 
 long TargetManager::liveDoneAll() {
+  if (sharded()) { TargetManager& s = onlyShard("resident mode (target_manager_live_*_all)"); DeviceGuard g(shard_dev_[0]); return s.liveDoneAll(); }
   lock_guard<mutex> lg(target_lock_);
   long mn = -1;
   for (auto& b : batches_) {
@@ -1376,6 +1639,7 @@ long TargetManager::liveDoneAll() {
 }
 
 bool TargetManager::liveWaitAll(long tick, double timeout_s) {
+  if (sharded()) { TargetManager& s = onlyShard("resident mode (target_manager_live_*_all)"); DeviceGuard g(shard_dev_[0]); return s.liveWaitAll(tick, timeout_s); }
   std::vector<Batch*> open;   // the list under the lock, the spinning without it (posts come from other threads)
   {
     lock_guard<mutex> lg(target_lock_);
@@ -1387,6 +1651,7 @@ bool TargetManager::liveWaitAll(long tick, double timeout_s) {
 }
 
 long TargetManager::liveStopAll() {
+  if (sharded()) { TargetManager& s = onlyShard("resident mode (target_manager_live_*_all)"); DeviceGuard g(shard_dev_[0]); return s.liveStopAll(); }
   lock_guard<mutex> lg(target_lock_);
   long served = -1;
   std::string err;
@@ -1406,7 +1671,268 @@ long TargetManager::liveStopAll() {
 
 void TargetManager::synchronize() {
   lock_guard<mutex> lg(target_lock_);
+  for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(shard_dev_[k]); shards_[k]->synchronize(); }
   for (auto& b : batches_) b->synchronize();
+}
+
+// ---------------------------------------------------------------- several devices
+DeviceGuard::DeviceGuard(int d) : dev(d) {
+  TE_HIP_CHECK(hipGetDevice(&prev));
+  if (prev != dev) TE_HIP_CHECK(hipSetDevice(dev));
+}
+DeviceGuard::~DeviceGuard() {
+  if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+}
+
+int TargetManager::numBatches() const {
+  if (!sharded()) return (int)batches_.size();
+  int n = 0;
+  for (const auto& s : shards_) n += (int)s->batches_.size();
+  return n;
+}
+
+Batch* TargetManager::batch(int i) {
+  if (!sharded()) return batches_[(size_t)i].get();
+  for (auto& s : shards_) {
+    if (i < (int)s->batches_.size()) return s->batches_[(size_t)i].get();
+    i -= (int)s->batches_.size();
+  }
+  return nullptr;
+}
+
+int TargetManager::batchShard(int i) const {
+  if (i < 0 || i >= numBatches()) return -1;
+  if (!sharded()) return 0;
+  for (size_t k = 0; k < shards_.size(); ++k) {
+    if (i < (int)shards_[k]->batches_.size()) return (int)k;
+    i -= (int)shards_[k]->batches_.size();
+  }
+  return -1;
+}
+
+int TargetManager::shardDevice(int k) const {
+  if (k < 0 || k >= numShards()) return -1;
+  return sharded() ? shard_dev_[(size_t)k] : home_dev_;
+}
+
+int TargetManager::shardOf(unsigned id) {
+  lock_guard<mutex> lg(target_lock_);
+  if (sharded()) return shard_map_.shard_of(id);
+  return targets_.contains(id) ? 0 : -1;
+}
+
+void TargetManager::copySettingsTo(TargetManager& s) const {
+  s.default_Q_ = default_Q_; s.default_R_ = default_R_; s.default_P_ = default_P_;
+  s.default_type_ = default_type_; s.default_values_loaded_ = default_values_loaded_;
+  s.verbose_ = verbose_; s.filters_length_ = filters_length_;
+  s.keep_meas_ = keep_meas_;
+  s.log_dir_.clear();   // the manager writes the logs of every shard itself (log())
+}
+
+void TargetManager::setDevices(const int* devices, int n) {
+  lock_guard<mutex> lg(target_lock_);
+  if (targets_.size() > 0 || shard_map_.size() > 0)
+    throw std::runtime_error("target_estimation_amd: set_devices: the manager already holds targets (call it before the first init)");
+  if (n < 1) throw std::invalid_argument("target_estimation_amd: set_devices: at least one device is needed");
+  if (!devices) throw std::invalid_argument("target_estimation_amd: set_devices: NULL device list");
+  if (stream_ != nullptr)   // a stream belongs to one device: the shards would silently fall back to their default streams
+    throw std::runtime_error("target_estimation_amd: set_devices after set_stream: set each shard's stream with set_shard_stream instead");
+  int count = 0;
+  TE_HIP_CHECK(hipGetDeviceCount(&count));
+  for (int k = 0; k < n; ++k)
+    if (devices[k] < 0 || devices[k] >= count)
+      throw std::invalid_argument("target_estimation_amd: set_devices: device index " + std::to_string(devices[k]) + " out of range (" +
+                                  std::to_string(count) + " devices)");
+  std::vector<std::unique_ptr<TargetManager>> fresh;
+  if (!(n == 1 && devices[0] == home_dev_)) {   // one shard on the creation device: the manager itself
+    for (int k = 0; k < n; ++k) {
+      DeviceGuard g(devices[k]);
+      fresh.emplace_back(new TargetManager(dtype_, lanes_));
+      copySettingsTo(*fresh.back());
+    }
+    // Peer access between distinct devices, so that one pose_out reaches every shard (getEstAllById).  Not yet run across
+    // devices: the machines this was built on have one GPU.
+    for (int a = 0; a < n; ++a)
+      for (int b = 0; b < n; ++b) {
+        if (devices[a] == devices[b]) continue;
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, devices[a], devices[b]) != hipSuccess || !can) continue;
+        DeviceGuard g(devices[a]);
+        const hipError_t e = hipDeviceEnablePeerAccess(devices[b], 0);
+        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) TE_HIP_CHECK(e);
+        (void)hipGetLastError();
+      }
+  }
+  for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(shard_dev_[k]); shards_[k].reset(); }
+  shards_ = std::move(fresh);
+  shard_dev_.assign(devices, devices + (shards_.empty() ? 0 : n));
+  shard_map_.reset(shards_.empty() ? 0 : n);
+  ranks_dirty_ = true;
+}
+
+void TargetManager::setShardStream(int k, hipStream_t s) {
+  if (k < 0 || k >= numShards()) throw std::invalid_argument("target_estimation_amd: set_shard_stream: no shard " + std::to_string(k));
+  if (!sharded()) { setStream(s); return; }
+  lock_guard<mutex> lg(target_lock_);
+  DeviceGuard g(shard_dev_[(size_t)k]);
+  shards_[(size_t)k]->setStream(s);
+}
+
+TargetManager& TargetManager::onlyShard(const char* what) {
+  if (shards_.size() != 1)
+    throw std::runtime_error(std::string("target_estimation_amd: ") + what + " is refused on a manager with more than one shard");
+  return *shards_[0];
+}
+
+TargetManager::Split TargetManager::splitIds(const unsigned* ids, long n) const {
+  Split sp;
+  sp.src.resize(shards_.size());
+  for (long i = 0; i < n; ++i) {
+    const int k = shard_map_.shard_of(ids[i]);
+    if (k < 0) sp.unknown.push_back(i);
+    else sp.src[(size_t)k].push_back(i);
+  }
+  return sp;
+}
+
+// A batched creation on a sharded manager: new ids only (in the caller's order), cut into one contiguous run per shard by the
+// placement rule, each run created by the shard's own initBatch / initBatchClasses.
+long TargetManager::initBatchSharded(target_t type, const unsigned* ids, long n, double dt0, double t0, const double* Q, const double* R,
+                                     const double* P0, bool per_target_P0, const double* p0, const double* v0, const double* a0,
+                                     long n_classes, const unsigned* class_of) {
+  lock_guard<mutex> lg(target_lock_);
+  const int N = model_n((int)type);
+  if (class_of)
+    for (long i = 0; i < n; ++i)
+      if (class_of[i] >= (unsigned long)n_classes) throw std::invalid_argument("target_estimation_amd: class index out of range");
+  std::vector<long> keep;
+  keep.reserve((size_t)(n > 0 ? n : 0));
+  {
+    IdTable seen;
+    seen.reserve((size_t)(n > 0 ? n : 0));
+    for (long i = 0; i < n; ++i) {
+      if (shard_map_.contains(ids[i]) || seen.contains(ids[i])) {
+        if (verbose_) std::cout << "Target(" << ids[i] << ") already exists!" << std::endl;
+        continue;
+      }
+      seen.set(ids[i], Loc{0, 0});
+      keep.push_back(i);
+    }
+  }
+  if (keep.empty()) return 0;
+  const long k = (long)keep.size();
+  const std::vector<long> amount = shard_map_.place_amounts((int)type, k);
+  long created = 0, at = 0;
+  for (size_t s = 0; s < shards_.size(); ++s) {
+    const long m = amount[s];
+    if (!m) continue;
+    std::vector<unsigned> ids2((size_t)m), cls2(class_of ? (size_t)m : 0);
+    std::vector<double> p2((size_t)m * 7), v2(v0 ? (size_t)m * 6 : 0), a2(a0 ? (size_t)m * 6 : 0), P2(per_target_P0 ? (size_t)(m * N * N) : 0);
+    for (long j = 0; j < m; ++j) {
+      const long i = keep[(size_t)(at + j)];
+      ids2[(size_t)j] = ids[i];
+      std::memcpy(&p2[(size_t)j * 7], p0 + i * 7, sizeof(double) * 7);
+      if (v0) std::memcpy(&v2[(size_t)j * 6], v0 + i * 6, sizeof(double) * 6);
+      if (a0) std::memcpy(&a2[(size_t)j * 6], a0 + i * 6, sizeof(double) * 6);
+      if (per_target_P0) std::memcpy(&P2[(size_t)(j * N * N)], P0 + i * N * N, sizeof(double) * (size_t)(N * N));
+      if (class_of) cls2[(size_t)j] = class_of[i];
+    }
+    at += m;
+    long got;
+    {
+      DeviceGuard g(shard_dev_[s]);
+      if (class_of)
+        got = shards_[s]->initBatchClasses(type, ids2.data(), m, dt0, t0, n_classes, Q, R, P0, cls2.data(), p2.data(), v0 ? v2.data() : nullptr,
+                                           a0 ? a2.data() : nullptr);
+      else
+        got = shards_[s]->initBatch(type, ids2.data(), m, dt0, t0, Q, R, per_target_P0 ? P2.data() : P0, per_target_P0, p2.data(),
+                                    v0 ? v2.data() : nullptr, a0 ? a2.data() : nullptr);
+    }
+    for (long j = 0; j < m; ++j) shard_map_.insert(ids2[(size_t)j], (int)s, (int)type);
+    created += got;
+  }
+  ranks_dirty_ = true;
+  noteBatchKeys();
+  return created;
+}
+
+void TargetManager::noteBatchKeys() {
+  for (auto& sh : shards_)
+    for (auto& b : sh->batches_) {
+      const auto key = std::make_pair(b->type(), b->lanes_code());
+      if (std::find(batch_keys_.begin(), batch_keys_.end(), key) == batch_keys_.end()) batch_keys_.push_back(key);
+    }
+}
+
+void TargetManager::closeLogFilesOf(unsigned id) {
+  auto lf = log_files_.find(id);   // a logged target that goes away closes its files (a later target of that id appends)
+  if (lf == log_files_.end()) return;
+  for (std::FILE* f : lf->second.f) if (f) std::fclose(f);
+  log_files_.erase(lf);
+}
+
+// rank_of_slot of every batch of this manager from the ascending ids of the whole (possibly sharded) manager, uploaded to the
+// batch's device (the current device: the caller's DeviceGuard)
+void TargetManager::uploadRanks(const std::vector<unsigned>& sorted_all) {
+  if (rank_maps_.size() < batches_.size()) rank_maps_.resize(batches_.size());
+  for (size_t b = 0; b < batches_.size(); ++b) {
+    const long n = batches_[b]->size();
+    if (!n) continue;
+    RankMap& r = rank_maps_[b];
+    const hipStream_t st = batches_[b]->stream();
+    if (r.cap < n) {   // a map that grows: the launches and the upload that still read the old buffers finish first
+      const long want = std::max(n, r.cap * 2);
+      TE_HIP_CHECK(hipStreamSynchronize(st));
+      device_free(r.dev);
+      if (r.host) (void)hipHostFree(r.host);
+      r.dev = nullptr; r.host = nullptr; r.cap = 0;
+      TE_HIP_CHECK(hipMalloc((void**)&r.dev, sizeof(int) * (size_t)want));
+      TE_HIP_CHECK(hipHostMalloc((void**)&r.host, sizeof(int) * (size_t)want, hipHostMallocDefault));
+      if (!r.copied) TE_HIP_CHECK(hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
+      r.cap = want;
+    } else {
+      TE_HIP_CHECK(hipEventSynchronize(r.copied));   // the previous upload has left the staging buffer (long since, as a rule)
+    }
+    ranks_of_slots(sorted_all, batches_[b]->slot_ids().data(), n, r.host);
+    TE_HIP_CHECK(hipMemcpyAsync(r.dev, r.host, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));   // stream-ordered, no host wait
+    TE_HIP_CHECK(hipEventRecord(r.copied, st));
+  }
+}
+
+void TargetManager::launchRows(double* pose_out) {
+  for (size_t b = 0; b < batches_.size(); ++b)
+    if (batches_[b]->size() > 0) batches_[b]->outputs_rows_dev(pose_out, rank_maps_[b].dev);
+}
+
+long TargetManager::getEstAllById(double* pose_out, long capacity) {
+  lock_guard<mutex> lg(target_lock_);
+  const long rows = sharded() ? (long)shard_map_.size() : (long)targets_.size();
+  if (!pose_out) return rows;
+  if (capacity < rows) throw std::invalid_argument("target_estimation_amd: get_est_all_by_id: capacity " + std::to_string(capacity) +
+                                                   " is smaller than the " + std::to_string(rows) + " targets");
+  if (rows == 0) return 0;
+  if (!sharded()) {
+    if (ranks_dirty_) { uploadRanks(targets_.sorted_ids()); ranks_dirty_ = false; }
+    launchRows(pose_out);
+    return rows;
+  }
+  if (ranks_dirty_) {
+    std::vector<std::vector<unsigned>> lists;
+    for (auto& s : shards_) lists.push_back(s->getAvailableTargets());
+    const std::vector<unsigned> all = merge_sorted_ids(lists);
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      DeviceGuard g(shard_dev_[k]);
+      lock_guard<mutex> sl(shards_[k]->target_lock_);
+      shards_[k]->uploadRanks(all);
+    }
+    ranks_dirty_ = false;
+  }
+  for (size_t k = 0; k < shards_.size(); ++k) {   // every shard's launches on its own stream; none waits for another
+    DeviceGuard g(shard_dev_[k]);
+    lock_guard<mutex> sl(shards_[k]->target_lock_);
+    shards_[k]->launchRows(pose_out);
+  }
+  return rows;
 }
 
 }  // namespace te

@@ -29,8 +29,19 @@
 #include "batch_store.hpp"
 #include "id_resolve.hpp"
 #include "id_table.hpp"
+#include "shard_map.hpp"
 
 namespace te {
+
+// makes `dev` the calling thread's current HIP device for the guard's lifetime and restores the previous one (every call into
+// a shard of a manager that spans several devices: Batch reads the current device)
+struct DeviceGuard {
+  int prev = -1, dev;
+  explicit DeviceGuard(int d);
+  ~DeviceGuard();
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
 
 // true if Q, R and the n_P0 covariances have no entry between different axis groups (te_layout.hpp)
 bool is_axis_separable(int type, const double* Q, const double* R, const double* P0, long n_P0);
@@ -166,11 +177,27 @@ class TargetManager {
   long liveDoneAll();                       // ticks every wavefront of every batch has finished
   bool liveWaitAll(long tick, double timeout_s);
   long liveStopAll();                       // returns the ticks served (the same for every batch)
-  int numBatches() const { return (int)batches_.size(); }
-  Batch* batch(int i) { return batches_[(size_t)i].get(); }
+  // batches of every shard, shard-major (a manager on one device: its own batches)
+  int numBatches() const;
+  Batch* batch(int i);
   Batch* batchOfType(int type);
-  void setStream(hipStream_t s);
+  void setStream(hipStream_t s);   // refused on a manager with more than one shard (setShardStream)
   hipStream_t stream() const { return stream_; }
+
+  // ---- several devices (target_manager_set_devices) ----
+  // n shards, shard k a complete TargetManager on HIP device devices[k] (repeats allowed).  Only before the first target;
+  // n == 1 on the creation device leaves the manager unsharded.  Throws and leaves the manager unchanged otherwise.
+  void setDevices(const int* devices, int n);
+  int numShards() const { return shards_.empty() ? 1 : (int)shards_.size(); }
+  int shardDevice(int k) const;      // -1: no such shard
+  int shardOf(unsigned id);          // -1: unknown id
+  int batchShard(int i) const;       // shard of batch i (numBatches order), -1: no such batch
+  void setShardStream(int k, hipStream_t s);
+  // pose7 of every target in ascending id order (getAvailableTargets) into pose_out [size()][7] (device memory every shard's
+  // device reaches, or pinned host memory); one outputs_rows_kernel launch per batch, asynchronous (complete at synchronize()).
+  // After a change of membership the row maps are rebuilt on the host; a map that grows waits for its batch's stream.
+  // pose_out == null only counts.  Returns the number of rows.
+  long getEstAllById(double* pose_out, long capacity);
   // pose7 rows (doubles) of every target, batch after batch in slot order, into out_dev [size()][7] on stream `st`
   // (the gather's send side, pose_gather.hpp); out_dev == null only counts.  Returns the number of rows.
   long posesToDevice(double* out_dev, long capacity, hipStream_t st);
@@ -211,6 +238,11 @@ class TargetManager {
   std::unordered_map<unsigned, LogFiles> log_files_;    // per selected target, kept open
   std::FILE* log_all_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   void closeLogFiles();
+  void closeLogFilesOf(unsigned id);
+  // one target's log rows, formatted per channel (log()); batch: the batch index, or on a sharded manager its (model, layout) group
+  struct LogRow { unsigned id = 0; int batch = 0; std::string ch[7]; };
+  void logCollect(const std::vector<unsigned>& ids, std::vector<LogRow>& rows);
+  void logWrite(const std::vector<LogRow>& rows, bool per_target);
   // recorded all-batches sequences (stepSequenceAll)
   struct SeqGraph {
     long n_ticks; double dt; bool query; double origin[3]; double radius;
@@ -245,6 +277,70 @@ class TargetManager {
   bool resolveOnDevice(const unsigned* ids, long n, ResolveCounters& out);
   void devIdsFree();
   bool seq_flip_ = false;   // zig-zag across the whole tick: the next eager all-batches tick runs last batch first, tiles backwards
+
+  // ---- shards (setDevices).  Empty: the manager is its own only shard.  Every call into a shard holds this manager's lock
+  // (which guards the map) and a DeviceGuard on the shard's device.
+  std::vector<std::unique_ptr<TargetManager>> shards_;
+  std::vector<int> shard_dev_;
+  ShardMap shard_map_;
+  int home_dev_ = 0;        // the device current at construction
+  bool sharded() const { return !shards_.empty(); }
+  void copySettingsTo(TargetManager& s) const;
+  // (model, layout) of the shards' batches in order of first creation: the batch order an unsharded manager would have (log())
+  std::vector<std::pair<int, int>> batch_keys_;
+  void noteBatchKeys();
+  // the call f(shard) on the shard of id (shard 0 for an unknown id: it answers as an unsharded manager does)
+  template <class F>
+  auto routeId(unsigned id, F&& f) -> decltype(f(*this)) {
+    std::lock_guard<std::mutex> lg(target_lock_);
+    const int k = shard_map_.shard_of(id);
+    const size_t kk = k < 0 ? 0 : (size_t)k;
+    DeviceGuard g(shard_dev_[kk]);
+    return f(*shards_[kk]);
+  }
+  // the one shard of a single-shard manager for the calls refused with more than one (live mode, gather, setStream)
+  TargetManager& onlyShard(const char* what);
+  // ids of a call split by shard: positions into the caller's arrays, in the caller's order; unknown ids in `unknown`
+  struct Split { std::vector<std::vector<long>> src; std::vector<long> unknown; };
+  Split splitIds(const unsigned* ids, long n) const;
+  // the fan-out of a host-array call: f(shard, its ids, their positions in the caller's arrays) for every shard that holds some of
+  // the ids, under the shard's DeviceGuard.  Caller holds target_lock_.
+  template <class F>
+  void forShards(const Split& sp, const unsigned* ids, F&& f) {
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      const std::vector<long>& src = sp.src[k];
+      if (src.empty()) continue;
+      std::vector<unsigned> ids2(src.size());
+      for (size_t j = 0; j < src.size(); ++j) ids2[j] = ids[src[j]];
+      DeviceGuard g(shard_dev_[k]);
+      f(*shards_[k], ids2, src);
+    }
+  }
+  // rows of width w of the caller's array at positions pos, packed (empty for a null array) / packed rows back at pos
+  template <class T>
+  static std::vector<T> gatherRows(const T* a, const std::vector<long>& pos, long w) {
+    std::vector<T> out;
+    if (!a) return out;
+    out.resize(pos.size() * (size_t)w);
+    for (size_t j = 0; j < pos.size(); ++j)
+      for (long c = 0; c < w; ++c) out[j * (size_t)w + (size_t)c] = a[pos[j] * w + c];
+    return out;
+  }
+  template <class T>
+  static void scatterRows(T* a, const std::vector<T>& rows, const std::vector<long>& pos, long w) {
+    if (!a) return;
+    for (size_t j = 0; j < pos.size(); ++j)
+      for (long c = 0; c < w; ++c) a[pos[j] * w + c] = rows[j * (size_t)w + (size_t)c];
+  }
+  long initBatchSharded(target_t type, const unsigned* ids, long n, double dt0, double t0, const double* Q, const double* R,
+                        const double* P0, bool per_target_P0, const double* p0, const double* v0, const double* a0,
+                        long n_classes, const unsigned* class_of);
+  // per batch: rank_of_slot on the batch's device (getEstAllById), rebuilt after a change of membership
+  struct RankMap { int* dev = nullptr; int* host = nullptr; long cap = 0; hipEvent_t copied = nullptr; };   // host: pinned staging
+  std::vector<RankMap> rank_maps_;
+  bool ranks_dirty_ = true;
+  void uploadRanks(const std::vector<unsigned>& sorted_all);   // caller holds target_lock_
+  void launchRows(double* pose_out);                           // caller holds target_lock_
 };
 
 }  // namespace te

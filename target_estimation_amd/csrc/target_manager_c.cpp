@@ -553,6 +553,7 @@ void target_comm_delete(target_comm_c* comm) {
 
 int target_manager_gather_pose_begin(target_manager_c* self, target_comm_c* comm, int root, const long* counts, double* recv_dev) {
   return guarded("target_manager_gather_pose_begin", [&] {
+    if (M(self)->numShards() > 1) throw std::runtime_error("the RCCL gather is refused on a manager with more than one shard");
     if (!comm || !counts) throw std::invalid_argument("NULL communicator or counts");
     ((te::PoseComm*)comm)->begin(M(self), root, counts, recv_dev);
   });
@@ -680,6 +681,29 @@ int target_manager_set_log_targets(target_manager_c* self, const unsigned int* i
     if (n > 0 && !ids) throw std::invalid_argument("NULL id list");
     M(self)->setLogTargets(ids, n);
   });
+}
+
+// ---------------------------------------------------------------- one manager over several devices
+int target_manager_set_devices(target_manager_c* m, const int* devices, int n) {
+  return guarded("target_manager_set_devices", [&] { M(m)->setDevices(devices, n); });
+}
+int target_manager_num_shards(target_manager_c* m) {
+  return guarded_value<int>("target_manager_num_shards", -1, [&] { return M(m)->numShards(); });
+}
+int target_manager_shard_device(target_manager_c* m, int k) {
+  return guarded_value<int>("target_manager_shard_device", -1, [&] { return M(m)->shardDevice(k); });
+}
+int target_manager_shard_of(target_manager_c* m, unsigned int id) {
+  return guarded_value<int>("target_manager_shard_of", -1, [&] { return M(m)->shardOf(id); });
+}
+int target_manager_batch_shard(target_manager_c* m, int index) {
+  return guarded_value<int>("target_manager_batch_shard", -1, [&] { return M(m)->batchShard(index); });
+}
+int target_manager_set_shard_stream(target_manager_c* m, int k, void* hip_stream) {
+  return guarded("target_manager_set_shard_stream", [&] { M(m)->setShardStream(k, (hipStream_t)hip_stream); });
+}
+long target_manager_get_est_all_by_id(target_manager_c* m, double* pose_out, long capacity) {
+  return guarded_value<long>("target_manager_get_est_all_by_id", -1L, [&] { return M(m)->getEstAllById(pose_out, capacity); });
 }
 
 // ---------------------------------------------------------------- synthetic measurement streams

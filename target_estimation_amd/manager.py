@@ -304,13 +304,63 @@ class MeasurementIngest:
 class TargetManager:
     """ctypes mirror of the reference TargetManager; dtype 'f64' (reference precision) or 'f32'."""
 
-    def __init__(self, file=None, dtype="f64", lanes_per_target=0):
+    def __init__(self, file=None, dtype="f64", lanes_per_target=0, devices=None):
+        """devices: HIP device indices, one shard each (repeats allowed; target_manager_set_devices).  None: unsharded."""
         self._lib = capi.lib()
         f = None if file is None else str(file).encode()
         self._h = self._lib.target_manager_new_ex(f, DTYPES[dtype], int(lanes_per_target))
         if not self._h:
             raise RuntimeError("target_manager_new failed: %s" % capi.last_error())
         self.dtype = dtype
+        if devices is not None:
+            try:
+                self.set_devices(devices)
+            except Exception:
+                self.close()
+                raise
+
+    # ---- several devices (target_manager_set_devices) -----------------------------------------
+    def set_devices(self, devices):
+        devs = np.ascontiguousarray(np.asarray(list(devices), dtype=np.int32))
+        _check(self._lib.target_manager_set_devices(self._h, devs.ctypes.data_as(C.POINTER(C.c_int)), len(devs)),
+               "target_manager_set_devices")
+
+    @property
+    def num_shards(self):
+        return self._lib.target_manager_num_shards(self._h)
+
+    def shard_device(self, k):
+        return self._lib.target_manager_shard_device(self._h, int(k))
+
+    def shard_of(self, id):
+        return self._lib.target_manager_shard_of(self._h, int(id))
+
+    def batch_shard(self, i):
+        return self._lib.target_manager_batch_shard(self._h, int(i))
+
+    def set_shard_stream(self, k, stream_ptr):
+        _check(self._lib.target_manager_set_shard_stream(self._h, int(k), stream_ptr), "target_manager_set_shard_stream")
+
+    def get_est_all_by_id(self, out=None):
+        """pose7 of every target in ascending id order (get_available_targets).  out: a torch tensor [>= size, 7] of doubles
+        on the GPU or in pinned host memory (filled asynchronously; complete after synchronize()), or None: a numpy array
+        (through a pinned staging buffer, synchronised here)."""
+        if out is not None:
+            import torch
+            if out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 7 or not out.is_contiguous():
+                raise ValueError("get_est_all_by_id: out must be a contiguous float64 tensor [rows, 7], got %s %s" % (out.dtype, tuple(out.shape)))
+            n = self._lib.target_manager_get_est_all_by_id(self._h, out.data_ptr(), out.shape[0])
+            if n < 0:
+                raise RuntimeError("target_manager_get_est_all_by_id: %s" % capi.last_error())
+            return out[:n]
+        import torch
+        n = self.size()
+        buf = torch.empty((max(n, 1), 7), dtype=torch.float64, pin_memory=True)
+        k = self._lib.target_manager_get_est_all_by_id(self._h, buf.data_ptr(), buf.shape[0])
+        if k < 0:
+            raise RuntimeError("target_manager_get_est_all_by_id: %s" % capi.last_error())
+        self.synchronize()
+        return buf[:k].numpy().copy()
 
     def close(self):
         if getattr(self, "_h", None):
