@@ -30,8 +30,9 @@ struct PoseStream {
 
 class Batch {
  public:
-  // `owner_lock`: the mutex of the manager that owns the batch (TargetManager::target_lock_); the C boundary takes it
-  // around every call made through a batch handle, so that those calls and the manager's own are serialised
+  // `owner_lock`: the one mutex of the manager whose shard owns the batch (TargetManager::target_lock_, whatever the number
+  // of shards); the C boundary takes it around every call made through a batch handle, so that those calls and the
+  // manager's own are serialised
   Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock = nullptr);
   ~Batch();
   Batch(const Batch&) = delete;

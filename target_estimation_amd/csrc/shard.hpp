@@ -1,0 +1,194 @@
+// shard.hpp -- everything a TargetManager holds on ONE device: the batches, the id -> (batch, slot) table, the device-side id
+// resolution, the recorded all-batches sequences and the row maps of getEstAllById.  A manager owns one Shard per device it
+// spans (target_manager.hpp), exactly one unless setDevices said otherwise.
+//
+// CONTRACT, for every method: the caller holds the owning manager's lock and has made the shard's device the current HIP
+// device.  A Shard has no lock of its own, writes no log file, reads no environment and knows no other shard; what it needs of
+// the manager's settings it reads through `ShardSettings`, which the manager owns and may change between calls.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "batch_store.hpp"
+#include "id_table.hpp"
+#include "row_split.hpp"
+
+namespace te {
+
+struct ResolveCounters;   // id_resolve.hpp (kernels: included by shard.cpp only)
+
+// true if Q, R and the n_P0 covariances have no entry between different axis groups (te_layout.hpp)
+bool is_axis_separable(int type, const double* Q, const double* R, const double* P0, long n_P0);
+// unit quaternion [x y z w] -> rotation matrix (row-major), Eigen's Quaterniond::toRotationMatrix
+void host_quat_to_rot(const double* q, double* R);
+
+// row i of a sphere query's outputs (any may be null) for a target that does not exist or never meets the sphere
+inline void no_intersection(long i, double* delta, double* pose, unsigned char* converged, double* filt) {
+  if (delta) delta[i] = -1;
+  if (converged) converged[i] = 0;
+  if (pose) { for (int c = 0; c < 6; ++c) pose[i * 7 + c] = 0.0; pose[i * 7 + 6] = 1.0; }
+  if (filt) { filt[i * 2] = 0.0; filt[i * 2 + 1] = 0.0; }
+}
+
+// the manager's settings as its shards read them (one copy, in the manager)
+struct ShardSettings {
+  int dtype = F64;
+  int lanes = 0;              // lanes code asked for at construction, 0 = automatic (Shard::chooseLayout)
+  bool verbose = false;       // TARGET_ESTIMATION_VERBOSE
+  bool keep_meas = false;     // setKeepMeasurement: batches created later inherit the measured-pose rows
+  int filters_length = 250;   // setIntersectionFiltersLength
+  long small_batch_most = 0;  // the largest host-array call that goes through the one-target queue (TE_SMALL_BATCH_QUEUE)
+  bool population_tick = true;   // TE_POPULATION_TICK
+};
+
+// one target's log rows, formatted per channel (TargetManager::log); batch: the shard's batch index as logCollect leaves it
+struct LogRow { unsigned id = 0; int batch = 0; std::string ch[7]; };
+
+class Shard {
+ public:
+  // `owner_lock`: the manager's mutex, handed to every Batch (Batch::owner_lock); the shard itself never takes it
+  Shard(const ShardSettings& settings, std::mutex* owner_lock);
+  ~Shard();
+  Shard(const Shard&) = delete;
+  Shard& operator=(const Shard&) = delete;
+
+  // ---- what the manager reads
+  size_t size() const { return targets_.size(); }
+  bool contains(unsigned id) const { return targets_.contains(id); }
+  std::vector<unsigned> sortedIds() const { return targets_.sorted_ids(); }   // ascending, as the reference's std::map iteration
+  const std::vector<std::unique_ptr<Batch>>& batches() const { return batches_; }
+  const Batch* batchOf(unsigned id) const;   // null: unknown id
+  Batch* batchOfType(int type);
+  hipStream_t stream() const { return stream_; }
+  void setStream(hipStream_t s);
+  void keepMeasurementChanged();   // settings.keep_meas to every batch; drops the recorded sequences
+  void synchronize();
+
+  // ---- by id (return values and messages of the manager's methods of the same purpose)
+  bool init(int type, unsigned id, double t0, const double* Q, const double* R, const double* P0, const double* p0, const double* v0,
+            const double* a0);   // false: the id exists already (said so)
+  // (update and outputsOne are the reference's one-target cycle, a latency path measured in nanoseconds per call: inline)
+  bool update(unsigned id, double dt, const double* meas) {   // meas null: prediction only
+    Loc loc;
+    if (!find(id, loc)) { notFound(id); return false; }
+    batches_[(size_t)loc.batch]->step_one(loc.slot, dt, meas);
+    return true;
+  }
+  bool erase(unsigned id);
+  bool outputsOne(unsigned id, double* pose7, double* twist6, double* acc6, bool at_time, double t1) {
+    Loc loc;
+    if (!find(id, loc)) return false;
+    batches_[(size_t)loc.batch]->outputs_one(loc.slot, pose7, twist6, acc6, at_time, t1);
+    return true;
+  }
+  bool measuredPose(unsigned id, double* pose7);
+  bool dims(unsigned id, int& n, int& m);
+  bool modelMatrices(unsigned id, double* Q, double* R, double* P0);
+  bool time(unsigned id, double& t);
+  int state(unsigned id, double* x, double* P);
+  long long numberMeasurements(unsigned id);
+  double intersectTime(unsigned id, double t1, const double* origin, double radius);
+  bool intersectPose(unsigned id, double t1, const double* origin, double radius, double* pose7, double* delta);
+
+  // ---- host arrays
+  long initBatch(int type, const unsigned* ids, long n, double t0, const double* Q, const double* R, const double* P0, bool per_target_P0,
+                 const double* p0, const double* v0, const double* a0);
+  long initBatchClasses(int type, const unsigned* ids, long n, double t0, long n_classes, const double* Q, const double* R, const double* P0,
+                        const unsigned* class_of, const double* p0, const double* v0, const double* a0);
+  void updateAll(double dt);
+  long updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas);
+  long eraseBatch(const unsigned* ids, long n, std::vector<unsigned>& erased);   // appends the ids that went away
+  long getPoseBatch(const unsigned* ids, long n, double* pose, double* twist, double* acc, unsigned char* found, bool at_time, double t1);
+  long getStateBatch(const unsigned* ids, long n, double* x, double* P);
+  long intersectGatedBatch(const unsigned* ids, long n, double t1, double pos_th, double ang_th, const double* origin, double radius,
+                           double* delta, double* pose, unsigned char* converged, unsigned char* found, double* filt);
+  long intersectBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, double* delta, double* pose,
+                      unsigned char* found);
+
+  // ---- every batch at once (TargetManager::stepSequenceAll, live*All, posesToDevice, getEstAllById, log)
+  bool populationTick() const;   // the tick of all batches as one launch (kf_population.hpp)
+  void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query, const double* origin, double radius,
+                       int use_graph);
+  void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
+                    const double* origin, double radius);
+  void livePostAll(long n_ticks, bool one_doorbell_per_tick);
+  long liveDoneAll();
+  // THE exception to the contract: liveWaitAll takes this list under the manager's lock and spins on it without (posts come
+  // from other threads)
+  std::vector<Batch*> liveOpenBatches();
+  long liveStopAll();
+  long rows() const;                    // slots of every batch
+  void posesToDevice(double* out_dev);  // pose7 rows, batch after batch in slot order, on the shard's stream
+  // the rows of the ids that this shard holds, grouped by batch (batch order), in the order of `ids` inside a batch
+  void logCollect(const std::vector<unsigned>& ids, std::vector<LogRow>& rows);
+  // rank_of_slot of every batch from the ascending ids of the WHOLE manager, uploaded to the shard's device / one
+  // outputs_rows_kernel launch per batch with them
+  void uploadRanks(const std::vector<unsigned>& sorted_all);
+  void launchRows(double* pose_out);
+
+ private:
+  using Loc = TargetLoc;
+  // lanes code of a new target's batch: the manager's explicit choice, or (auto) the axis-separable
+  // layout when Q, R and every P0 allow it
+  int chooseLayout(int type, const double* Q, const double* R, const double* P0, long n_P0) const;
+  // the batch of (model, layout) -- created on first use -- and the parameter class of (Q, R) inside it
+  int findOrCreateBatch(int type, const double* Q, const double* R, int lanes_code, int& cls);
+  bool find(unsigned id, Loc& loc) const { return targets_.find(id, loc); }
+  // ids of a host-array call by batch: sp.src[b] = their positions in the caller's arrays, slots[b] = their slots, both in
+  // the caller's order; before_each(b, loc) runs ahead of every known id's entry (updateBatch's repeated-id flush)
+  struct BySlot { Split sp; std::vector<std::vector<int>> slots; long known = 0; };
+  template <class Before>
+  void splitBySlot(const unsigned* ids, long n, BySlot& by, Before&& before_each) const;
+  Batch* wholeBatch(const unsigned* ids, long n) const;   // the batch whose ids, in slot order, are exactly these; or null
+  void notFound(unsigned id) const;   // "Target(id) does not exist!"
+
+  const ShardSettings& set_;
+  std::mutex* const owner_lock_;
+  IdTable targets_;   // id -> (batch, slot); the reference's std::map<unsigned, TargetPtr> (target_manager.hpp:201)
+  std::vector<std::unique_ptr<Batch>> batches_;
+  hipStream_t stream_ = nullptr;
+
+  // recorded all-batches sequences (stepSequenceAll)
+  struct SeqGraph {
+    long n_ticks; double dt; bool query; double origin[3]; double radius;
+    std::vector<Batch::SeqSpec> specs;
+    std::vector<Batch::DevIdentity> ident;
+    hipGraph_t graph; hipGraphExec_t exec;
+  };
+  std::vector<SeqGraph> seq_graphs_;
+  std::vector<hipStream_t> branch_streams_;   // [0]: the capture stream
+  std::vector<hipEvent_t> branch_events_;
+  void dropSeqGraphs();
+  void enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin, double radius,
+                             bool reverse, bool ab);
+  bool seq_flip_ = false;   // zig-zag across the whole tick: the next eager all-batches tick runs last batch first, tiles backwards
+
+  // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call
+  struct DevIds {
+    unsigned* keys = nullptr; unsigned* vals = nullptr; int* seen = nullptr;
+    int log2cap = 0; bool dirty = true; int epoch = 0;
+    long cap = 0;                       // entries the staging holds
+    unsigned* ids = nullptr; int* loc = nullptr; int* idx = nullptr;
+    double* aos = nullptr; void* soa = nullptr; unsigned char* mask = nullptr; unsigned char* found = nullptr;
+    double* out = nullptr;              // [cap][7 + 6 + 6] getter outputs
+    ResolveCounters* counters = nullptr;
+    ResolveCounters* h_counters = nullptr;   // pinned
+  } dev_ids_;
+  static constexpr long kDevResolveMin = 8192;   // below this the host table is faster than the extra launches
+  bool smallBatchPath(long n) const;
+  void devIdsReserve(long n);
+  void devIdsRebuild();
+  // loc[e] of every id on the device + the per-batch counts on the host; false: not applicable (too many batches)
+  bool resolveOnDevice(const unsigned* ids, long n, ResolveCounters& out);
+  void devIdsFree();
+
+  // per batch: rank_of_slot on the batch's device (getEstAllById), rebuilt after a change of membership
+  struct RankMap { int* dev = nullptr; int* host = nullptr; long cap = 0; hipEvent_t copied = nullptr; };   // host: pinned staging
+  std::vector<RankMap> rank_maps_;
+};
+
+}  // namespace te

@@ -20,31 +20,27 @@
 #include <cstdio>
 #include <functional>
 #include <unordered_map>
-#include <map>
+#include <utility>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "batch_store.hpp"
-#include "id_resolve.hpp"
-#include "id_table.hpp"
+#include "shard.hpp"
 #include "shard_map.hpp"
 
 namespace te {
 
 // makes `dev` the calling thread's current HIP device for the guard's lifetime and restores the previous one (every call into
-// a shard of a manager that spans several devices: Batch reads the current device)
+// a shard of a manager whose devices were named: Batch reads the current device).  dev < 0: does nothing.
 struct DeviceGuard {
   int prev = -1, dev;
-  explicit DeviceGuard(int d);
-  ~DeviceGuard();
+  explicit DeviceGuard(int d) : dev(d) { if (d >= 0) enter(); }
+  ~DeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
+  void enter();
 };
-
-// true if Q, R and the n_P0 covariances have no entry between different axis groups (te_layout.hpp)
-bool is_axis_separable(int type, const double* Q, const double* R, const double* P0, long n_P0);
 
 class TargetManager {
  public:
@@ -92,7 +88,7 @@ class TargetManager {
   static constexpr long kLogAutoSelect = 64;
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121): kept only on request (measured_pose.hpp)
   void setKeepMeasurement(bool on);
-  bool keepMeasurement() const { return keep_meas_; }
+  bool keepMeasurement() const { return settings_.keep_meas; }
   bool getTargetMeasuredPose(unsigned id, double* pose7);          // false: unknown id or not kept
   // TargetInterface::getPeriodEstimate (target_interface.cpp:80-87): 2 pi / |omega| of the current twist, -1 if not rotating
   bool getTargetPeriodEstimate(unsigned id, double& period);
@@ -145,7 +141,7 @@ class TargetManager {
   // Returns whether the filtered position / angle errors are below the thresholds.
   bool getIntersectionPoseWithSphere(unsigned id, double t1, double pos_th, double ang_th, const double* origin,
                                      double radius, double* pose7);
-  void setIntersectionFiltersLength(int n) { filters_length_ = n; }   // IntersectionSolver ctor, default 250
+  void setIntersectionFiltersLength(int n) { settings_.filters_length = n; }   // IntersectionSolver ctor, default 250
   long intersectGatedBatch(const unsigned* ids, long n, double t1, double pos_th, double ang_th, const double* origin,
                            double radius, double* delta, double* pose, unsigned char* converged, unsigned char* found,
                            double* filt = nullptr);
@@ -157,7 +153,7 @@ class TargetManager {
   // independent, so with use_graph != 0 each batch's chain of launches is its own branch of one hipGraph
   // and the branches run concurrently; the query runs inside the step kernel (QUERY variants).
   // use_graph == 2 records without launching.  use_graph == 0 issues the same launches eagerly, batch after batch per tick.
-  bool populationTickNow() { std::lock_guard<std::mutex> lg(target_lock_); return populationTick(); }
+  bool populationTickNow();
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
                        const double* origin, double radius, int use_graph);
   // The same with a per-tick pose stream per batch (poses[b], PoseStream; one with a null dev writes nothing for that batch):
@@ -182,13 +178,13 @@ class TargetManager {
   Batch* batch(int i);
   Batch* batchOfType(int type);
   void setStream(hipStream_t s);   // refused on a manager with more than one shard (setShardStream)
-  hipStream_t stream() const { return stream_; }
+  hipStream_t stream() const { return several() ? nullptr : shards_[0]->stream(); }
 
   // ---- several devices (target_manager_set_devices) ----
-  // n shards, shard k a complete TargetManager on HIP device devices[k] (repeats allowed).  Only before the first target;
-  // n == 1 on the creation device leaves the manager unsharded.  Throws and leaves the manager unchanged otherwise.
+  // n shards (shard.hpp), shard k on HIP device devices[k] (repeats allowed).  Only before the first target; n == 1 on the
+  // creation device is the manager as constructed.  Throws and leaves the manager unchanged otherwise.
   void setDevices(const int* devices, int n);
-  int numShards() const { return shards_.empty() ? 1 : (int)shards_.size(); }
+  int numShards() const { return (int)shards_.size(); }
   int shardDevice(int k) const;      // -1: no such shard
   int shardOf(unsigned id);          // -1: unknown id
   int batchShard(int i) const;       // shard of batch i (numBatches order), -1: no such batch
@@ -206,141 +202,95 @@ class TargetManager {
   // destination [rows][7] -- and launches the outputs kernels into it.  Returns the row count.
   long posesForGather(long expect_rows, const std::function<double*(long, hipStream_t)>& prepare);
   void synchronize();
-  int dtype() const { return dtype_; }
+  int dtype() const { return settings_.dtype; }
   bool defaultsLoaded() const { return default_values_loaded_; }
   int defaultType() const { return (int)default_type_; }
 
  protected:
-  using Loc = TargetLoc;
   bool loadYamlFile(const std::string& file, std::vector<double>& Q, std::vector<double>& R, std::vector<double>& P,
                     target_t& type);  // target_manager.cpp:67-104
-  // lanes code of a new target's batch: the manager's explicit choice, or (auto) the axis-separable
-  // layout when Q, R and every P0 allow it
-  int chooseLayout(int type, const double* Q, const double* R, const double* P0, long n_P0) const;
-  // the batch of (model, layout) -- created on first use -- and the parameter class of (Q, R) inside it
-  int findOrCreateBatch(int type, const double* Q, const double* R, int lanes_code, int& cls);
-  bool find(unsigned id, Loc& loc);
 
-  IdTable targets_;   // id -> (batch, slot); the reference's std::map<unsigned, TargetPtr> (target_manager.hpp:201)
-  std::vector<std::unique_ptr<Batch>> batches_;
-  std::mutex target_lock_;
+ private:
+  std::mutex target_lock_;   // THE lock: every public method takes it once; shards and batches have none of their own
+  ShardSettings settings_;   // what the shards read (shard.hpp)
   std::vector<double> default_Q_, default_P_, default_R_;
   target_t default_type_ = UNIFORM_VELOCITY;
   bool default_values_loaded_ = false;
-  int dtype_, lanes_;
-  hipStream_t stream_ = nullptr;
-  bool verbose_ = false;
-  int filters_length_ = 250;
+
+  // ---- shards.  Never empty: without setDevices one shard on the device current at construction, and then no DeviceGuard
+  // and no ShardMap (the shard's own id table answers).  With setDevices: shard k on shard_dev_[k] under a DeviceGuard, and
+  // with more than one shard the ShardMap says which shard holds an id.
+  std::vector<std::unique_ptr<Shard>> shards_;
+  std::vector<int> shard_dev_;
+  bool placed_ = false;     // setDevices named the devices
+  int home_dev_ = 0;        // the device current at construction
+  ShardMap shard_map_;      // more than one shard only
+  bool ranks_dirty_ = true; // membership changed since the row maps of getEstAllById were uploaded
+  // (model, layout) of the shards' batches in order of first creation: the batch order one shard would have (log()); more than one shard only
+  std::vector<std::pair<int, int>> batch_keys_;
+  void noteBatchKeys();
+  bool several() const { return shards_.size() > 1; }
+  int guardDev(size_t k) const { return placed_ ? shard_dev_[k] : -1; }   // what a DeviceGuard around a call into shard k takes
+  size_t count() const { return several() ? shard_map_.size() : shards_[0]->size(); }
+  std::vector<unsigned> sortedIds() const;
+  // the shard that answers for id (shard 0 for an id that no shard holds: it answers as a manager on one device does)
+  size_t shardFor(unsigned id) const {
+    if (!several()) return 0;
+    const int k = shard_map_.shard_of(id);
+    return k < 0 ? 0 : (size_t)k;
+  }
+  // THE routing point of the by-id calls: lock, the id's shard made current, f(shard).  (Always inline, like getOne: left
+  // to itself the compiler calls the instantiation through the PLT, which the one-target cycle pays per call.)
+  template <class F>
+  __attribute__((always_inline)) auto routeId(unsigned id, F&& f) -> decltype(f(std::declval<Shard&>())) {
+    std::lock_guard<std::mutex> lg(target_lock_);
+    const size_t k = shardFor(id);
+    DeviceGuard g(guardDev(k));
+    return f(*shards_[k]);
+  }
+  // THE routing point of the host-array calls (caller holds target_lock_): the ids by shard (row_split.hpp), then
+  // f(shard, k, its ids, how many, pos) for every shard that holds some, made current; pos = their positions in the caller's
+  // arrays.  One shard takes the call whole: no split, the caller's ids and pos == null.
+  Split splitIds(const unsigned* ids, long n) const;
+  template <class F>
+  void forShards(const Split& sp, const unsigned* ids, long n, F&& f) {
+    if (!several()) {
+      DeviceGuard g(guardDev(0));
+      f(*shards_[0], (size_t)0, ids, n, (const std::vector<long>*)nullptr);
+      return;
+    }
+    for (size_t k = 0; k < shards_.size(); ++k) {
+      if (sp.src[k].empty()) continue;
+      const std::vector<unsigned> ids2 = gatherRows(ids, sp.src[k], 1);
+      DeviceGuard g(guardDev(k));
+      f(*shards_[k], k, ids2.data(), (long)ids2.size(), &sp.src[k]);
+    }
+  }
+  // THE refusal, for the calls that need the manager to be one shard (live mode, gather, setStream): lock, the check, the
+  // shard made current, f(shard)
+  void requireOneShard(const char* what) const;
+  template <class F>
+  auto onlyShard(const char* what, F&& f) -> decltype(f(std::declval<Shard&>())) {
+    std::lock_guard<std::mutex> lg(target_lock_);
+    requireOneShard(what);
+    DeviceGuard g(guardDev(0));
+    return f(*shards_[0]);
+  }
+  __attribute__((always_inline)) bool getOne(unsigned id, double* pose7, double* twist6, double* acc6, bool at_time, double t1) {   // the six one-target getters
+    return routeId(id, [&](Shard& s) { return s.outputsOne(id, pose7, twist6, acc6, at_time, t1); });
+  }
+  long createBatch(target_t type, const unsigned* ids, long n, double t0, const double* Q, const double* R, const double* P0,
+                   bool per_target_P0, const double* p0, const double* v0, const double* a0, long n_classes, const unsigned* class_of);
+
+  // ---- log()
   std::string log_dir_;
-  bool keep_meas_ = false;
   std::vector<unsigned> log_ids_;                       // explicit selection (sorted); empty = automatic
   struct LogFiles { std::FILE* f[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; };
   std::unordered_map<unsigned, LogFiles> log_files_;    // per selected target, kept open
   std::FILE* log_all_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   void closeLogFiles();
   void closeLogFilesOf(unsigned id);
-  // one target's log rows, formatted per channel (log()); batch: the batch index, or on a sharded manager its (model, layout) group
-  struct LogRow { unsigned id = 0; int batch = 0; std::string ch[7]; };
-  void logCollect(const std::vector<unsigned>& ids, std::vector<LogRow>& rows);
   void logWrite(const std::vector<LogRow>& rows, bool per_target);
-  // recorded all-batches sequences (stepSequenceAll)
-  struct SeqGraph {
-    long n_ticks; double dt; bool query; double origin[3]; double radius;
-    std::vector<Batch::SeqSpec> specs;
-    std::vector<Batch::DevIdentity> ident;
-    hipGraph_t graph; hipGraphExec_t exec;
-  };
-  std::vector<SeqGraph> seq_graphs_;
-  std::vector<hipStream_t> branch_streams_;   // [0]: the capture stream
-  bool populationTick() const;   // the tick of all batches as one launch (kf_population.hpp); caller holds target_lock_
-  void enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin, double radius,
-                             bool reverse, bool ab);
-  std::vector<hipEvent_t> branch_events_;
-  void dropSeqGraphs();
-  // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call
-  struct DevIds {
-    unsigned* keys = nullptr; unsigned* vals = nullptr; int* seen = nullptr;
-    int log2cap = 0; bool dirty = true; int epoch = 0;
-    long cap = 0;                       // entries the staging holds
-    unsigned* ids = nullptr; int* loc = nullptr; int* idx = nullptr;
-    double* aos = nullptr; void* soa = nullptr; unsigned char* mask = nullptr; unsigned char* found = nullptr;
-    double* out = nullptr;              // [cap][7 + 6 + 6] getter outputs
-    ResolveCounters* counters = nullptr;
-    ResolveCounters* h_counters = nullptr;   // pinned
-  } dev_ids_;
-  static constexpr long kDevResolveMin = 8192;   // below this the host table is faster than the extra launches
-  static constexpr long kSmallBatchQueue = 1024; // host-array calls of at most this many targets go through the one-target queue (updateBatch)
-  bool smallBatchPath(const unsigned* ids, long n) const;
-  void devIdsReserve(long n);
-  void devIdsRebuild();
-  // loc[e] of every id on the device + the per-batch counts on the host; false: not applicable (too many batches)
-  bool resolveOnDevice(const unsigned* ids, long n, ResolveCounters& out);
-  void devIdsFree();
-  bool seq_flip_ = false;   // zig-zag across the whole tick: the next eager all-batches tick runs last batch first, tiles backwards
-
-  // ---- shards (setDevices).  Empty: the manager is its own only shard.  Every call into a shard holds this manager's lock
-  // (which guards the map) and a DeviceGuard on the shard's device.
-  std::vector<std::unique_ptr<TargetManager>> shards_;
-  std::vector<int> shard_dev_;
-  ShardMap shard_map_;
-  int home_dev_ = 0;        // the device current at construction
-  bool sharded() const { return !shards_.empty(); }
-  void copySettingsTo(TargetManager& s) const;
-  // (model, layout) of the shards' batches in order of first creation: the batch order an unsharded manager would have (log())
-  std::vector<std::pair<int, int>> batch_keys_;
-  void noteBatchKeys();
-  // the call f(shard) on the shard of id (shard 0 for an unknown id: it answers as an unsharded manager does)
-  template <class F>
-  auto routeId(unsigned id, F&& f) -> decltype(f(*this)) {
-    std::lock_guard<std::mutex> lg(target_lock_);
-    const int k = shard_map_.shard_of(id);
-    const size_t kk = k < 0 ? 0 : (size_t)k;
-    DeviceGuard g(shard_dev_[kk]);
-    return f(*shards_[kk]);
-  }
-  // the one shard of a single-shard manager for the calls refused with more than one (live mode, gather, setStream)
-  TargetManager& onlyShard(const char* what);
-  // ids of a call split by shard: positions into the caller's arrays, in the caller's order; unknown ids in `unknown`
-  struct Split { std::vector<std::vector<long>> src; std::vector<long> unknown; };
-  Split splitIds(const unsigned* ids, long n) const;
-  // the fan-out of a host-array call: f(shard, its ids, their positions in the caller's arrays) for every shard that holds some of
-  // the ids, under the shard's DeviceGuard.  Caller holds target_lock_.
-  template <class F>
-  void forShards(const Split& sp, const unsigned* ids, F&& f) {
-    for (size_t k = 0; k < shards_.size(); ++k) {
-      const std::vector<long>& src = sp.src[k];
-      if (src.empty()) continue;
-      std::vector<unsigned> ids2(src.size());
-      for (size_t j = 0; j < src.size(); ++j) ids2[j] = ids[src[j]];
-      DeviceGuard g(shard_dev_[k]);
-      f(*shards_[k], ids2, src);
-    }
-  }
-  // rows of width w of the caller's array at positions pos, packed (empty for a null array) / packed rows back at pos
-  template <class T>
-  static std::vector<T> gatherRows(const T* a, const std::vector<long>& pos, long w) {
-    std::vector<T> out;
-    if (!a) return out;
-    out.resize(pos.size() * (size_t)w);
-    for (size_t j = 0; j < pos.size(); ++j)
-      for (long c = 0; c < w; ++c) out[j * (size_t)w + (size_t)c] = a[pos[j] * w + c];
-    return out;
-  }
-  template <class T>
-  static void scatterRows(T* a, const std::vector<T>& rows, const std::vector<long>& pos, long w) {
-    if (!a) return;
-    for (size_t j = 0; j < pos.size(); ++j)
-      for (long c = 0; c < w; ++c) a[pos[j] * w + c] = rows[j * (size_t)w + (size_t)c];
-  }
-  long initBatchSharded(target_t type, const unsigned* ids, long n, double dt0, double t0, const double* Q, const double* R,
-                        const double* P0, bool per_target_P0, const double* p0, const double* v0, const double* a0,
-                        long n_classes, const unsigned* class_of);
-  // per batch: rank_of_slot on the batch's device (getEstAllById), rebuilt after a change of membership
-  struct RankMap { int* dev = nullptr; int* host = nullptr; long cap = 0; hipEvent_t copied = nullptr; };   // host: pinned staging
-  std::vector<RankMap> rank_maps_;
-  bool ranks_dirty_ = true;
-  void uploadRanks(const std::vector<unsigned>& sorted_all);   // caller holds target_lock_
-  void launchRows(double* pose_out);                           // caller holds target_lock_
 };
 
 }  // namespace te

@@ -1,4 +1,5 @@
-// shard_map_test.cpp -- host checks of csrc/shard_map.hpp (placement rule, merged enumeration, rank_of_slot), built with
+// shard_map_test.cpp -- host checks of csrc/shard_map.hpp (placement rule, merged enumeration, rank_of_slot) and of
+// csrc/row_split.hpp (the gather / scatter of a host-array call split by shard or by batch), built with
 // g++ -fsanitize=address,undefined by tests/test_shard_map_host.py.  Prints "shard map tests ok" on success.
 #include <algorithm>
 #include <cstdio>
@@ -6,6 +7,7 @@
 #include <random>
 #include <vector>
 
+#include "../../target_estimation_amd/csrc/row_split.hpp"
 #include "../../target_estimation_amd/csrc/shard_map.hpp"
 
 using te::ShardMap;
@@ -164,7 +166,76 @@ static void test_ranks() {
   CHECK(r[0] == 1 && r[1] == -1 && r[2] == 2);
 }
 
+// gather -> scatter over a split of n rows into parts: every width from 1 to n * n, null arrays, empty position lists
+static void test_row_split() {
+  std::mt19937 rng(23);
+  const long n = 7;
+  for (long w : {1L, 2L, 6L, 7L, n * n}) {
+    std::vector<double> a((size_t)(n * w));
+    for (size_t i = 0; i < a.size(); ++i) a[i] = (double)i + 0.5;
+    // a split as splitIds makes it: every position in exactly one part or in `unknown`, the caller's order kept inside a part
+    te::Split sp;
+    sp.src.resize(3);
+    for (long i = 0; i < n; ++i) {
+      const unsigned k = rng() % 4;
+      if (k == 3) sp.unknown.push_back(i); else sp.src[k].push_back(i);
+    }
+    std::vector<double> back((size_t)(n * w), -1.0);
+    for (const auto& pos : sp.src) {
+      const std::vector<double> rows = te::gatherRows(a.data(), pos, w);
+      CHECK(rows.size() == pos.size() * (size_t)w);
+      for (size_t j = 0; j < pos.size(); ++j)
+        for (long c = 0; c < w; ++c) CHECK(rows[j * (size_t)w + (size_t)c] == a[(size_t)(pos[j] * w + c)]);
+      te::scatterRows(back.data(), rows, pos, w);
+    }
+    for (long i = 0; i < n; ++i) {   // the round trip restores every row that belongs to a part and touches no other
+      const bool unknown = std::find(sp.unknown.begin(), sp.unknown.end(), i) != sp.unknown.end();
+      for (long c = 0; c < w; ++c) CHECK(back[(size_t)(i * w + c)] == (unknown ? -1.0 : a[(size_t)(i * w + c)]));
+    }
+    // null arrays: nothing gathered, nothing written
+    CHECK(te::gatherRows((const double*)nullptr, sp.src[0], w).empty());
+    te::scatterRows((double*)nullptr, std::vector<double>(), sp.src[0], w);
+    // empty position lists
+    const std::vector<long> none;
+    CHECK(te::gatherRows(a.data(), none, w).empty());
+    std::vector<double> untouched = back;
+    te::scatterRows(back.data(), std::vector<double>(), none, w);
+    CHECK(back == untouched);
+
+    // RowsIn / RowsOut: pos == null is the caller's array itself, a null array stays null, a packed output comes back at pos
+    const std::vector<long> pos = {5, 0, 3};
+    te::RowsIn<double> whole(a.data(), nullptr, w), packed(a.data(), &pos, w), absent((const double*)nullptr, &pos, w);
+    CHECK(whole.get() == a.data() && absent.get() == nullptr && packed.get() != a.data());
+    for (size_t j = 0; j < pos.size(); ++j)
+      for (long c = 0; c < w; ++c) CHECK(packed.get()[j * (size_t)w + (size_t)c] == a[(size_t)(pos[j] * w + c)]);
+    te::RowsIn<double> nothing(a.data(), &none, w);   // (never read: a part without rows is not called)
+    (void)nothing;
+    std::vector<double> out((size_t)(n * w), -2.0);
+    te::RowsOut<double> direct(out.data(), nullptr, w), buffered(out.data(), &pos, w), missing((double*)nullptr, &pos, w);
+    CHECK(direct.get() == out.data() && missing.get() == nullptr && buffered.get() != out.data());
+    for (size_t j = 0; j < pos.size() * (size_t)w; ++j) { CHECK(buffered.get()[j] == 0.0); buffered.get()[j] = 100.0 + (double)j; }
+    direct.scatter();    // nothing to do
+    missing.scatter();   // nowhere to write
+    for (double v : out) CHECK(v == -2.0);
+    buffered.scatter();
+    for (long i = 0; i < n; ++i) {
+      const auto it = std::find(pos.begin(), pos.end(), i);
+      for (long c = 0; c < w; ++c)
+        CHECK(out[(size_t)(i * w + c)] == (it == pos.end() ? -2.0 : 100.0 + (double)((it - pos.begin()) * w + c)));
+    }
+  }
+  // new ids only: ids that exist and ids named twice in the call are left out and reported, in the caller's order
+  const unsigned ids[8] = {4, 9, 4, 2, 7, 9, 11, 2};
+  std::vector<unsigned> again;
+  const std::vector<long> keep = te::newIdsOnly(ids, 8, [](unsigned id) { return id == 7; }, [&](unsigned id) { again.push_back(id); });
+  CHECK(keep == std::vector<long>({0, 1, 3, 6}));
+  CHECK(again == std::vector<unsigned>({4, 7, 9, 2}));
+  CHECK(te::newIdsOnly(ids, 0, [](unsigned) { return false; }, [](unsigned) {}).empty());
+  CHECK(te::newIdsOnly(nullptr, -3, [](unsigned) { return false; }, [](unsigned) {}).empty());
+}
+
 int main() {
+  test_row_split();
   test_single_creations();
   test_batched_runs();
   test_erase_and_recreate();

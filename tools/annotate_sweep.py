@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Join tools/sweep.py output (stdin) with the compiler's resource table (profiles/r02_kernel_resources.txt) and mark the
-lanes codes the library picks by itself (csrc/target_manager.cpp chooseLayout, kf_model_*.hip defaults).
+lanes codes the library picks by itself (csrc/shard.cpp chooseLayout, kf_model_*.hip defaults).
     python tools/sweep.py --steps 100 --sizes 1000000 > gpurun_out/sweep.txt     (GPU box)
     python tools/annotate_sweep.py < gpurun_out/sweep.txt > profiles/r02_layout_sweep.txt"""
 import os
