@@ -206,6 +206,21 @@ int target_batch_lanes_per_target(target_batch_c* b);
 int target_batch_is_symmetric_packed(target_batch_c* b);
 /* 0 full P, 1 symmetric-packed, 2 axis-separable, 3 axis-separable with symmetric-packed groups */
 int target_batch_layout(target_batch_c* b);
+/* 1 if the batch is in the SHARED-AXES storage form of layout 3, else 0.  In every shipped model file the x, y and z chains
+ * have the same Q block, R entry and P0 block (and so have roll, pitch and yaw of angular_rates); the covariance recursion of a
+ * [p v (a)] chain reads nothing else but dt and the target's own has-measurement bit, so inside one target those blocks are the
+ * same bits on every tick.  An fp64 batch whose matrices pass that test exactly (doubles compared entry by entry, every P0
+ * handed in included) stores and steps ONE block per kind of axis: same results bit for bit, fewer bytes per tick
+ * (target_batch_algorithmic_bytes, target_batch_record_words and target_batch_resident_bytes_per_target report the form's
+ * own figures; target_batch_layout and target_batch_lanes_per_target do not change).  The batch is expanded to the plain
+ * records, once and for good, by the first call the form does not serve: a second (Q, R) class, a P0 whose blocks differ,
+ * target_batch_step_fused[_poses], target_batch_live_start / target_manager_live_start_all.  TE_SHARED_AXES=0 in the environment, or
+ * target_manager_set_shared_axes(m, 0) before the manager's first target is created (an error afterwards), keeps every
+ * batch plain. */
+int target_batch_shared_axes(target_batch_c* b);
+int target_manager_set_shared_axes(target_manager_c* self, int on);
+/* words of one target's record in HBM: x + unwrap memory + the stored words of P */
+int target_batch_record_words(target_batch_c* b);
 /* number of distinct (Q, R) parameter classes among the batch's targets */
 int target_batch_num_classes(target_batch_c* b);
 /* bytes one predict+update cycle of one target must move ((2n + 2n^2 + 7 (+6)) * w, or

@@ -61,6 +61,16 @@ double live_sessions_share() {
 
 
 const Ops* get_ops(int type, int dtype, int g) {
+  if (g == kLanesSeparableShared) {   // the shared-axes storage form of 301: fp64 only
+    if (dtype != F64) return nullptr;
+    switch (type) {
+      case UNIFORM_VELOCITY: return get_ops_shared_uv();
+      case UNIFORM_ACCELERATION: return get_ops_shared_ua();
+      case ANGULAR_RATES: return get_ops_shared_ar();
+      case ANGULAR_VELOCITIES: return get_ops_shared_av();
+      default: return nullptr;
+    }
+  }
   switch (type) {
     case UNIFORM_VELOCITY: return get_ops_uv(dtype, g);
     case UNIFORM_ACCELERATION: return get_ops_ua(dtype, g);
@@ -70,10 +80,35 @@ const Ops* get_ops(int type, int dtype, int g) {
   }
 }
 
-Batch::Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock)
+Batch::Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock, bool allow_shared)
     : type_(type), dtype_(dtype), lanes_code_(lanes), owner_lock_(owner_lock), ops_(get_ops(type, dtype, lanes)), stream_(stream) {
   if (!ops_) throw std::runtime_error("target_estimation_amd: unsupported (model, precision, lanes-per-target) combination");
+  if (allow_shared && lanes == kLanesSeparablePacked && dtype == F64 && shared_axes_qr_ok(type, Q, R)) {
+    const Ops* shared = get_ops(type, dtype, kLanesSeparableShared);
+    if (shared) ops_ = shared;
+  }
   add_class(Q, R);
+}
+
+void Batch::demote_shared() {
+  if (!shared_axes()) return;
+  flush();   // queued creations and one-target steps are for the records as they are
+  const Ops* plain = get_ops(type_, dtype_, lanes_code_);
+  if (cap_ > 0) {
+    const size_t bytes = (size_t)(cap_ / plain->L.tpw) * (size_t)plain->L.tile_bytes;
+    char* rec = nullptr;
+    TE_HIP_CHECK(hipMalloc((void**)&rec, bytes));
+    TE_HIP_CHECK(hipMemsetAsync(rec, 0, bytes, stream_));
+    ops_->expand(d_rec_, rec, n_, stream_);
+    TE_HIP_CHECK(hipGetLastError());
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+    device_free(d_rec_);
+    device_free(d_rec_alt_); d_rec_alt_ = nullptr; alt_failed_ = false;   // re-created in the plain form by the next A -> B tick
+    d_rec_ = rec;
+  }
+  ops_ = plain;
+  cache_valid_ = false;
+  drop_graphs();   // (the manager's all-batches recordings miss on dev_identity().ops)
 }
 
 static std::string class_key(const double* Q, int nq, const double* R, int nr) {
@@ -90,6 +125,7 @@ int Batch::find_class(const double* Q, const double* R) const {
 }
 
 int Batch::add_class(const double* Q, const double* R) {
+  if (n_classes_ >= 1) demote_shared();   // the shared-axes form has no per-class kernels
   const int n = ops_->L.n, m = ops_->L.m;
   const bool sep = ops_->L.layout == LAYOUT_SEPARABLE || ops_->L.layout == LAYOUT_SEPARABLE_PACKED;
   const int words = qr_words(type_, sep);   // te_layout.hpp: full [Q | R], or only the in-group entries (separable layouts)
@@ -273,11 +309,12 @@ long Batch::algorithmic_bytes_per_cycle() const {
   long pwords = 2 * n * n;
   if (ops_->L.layout == LAYOUT_PACKED) pwords = n * (n + 1);
   if (ops_->L.layout == LAYOUT_SEPARABLE || ops_->L.layout == LAYOUT_SEPARABLE_PACKED) {
-    // only the entries inside an axis group exist (the others are structural zeros): read + write
+    // only the entries inside an axis group exist (the others are structural zeros): read + write; in the shared-axes form
+    // only those of the first axis of every kind (te_layout.hpp share_rep): the form's own, smaller figure
     pwords = 0;
     for (int r = 0; r < n; ++r)
       for (int c = (ops_->L.layout == LAYOUT_SEPARABLE_PACKED ? r : 0); c < n; ++c)
-        pwords += group_of(type_, r) == group_of(type_, c) ? 2 : 0;
+        pwords += (group_of(type_, r) == group_of(type_, c) && (!shared_axes() || share_rep(type_, r) == r)) ? 2 : 0;
   }
   // measurement words the step kernel READS: [x y z] for the linear models, [x y z qx qy qz qw] for the angular
   // ones (kf_step_sep.hpp MW, kf_step.hpp ymeas_own/qmeas); SURVEY 8d's formula charges 7 for every model
@@ -344,6 +381,8 @@ long Batch::append(long count, const unsigned* ids, double t0, const double* P0,
                    const double* p0, const double* v0, const double* a0, int cls, const int* cls_of, const int* P0_index,
                    long P0_count) {
   const int N = ops_->L.n;
+  // the shared-axes form rests on every initial covariance having equal blocks on the axes of a kind: one that has not ends it
+  if (count > 0 && shared_axes() && !shared_axes_p0_ok(type_, P0, P0_index ? P0_count : (per_target_P0 ? count : 1))) demote_shared();
   // ONE target (the reference's TargetManager::init, called target by target): queued.  The slot, its id and the host
   // mirrors exist at once; the record is written by the next flush() -- one init launch for a whole run of creations with
   // the same (t0, P0, class) instead of three copies, a launch and a synchronisation each (28 us -> 0.3 us per target).
@@ -667,6 +706,7 @@ void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick
                        const unsigned char* has_base, long has_stride, const PoseStream& poses) {
   check_pose_stream(poses);
   touch();
+  demote_shared();   // (the temporally fused kernels exist for the plain form only)
   if (n_ == 0 || n_ticks <= 0) return;
   StepParams p = base_params();
   p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
@@ -687,6 +727,7 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
                        long ring_ticks, long first_entry, long max_ticks, double idle_limit_s, const double* q_origin, double q_radius,
                        double* q_delta_dev, double* q_pose_dev) {
   touch();   // ends a previous session, runs queued one-target steps
+  demote_shared();   // the resident kernels hold plain records (before the session exists: this frees device memory)
   if (q_delta_dev && !q_origin) throw std::invalid_argument("target_estimation_amd: live_start: query without an origin");
   if (n_ == 0) throw std::runtime_error("target_estimation_amd: live mode on an empty batch");
   if (!meas_ring || ring_ticks <= 0 || max_ticks <= 0 || first_entry < 0 || ld < n_ || tick_stride < 7 * ld || (has_ring && has_stride < n_))
@@ -1333,6 +1374,7 @@ void Batch::get_state(const int* slots, long n, double* x, double* P) {
 
 void Batch::set_state(const int* slots, long n, const double* x, const double* P, const double* unwrap) {
   touch();
+  demote_shared();   // a caller's P need not have equal blocks on the axes of a kind
   if (n <= 0) return;
   const int N = ops_->L.n;
   stage_reserve(n);

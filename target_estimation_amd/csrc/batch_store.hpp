@@ -33,7 +33,12 @@ class Batch {
   // `owner_lock`: the one mutex of the manager whose shard owns the batch (TargetManager::target_lock_, whatever the number
   // of shards); the C boundary takes it around every call made through a batch handle, so that those calls and the
   // manager's own are serialised
-  Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock = nullptr);
+  // allow_shared: an fp64 batch in the separable layout with packed groups (lanes 301) whose Q and R allow it (te_layout.hpp,
+  // shared_axes_qr_ok) starts in the shared-axes storage form: one covariance block per kind of axis instead of one per axis.
+  // Same results bit for bit, fewer bytes per tick.  The batch leaves the form for good (demote_shared) when something arrives
+  // that it does not serve; lanes_code() and layout().layout read 301 / 3 in both forms.
+  Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock = nullptr,
+        bool allow_shared = false);
   ~Batch();
   Batch(const Batch&) = delete;
   Batch& operator=(const Batch&) = delete;
@@ -45,6 +50,12 @@ class Batch {
   int n_state() const { return ops_->L.n; }
   int n_meas() const { return ops_->L.m; }
   const LayoutInfo& layout() const { return ops_->L; }
+  bool shared_axes() const { return ops_->L.shared_axes != 0; }
+  // Expand a shared-axes batch to the plain records of its layout, once and for good: a new record buffer, every kind's block
+  // copied to each of its axes (exact), the plain launch table from then on; recorded sequences are dropped.  Called by the batch
+  // itself ahead of what the shared form does not serve: a second (Q, R) class, an initial covariance whose blocks differ between
+  // the axes of a kind, step_fused, live_start, set_state.  No-op for a plain batch.
+  void demote_shared();
   long size() const { return n_; }
   bool getter_table_is_cheap() const { return n_ <= kCacheMax; }   // (its one-target getters read a host-resident table from the first call after a change)
   size_t elem_size() const { return dtype_ == F64 ? 8 : 4; }
@@ -123,7 +134,11 @@ class Batch {
   long live_stop();            // returns the ticks served
   bool live_active() const { return live_.active; }
   // targets a session can hold; with_outputs: one with the per-tick query or pose output (a larger kernel: fewer)
-  long live_capacity_targets(bool with_outputs = false) const { return ops_->live_capacity ? ops_->live_capacity(with_outputs ? 1 : 0) * ops_->L.tpw : 0; }
+  // (a shared-axes batch answers for the plain form, which is what live_start would run)
+  long live_capacity_targets(bool with_outputs = false) const {
+    const Ops* o = shared_axes() ? get_ops(type_, dtype_, lanes_code_) : ops_;
+    return o->live_capacity ? o->live_capacity(with_outputs ? 1 : 0) * o->L.tpw : 0;
+  }
   bool live_pose_output_set() const { return live_.pose_out != nullptr; }
   bool live_running() const { return live_.active && __atomic_load_n(live_.h_done + 2, __ATOMIC_ACQUIRE) == 0; }   // the relay has not left (its last store)
   // One tick over the listed slots, host inputs (meas rows follow the order of `slots`).
@@ -198,8 +213,9 @@ class Batch {
   void swap_records() { std::swap(d_rec_, d_rec_alt_); }
   void account_sequence(long n_ticks, double dt, bool all_measured);
   // identity of everything a recorded launch sequence refers to
-  struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; };
-  DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_}; }
+  // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
+  struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; };
+  DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_}; }
   void prepare() { touch(); }
 
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121), optional: see measured_pose.hpp

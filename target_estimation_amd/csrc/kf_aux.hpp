@@ -177,6 +177,25 @@ __global__ void move_records_kernel(char* rec, const int* src, const int* dst, l
   if (tid == 0) { t_base[d] = t_base[s]; nm_base[d] = nm_base[s]; if (cls) cls[d] = cls[s]; }
 }
 
+// A batch in the shared-axes storage form (te_layout.hpp) leaves it: slot by slot, x, the unwrap memory and every stored word of
+// P of the plain LAYOUT_SEPARABLE_PACKED record, read from the shared record (whose p_word maps every axis of a kind to the
+// kind's one block).  A copy: exact.  Once per batch at most, thread per target.
+template <class M, typename T>
+__global__ void expand_shared_kernel(char* rec, char* rec_plain, long n) {
+  using CS = Cfg<M, T, 1, LAYOUT_SEPARABLE_SHARED>;
+  using CP = Cfg<M, T, 1, LAYOUT_SEPARABLE_PACKED>;
+  constexpr int N = CS::N;
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n) return;
+  for (int r = 0; r < N; ++r) {
+    state_set<CP, T>(rec_plain, slot, r, N, state_get<CS, T>(rec, slot, r, N));
+    for (int c = r; c < N; ++c) state_set<CP, T>(rec_plain, slot, r, c, state_get<CS, T>(rec, slot, r, c));   // (no-op between groups)
+  }
+  if constexpr (M::ANGULAR) {
+    for (int cc = 0; cc < 3; ++cc) *unwrap_ptr<CP, T>(rec_plain, slot, cc) = *unwrap_ptr<CS, T>(rec, slot, cc);
+  }
+}
+
 // measurements: AoS doubles [n][7] (the reference's Vector7d rows) -> SoA T [7][ld]
 template <typename T>
 __global__ void pack_meas_kernel(const double* aos, long n, T* soa, long ld) {

@@ -77,6 +77,9 @@ struct Ops {
   void (*pack_meas)(const double* aos, long n, void* soa, long ld, hipStream_t);
   void (*intersect)(const IntersectArgs&, hipStream_t);
   void (*outputs_rows)(const OutArgs&, hipStream_t);   // outputs_rows_kernel: poses at OutArgs::row_of_slot
+  // shared-axes storage form only (L.shared_axes; null otherwise): write the n records of `rec` as plain LAYOUT_SEPARABLE_PACKED
+  // records into `rec_plain` (a zero-filled buffer of the plain form's tiles), every kind's block copied to each of its axes
+  void (*expand)(char* rec, char* rec_plain, long n, hipStream_t) = nullptr;
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported
@@ -85,5 +88,10 @@ const Ops* get_ops_uv(int dtype, int g);
 const Ops* get_ops_ua(int dtype, int g);
 const Ops* get_ops_ar(int dtype, int g);
 const Ops* get_ops_av(int dtype, int g);
+// the shared-axes storage form of the separable layout with packed groups (lanes code kLanesSeparableShared, fp64)
+const Ops* get_ops_shared_uv();
+const Ops* get_ops_shared_ua();
+const Ops* get_ops_shared_ar();
+const Ops* get_ops_shared_av();
 
 }  // namespace te

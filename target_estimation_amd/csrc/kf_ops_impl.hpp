@@ -62,6 +62,10 @@ struct OpsImpl {
                                                (M::TYPE == ANGULAR_RATES || M::TYPE == UNIFORM_ACCELERATION);
   static void step(const StepParams& p, hipStream_t s) {
     if (p.n <= 0) return;
+    if constexpr (C::SHARED) {   // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
+      if (p.live_posted || p.cls || p.n_ticks > 1)
+        throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
+    }
     StepArgs<T> a = make_step_args<T>(p);
     if (p.live_posted) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
       if constexpr (kHasLive) {
@@ -150,16 +154,20 @@ struct OpsImpl {
       const int wpb = waves <= small_grid ? 1 : 4;
       const unsigned b4 = (unsigned)((waves + wpb - 1) / wpb);
       const dim3 blk(64 * wpb);
-      if (p.cls && p.idx)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, true, false, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.cls && p.rec_out)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.cls)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true>), dim3(b4), blk, 0, s, a);
+      if (p.cls) {
+        if constexpr (!C::SHARED) {
+          if (p.idx)
+            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, true, false, false, true>), dim3(b4), blk, 0, s, a);
+          else if (p.rec_out)
+            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true, false, true>), dim3(b4), blk, 0, s, a);
+          else
+            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true>), dim3(b4), blk, 0, s, a);
+        }
+      }
       else if (p.pose && p.rec_out)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, true, true>), dim3(b4), blk, 0, s, a);
       else if (p.pose && p.n_ticks > 1) {
-        if constexpr (!kFusedPoseTickByTick)
+        if constexpr (!kFusedPoseTickByTick && !C::SHARED)
           hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
       }
       else if (p.pose && p.q_delta)
@@ -168,8 +176,10 @@ struct OpsImpl {
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
       else if (p.rec_out)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.n_ticks > 1)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true>), dim3(b4), blk, 0, s, a);
+      else if (p.n_ticks > 1) {
+        if constexpr (!C::SHARED)
+          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true>), dim3(b4), blk, 0, s, a);
+      }
       else if (p.idx)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, true>), dim3(b4), blk, 0, s, a);
       else if (p.q_delta)
@@ -239,10 +249,18 @@ struct OpsImpl {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((intersect_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
   }
+  static void expand(char* rec, char* rec_plain, long n, hipStream_t s) {
+    if constexpr (C::SHARED) {
+      if (n <= 0) return;
+      hipLaunchKernelGGL((expand_shared_kernel<M, T>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, rec, rec_plain, n);
+    }
+  }
   static const Ops* get() {
+    // (host code sees the shared-axes form as layout 3 with the flag set: te_layout.hpp)
     static const Ops ops = {
-        LayoutInfo{C::N, C::K, G, LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD},
-        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows};
+        LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0},
+        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows,
+        C::SHARED ? &expand : nullptr};
     return &ops;
   }
 };

@@ -8,17 +8,19 @@ namespace te {
 
 // the grid of a population tick, POSE or not (the POSE variants are instantiated in kf_population_f{64,32}_pose.hip: one
 // population translation unit already takes a minute to compile, so the pose stream's three kernels per precision get their own)
-template <typename T, bool POSE>
+// SHARED: the parts are batches in the shared-axes storage form (fp64; kf_population_f64_shared{,_pose}.hip)
+template <typename T, bool POSE, bool SHARED = false>
 void launch_population_grid(const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s) {
   const dim3 blk(64 * wpb);
-  if (query) hipLaunchKernelGGL((kf_step_population_kernel<T, true, false, POSE>), dim3(blocks), blk, 0, s, p);
-  else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true, POSE>), dim3(blocks), blk, 0, s, p);
-  else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, POSE>), dim3(blocks), blk, 0, s, p);
+  if (query) hipLaunchKernelGGL((kf_step_population_kernel<T, true, false, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
+  else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
+  else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
 }
+void launch_population_grid_pose_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
 void launch_population_grid_pose(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
 void launch_population_grid_pose(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
 
-template <typename T>
+template <typename T, bool SHARED = false>
 void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s) {
   constexpr int TPW = 64;   // thread per target in every separable layout
   PopulationArgs<T> p;
@@ -47,8 +49,13 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   }
   if (end == 0) return;
   p.reverse_blocks = reverse ? 1 : 0;
-  if (pose) launch_population_grid_pose(p, end, (unsigned)wpb, query, ab, s);
-  else launch_population_grid<T, false>(p, end, (unsigned)wpb, query, ab, s);
+  if constexpr (SHARED) {
+    if (pose) launch_population_grid_pose_shared(p, end, (unsigned)wpb, query, ab, s);
+    else launch_population_grid<T, false, true>(p, end, (unsigned)wpb, query, ab, s);
+  } else {
+    if (pose) launch_population_grid_pose(p, end, (unsigned)wpb, query, ab, s);
+    else launch_population_grid<T, false>(p, end, (unsigned)wpb, query, ab, s);
+  }
 }
 
 }  // namespace te

@@ -75,6 +75,82 @@ __device__ __forceinline__ void sep_linear_axis(T* x, T (&P)[NB][NB], const T (&
   }
 }
 
+// The same step as two halves that meet only in the gain Kg, for batches in the shared-axes storage form (te_layout.hpp,
+// share_rep), which run the covariance half once per KIND of axis and the state half per axis with the kind's Kg:
+//   sep_linear_cov   : P^- = A P A^T + Q, and with a measurement S^-1, Kg = P^-[:,0] / S, P = (I - Kg C) P^-.  Reads P, Q, R, dt
+//                      and `has` -- never x or the measurement.
+//   sep_linear_state : x^- = A x, and with a measurement x += Kg (y - x0).
+// Operation for operation the statements of sep_linear_axis above, which stays as it is for every other batch: the register
+// allocation of the kernels that sit at an occupancy limit follows its statement order (built from the halves, the per-class
+// angular_rates fp64 kernels spilled 116 B per lane and the resident ones lost a wavefront per SIMD).  tests/test_gpu_shared_axes.py
+// holds the two forms to the same bits.
+template <int NB, typename T>
+__device__ __forceinline__ void sep_linear_cov(T (&P)[NB][NB], const T (&Q)[NB][NB], T r_meas, T dt, bool has, T (&Kg)[NB]) {
+#pragma clang fp contract(off)  // only the explicit fma calls fuse: same roundings as the dense kernel
+  using F = Mth<T>;
+  const T hdt = (T)0.5 * dt * dt;
+  // AP = A P (rows)
+#pragma unroll
+  for (int b = 0; b + 1 < NB; ++b) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      T v = F::fma(dt, P[b + 1][c], P[b][c]);
+      if (NB == 3 && b == 0) v = F::fma(hdt, P[b + 2][c], v);
+      P[b][c] = v;
+    }
+  }
+  // (AP) A^T (columns), + Q
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      T v = P[b][c];
+      if (c + 1 < NB) {
+        v = F::fma(dt, P[b][c + 1], v);
+        if (NB == 3 && c == 0) v = F::fma(hdt, P[b][c + 2], v);
+      }
+      P[b][c] = v + Q[b][c];
+    }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) Kg[b] = (T)0;   // (unused without a measurement)
+  if (!has) return;
+  // S = P00 + R ; K = P[:,0] / S ; P = (I - K C) P
+  const T inv = (T)1 / (P[0][0] + r_meas);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) Kg[b] = P[b][0] * inv;
+  T top[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) top[c] = P[0][c];
+  const T d0 = (T)1 - Kg[0];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) {
+    P[0][c] = d0 * top[c];
+#pragma unroll
+    for (int b = 1; b < NB; ++b) {
+      const T t = ((T)0 - Kg[b]) * top[c];
+      P[b][c] = t + P[b][c];
+    }
+  }
+}
+
+template <int NB, typename T>
+__device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, const T (&Kg)[NB]) {
+#pragma clang fp contract(off)
+  using F = Mth<T>;
+  const T hdt = (T)0.5 * dt * dt;
+  // x^- = A x
+#pragma unroll
+  for (int b = 0; b + 1 < NB; ++b) {
+    x[b] = F::fma(dt, x[b + 1], x[b]);
+    if (NB == 3 && b == 0) x[b] = F::fma(hdt, x[b + 2], x[b]);
+  }
+  if (!has) return;
+  // x += K (y - x0)
+  const T nu = y - x[0];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
+}
+
 // QUERY: the own-time sphere-intersection query of the target (kf_aux.hpp, sphere_query) runs on the
 // posterior state while it is still in registers -- BASELINE.json configs[4], "per-step interception
 // point fused on-GPU": one launch per tick instead of step + query.
@@ -154,6 +230,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   static_assert(!LIVE || (FUSED && !INDEXED && !QUERY && !PERQR), "live launches are dense multi-tick launches");
   using C = Cfg<M, T, 1, LAYOUT>;
   static_assert(C::SEP, "separable layouts only");
+  static_assert(!C::SHARED || (!FUSED && !PERQR && !LIVE), "the shared-axes storage form: single-tick launches of one-class batches (the host expands the batch first)");
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -282,12 +359,17 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   // Q and R of every chain are uniform (scalar loads): when they fit the scalar registers they are requested
   // once, here, behind the record loads, instead of chain by chain with a wait each (a serial chain of
   // scalar-cache round trips that a small, latency-bound batch feels directly).
-  constexpr int QR_NEED = NLIN * LB * LB + NLIN + (M::EKF ? 36 + 9 : 0);
+  // Shared-axes form: axis i takes the covariance half of its chain from the first axis of its kind (`lead`); only the lead
+  // chains have P words in the record and read Q and R.
+  auto lead = [](int i) constexpr { return !C::SHARED || i % 3 == 0; };
+  constexpr int NCOV = C::SHARED ? NLIN / 3 : NLIN;   // chains whose covariance half runs
+  constexpr int QR_NEED = NCOV * LB * LB + NCOV + (M::EKF ? 36 + 9 : 0);
   constexpr bool HOIST_QR = !PERQR && QR_NEED * (int)sizeof(T) <= 256;
   T Qlin[HOIST_QR ? NLIN : 1][LB][LB], Rlin[HOIST_QR ? NLIN : 1], Qatt[HOIST_QR && M::EKF ? 6 : 1][6], Ratt[HOIST_QR && M::EKF ? 3 : 1][3];
   if constexpr (HOIST_QR) {
 #pragma unroll
     for (int i = 0; i < NLIN; ++i) {
+      if (!lead(i)) continue;
 #pragma unroll
       for (int b = 0; b < LB; ++b)
 #pragma unroll
@@ -344,6 +426,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     if (tick == 0) {
 #pragma unroll
       for (int i = 0; i < NLIN; ++i) {
+        if (!lead(i)) continue;
 #pragma unroll
         for (int b = 0; b < LB; ++b)
 #pragma unroll
@@ -381,65 +464,109 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #define XS_(r, v) WR(C::X_OFF + (r), (v))
 
   // ---- the [p v (a)] chains
+  if constexpr (C::SHARED) {
+    // one covariance half per kind of axis (its lead axis i % 3 == 0 owns the kind's block), one state half per axis
+    T Kg[LB];
 #pragma unroll
-  for (int i = 0; i < NLIN; ++i) {
-    T xs[LB], Pb[LB][LB], Qb[LB][LB];
-    T r_meas = T(0);   // (every path assigns it; the per-class branches hide that from the compiler)
+    for (int b = 0; b < LB; ++b) Kg[b] = T(0);
 #pragma unroll
-    for (int b = 0; b < LB; ++b) {
-      xs[b] = XR_(i + STRIDE * b);
-#pragma unroll
-      for (int c = 0; c < LB; ++c) Pb[b][c] = RD(C::PWORD.v[i + STRIDE * b][i + STRIDE * c]);
-    }
-    if constexpr (HOIST_QR) {
-#pragma unroll
-      for (int b = 0; b < LB; ++b)
-#pragma unroll
-        for (int c = 0; c < LB; ++c) Qb[b][c] = Qlin[i][b][c];
-      r_meas = Rlin[i];
-    } else {
-      if constexpr (PERQR) {
-        const T* Qsrc = lane_row();
-        if (cls_uniform) {   // wave-uniform branch: scalar loads from the one row
-#pragma unroll
-          for (int b = 0; b < LB; ++b)
-#pragma unroll
-            for (int c = 0; c < LB; ++c) Qb[b][c] = Qu[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
-          r_meas = Qu[C::RWORD.v[i][i]];
-          Qsrc = nullptr;
-        }
-        if (Qsrc != nullptr) {
-#pragma unroll
-          for (int b = 0; b < LB; ++b)
-#pragma unroll
-            for (int c = 0; c < LB; ++c) Qb[b][c] = Qsrc[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
-          r_meas = Qsrc[C::RWORD.v[i][i]];
-        }
-      } else {
+    for (int i = 0; i < NLIN; ++i) {
+      if (lead(i)) {   // (a constant once the loop is unrolled)
+        T Pb[LB][LB], Qb[LB][LB];
 #pragma unroll
         for (int b = 0; b < LB; ++b)
 #pragma unroll
-          for (int c = 0; c < LB; ++c) Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
-        r_meas = Qm[C::RWORD.v[i][i]];
+          for (int c = 0; c < LB; ++c) {
+            Pb[b][c] = mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            if constexpr (HOIST_QR) Qb[b][c] = Qlin[i][b][c];
+            else Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+          }
+        T r_meas;
+        if constexpr (HOIST_QR) r_meas = Rlin[i];
+        else r_meas = Qm[C::RWORD.v[i][i]];
+        sep_linear_cov<LB, T>(Pb, Qb, r_meas, dt, has, Kg);
+#pragma unroll
+        for (int b = 0; b < LB; ++b)
+#pragma unroll
+          for (int c = b; c < LB; ++c) mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]] = Pb[b][c];
       }
+      T xs[LB];
+#pragma unroll
+      for (int b = 0; b < LB; ++b) xs[b] = XW_(i + STRIDE * b);
+      T y = 0;
+      if (has) {
+        if (!M::ANGULAR || i < 3) {
+          y = ymeas[i];
+        } else {
+          y = unwrap_angle(UWW_(i - 3), mrpy[i - 3]);   // angular_rates.cpp:85-88
+          UWW_(i - 3) = y;
+        }
+      }
+      sep_linear_state<LB, T>(xs, dt, has, y, Kg);
+#pragma unroll
+      for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
     }
-    T y = 0;
-    if (has) {
-      if (!M::ANGULAR || i < 3) {
-        y = ymeas[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < NLIN; ++i) {
+      T xs[LB], Pb[LB][LB], Qb[LB][LB];
+      T r_meas = T(0);   // (every path assigns it; the per-class branches hide that from the compiler)
+#pragma unroll
+      for (int b = 0; b < LB; ++b) {
+        xs[b] = XR_(i + STRIDE * b);
+#pragma unroll
+        for (int c = 0; c < LB; ++c) Pb[b][c] = RD(C::PWORD.v[i + STRIDE * b][i + STRIDE * c]);
+      }
+      if constexpr (HOIST_QR) {
+#pragma unroll
+        for (int b = 0; b < LB; ++b)
+#pragma unroll
+          for (int c = 0; c < LB; ++c) Qb[b][c] = Qlin[i][b][c];
+        r_meas = Rlin[i];
       } else {
-        y = unwrap_angle(UWW_(i - 3), mrpy[i - 3]);   // angular_rates.cpp:85-88
-        UWW_(i - 3) = y;
+        if constexpr (PERQR) {
+          const T* Qsrc = lane_row();
+          if (cls_uniform) {   // wave-uniform branch: scalar loads from the one row
+#pragma unroll
+            for (int b = 0; b < LB; ++b)
+#pragma unroll
+              for (int c = 0; c < LB; ++c) Qb[b][c] = Qu[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            r_meas = Qu[C::RWORD.v[i][i]];
+            Qsrc = nullptr;
+          }
+          if (Qsrc != nullptr) {
+#pragma unroll
+            for (int b = 0; b < LB; ++b)
+#pragma unroll
+              for (int c = 0; c < LB; ++c) Qb[b][c] = Qsrc[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            r_meas = Qsrc[C::RWORD.v[i][i]];
+          }
+        } else {
+#pragma unroll
+          for (int b = 0; b < LB; ++b)
+#pragma unroll
+            for (int c = 0; c < LB; ++c) Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+          r_meas = Qm[C::RWORD.v[i][i]];
+        }
       }
-    }
-    sep_linear_axis<LB, T>(xs, Pb, Qb, r_meas, dt, has, y);
+      T y = 0;
+      if (has) {
+        if (!M::ANGULAR || i < 3) {
+          y = ymeas[i];
+        } else {
+          y = unwrap_angle(UWW_(i - 3), mrpy[i - 3]);   // angular_rates.cpp:85-88
+          UWW_(i - 3) = y;
+        }
+      }
+      sep_linear_axis<LB, T>(xs, Pb, Qb, r_meas, dt, has, y);
 #pragma unroll
-    for (int b = 0; b < LB; ++b) {
-      XS_(i + STRIDE * b, xs[b]);
+      for (int b = 0; b < LB; ++b) {
+        XS_(i + STRIDE * b, xs[b]);
 #pragma unroll
-      for (int c = (C::SEPPK ? b : 0); c < LB; ++c) WR(C::PWORD.v[i + STRIDE * b][i + STRIDE * c], Pb[b][c]);
+        for (int c = (C::SEPPK ? b : 0); c < LB; ++c) WR(C::PWORD.v[i + STRIDE * b][i + STRIDE * c], Pb[b][c]);
+      }
+      if constexpr (NPARK > 0) __builtin_amdgcn_sched_barrier(0);   // a parked chain's words are read when its turn comes, not ahead of it
     }
-    if constexpr (NPARK > 0) __builtin_amdgcn_sched_barrier(0);   // a parked chain's words are read when its turn comes, not ahead of it
   }
 
   // ---- EKF attitude group: local rows 0..2 = rpy (global 3..5), 3..5 = omega (global 9..11)
@@ -764,13 +891,14 @@ struct PopulationArgs {
   int reverse_blocks;      // zig-zag over the whole population: walk the workgroups (parts and their tiles) last to first
 };
 
-template <typename T, bool QUERY, bool AB, bool POSE = false>
+// SHARED: every part is a batch in the shared-axes storage form (te_layout.hpp LAYOUT_SEPARABLE_SHARED; fp64 only).
+template <typename T, bool QUERY, bool AB, bool POSE = false, bool SHARED = false>
 __global__ void __launch_bounds__(256) kf_step_population_kernel(const PopulationArgs<T> p) {
   const int lane = (int)(threadIdx.x & 63);
   const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
   unsigned b = blockIdx.x;
   if (p.reverse_blocks) b = gridDim.x - 1 - b;
-  constexpr int L = LAYOUT_SEPARABLE_PACKED;
+  constexpr int L = SHARED ? LAYOUT_SEPARABLE_SHARED : LAYOUT_SEPARABLE_PACKED;
   if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[0], (long)b * wpb + wave, lane);
   else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
   else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);

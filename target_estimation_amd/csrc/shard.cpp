@@ -127,6 +127,10 @@ bool is_axis_separable(int type, const double* Q, const double* R, const double*
   return true;
 }
 
+bool axes_shareable(int type, const double* Q, const double* R, const double* P0, long n_P0) {
+  return is_axis_separable(type, Q, R, P0, n_P0) && shared_axes_qr_ok(type, Q, R) && shared_axes_p0_ok(type, P0, n_P0);
+}
+
 // exact symmetry of Q, R and every P0 (covariances are; the reference accepts any matrix)
 static bool all_symmetric(int type, const double* Q, const double* R, const double* P0, long n_P0) {
   const int n = model_n(type), m = model_m(type);
@@ -179,7 +183,8 @@ int Shard::findOrCreateBatch(int type, const double* Q, const double* R, int lan
       if (cls < 0) cls = batches_[b]->add_class(Q, R);
       return (int)b;
     }
-  batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_));
+  // (the batch itself decides from Q and R whether it starts in the shared-axes form, and from every P0 whether it stays in it)
+  batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes));
   if (set_.keep_meas) batches_.back()->set_keep_measurement(true);
   cls = 0;
   return (int)batches_.size() - 1;
@@ -726,15 +731,16 @@ void Shard::dropSeqGraphs() {
 // model.  ShardSettings::population_tick off (TE_POPULATION_TICK=0) keeps the launch per batch (experiments, and the comparison in profiles/).
 bool Shard::populationTick() const {
   if (!set_.population_tick) return false;
-  int present = 0;
+  int present = 0, shared = 0;
   bool seen[4] = {false, false, false, false};
   for (const auto& b : batches_) {
     if (b->size() == 0) continue;
     if (!b->population_ready() || b->type() < 0 || b->type() > 3 || seen[b->type()]) return false;
     seen[b->type()] = true;
     ++present;
+    shared += b->shared_axes() ? 1 : 0;
   }
-  return present >= 2;
+  return present >= 2 && (shared == 0 || shared == present);   // (one kernel steps all parts: all in the shared-axes form, or none)
 }
 
 void Shard::enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin,
@@ -742,7 +748,7 @@ void Shard::enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch
   StepParams parts[4];
   for (auto& q : parts) { q = StepParams{}; q.n = 0; q.idx = nullptr; }
   Batch* swap[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ab_all = ab;
+  bool ab_all = ab, shared = false;
   for (int pass = 0; pass < 2; ++pass) {   // (a batch without room for its second record buffer puts the whole tick in place)
     for (size_t b = 0; b < batches_.size(); ++b) {
       if (batches_[b]->size() == 0) continue;
@@ -750,11 +756,12 @@ void Shard::enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch
       parts[t] = batches_[b]->tick_params(s, dt, specs[b], query, origin, radius, ab_all);
       if (ab_all && !parts[t].rec_out) { ab_all = false; break; }
       swap[t] = batches_[b].get();
+      shared = batches_[b]->shared_axes();   // (populationTick: the same for every non-empty batch)
     }
     if (ab_all == ab || pass == 1) break;
   }
   if (!ab_all) for (auto& q : parts) q.rec_out = nullptr;
-  launch_population_step(set_.dtype, parts, query, ab_all, reverse, st);
+  launch_population_step(set_.dtype, parts, query, ab_all, reverse, st, shared);
   if (ab_all) for (auto* b : swap) if (b) b->swap_records();
 }
 
@@ -802,7 +809,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
              x.poses.dev == y.poses.dev && x.poses.ld == y.poses.ld && x.poses.tick_stride == y.poses.tick_stride && x.poses.ring == y.poses.ring;
     };
     auto same_id = [](const Batch::DevIdentity& x, const Batch::DevIdentity& y) {
-      return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n;
+      return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n && x.ops == y.ops;
     };
     SeqGraph* hit = nullptr;
     for (auto& g : seq_graphs_) {

@@ -23,6 +23,9 @@ struct ResolveCounters;   // id_resolve.hpp (kernels: included by shard.cpp only
 
 // true if Q, R and the n_P0 covariances have no entry between different axis groups (te_layout.hpp)
 bool is_axis_separable(int type, const double* Q, const double* R, const double* P0, long n_P0);
+// true if, on top of that, the axes of every kind (x, y, z; roll, pitch, yaw of angular_rates) have equal Q blocks, R entries and
+// blocks in each of the n_P0 covariances, compared exactly: what the shared-axes storage form needs (te_layout.hpp, Batch)
+bool axes_shareable(int type, const double* Q, const double* R, const double* P0, long n_P0);
 // unit quaternion [x y z w] -> rotation matrix (row-major), Eigen's Quaterniond::toRotationMatrix
 void host_quat_to_rot(const double* q, double* R);
 
@@ -43,6 +46,7 @@ struct ShardSettings {
   int filters_length = 250;   // setIntersectionFiltersLength
   long small_batch_most = 0;  // the largest host-array call that goes through the one-target queue (TE_SMALL_BATCH_QUEUE)
   bool population_tick = true;   // TE_POPULATION_TICK
+  bool shared_axes = true;       // TE_SHARED_AXES / TargetManager::setSharedAxes: new fp64 batches may use the shared-axes storage form (Batch)
 };
 
 // one target's log rows, formatted per channel (TargetManager::log); batch: the shard's batch index as logCollect leaves it

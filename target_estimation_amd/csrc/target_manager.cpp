@@ -28,6 +28,8 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) {
   settings_.small_batch_most = most;
   static const bool pop = [] { const char* e = std::getenv("TE_POPULATION_TICK"); return !(e && e[0] == '0'); }();
   settings_.population_tick = pop;
+  static const bool shared = [] { const char* e = std::getenv("TE_SHARED_AXES"); return !(e && e[0] == '0'); }();
+  settings_.shared_axes = shared;
   const char* ld = std::getenv("TARGET_ESTIMATION_LOG_DIR");
   if (ld && ld[0]) { log_dir_ = ld; settings_.keep_meas = true; }   // batches created later inherit the measured-pose rows
   int count = 0;
@@ -125,6 +127,13 @@ void TargetManager::setLogTargets(const unsigned* ids, long n) {
   log_ids_.assign(ids, ids + (n > 0 ? n : 0));
   std::sort(log_ids_.begin(), log_ids_.end());
   log_ids_.erase(std::unique(log_ids_.begin(), log_ids_.end()), log_ids_.end());
+}
+
+void TargetManager::setSharedAxes(bool on) {
+  lock_guard<mutex> lg(target_lock_);
+  for (const auto& sh : shards_)
+    if (!sh->batches().empty()) throw std::runtime_error("target_estimation_amd: setSharedAxes: set it before the first target is created");
+  settings_.shared_axes = on;
 }
 
 void TargetManager::setKeepMeasurement(bool on) {

@@ -89,6 +89,10 @@ class TargetManager {
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121): kept only on request (measured_pose.hpp)
   void setKeepMeasurement(bool on);
   bool keepMeasurement() const { return settings_.keep_meas; }
+  // May the fp64 batches this manager creates use the shared-axes storage form (batch_store.hpp)?  Default: yes unless
+  // TE_SHARED_AXES=0.  Batches that exist keep their form, so set it before the first init; throws once there is a batch.
+  void setSharedAxes(bool on);
+  bool sharedAxes() const { return settings_.shared_axes; }
   bool getTargetMeasuredPose(unsigned id, double* pose7);          // false: unknown id or not kept
   // TargetInterface::getPeriodEstimate (target_interface.cpp:80-87): 2 pi / |omega| of the current twist, -1 if not rotating
   bool getTargetPeriodEstimate(unsigned id, double& period);

@@ -362,6 +362,12 @@ int target_batch_is_symmetric_packed(target_batch_c* b) {
 int target_batch_layout(target_batch_c* b) {
   return guarded_value<int>("target_batch_layout", -1, [&]() -> int { return B(b)->layout().layout; });
 }
+int target_batch_shared_axes(target_batch_c* b) {
+  return guarded_value<int>("target_batch_shared_axes", -1, [&]() -> int { return B(b)->shared_axes() ? 1 : 0; });
+}
+int target_batch_record_words(target_batch_c* b) {
+  return guarded_value<int>("target_batch_record_words", -1, [&]() -> int { return B(b)->layout().record_words; });
+}
 long target_batch_algorithmic_bytes(target_batch_c* b) {
   return guarded_value<long>("target_batch_algorithmic_bytes", -1, [&]() -> long { return B(b)->algorithmic_bytes_per_cycle(); });
 }
@@ -650,6 +656,9 @@ void target_intersection_solver_last_errors(target_intersection_solver_c* solver
 }
 
 // ---------------------------------------------------------------- TargetInterface / estimator getters
+int target_manager_set_shared_axes(target_manager_c* self, int on) {
+  return guarded("target_manager_set_shared_axes", [&] { M(self)->setSharedAxes(on != 0); });
+}
 int target_manager_set_keep_measurement(target_manager_c* self, int on) {
   return guarded("target_manager_set_keep_measurement", [&] { M(self)->setKeepMeasurement(on != 0); });
 }

@@ -43,10 +43,48 @@ struct ModelUA { static constexpr int TYPE = UNIFORM_ACCELERATION, N = 9, K = 3,
 struct ModelAR { static constexpr int TYPE = ANGULAR_RATES, N = 18, K = 6, NB = 3; static constexpr bool ANGULAR = true, EKF = false; };
 struct ModelAV { static constexpr int TYPE = ANGULAR_VELOCITIES, N = 12, K = 6, NB = 2; static constexpr bool ANGULAR = true, EKF = true; };
 
-enum Layout : int { LAYOUT_FULL = 0, LAYOUT_PACKED = 1, LAYOUT_SEPARABLE = 2, LAYOUT_SEPARABLE_PACKED = 3 };
+// LAYOUT_SEPARABLE_SHARED is not a public layout but a second STORAGE FORM of LAYOUT_SEPARABLE_PACKED ("shared axes"): the
+// axes of one kind -- x, y, z of every model; roll, pitch, yaw of angular_rates -- keep ONE covariance block between them
+// (see share_rep below).  Host code sees it as layout 3 with LayoutInfo::shared_axes set.
+enum Layout : int { LAYOUT_FULL = 0, LAYOUT_PACKED = 1, LAYOUT_SEPARABLE = 2, LAYOUT_SEPARABLE_PACKED = 3, LAYOUT_SEPARABLE_SHARED = 4 };
+constexpr int kLanesSeparablePacked = 301;   // lanes code of LAYOUT_SEPARABLE_PACKED (1 + TARGET_LAYOUT_AXIS_SEPARABLE_PACKED)
+constexpr int kLanesSeparableShared = 401;   // internal: its shared-axes storage form (never reported: Batch::lanes_code stays 301)
 
 constexpr int model_n(int type) { return type == UNIFORM_VELOCITY ? 6 : type == UNIFORM_ACCELERATION ? 9 : type == ANGULAR_RATES ? 18 : 12; }
 constexpr int model_m(int type) { return (type == UNIFORM_VELOCITY || type == UNIFORM_ACCELERATION) ? 3 : 6; }
+
+// Shared axes.  The covariance part of a [p v (a)] chain (kf_step_sep.hpp, sep_linear_cov) reads the chain's P block, its Q
+// block, its R entry, dt and the target's `has` bit -- never x or the measurement, and dt / has are per target.  Chains of one
+// KIND whose Q block, R entry and P0 block are equal therefore carry the same P block, bit for bit, on every tick: it is stored
+// and stepped once.  Kinds: the translational axes {0, 1, 2} of every model, the rotational axes {3, 4, 5} of angular_rates
+// (the attitude of angular_velocities is one coupled EKF group and is never shared).
+// share_rep(type, r): the row whose block stands for row r's -- the same state of the FIRST axis of r's kind (r itself for a
+// row that is not shared).
+constexpr int share_rep(int type, int r) {
+  const int k = model_m(type);   // axes = rows r % k
+  const int axis = r % k;
+  return (axis < 3 || type == ANGULAR_RATES) ? r - axis % 3 : r;
+}
+// May a batch with these matrices use the shared form?  Exact comparison of doubles, entry by entry, of every axis of a kind
+// with the kind's first axis: the Q blocks and R entries ...
+inline bool shared_axes_qr_ok(int type, const double* Q, const double* R) {
+  const int n = model_n(type), m = model_m(type);
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < n; ++c)
+      if (group_of(type, r) == group_of(type, c) && Q[r * n + c] != Q[share_rep(type, r) * n + share_rep(type, c)]) return false;
+  for (int r = 0; r < m; ++r)
+    if (R[r * m + r] != R[share_rep(type, r) * m + share_rep(type, r)]) return false;
+  return true;
+}
+// ... and the blocks of every one of the n_P0 initial covariances handed in
+inline bool shared_axes_p0_ok(int type, const double* P0, long n_P0) {
+  const int n = model_n(type);
+  for (long k = 0; k < n_P0; ++k)
+    for (int r = 0; r < n; ++r)
+      for (int c = 0; c < n; ++c)
+        if (group_of(type, r) == group_of(type, c) && P0[k * n * n + r * n + c] != P0[k * n * n + share_rep(type, r) * n + share_rep(type, c)]) return false;
+  return true;
+}
 
 // Position of Q(r, c) / R(r, c) inside one parameter-class row of a batch's (Q, R) table.  Dense layouts: the full
 // matrices, row-major, [Q | R].  Separable layouts: only the entries inside an axis group (the others are zero by the
@@ -103,9 +141,13 @@ struct Cfg {
   static constexpr int G = G_;
   static constexpr int LAYOUT = LAYOUT_;
   static constexpr bool PK = LAYOUT_ == LAYOUT_PACKED;
-  static constexpr bool SEP = LAYOUT_ == LAYOUT_SEPARABLE || LAYOUT_ == LAYOUT_SEPARABLE_PACKED;
-  static constexpr bool SEPPK = LAYOUT_ == LAYOUT_SEPARABLE_PACKED;   // group blocks stored as upper triangles
-  static_assert(!(LAYOUT_ == LAYOUT_SEPARABLE || LAYOUT_ == LAYOUT_SEPARABLE_PACKED) || G_ == 1, "separable storage uses the thread-per-target mapping");
+  static constexpr bool SHARED = LAYOUT_ == LAYOUT_SEPARABLE_SHARED;  // packed groups, one block per kind of axis (share_rep)
+  static constexpr bool SEP = LAYOUT_ == LAYOUT_SEPARABLE || LAYOUT_ == LAYOUT_SEPARABLE_PACKED || SHARED;
+  static constexpr bool SEPPK = LAYOUT_ == LAYOUT_SEPARABLE_PACKED || SHARED;   // group blocks stored as upper triangles
+  static_assert(!SEP || G_ == 1, "separable storage uses the thread-per-target mapping");
+  static_assert(!SHARED || sizeof(T) == 8, "the shared-axes storage form is fp64 only");
+  // does the record hold a word for (r, c), r and c in one group?  (shared form: only for the first axis of a kind)
+  static constexpr bool stored_row(int r) { return !SHARED || share_rep(M::TYPE, r) == r; }
   static constexpr int N = M::N, K = M::K, NB = M::NB;
   static_assert(K % G == 0, "lanes per target must divide the block size");
   static constexpr int RPL = N / G;           // rows of x / P per lane
@@ -116,7 +158,7 @@ struct Cfg {
   static constexpr int sep_count() {
     int k = 0;
     for (int r = 0; r < M::N; ++r)
-      for (int c = (LAYOUT_ == LAYOUT_SEPARABLE_PACKED ? r : 0); c < M::N; ++c) k += group_of(M::TYPE, r) == group_of(M::TYPE, c) ? 1 : 0;
+      for (int c = (SEPPK ? r : 0); c < M::N; ++c) k += (group_of(M::TYPE, r) == group_of(M::TYPE, c) && stored_row(r)) ? 1 : 0;
     return k;
   }
   static constexpr int TRI = N * (N + 1) / 2;                  // words of the upper triangle
@@ -172,12 +214,13 @@ struct Cfg {
   static constexpr int p_word(int r, int c) {
     if (SEP) {
       if (group_of(M::TYPE, r) != group_of(M::TYPE, c)) return -1;
+      if (SHARED) { r = share_rep(M::TYPE, r); c = share_rep(M::TYPE, c); }   // every axis of a kind -> the kind's one block
       const int r0 = (SEPPK && c < r) ? c : r, c0 = (SEPPK && c < r) ? r : c;
       int k = 0;
       for (int rr = 0; rr < N; ++rr)
         for (int cc = (SEPPK ? rr : 0); cc < N; ++cc) {
           if (rr == r0 && cc == c0) return k;
-          k += group_of(M::TYPE, rr) == group_of(M::TYPE, cc) ? 1 : 0;
+          k += (group_of(M::TYPE, rr) == group_of(M::TYPE, cc) && stored_row(rr)) ? 1 : 0;
         }
       return -1;
     }
@@ -259,6 +302,7 @@ constexpr long kLiveScan = 64 * 32;      // progress words the relay reads per r
 struct LayoutInfo {
   int n, m, g, layout, tpw, lpt, record_words;
   long tile_bytes, tile_payload;
+  int shared_axes = 0;   // 1: the shared-axes storage form of layout 3 (LAYOUT_SEPARABLE_SHARED)
 };
 
 }  // namespace te

@@ -71,6 +71,9 @@ class Batch:
     lanes_per_target = property(lambda s: s._lib.target_batch_lanes_per_target(s._h))
     symmetric_packed = property(lambda s: bool(s._lib.target_batch_is_symmetric_packed(s._h)))
     layout = property(lambda s: ("full", "symmetric_packed", "axis_separable", "axis_separable_packed")[s._lib.target_batch_layout(s._h)])
+    # the shared-axes storage form of axis_separable_packed (target_batch_shared_axes): one covariance block per kind of axis
+    shared_axes = property(lambda s: s._lib.target_batch_shared_axes(s._h))
+    record_words = property(lambda s: s._lib.target_batch_record_words(s._h))
     num_classes = property(lambda s: s._lib.target_batch_num_classes(s._h))
     algorithmic_bytes = property(lambda s: s._lib.target_batch_algorithmic_bytes(s._h))
     resident_bytes_per_target = property(lambda s: s._lib.target_batch_resident_bytes_per_target(s._h))
@@ -304,14 +307,18 @@ class MeasurementIngest:
 class TargetManager:
     """ctypes mirror of the reference TargetManager; dtype 'f64' (reference precision) or 'f32'."""
 
-    def __init__(self, file=None, dtype="f64", lanes_per_target=0, devices=None):
-        """devices: HIP device indices, one shard each (repeats allowed; target_manager_set_devices).  None: unsharded."""
+    def __init__(self, file=None, dtype="f64", lanes_per_target=0, devices=None, shared_axes=None):
+        """devices: HIP device indices, one shard each (repeats allowed; target_manager_set_devices).  None: unsharded.
+        shared_axes: False keeps this manager's batches out of the shared-axes storage form (target_manager_set_shared_axes);
+        None: the default (on unless TE_SHARED_AXES=0)."""
         self._lib = capi.lib()
         f = None if file is None else str(file).encode()
         self._h = self._lib.target_manager_new_ex(f, DTYPES[dtype], int(lanes_per_target))
         if not self._h:
             raise RuntimeError("target_manager_new failed: %s" % capi.last_error())
         self.dtype = dtype
+        if shared_axes is not None:
+            _check(self._lib.target_manager_set_shared_axes(self._h, 1 if shared_axes else 0), "target_manager_set_shared_axes")
         if devices is not None:
             try:
                 self.set_devices(devices)

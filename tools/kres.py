@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise hipcc -Rpass-analysis=kernel-resource-usage output (stdin) as one line per kernel:
    hipcc --offload-arch=gfx950 -O3 -std=c++17 -c kf_model_ar.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | tools/kres.py [substring]
-Template arguments: kf_step_sep_kernel<model, T, layout(2 separable, 3 separable+packed), INDEXED, FUSED, QUERY, PERQR>;
+Template arguments: kf_step_sep_kernel<model, T, layout(2 separable, 3 separable+packed, 4 its shared-axes form), INDEXED, FUSED, QUERY, PERQR>;
 kf_step_kernel<model, T, lanes per target, layout(0 full, 1 packed), INDEXED, FUSED, QUERY, PERQR>."""
 import re
 import subprocess
