@@ -33,6 +33,12 @@ int orc_poly_roots(const double* coeffs, int ncoeffs, double* roots_re_im) {
   int deg = ncoeffs - 1;
   while (deg > 0 && coeffs[deg] == 0.0) --deg;
   if (deg <= 0) return 0;
+  /* A zero constant term (the target ON the sphere): 0 is a root exactly and the others are the quotient's.  The iteration would
+   * return it as +-1e-89, and lowest_real_root's answer hangs on that sign: 0 if the sign is +, "a negative root: -1" if -. */
+  if (coeffs[0] == 0.0) {
+    roots_re_im[0] = roots_re_im[1] = 0.0;
+    return 1 + orc_poly_roots(coeffs + 1, deg, roots_re_im + 2);
+  }
   long double complex z[8];
   long double a[9];
   for (int i = 0; i <= deg; ++i) a[i] = (long double)coeffs[i] / (long double)coeffs[deg];
