@@ -219,6 +219,28 @@ int target_batch_layout(target_batch_c* b);
  * batch plain. */
 int target_batch_shared_axes(target_batch_c* b);
 int target_manager_set_shared_axes(target_manager_c* self, int on);
+/* UNIFORM TILES, a property of batches in the shared-axes form (uniform_velocity, uniform_acceleration, angular_rates; the
+ * angular_velocities kernels are built without it).  The same argument holds BETWEEN targets: two targets whose linear-chain
+ * covariance words are the same bits, and which receive the same dt and the same has-measurement bit, hold the same bits after
+ * the tick.  A population created in bulk and measured every tick is in that state tile after tile (a tile = the 64 targets of
+ * one wavefront).  The dense step kernels find such tiles themselves -- a tile counts as uniform only after the kernel has
+ * compared the bits of its lanes, and stops being one, in the same kernel, on the tick whose has-bits split it -- and keep ONE
+ * copy of those words per tile (12 / 6 / 3 words: angular_rates / uniform_acceleration / uniform_velocity; about 1.5 B per
+ * target of side arrays, not counted in target_batch_resident_bytes_per_target).  A uniform tile's dense tick neither reads nor
+ * writes the 16-byte record chunks that hold only such words (6 / 3 / 1 of them): same results bit for bit, fewer bytes.
+ * Nothing is deferred: records, blocks and flags are the complete state after every tick.  Everything that is not a dense tick --
+ * by-id updates, creations, erasures, leaving the shared form -- first writes the blocks back into the
+ * records (one dense pass, exact) and clears the flags; target_batch_get_state and the pose / twist / intersection getters do
+ * not.  Tiles are looked at for promotion only after 2 consecutive dense ticks without such a call (TE_UNIFORM_TILES_AFTER
+ * overrides), so a caller who interleaves by-id updates with dense ticks never pays that pass per tick; recorded sequences
+ * always look.  TE_UNIFORM_TILES=0, or target_manager_set_uniform_tiles(m, 0) before the manager's first target (an error
+ * afterwards), switches it off.
+ * target_batch_uniform_tiles: the number of tiles flagged now.  It reads the flags back on the batch's stream: a SYNCHRONISING
+ * call that first runs the queued one-target steps (they settle the tiles).  target_batch_algorithmic_bytes reports what the next dense tick moves given the flags (the same read-back, after the same
+ * queued steps): per target of a flagged tile 32 B less per skipped chunk, plus the tile's 2 x 8 x words + 4 B of block
+ * and flag traffic divided by its targets; the mean over the batch, rounded down; with no tile flagged, the form's constant. */
+long target_batch_uniform_tiles(target_batch_c* b);
+int target_manager_set_uniform_tiles(target_manager_c* self, int on);
 /* words of one target's record in HBM: x + unwrap memory + the stored words of P */
 int target_batch_record_words(target_batch_c* b);
 /* number of distinct (Q, R) parameter classes among the batch's targets */

@@ -123,6 +123,8 @@ SIGNATURES = {
     "target_batch_layout": (C.c_int, [C.c_void_p]),
     "target_batch_shared_axes": (C.c_int, [C.c_void_p]),
     "target_manager_set_shared_axes": (C.c_int, [C.c_void_p, C.c_int]),
+    "target_batch_uniform_tiles": (C.c_long, [C.c_void_p]),
+    "target_manager_set_uniform_tiles": (C.c_int, [C.c_void_p, C.c_int]),
     "target_batch_record_words": (C.c_int, [C.c_void_p]),
     "target_batch_algorithmic_bytes": (C.c_long, [C.c_void_p]),
     "target_batch_resident_bytes_per_target": (C.c_double, [C.c_void_p]),

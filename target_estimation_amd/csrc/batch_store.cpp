@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -80,8 +81,9 @@ const Ops* get_ops(int type, int dtype, int g) {
   }
 }
 
-Batch::Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock, bool allow_shared)
-    : type_(type), dtype_(dtype), lanes_code_(lanes), owner_lock_(owner_lock), ops_(get_ops(type, dtype, lanes)), stream_(stream) {
+Batch::Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock, bool allow_shared,
+             bool allow_uniform_tiles)
+    : type_(type), dtype_(dtype), lanes_code_(lanes), owner_lock_(owner_lock), ops_(get_ops(type, dtype, lanes)), stream_(stream), ut_on_(allow_uniform_tiles) {
   if (!ops_) throw std::runtime_error("target_estimation_amd: unsupported (model, precision, lanes-per-target) combination");
   if (allow_shared && lanes == kLanesSeparablePacked && dtype == F64 && shared_axes_qr_ok(type, Q, R)) {
     const Ops* shared = get_ops(type, dtype, kLanesSeparableShared);
@@ -99,10 +101,11 @@ void Batch::demote_shared() {
     char* rec = nullptr;
     TE_HIP_CHECK(hipMalloc((void**)&rec, bytes));
     TE_HIP_CHECK(hipMemsetAsync(rec, 0, bytes, stream_));
-    ops_->expand(d_rec_, rec, n_, stream_);
+    ops_->expand(records(), rec, n_, stream_);
     TE_HIP_CHECK(hipGetLastError());
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
     device_free(d_rec_);
+    device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;   // (the plain form has no uniform tiles)
     device_free(d_rec_alt_); d_rec_alt_ = nullptr; alt_failed_ = false;   // re-created in the plain form by the next A -> B tick
     d_rec_ = rec;
   }
@@ -241,9 +244,62 @@ bool Batch::initial_covariance(long slot, double* P0) {
   return true;
 }
 
-StepParams Batch::base_params() const {
+long Batch::promote_after() {
+  static const long v = [] { const char* e = std::getenv("TE_UNIFORM_TILES_AFTER"); const long k = e ? std::atol(e) : 2L; return k < 0 ? 0L : k; }();
+  return v;
+}
+
+void Batch::settle_tiles() {
+  dense_streak_ = 0;
+  if (!ut_flagged_) return;
+  ut_flagged_ = false;
+  if (!d_tile_uni_) return;
+  if (n_ > 0 && ops_->settle) {
+    ops_->settle(d_rec_, n_, d_tile_blk_, d_tile_uni_, stream_);
+    TE_HIP_CHECK(hipGetLastError());
+  }
+  // (also for a batch emptied by erases: its flags would otherwise outlive the targets they described)
+  TE_HIP_CHECK(hipMemsetAsync(d_tile_uni_, 0, sizeof(int) * (size_t)(cap_ / ops_->L.tpw), stream_));
+}
+
+long Batch::count_uniform(long* targets_in_them) {
+  if (targets_in_them) *targets_in_them = 0;
+  if (!ut_flagged_ || !d_tile_uni_ || n_ <= 0) return 0;
+  const long tpw = ops_->L.tpw, tiles = (n_ + tpw - 1) / tpw;
+  std::vector<int> h((size_t)tiles);
+  TE_HIP_CHECK(hipMemcpyAsync(h.data(), d_tile_uni_, sizeof(int) * (size_t)tiles, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  long k = 0, targets = 0;
+  for (long t = 0; t < tiles; ++t)
+    if (h[(size_t)t] != 0) { ++k; targets += std::min(tpw, n_ - t * tpw); }
+  if (targets_in_them) *targets_in_them = targets;
+  return k;
+}
+
+long Batch::uniform_tiles() {
+  flush();   // (a queued one-target step settles the tiles when it runs: it has happened as far as the caller knows)
+  return count_uniform(nullptr);
+}
+
+StepParams Batch::dense_params() {
   StepParams p;
   p.rec = d_rec_; p.qr = d_qr_; p.cls = n_classes_ > 1 ? d_cls_ : nullptr; p.n = n_; p.idx = nullptr;
+  p.meas = nullptr; p.meas_ld = 0; p.has_meas = nullptr; p.dt_per = nullptr; p.dt = 0.0;
+  p.t_base = d_tbase_; p.nm_base = d_nmbase_;
+  if (uniform_tiles_enabled() && d_tile_uni_) {
+    p.tile_blk = d_tile_blk_; p.tile_uni = d_tile_uni_;
+    p.promote = (recording_ || dense_streak_ >= promote_after()) ? 1 : 0;
+    if (!recording_) {   // (a recording launches nothing: note_replay() when it is replayed)
+      if (p.promote) ut_flagged_ = true;
+      ++dense_streak_;
+    }
+  }
+  return p;
+}
+
+StepParams Batch::base_params() {
+  StepParams p;
+  p.rec = records(); p.qr = d_qr_; p.cls = n_classes_ > 1 ? d_cls_ : nullptr; p.n = n_; p.idx = nullptr;
   p.meas = nullptr; p.meas_ld = 0; p.has_meas = nullptr; p.dt_per = nullptr; p.dt = 0.0;
   p.t_base = d_tbase_; p.nm_base = d_nmbase_;
   return p;
@@ -256,6 +312,7 @@ Batch::~Batch() {
   (void)hipStreamSynchronize(stream_);
   drop_graphs();
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
+  device_free(d_tile_blk_); device_free(d_tile_uni_);
   device_free(d_qr_); device_free(d_rec_); device_free(d_rec_alt_); device_free(d_tbase_); device_free(d_nmbase_); device_free(d_cls_);
   device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
@@ -302,7 +359,7 @@ void Batch::synchronize() {
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
-long Batch::algorithmic_bytes_per_cycle() const {
+long Batch::algorithmic_bytes_per_cycle() {
   const long n = ops_->L.n;
   const bool angular = (type_ == ANGULAR_RATES || type_ == ANGULAR_VELOCITIES);
   // full P: 2n + 2n^2 + 7 (+6); symmetric-packed P: 2n + n(n+1) + 7 (+6)
@@ -318,12 +375,24 @@ long Batch::algorithmic_bytes_per_cycle() const {
   }
   // measurement words the step kernel READS: [x y z] for the linear models, [x y z qx qy qz qw] for the angular
   // ones (kf_step_sep.hpp MW, kf_step.hpp ymeas_own/qmeas); SURVEY 8d's formula charges 7 for every model
-  return (2 * n + pwords + (angular ? 7 + 6 : 3)) * (long)elem_size();
+  const long full = (2 * n + pwords + (angular ? 7 + 6 : 3)) * (long)elem_size();
+  // Uniform tiles: what the NEXT dense tick moves, given the flags as they are.  A flagged tile's targets move 16 B less per
+  // linear-covariance chunk, read and written, and the tile moves its block (LW words read and written) and its flag (4 B);
+  // every other tile as ever.  The mean over the batch, rounded down (the roofline fraction is never flattered); with no tile
+  // flagged, exactly the figure above.
+  if (!uniform_tiles_enabled()) return full;
+  flush();   // (as uniform_tiles(): a queued one-target step settles the tiles when it runs)
+  long in_them = 0;
+  const long k = count_uniform(&in_them);
+  if (k == 0) return full;
+  const long total = n_ * full - in_them * 2L * 16L * ops_->L.lin_chunks + k * (2L * 8L * ops_->L.lin_words + 4L);
+  return total / n_;
 }
 
 
 void Batch::reserve(long n) {
   if (n <= cap_) return;
+  settle_tiles();   // (the records move as plain records; the new tile arrays start with no tile flagged)
   const long tpw = ops_->L.tpw;
   long want = std::max(n, cap_ * 2);
   want = (want + tpw - 1) / tpw * tpw;
@@ -357,6 +426,15 @@ void Batch::reserve(long n) {
     d_lastmeas_ = lm;
   }
   d_rec_ = rec; d_tbase_ = tb; d_nmbase_ = nm; d_cls_ = cl; cap_ = want;
+  device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;
+  if (uniform_tiles_enabled()) {   // about 1.5 B per target (angular_rates: 96 + 4 B per 64)
+    const size_t tiles = (size_t)(want / tpw);
+    TE_HIP_CHECK(hipMalloc((void**)&d_tile_blk_, sizeof(double) * tiles * (size_t)ops_->L.lin_words));
+    TE_HIP_CHECK(hipMalloc((void**)&d_tile_uni_, sizeof(int) * tiles));
+    TE_HIP_CHECK(hipMemsetAsync(d_tile_blk_, 0, sizeof(double) * tiles * (size_t)ops_->L.lin_words, stream_));
+    TE_HIP_CHECK(hipMemsetAsync(d_tile_uni_, 0, sizeof(int) * tiles, stream_));
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  }
   drop_graphs();
 }
 
@@ -442,7 +520,7 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
   }
   TE_HIP_CHECK(hipMemcpyAsync(d_P0_, P0, sizeof(double) * p0_words, hipMemcpyHostToDevice, stream_));
   InitArgs a;
-  a.rec = d_rec_; a.idx = d_idx_; a.n = count; a.p0 = d_p0; a.v0 = v0 ? d_v0 : nullptr; a.a0 = a0 ? d_a0 : nullptr;
+  a.rec = records(); a.idx = d_idx_; a.n = count; a.p0 = d_p0; a.v0 = v0 ? d_v0 : nullptr; a.a0 = a0 ? d_a0 : nullptr;
   a.P0 = d_P0_; a.per_target_P0 = per_target_P0 ? 1 : 0;
   a.cls = d_cls_; a.cls_value = cls;
   if (cls_of || P0_index) {   // per-entry class / initial-covariance indices: behind the slot list in the index staging
@@ -484,7 +562,7 @@ unsigned Batch::erase_slot(long slot) {
   const long last = n_ - 1;
   unsigned moved = slot_ids_[(size_t)slot];
   if (slot != last) {
-    ops_->move_record(d_rec_, last, slot, d_tbase_, d_nmbase_, d_cls_, stream_);
+    ops_->move_record(records(), last, slot, d_tbase_, d_nmbase_, d_cls_, stream_);
     TE_HIP_CHECK(hipGetLastError());
     gate_move(last, slot);
     if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_ + 7 * slot, d_lastmeas_ + 7 * last, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
@@ -522,7 +600,7 @@ void Batch::erase_slots(const int* slots, long k, std::vector<std::pair<unsigned
     stage_reserve(2 * m);
     TE_HIP_CHECK(hipMemcpyAsync(d_idx_, src.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
     TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + m, dst.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
-    ops_->move_records(d_rec_, d_idx_, d_idx_ + m, m, d_tbase_, d_nmbase_, d_cls_, stream_);
+    ops_->move_records(records(), d_idx_, d_idx_ + m, m, d_tbase_, d_nmbase_, d_cls_, stream_);
     TE_HIP_CHECK(hipGetLastError());
     for (long j = 0; j < m; ++j) {
       gate_move(src[(size_t)j], dst[(size_t)j]);
@@ -542,7 +620,7 @@ void Batch::erase_slots(const int* slots, long k, std::vector<std::pair<unsigned
 void Batch::step_dense(double dt, const void* meas_dev, long ld, const unsigned char* has_dev) {
   touch();
   if (n_ == 0) return;
-  StepParams p = base_params();
+  StepParams p = dense_params();
   p.meas = meas_dev; p.meas_ld = ld; p.has_meas = has_dev; p.dt = dt;
   p.reverse = (flip_ && zigzag()) ? 1 : 0;   // zig-zag: consecutive dense ticks walk the tiles in opposite directions
   flip_ = !flip_;
@@ -574,7 +652,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
   const size_t es = elem_size();
   auto params = [&](long s0) {
     const long s = ring_ticks > 0 ? s0 % ring_ticks : s0;   // the measurements form a ring of ring_ticks ticks
-    StepParams p = base_params();
+    StepParams p = dense_params();
     p.meas = meas_base ? static_cast<const char*>(meas_base) + (size_t)(s * tick_stride) * es : nullptr;
     p.meas_ld = ld;
     p.has_meas = has_base ? has_base + s * has_stride : nullptr;
@@ -613,6 +691,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
       GraphEntry e{n_ticks, tick_stride, ld, has_stride, n_, dt, meas_base, has_base, d_rec_, nullptr, nullptr, ring_ticks};
       e.poses = poses;
       TE_HIP_CHECK(hipStreamBeginCapture(cap_stream_, hipStreamCaptureModeThreadLocal));
+      recording_ = true;   // (a recording is a dense streak: its ticks promote)
       try {
         for (long s = 0; s < n_ticks; ++s) {
           launch_step(params(s), cap_stream_);
@@ -623,11 +702,13 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
         }
         TE_HIP_CHECK(hipGetLastError());
       } catch (...) {
+        recording_ = false;
         hipGraph_t broken = nullptr;
         (void)hipStreamEndCapture(cap_stream_, &broken);   // never leave the stream in capture mode
         if (broken) (void)hipGraphDestroy(broken);
         throw;
       }
+      recording_ = false;
       TE_HIP_CHECK(hipStreamEndCapture(cap_stream_, &e.graph));
       if (hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGraphDestroy(e.graph);
@@ -639,6 +720,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     hit->last_use = ++graph_clock_;
     if (use_graph == 2) return;  // record only
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
+    note_replay(n_ticks);
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
   t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
@@ -652,7 +734,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   const bool fused_q = ops_->fused_query && n_classes_ == 1;
-  StepParams p = base_params();
+  StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
@@ -668,7 +750,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   if (p.rec_out) std::swap(d_rec_, d_rec_alt_);
   if (query && !fused_q) {
     IntersectArgs a;
-    a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
+    a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
     a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
     a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
     ops_->intersect(a, st);
@@ -683,7 +765,7 @@ StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, c
   double* pose_block = q.poses.block(s);
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
-  StepParams p = base_params();
+  StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
@@ -953,7 +1035,7 @@ void Batch::outputs_indexed_dev(const int* idx_dev, long n, double* pose_dev, do
   flush();
   if (n <= 0) return;
   OutArgs a;
-  a.rec = d_rec_; a.idx = idx_dev; a.n = n; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
+  a.rec = records_as_stored(); a.idx = idx_dev; a.n = n; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
   a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
   ops_->outputs(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -1123,7 +1205,7 @@ void Batch::flush() {
   launch_step(p, stream_);
   if (cache_valid_ && !fused) {   // keep the getter table current: only the stepped slots change
     OutArgs a;
-    a.rec = d_rec_; a.idx = p.idx; a.n = k; a.by_slot = 1;
+    a.rec = records_as_stored(); a.idx = p.idx; a.n = k; a.by_slot = 1;
     a.pose = d_cache_; a.twist = d_cache_ + 7 * n_; a.acc = d_cache_ + 13 * n_;
     a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_;
     if (seq != 0 && k <= kOutputsBlock) { a.done_flag = d_done_; a.done_seq = seq; }
@@ -1156,7 +1238,7 @@ void Batch::outputs(const int* slots, long n, double* pose, double* twist, doubl
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   OutArgs a;
-  a.rec = d_rec_; a.idx = slots ? d_idx_ : nullptr; a.n = n;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n;
   a.pose = pose ? d_aos_ : nullptr; a.twist = twist ? d_aos_ + 7 * n : nullptr; a.acc = acc ? d_aos_ + 13 * n : nullptr;
   a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
   ops_->outputs(a, stream_);
@@ -1171,7 +1253,7 @@ void Batch::outputs_dev(double* pose_dev, double* twist_dev, double* acc_dev, bo
   flush();
   if (n_ == 0) return;
   OutArgs a;
-  a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
+  a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
   a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
   ops_->outputs(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -1181,7 +1263,7 @@ void Batch::outputs_rows_dev(double* pose_dev, const int* row_of_slot_dev) {
   flush();
   if (n_ == 0) return;
   OutArgs a;
-  a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = nullptr; a.acc = nullptr;
+  a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = nullptr; a.acc = nullptr;
   a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_; a.row_of_slot = row_of_slot_dev;
   ops_->outputs_rows(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -1201,7 +1283,7 @@ void Batch::outputs_one(long slot, double* pose, double* twist, double* acc, boo
   if (!cache_valid_) {
     cache_reserve(n_);
     OutArgs a;
-    a.rec = d_rec_; a.idx = nullptr; a.n = n_;
+    a.rec = records_as_stored(); a.idx = nullptr; a.n = n_;
     a.pose = d_cache_; a.twist = d_cache_ + 7 * n_; a.acc = d_cache_ + 13 * n_;
     a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_;
     ops_->outputs(a, stream_);
@@ -1220,7 +1302,7 @@ void Batch::intersect(const int* slots, long n, double t1, const double* origin,
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   IntersectArgs a;
-  a.rec = d_rec_; a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
   a.t_acc = t_acc_; a.t_base = d_tbase_;
   a.delta = d_aos_; a.pose = pose ? d_aos_ + n : nullptr;
@@ -1235,7 +1317,7 @@ void Batch::intersect_dev(double t1, const double* origin, double radius, double
   flush();
   if (n_ == 0) return;
   IntersectArgs a;
-  a.rec = d_rec_; a.idx = nullptr; a.n = n_; a.t1 = t1;
+  a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
   a.t_acc = t_acc_; a.t_base = d_tbase_; a.delta = delta_dev; a.pose = pose_dev;
   ops_->intersect(a, stream_);
@@ -1293,7 +1375,7 @@ void Batch::intersect_gated(const int* slots, long n, double t1, const double* o
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   IntersectArgs a;
-  a.rec = d_rec_; a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
   a.t_acc = t_acc_; a.t_base = d_tbase_;
   a.delta = d_aos_; a.pose = d_aos_ + n;                 // [n] + [n][7]
@@ -1364,7 +1446,7 @@ void Batch::get_state(const int* slots, long n, double* x, double* P) {
   }
   double* dx = x ? reinterpret_cast<double*>(buf) : nullptr;
   double* dP = P ? reinterpret_cast<double*>(buf + bx) : nullptr;
-  ops_->get_state(d_rec_, slots ? d_idx_ : nullptr, n, dx, dP, stream_);
+  ops_->get_state(records_as_stored(), slots ? d_idx_ : nullptr, n, dx, dP, ut_flagged_ ? d_tile_blk_ : nullptr, ut_flagged_ ? d_tile_uni_ : nullptr, stream_);
   TE_HIP_CHECK(hipGetLastError());
   if (x) TE_HIP_CHECK(hipMemcpyAsync(x, dx, bx, hipMemcpyDeviceToHost, stream_));
   if (P) TE_HIP_CHECK(hipMemcpyAsync(P, dP, bP, hipMemcpyDeviceToHost, stream_));
@@ -1383,7 +1465,7 @@ void Batch::set_state(const int* slots, long n, const double* x, const double* P
   if (x) { TE_HIP_CHECK(hipMalloc((void**)&dx, sizeof(double) * N * n)); TE_HIP_CHECK(hipMemcpyAsync(dx, x, sizeof(double) * N * n, hipMemcpyHostToDevice, stream_)); }
   if (P) { TE_HIP_CHECK(hipMalloc((void**)&dP, sizeof(double) * N * N * n)); TE_HIP_CHECK(hipMemcpyAsync(dP, P, sizeof(double) * N * N * n, hipMemcpyHostToDevice, stream_)); }
   if (unwrap) { TE_HIP_CHECK(hipMalloc((void**)&du, sizeof(double) * 3 * n)); TE_HIP_CHECK(hipMemcpyAsync(du, unwrap, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream_)); }
-  ops_->set_state(d_rec_, slots ? d_idx_ : nullptr, n, dx, dP, du, stream_);
+  ops_->set_state(records(), slots ? d_idx_ : nullptr, n, dx, dP, du, stream_);
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   device_free(dx); device_free(dP); device_free(du);
@@ -1424,3 +1506,20 @@ double Batch::time(long slot) {
 }
 
 }  // namespace te
+
+#ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library
+// Batch::set_state has no entry in the public headers; tests/test_gpu_uniform_tiles.py reaches it through this one (slots = null:
+// slots 0 .. n - 1; x [n][N], P [n][N][N], host arrays).  0, or -1 and the message on stderr.
+extern "C" int te_test_batch_set_state(void* batch, long n, const double* x, const double* P) {
+  try {
+    te::Batch* b = static_cast<te::Batch*>(batch);
+    std::unique_lock<std::mutex> l;
+    if (b->owner_lock()) l = std::unique_lock<std::mutex>(*b->owner_lock());
+    b->set_state(nullptr, n, x, P, nullptr);
+    return 0;
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "te_test_batch_set_state: %s\n", e.what());
+    return -1;
+  }
+}
+#endif

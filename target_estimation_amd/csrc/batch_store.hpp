@@ -37,8 +37,9 @@ class Batch {
   // shared_axes_qr_ok) starts in the shared-axes storage form: one covariance block per kind of axis instead of one per axis.
   // Same results bit for bit, fewer bytes per tick.  The batch leaves the form for good (demote_shared) when something arrives
   // that it does not serve; lanes_code() and layout().layout read 301 / 3 in both forms.
+  // allow_uniform_tiles: a batch in that form whose kernels have the feature (LayoutInfo::lin_words) keeps uniform tiles, see below
   Batch(int type, int dtype, int lanes, const double* Q, const double* R, hipStream_t stream, std::mutex* owner_lock = nullptr,
-        bool allow_shared = false);
+        bool allow_shared = false, bool allow_uniform_tiles = true);
   ~Batch();
   Batch(const Batch&) = delete;
   Batch& operator=(const Batch&) = delete;
@@ -56,6 +57,23 @@ class Batch {
   // itself ahead of what the shared form does not serve: a second (Q, R) class, an initial covariance whose blocks differ between
   // the axes of a kind, step_fused, live_start, set_state.  No-op for a plain batch.
   void demote_shared();
+  // UNIFORM TILES (te_layout.hpp Cfg::UT; kf_step.hpp StepArgs::tile_uni).  The linear P words of a chain are a function of the
+  // block before the tick, Q, R, dt and the has-bit, so the targets of a tile that agree on them keep agreeing while they get the
+  // same dt and has-bit -- a population created in bulk and measured every tick, tile after tile.  The dense step finds such
+  // tiles itself (a launch with StepParams::promote compares the lanes' bits), keeps ONE copy of the words per tile in
+  // d_tile_blk_ and neither loads nor stores the record's linear-covariance chunks of a flagged tile; it ends a tile's uniformity
+  // itself on the tick whose has-bits split it.  Records + blocks + flags are the whole, current state after every tick.
+  // Every launch that is not a dense tick of the form, get_state and an x-only reader must see plain records: it gets them
+  // through records(), i.e. behind settle_tiles() -- one dense launch that writes each flagged tile's block back into its lanes
+  // (an exact copy) and clears the flags; a no-op while no promoting launch has run since the last one.  Dense ticks promote only
+  // after promote_after() consecutive ones since the last settle (default 2, env TE_UNIFORM_TILES_AFTER), so that a caller who
+  // interleaves by-id updates with dense ticks never pays a settle pass per tick; recorded sequences always promote.
+  bool uniform_tiles_enabled() const { return ut_on_ && ops_->L.lin_words > 0; }
+  void settle_tiles();
+  long uniform_tiles();        // tiles flagged now: reads the flags back on the batch's stream (SYNCHRONISES)
+  static long promote_after();
+  void set_recording(bool on) { recording_ = on; }   // the dense ticks enqueued meanwhile go into a recorded graph
+  void note_replay(long n_ticks) { if (uniform_tiles_enabled()) { ut_flagged_ = true; dense_streak_ += n_ticks; } }   // a recorded sequence was launched
   long size() const { return n_; }
   bool getter_table_is_cheap() const { return n_ <= kCacheMax; }   // (its one-target getters read a host-resident table from the first call after a change)
   size_t elem_size() const { return dtype_ == F64 ? 8 : 4; }
@@ -215,6 +233,7 @@ class Batch {
   // identity of everything a recorded launch sequence refers to
   // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
   struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; };
+  // (the tile arrays are allocated and freed with the records: rec identifies them too)
   DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_}; }
   void prepare() { touch(); }
 
@@ -236,7 +255,8 @@ class Batch {
 
   // bytes of HBM one predict+update cycle must move for one target (state read+write + the
   // measurement words the model reads); used by the roofline accounting
-  long algorithmic_bytes_per_cycle() const;
+  // (with uniform tiles: of the NEXT dense tick given the tile flags, which it reads back -- it synchronises once tiles may be flagged)
+  long algorithmic_bytes_per_cycle();
   long state_bytes() const { return (n_ + ops_->L.tpw - 1) / ops_->L.tpw * ops_->L.tile_bytes; }
   static long zigzag_min_bytes();   // default 128 MB (env TE_ZIGZAG_MIN_MB)
   // A -> B ticks with nontemporal stores (kf_step.hpp StepArgs::rec_out) instead of in-place read-modify-write: the policy of
@@ -244,7 +264,7 @@ class Batch {
   // Below it the zig-zag in place wins (the Infinity Cache still holds a useful share of the state); costs a second record buffer.
   static long pingpong_min_bytes();
   bool pingpong() const { return pingpong_min_bytes() >= 0 && state_bytes() >= pingpong_min_bytes(); }
-  char* records_dev() const { return d_rec_; }
+  char* records_dev() { return records(); }
 
  private:
   void reserve(long n);
@@ -263,7 +283,20 @@ class Batch {
   // Zig-zag only pays when the state does not fit the Infinity Cache, and it costs when the state is L2-resident: a tile
   // walked backwards lands on another XCD, whose L2 does not hold it (10^5 UA fp32: 4.7 -> 8.2 us per tick).
   bool zigzag() const { return state_bytes() >= zigzag_min_bytes(); }
-  StepParams base_params() const;
+  StepParams base_params();          // launches that need plain records (indexed, fused, live): behind settle_tiles()
+  StepParams dense_params();         // a dense single tick: the records as stored, with the batch's tile arrays
+  // The records.  records(): settled -- for everything that reads or writes P words of a record and is not a dense tick of the
+  // form.  records_as_stored(): as the dense ticks leave them (the linear-covariance chunks of a flagged tile unspecified) -- for
+  // the dense ticks, get_state (which honours the flags) and readers of x alone (outputs, intersections).
+  char* records() { settle_tiles(); return d_rec_; }
+  char* records_as_stored() const { return d_rec_; }
+  long count_uniform(long* targets_in_them);   // flagged tiles (and the targets in them); synchronises
+  bool ut_on_ = true;
+  double* d_tile_blk_ = nullptr;   // [cap_ / tpw][L.lin_words], allocated with the records
+  int* d_tile_uni_ = nullptr;      // [cap_ / tpw]
+  bool ut_flagged_ = false;        // a promoting launch has run since the last settle: tiles may be flagged
+  long dense_streak_ = 0;          // consecutive dense ticks since the last settle
+  bool recording_ = false;
   void launch_step(const StepParams& p, hipStream_t st, int meas_rows = 7);   // ops_->step + the measured-pose rows when kept
   bool keep_meas_ = false;
   int host_meas_rows_ = 7;         // measurement rows the host SoA path transported for the tick being enqueued

@@ -117,8 +117,10 @@ __global__ void init_kernel(const InitArgs a) {
 }
 
 // x [n][N] and P [n][N*N] (row-major, doubles) of the listed slots; one thread per (entry,row)
+// tile_uni / tile_blk (or null): the batch's uniform tiles (te_layout.hpp Cfg::UT) -- the linear P words of a flagged tile are
+// read from the tile's block.  Read-only: a caller that polls the state does not end a tile's uniformity.
 template <class M, typename T, int G, int LAYOUT>
-__global__ void get_state_kernel(char* rec, const int* idx, long n, double* x_out, double* P_out) {
+__global__ void get_state_kernel(char* rec, const int* idx, long n, double* x_out, double* P_out, const double* tile_blk, const int* tile_uni) {
   using C = Cfg<M, T, G, LAYOUT>;
   constexpr int N = C::N;
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -127,8 +129,31 @@ __global__ void get_state_kernel(char* rec, const int* idx, long n, double* x_ou
   const int r = (int)(tid % N);
   const long slot = idx ? (long)idx[e] : e;
   if (x_out) x_out[e * N + r] = (double)state_get<C, T>(rec, slot, r, N);
-  if (P_out)
-    for (int c = 0; c < N; ++c) P_out[(e * N + r) * N + c] = (double)state_get<C, T>(rec, slot, r, c);
+  if (!P_out) return;
+  bool uni = false;
+  if constexpr (C::UT) uni = tile_uni != nullptr && tile_uni[slot / C::TPW] != 0;
+  for (int c = 0; c < N; ++c) {
+    double v = (double)state_get<C, T>(rec, slot, r, c);
+    if constexpr (C::UT) {
+      const int w = C::PWORD.v[r][c];
+      if (uni && w >= 0 && C::LIN.idx[w] >= 0) v = tile_blk[(slot / C::TPW) * C::LW + C::LIN.idx[w]];
+    }
+    P_out[(e * N + r) * N + c] = v;
+  }
+}
+
+// Uniform tiles: the block of every flagged tile back into the linear P words of its lanes' records (thread per target).  After
+// it, and with the flags cleared behind it, the records alone are the state again: what every launch that is not a dense tick
+// of the form expects (Batch::settle_tiles).  A copy: exact.
+template <class M, typename T>
+__global__ void settle_tiles_kernel(char* rec, long n, const double* tile_blk, const int* tile_uni) {
+  using C = Cfg<M, T, 1, LAYOUT_SEPARABLE_SHARED>;
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n) return;
+  const long tile = slot / C::TPW;
+  if (tile_uni[tile] == 0) return;
+  for (int k = 0; k < C::LW; ++k)
+    *reinterpret_cast<T*>(rec + tile * C::TILE_BYTES + record_word_offset<C, T>((int)(slot % C::TPW), C::LIN.w[k])) = (T)tile_blk[tile * C::LW + k];
 }
 
 template <class M, typename T, int G, int LAYOUT>

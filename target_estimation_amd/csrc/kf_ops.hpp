@@ -59,6 +59,10 @@ struct StepParams {
   long pose_ld = 0;
   long pose_tick_stride = 0;
   long pose_ring = 0;
+  // uniform tiles (StepArgs::tile_blk / tile_uni / promote): null / 0 for every launch but the dense ticks of a batch that keeps them
+  double* tile_blk = nullptr;
+  int* tile_uni = nullptr;
+  int promote = 0;
 };
 
 struct Ops {
@@ -69,7 +73,8 @@ struct Ops {
   // wavefronts of the live kernel the device can hold at once (0: this (model, precision, layout) has no live kernel)
   long (*live_capacity)(int with_outputs);   // resident wavefronts of the plain / the query-and-pose-output variant
   void (*init)(const InitArgs&, hipStream_t);
-  void (*get_state)(char* rec, const int* idx, long n, double* x, double* P, hipStream_t);
+  // tile_blk / tile_uni: the batch's uniform tiles, honoured read-only (null: none)
+  void (*get_state)(char* rec, const int* idx, long n, double* x, double* P, const double* tile_blk, const int* tile_uni, hipStream_t);
   void (*set_state)(char* rec, const int* idx, long n, const double* x, const double* P, const double* uw, hipStream_t);
   void (*move_record)(char* rec, long src, long dst, TClock* t_base, int* nm_base, int* cls, hipStream_t);
   void (*move_records)(char* rec, const int* src_dev, const int* dst_dev, long m, TClock* t_base, int* nm_base, int* cls, hipStream_t);
@@ -80,6 +85,9 @@ struct Ops {
   // shared-axes storage form only (L.shared_axes; null otherwise): write the n records of `rec` as plain LAYOUT_SEPARABLE_PACKED
   // records into `rec_plain` (a zero-filled buffer of the plain form's tiles), every kind's block copied to each of its axes
   void (*expand)(char* rec, char* rec_plain, long n, hipStream_t) = nullptr;
+  // uniform tiles (L.lin_words > 0; null otherwise): write every flagged tile's block back into the linear P words of its n-bounded
+  // lanes -- an exact copy; the caller clears the flags behind it
+  void (*settle)(char* rec, long n, const double* tile_blk, const int* tile_uni, hipStream_t) = nullptr;
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported

@@ -27,6 +27,7 @@ inline StepArgs<T> make_step_args(const StepParams& p) {
   a.live_ring = p.live_ring; a.live_first = p.live_first;
   a.live_spin_limit = p.live_spin_limit; a.live_idle_ticks = p.live_idle_ticks; a.live_flags = p.live_flags; a.live_pose = p.live_pose; a.live_pose_ld = p.live_pose_ld;
   a.pose = p.pose; a.pose_ld = p.pose_ld; a.pose_tick_stride = p.pose_tick_stride; a.pose_ring = p.pose_ring;
+  a.tile_blk = p.tile_blk; a.tile_uni = p.tile_uni; a.promote = p.promote;
   return a;
 }
 
@@ -66,6 +67,8 @@ struct OpsImpl {
       if (p.live_posted || p.cls || p.n_ticks > 1)
         throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
     }
+    if (p.tile_uni && (!C::UT || p.idx || !p.tile_blk))
+      throw std::runtime_error("target_estimation_amd: uniform tiles are a property of dense ticks of the shared-axes storage form");
     StepArgs<T> a = make_step_args<T>(p);
     if (p.live_posted) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
       if constexpr (kHasLive) {
@@ -211,10 +214,16 @@ struct OpsImpl {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((init_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + 127) / 128)), dim3(128), 0, s, a);
   }
-  static void get_state(char* rec, const int* idx, long n, double* x, double* P, hipStream_t s) {
+  static void get_state(char* rec, const int* idx, long n, double* x, double* P, const double* tile_blk, const int* tile_uni, hipStream_t s) {
     if (n <= 0) return;
     const long th = n * C::N;
-    hipLaunchKernelGGL((get_state_kernel<M, T, G, LAYOUT>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, rec, idx, n, x, P);
+    hipLaunchKernelGGL((get_state_kernel<M, T, G, LAYOUT>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, rec, idx, n, x, P, tile_blk, tile_uni);
+  }
+  static void settle(char* rec, long n, const double* tile_blk, const int* tile_uni, hipStream_t s) {
+    if constexpr (C::UT) {
+      if (n <= 0) return;
+      hipLaunchKernelGGL((settle_tiles_kernel<M, T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rec, n, tile_blk, tile_uni);
+    }
   }
   static void set_state(char* rec, const int* idx, long n, const double* x, const double* P, const double* uw, hipStream_t s) {
     if (n <= 0) return;
@@ -258,9 +267,10 @@ struct OpsImpl {
   static const Ops* get() {
     // (host code sees the shared-axes form as layout 3 with the flag set: te_layout.hpp)
     static const Ops ops = {
-        LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0},
+        LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
+                   C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
         C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows,
-        C::SHARED ? &expand : nullptr};
+        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr};
     return &ops;
   }
 };

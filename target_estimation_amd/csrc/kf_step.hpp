@@ -117,6 +117,14 @@ struct StepArgs {
   long pose_ld;
   long pose_tick_stride;
   long pose_ring;
+  // Uniform tiles (te_layout.hpp Cfg::UT; dense single-tick launches of the shared-axes form, null otherwise): tile_uni [tiles],
+  // 1 = every valid lane of the tile holds the linear P words of tile_blk [tiles][LW], bit for bit, and the record's
+  // linear-covariance chunks are unspecified.  The wavefront that owns the tile reads both, and updates them in place (the
+  // only copies, also in an A -> B tick): the flag falls when the tick's has-bits split the tile, and rises -- only in a launch
+  // with `promote` -- when the lanes are found to agree, bit for bit, after the tick.
+  double* tile_blk;
+  int* tile_uni;
+  int promote;
 };
 
 __device__ __forceinline__ long long wave_uniform_ll(long long v) {

@@ -151,6 +151,38 @@ __device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, cons
   for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
 }
 
+// Uniform tiles (te_layout.hpp Cfg::UT): a record in two parts -- its linear-covariance chunks (LIN), which a uniform tile neither
+// loads nor stores, and everything else (the other chunks and the tail row).
+template <class C, typename T, bool LIN>
+__device__ __forceinline__ void load_record_part(const char* tb, int lane, T* rec) {
+  static_assert(sizeof(T) == 8 && C::REM2 == 0, "the shared-axes form is fp64");
+#pragma unroll
+  for (int c = 0; c < C::NC; ++c) {
+    if (C::lin_chunk(c) != LIN) continue;
+    const double2 v = *reinterpret_cast<const double2*>(tb + (long)c * C::LPT * 16 + (long)lane * 16);
+    rec[c * 2] = v.x; rec[c * 2 + 1] = v.y;
+  }
+  if constexpr (C::REM1 && !LIN) rec[C::RW - 1] = *reinterpret_cast<const T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T));
+}
+template <class C, typename T, bool NT>
+__device__ __forceinline__ void store_record_nonlin(char* tb, int lane, const T* rec) {
+  static_assert(sizeof(T) == 8 && C::REM2 == 0, "the shared-axes form is fp64");
+#pragma unroll
+  for (int c = 0; c < C::NC; ++c) {
+    if (C::lin_chunk(c)) continue;
+    double2 v; v.x = rec[c * 2]; v.y = rec[c * 2 + 1];
+    if constexpr (NT) {
+      typedef float nt4 __attribute__((ext_vector_type(4)));
+      nt4 raw;
+      __builtin_memcpy(&raw, &v, 16);
+      __builtin_nontemporal_store(raw, reinterpret_cast<nt4*>(tb + (long)c * C::LPT * 16 + (long)lane * 16));
+    } else {
+      *reinterpret_cast<double2*>(tb + (long)c * C::LPT * 16 + (long)lane * 16) = v;
+    }
+  }
+  if constexpr (C::REM1) *reinterpret_cast<T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T)) = rec[C::RW - 1];
+}
+
 // QUERY: the own-time sphere-intersection query of the target (kf_aux.hpp, sphere_query) runs on the
 // posterior state while it is still in registers -- BASELINE.json configs[4], "per-step interception
 // point fused on-GPU": one launch per tick instead of step + query.
@@ -265,6 +297,14 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   }
   char* tb = a.rec + tile * C::TILE_BYTES;
   T mem[C::RW];
+  // uniform tiles: compiled into the dense launches of the shared-axes form (the indexed kernel sees settled records: Batch::settle_tiles)
+  constexpr bool UT = C::UT && !INDEXED;
+  int uni_flag = 0;
+  bool uni = false, uni_out = false;
+  constexpr bool BLK_EARLY = UT && uniform_tiles_block_early(M::TYPE);
+  T blk[BLK_EARLY ? C::LW : 1];
+  if constexpr (!UT) { (void)uni_flag; (void)uni; (void)uni_out; }
+  if constexpr (!BLK_EARLY) (void)blk;
   // LIVE: the parked part of the record (LivePark) lives in the wavefront's LDS for the whole session
   using Park = LivePark<C, M, T>;
   constexpr int NPARK = (LIVE != 0 && C::SEPPK) ? Park::SLOT.count : 0;
@@ -294,6 +334,21 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       if (Park::SLOT.v[C::RW - 1] >= 0) park_lds[Park::SLOT.v[C::RW - 1] * 64 + lane] = v;
       else mem[C::RW - 1] = v;
     }
+  } else if constexpr (UT) {
+    // The flag first (loads return in order: waiting for it waits for nothing else), then every part of the record that moves
+    // whatever the flag says.  What depends on the flag follows behind the measurement loads: the lanes' linear-covariance chunks
+    // in a tile that is not uniform, the tile's block (LW words at one address for the whole wavefront) in one that is -- unless
+    // the model asks for the block up front (te_layout.hpp uniform_tiles_block_early).
+    if (a.tile_uni != nullptr) {
+      uni_flag = a.tile_uni[tile];
+      if constexpr (BLK_EARLY) {
+#pragma unroll
+        for (int k = 0; k < C::LW; ++k) blk[k] = a.tile_blk[tile * C::LW + k];
+      }
+    }
+#pragma unroll
+    for (int w = 0; w < C::RW; ++w) mem[w] = 0;
+    if (valid) load_record_part<C, T, false>(tb, lt, mem);
   } else if (valid) {
     load_record<C, T>(tb, lt, mem);
   } else {
@@ -420,6 +475,18 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   }
   const bool has = valid && meas_t != nullptr && hmask != 0;
   n_has += has ? 1 : 0;
+  if constexpr (UT) {
+    uni = __builtin_amdgcn_readfirstlane(uni_flag) != 0;
+    if (uni) {   // (wave-uniform) every lane takes the tile's block
+#pragma unroll
+      for (int k = 0; k < C::LW; ++k) {
+        if constexpr (BLK_EARLY) mem[C::LIN.w[k]] = blk[k];
+        else mem[C::LIN.w[k]] = a.tile_blk[tile * C::LW + k];
+      }
+    } else if (valid) {
+      load_record_part<C, T, true>(tb, lt, mem);
+    }
+  }
   if constexpr (HOIST_QR) {
     // pin the hoisted Q / R values into scalar registers here, i.e. wait for their loads now, while the record
     // and measurement loads are still in flight (otherwise the compiler sinks them back next to their uses)
@@ -799,6 +866,26 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
   }  // tick loop
+  if constexpr (UT) {
+    // Does the tile leave this tick uniform?  Its lanes must have taken the same has-bit (dt is the launch's).  A uniform tile
+    // then stays one -- every lane has computed the same block from the same block -- and a tile that is not becomes one, in a
+    // launch that asks for it, if its valid lanes are found to agree on every linear P word, bit for bit.
+    if (a.tile_uni != nullptr) {
+      bool agree = true;
+      if (a.has_meas != nullptr) agree = __all(!valid || n_has == __builtin_amdgcn_readfirstlane(n_has)) != 0;
+      if (uni) {
+        uni_out = agree;
+      } else if (a.promote != 0 && agree) {
+        bool same = true;
+#pragma unroll
+        for (int k = 0; k < C::LW; ++k) {
+          const long long b = __double_as_longlong(mem[C::LIN.w[k]]);
+          same = same && b == wave_uniform_ll(b);
+        }
+        uni_out = __all(!valid || same) != 0;
+      }
+    }
+  }
   if (valid) {
     if constexpr (NPARK > 0) {   // the reverse of the session's first lines: chunk by chunk from the record's two homes
       using V = typename Vec16<T>::type;
@@ -818,6 +905,21 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       if constexpr (C::REM1)
         *reinterpret_cast<T*>(tb + C::TAIL1_OFF + (long)lt * (long)sizeof(T)) =
             Park::SLOT.v[C::RW - 1] >= 0 ? park_lds[Park::SLOT.v[C::RW - 1] * 64 + lane] : mem[C::RW - 1];
+    }
+    else if constexpr (UT) {
+      char* dst = AB ? a.rec_out + tile * C::TILE_BYTES : tb;
+      if (uni_out) {   // (wave-uniform) the tile's one block instead of 64 copies of it
+        store_record_nonlin<C, T, AB>(dst, lt, mem);
+        if (lane == 0) {   // (lane 0 of a dense wavefront that got here is valid)
+#pragma unroll
+          for (int k = 0; k < C::LW; ++k) a.tile_blk[tile * C::LW + k] = mem[C::LIN.w[k]];
+          if (!uni) a.tile_uni[tile] = 1;
+        }
+      } else {
+        if constexpr (AB) store_record<C, T, false, true>(dst, lt, mem);
+        else store_record<C, T>(dst, lt, mem);
+        if (uni && lane == 0) a.tile_uni[tile] = 0;
+      }
     }
     else if constexpr (AB) store_record<C, T, false, true>(a.rec_out + tile * C::TILE_BYTES, lt, mem);   // A -> B tick (StepArgs::rec_out)
     else store_record<C, T>(tb, lt, mem);

@@ -184,7 +184,7 @@ int Shard::findOrCreateBatch(int type, const double* Q, const double* R, int lan
       return (int)b;
     }
   // (the batch itself decides from Q and R whether it starts in the shared-axes form, and from every P0 whether it stays in it)
-  batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes));
+  batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes, set_.uniform_tiles));
   if (set_.keep_meas) batches_.back()->set_keep_measurement(true);
   cls = 0;
   return (int)batches_.size() - 1;
@@ -850,6 +850,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
         return Nodes(deps, deps + n);
       };
       TE_HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+      for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(true);   // (uniform tiles: a recording's ticks promote)
       try {
         Nodes leaves, none;
         if (populationTick()) {
@@ -874,11 +875,13 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
         TE_HIP_CHECK(hipGetLastError());
         if (!leaves.empty()) set_deps(leaves);
       } catch (...) {
+        for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(false);
         hipGraph_t broken = nullptr;
         (void)hipStreamEndCapture(cap, &broken);   // leave capture mode before reporting
         if (broken) (void)hipGraphDestroy(broken);
         throw;
       }
+      for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(false);
       TE_HIP_CHECK(hipStreamEndCapture(cap, &g.graph));
       TE_HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
       seq_graphs_.push_back(std::move(g));
@@ -886,6 +889,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     }
     if (use_graph == 2) return;
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
+    for (size_t b = 0; b < nb; ++b) batches_[b]->note_replay(n_ticks);
   }
   for (size_t b = 0; b < nb; ++b)
     if (batches_[b]->size() > 0) batches_[b]->account_sequence(n_ticks, dt, specs[b].meas_base && !specs[b].has_base);

@@ -46,6 +46,7 @@ struct ShardSettings {
   int filters_length = 250;   // setIntersectionFiltersLength
   long small_batch_most = 0;  // the largest host-array call that goes through the one-target queue (TE_SMALL_BATCH_QUEUE)
   bool population_tick = true;   // TE_POPULATION_TICK
+  bool uniform_tiles = true;     // TE_UNIFORM_TILES / TargetManager::setUniformTiles: new shared-axes batches keep uniform tiles (Batch)
   bool shared_axes = true;       // TE_SHARED_AXES / TargetManager::setSharedAxes: new fp64 batches may use the shared-axes storage form (Batch)
 };
 

@@ -30,6 +30,8 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) {
   settings_.population_tick = pop;
   static const bool shared = [] { const char* e = std::getenv("TE_SHARED_AXES"); return !(e && e[0] == '0'); }();
   settings_.shared_axes = shared;
+  static const bool uniform = [] { const char* e = std::getenv("TE_UNIFORM_TILES"); return !(e && e[0] == '0'); }();
+  settings_.uniform_tiles = uniform;
   const char* ld = std::getenv("TARGET_ESTIMATION_LOG_DIR");
   if (ld && ld[0]) { log_dir_ = ld; settings_.keep_meas = true; }   // batches created later inherit the measured-pose rows
   int count = 0;
@@ -134,6 +136,13 @@ void TargetManager::setSharedAxes(bool on) {
   for (const auto& sh : shards_)
     if (!sh->batches().empty()) throw std::runtime_error("target_estimation_amd: setSharedAxes: set it before the first target is created");
   settings_.shared_axes = on;
+}
+
+void TargetManager::setUniformTiles(bool on) {
+  lock_guard<mutex> lg(target_lock_);
+  for (const auto& sh : shards_)
+    if (!sh->batches().empty()) throw std::runtime_error("target_estimation_amd: setUniformTiles: set it before the first target is created");
+  settings_.uniform_tiles = on;
 }
 
 void TargetManager::setKeepMeasurement(bool on) {

@@ -93,6 +93,10 @@ class TargetManager {
   // TE_SHARED_AXES=0.  Batches that exist keep their form, so set it before the first init; throws once there is a batch.
   void setSharedAxes(bool on);
   bool sharedAxes() const { return settings_.shared_axes; }
+  // May its shared-axes batches keep uniform tiles (batch_store.hpp)?  Default: yes unless TE_UNIFORM_TILES=0.  As setSharedAxes:
+  // before the first init; throws once there is a batch.
+  void setUniformTiles(bool on);
+  bool uniformTiles() const { return settings_.uniform_tiles; }
   bool getTargetMeasuredPose(unsigned id, double* pose7);          // false: unknown id or not kept
   // TargetInterface::getPeriodEstimate (target_interface.cpp:80-87): 2 pi / |omega| of the current twist, -1 if not rotating
   bool getTargetPeriodEstimate(unsigned id, double& period);

@@ -365,11 +365,14 @@ int target_batch_layout(target_batch_c* b) {
 int target_batch_shared_axes(target_batch_c* b) {
   return guarded_value<int>("target_batch_shared_axes", -1, [&]() -> int { return B(b)->shared_axes() ? 1 : 0; });
 }
+long target_batch_uniform_tiles(target_batch_c* b) {
+  return guarded_value<long>("target_batch_uniform_tiles", -1, [&]() -> long { BatchLock lk(B(b)); return B(b)->uniform_tiles(); });
+}
 int target_batch_record_words(target_batch_c* b) {
   return guarded_value<int>("target_batch_record_words", -1, [&]() -> int { return B(b)->layout().record_words; });
 }
 long target_batch_algorithmic_bytes(target_batch_c* b) {
-  return guarded_value<long>("target_batch_algorithmic_bytes", -1, [&]() -> long { return B(b)->algorithmic_bytes_per_cycle(); });
+  return guarded_value<long>("target_batch_algorithmic_bytes", -1, [&]() -> long { BatchLock lk(B(b)); return B(b)->algorithmic_bytes_per_cycle(); });   // (reads the tile flags back: batch_store.cpp)
 }
 double target_batch_resident_bytes_per_target(target_batch_c* b) {
   return guarded_value<double>("target_batch_resident_bytes_per_target", -1.0,
@@ -658,6 +661,9 @@ void target_intersection_solver_last_errors(target_intersection_solver_c* solver
 // ---------------------------------------------------------------- TargetInterface / estimator getters
 int target_manager_set_shared_axes(target_manager_c* self, int on) {
   return guarded("target_manager_set_shared_axes", [&] { M(self)->setSharedAxes(on != 0); });
+}
+int target_manager_set_uniform_tiles(target_manager_c* self, int on) {
+  return guarded("target_manager_set_uniform_tiles", [&] { M(self)->setUniformTiles(on != 0); });
 }
 int target_manager_set_keep_measurement(target_manager_c* self, int on) {
   return guarded("target_manager_set_keep_measurement", [&] { M(self)->setKeepMeasurement(on != 0); });

@@ -128,6 +128,15 @@ constexpr int qr_r_word(int type, bool sep, int r, int c) {   // r, c < m: the m
   return sep ? qr_sep_word(type, true, r, c) : model_n(type) * model_n(type) + r * model_m(type) + c;
 }
 
+// Uniform tiles (Cfg::UT below): which models' shared-form kernels carry the feature.  A trait so that a kernel whose registers,
+// scratch or wavefronts per SIMD it would move stays as it was: angular_velocities sits at 162 of the 168 registers that three
+// wavefronts per SIMD allow and went to 166 - 168 with it, for 2 skippable words of 85 (profiles/r08_uniform_tiles_kernel_resources.txt).
+constexpr bool uniform_tiles_model(int type) { return type != ANGULAR_VELOCITIES; }
+// ... and whether a wavefront requests its tile's block up front, next to the flag, or only once the flag says it is needed.
+// Up front the block's words are live under the record loads: uniform_velocity and uniform_acceleration lost two wavefronts per
+// SIMD that way (44 -> 76, 74 -> 98 registers).  Behind the flag angular_rates lost one (119 -> 129; up front 127, four wavefronts).
+constexpr bool uniform_tiles_block_early(int type) { return type == ANGULAR_RATES; }
+
 // PK_ = symmetric-packed storage: only the upper triangle of P (r <= c, row-major, N(N+1)/2 words) is
 // kept in HBM.  G = 1 (thread per target): the mirror into the registers is a register rename.
 // G > 1: lane i of a target stores the i-th slice of ceil(N(N+1)/2 / G) words of the triangle; after
@@ -260,6 +269,39 @@ struct Cfg {
     return t;
   }
   static constexpr WordTable PWORD = make_table();
+  // Uniform tiles (shared-axes form only).  The P words of the [p v (a)] chains -- every stored P word of a linear model, those of
+  // the x, y, z chains of the EKF -- depend on the block before the tick, Q, R, dt and the has-bit alone (sep_linear_cov), so the
+  // 64 targets of a tile that agree on them bit for bit keep agreeing for as long as they receive the same dt and has-bit.  Such a
+  // tile keeps ONE copy of those LW words (Batch: tile_blk, flagged in tile_uni), and the dense step neither loads nor stores
+  // the record's LINEAR-COVARIANCE CHUNKS: the 16-byte chunks all of whose words are such P words.  A linear P word that shares
+  // its chunk with x or EKF words moves as ever.  UT: the form's kernels have the feature compiled in.
+  static constexpr bool UT = SHARED && uniform_tiles_model(M::TYPE);
+  static constexpr bool lin_row(int r) { return !M::EKF || (r % 6) < 3; }
+  struct LinTable { int n; int w[PW > 0 ? PW : 1]; int idx[RW]; bool chunk[NC > 0 ? NC : 1]; int n_chunks; };
+  static constexpr LinTable make_lin_table() {
+    LinTable t{};
+    for (int w = 0; w < RW; ++w) t.idx[w] = -1;
+    if (SHARED) {
+      for (int r = 0; r < N; ++r)
+        for (int c = r; c < N; ++c) {
+          const int w = PWORD.v[r][c];
+          if (w >= 0 && lin_row(r) && lin_row(c) && t.idx[w] < 0) t.idx[w] = 0;
+        }
+      for (int w = 0; w < RW; ++w)   // in record order
+        if (t.idx[w] == 0) { t.idx[w] = t.n; t.w[t.n++] = w; }
+      for (int c = 0; c < NC; ++c) {
+        bool all = true;
+        for (int k = 0; k < VW; ++k) all = all && t.idx[c * VW + k] >= 0;
+        t.chunk[c] = all;
+        t.n_chunks += all ? 1 : 0;
+      }
+    }
+    return t;
+  }
+  static constexpr LinTable LIN = make_lin_table();
+  static constexpr int LW = LIN.n;                    // linear P words of the form: the words of a tile's block
+  static constexpr int LIN_CHUNKS = LIN.n_chunks;     // chunks a uniform tile skips
+  static constexpr bool lin_chunk(int c) { return LIN.chunk[c]; }
   static constexpr int QR_WORDS = qr_words(M::TYPE, SEP);   // words of one parameter-class row
   struct QTable { int v[N][N]; };
   struct RTable { int v[K][K]; };
@@ -303,6 +345,8 @@ struct LayoutInfo {
   int n, m, g, layout, tpw, lpt, record_words;
   long tile_bytes, tile_payload;
   int shared_axes = 0;   // 1: the shared-axes storage form of layout 3 (LAYOUT_SEPARABLE_SHARED)
+  int lin_words = 0;     // uniform tiles (Cfg::UT): words of a tile's block (Cfg::LW), 0 = the kernels do not have the feature
+  int lin_chunks = 0;    // ... and the 16-byte chunks of a record that a uniform tile skips (Cfg::LIN_CHUNKS)
 };
 
 }  // namespace te

@@ -73,6 +73,9 @@ class Batch:
     layout = property(lambda s: ("full", "symmetric_packed", "axis_separable", "axis_separable_packed")[s._lib.target_batch_layout(s._h)])
     # the shared-axes storage form of axis_separable_packed (target_batch_shared_axes): one covariance block per kind of axis
     shared_axes = property(lambda s: s._lib.target_batch_shared_axes(s._h))
+    # tiles of the batch whose 64 targets share one copy of their linear-chain covariance words now (target_batch_uniform_tiles;
+    # reads the flags back: synchronises)
+    uniform_tiles = property(lambda s: s._lib.target_batch_uniform_tiles(s._h))
     record_words = property(lambda s: s._lib.target_batch_record_words(s._h))
     num_classes = property(lambda s: s._lib.target_batch_num_classes(s._h))
     algorithmic_bytes = property(lambda s: s._lib.target_batch_algorithmic_bytes(s._h))
@@ -307,10 +310,12 @@ class MeasurementIngest:
 class TargetManager:
     """ctypes mirror of the reference TargetManager; dtype 'f64' (reference precision) or 'f32'."""
 
-    def __init__(self, file=None, dtype="f64", lanes_per_target=0, devices=None, shared_axes=None):
+    def __init__(self, file=None, dtype="f64", lanes_per_target=0, devices=None, shared_axes=None, uniform_tiles=None):
         """devices: HIP device indices, one shard each (repeats allowed; target_manager_set_devices).  None: unsharded.
         shared_axes: False keeps this manager's batches out of the shared-axes storage form (target_manager_set_shared_axes);
-        None: the default (on unless TE_SHARED_AXES=0)."""
+        None: the default (on unless TE_SHARED_AXES=0).
+        uniform_tiles: False keeps its shared-axes batches from sharing covariance words between the targets of a tile
+        (target_manager_set_uniform_tiles); None: the default (on unless TE_UNIFORM_TILES=0)."""
         self._lib = capi.lib()
         f = None if file is None else str(file).encode()
         self._h = self._lib.target_manager_new_ex(f, DTYPES[dtype], int(lanes_per_target))
@@ -319,6 +324,8 @@ class TargetManager:
         self.dtype = dtype
         if shared_axes is not None:
             _check(self._lib.target_manager_set_shared_axes(self._h, 1 if shared_axes else 0), "target_manager_set_shared_axes")
+        if uniform_tiles is not None:
+            _check(self._lib.target_manager_set_uniform_tiles(self._h, 1 if uniform_tiles else 0), "target_manager_set_uniform_tiles")
         if devices is not None:
             try:
                 self.set_devices(devices)
