@@ -389,6 +389,50 @@ int target_batch_step_fused_poses(target_batch_c* b, long n_ticks, double dt, co
 int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, double dt,
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            long n_batches, int query, const double* origin, double radius, int use_graph);
+/* Per-tick innovations and NIS from launched ticks.  The two numbers that say how well the filter and the measurements agree
+ * exist inside every update -- the innovation nu = y - x^-[0:m] and the inverse innovation covariance S^-1
+ * (src/kalman.cpp:92-93, :137-138) -- and the ..._innov forms of the launched calls below stream them out: after tick s of the
+ * call, with b = (ring_ticks > 0 ? s % ring_ticks : s) and column j = slot j (target_batch_slot_ids order; columns >= the batch
+ * size are never written),
+ *   nis_dev[b * nis_tick_stride + j]                        = nu^T S^-1 nu of that tick, the normalised innovation squared;
+ *   innov_dev + b * innov_tick_stride, doubles SoA [m][ld]  : row c = nu_c, c = 0 .. m - 1 (only if innov_dev is not NULL).
+ * m is 3 for the linear models (x y z) and 6 for the angular ones (x y z roll pitch yaw).  The angular components are taken
+ * against the UNWRAPPED measured rpy, i.e. the same y the update uses; S^-1 is the inverse the gain uses, not a second one.
+ * fp32 batches compute in fp32 and store as double.  A stride of 0 overwrites one row / block every tick.
+ * A target without a measurement on that tick (mask 0, or a predict-only tick: meas_dev NULL) gets NIS = -1 and nu = 0.
+ * `poses` / `per_batch_poses` and the fused `query` keep their meaning and their results, bit for bit; so does the state.
+ * Who writes it: the kernel that did the step, while the values are in registers, for one-class batches in the axis-separable
+ * layouts (lanes 201 and 301, and 301 in the shared-axes storage form with or without uniform tiles -- the form serves the stream
+ * and the batch stays in it): single dense ticks and the one-launch population tick, one launch per tick as without the stream.
+ * A tick with an innovation stream runs IN PLACE: the A -> B variant is not taken for that call (same bits).  With `poses` in the
+ * same call the step is followed by the pose-writer launch, with query != 0 by the query launch per batch (what
+ * target_batch_intersect_sphere_dev runs): those combinations have no kernel of their own.  The dense layouts (coupled
+ * Q / R / P0, an explicit lanes_per_target outside 201 / 301, the symmetric-packed EKF) and batches with several (Q, R) classes
+ * are served by one innovation-writer launch BEFORE each tick's step -- it reads the records, the class rows and the unwrap
+ * memory and writes nothing else -- and then step as without the stream.
+ * use_graph 0 / 1 / 2 as for ..._poses: a recorded graph is keyed by the innovation stream too.  Bad arguments (ld < batch size,
+ * nis_tick_stride in (0, ld), innov_tick_stride in (0, m * ld), a negative value, ring_ticks < 0) return a negative code with
+ * target_manager_last_error set, and nothing is launched.  A NULL `innov` (or per_batch_innov), or a NULL nis_dev, gives exactly
+ * the ..._poses call.  target_batch_algorithmic_bytes keeps reporting the plain tick: the stream adds 8 B per target and tick
+ * for NIS, plus 8 * m B for the innovations.
+ * Not served (no innovation stream there): target_batch_step_fused, the resident mode (target_batch_live_*), the by-id / indexed
+ * launches, the one-target symbols and the Eigen facade. */
+typedef struct target_innov_stream_c {
+  double* nis_dev;          /* device memory; NULL = no innovation stream for this batch */
+  double* innov_dev;        /* device memory or NULL: NIS only */
+  long ld;                  /* >= batch size */
+  long nis_tick_stride;     /* doubles between the NIS rows of consecutive ticks (>= ld); 0 = every tick overwrites one row */
+  long innov_tick_stride;   /* the same for the [m][ld] innovation blocks (>= m * ld); 0 = overwrite */
+  long ring_ticks;          /* > 0: tick s writes block s % ring_ticks; 0: block s */
+} target_innov_stream_c;
+int target_batch_step_sequence_innov(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, const target_innov_stream_c* innov, int use_graph);
+/* per_batch_innov[i]: the innovation stream of batch i (NULL: none for any batch) */
+int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           const target_innov_stream_c* per_batch_innov, long n_batches,
+                                           int query, const double* origin, double radius, int use_graph);
 /* Resident ("live") mode (target_batch_live_* above) for EVERY batch of a manager at once (BASELINE.json configs[3] / configs[4]: two motion models per GPU, whose per-GPU
  * share is launch-bound): one resident kernel per batch, each on a stream of its own so that they are on the device together;
  * per_batch[i] describes batch i's ring as for target_manager_step_sequence_all (ring_ticks > 0); with query != 0 the own-time

@@ -26,6 +26,12 @@ class PoseStream(C.Structure):
     _fields_ = [("pose_dev", C.c_void_p), ("ld", C.c_long), ("tick_stride", C.c_long), ("ring_ticks", C.c_long)]
 
 
+class InnovStream(C.Structure):
+    """target_innov_stream_c of target_batch_c.h: the per-tick innovation / NIS stream of a launched tick"""
+    _fields_ = [("nis_dev", C.c_void_p), ("innov_dev", C.c_void_p), ("ld", C.c_long), ("nis_tick_stride", C.c_long),
+                ("innov_tick_stride", C.c_long), ("ring_ticks", C.c_long)]
+
+
 class StreamSpec(C.Structure):
     """target_stream_c of target_batch_c.h"""
     _fields_ = [("model", C.c_int), ("seed", C.c_ulonglong), ("first_target", C.c_long), ("dt", C.c_double),
@@ -150,6 +156,10 @@ SIGNATURES = {
                                                 C.POINTER(PoseStream)]),
     "target_manager_step_sequence_all_poses": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream), C.c_long,
                                                          C.c_int, c_double_p, C.c_double, C.c_int]),
+    "target_batch_step_sequence_innov": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                   C.c_long, C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_int]),
+    "target_manager_step_sequence_all_innov": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
+                                                         C.POINTER(InnovStream), C.c_long, C.c_int, c_double_p, C.c_double, C.c_int]),
     "target_batch_live_start": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long,
                                           C.c_long, C.c_double]),
     "target_batch_live_set_pose_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -644,9 +644,22 @@ void Batch::check_pose_stream(const PoseStream& q) const {
   if (q.ring < 0) throw std::invalid_argument("target_estimation_amd: pose stream: negative ring_ticks");
 }
 
+void Batch::check_innov_stream(const InnovStream& q) const {
+  if (!q.nis) return;
+  const long m = ops_->L.m;
+  if (q.ld < n_) throw std::invalid_argument("target_estimation_amd: innovation stream: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
+  if (q.nis_tick_stride < 0 || (q.nis_tick_stride > 0 && q.nis_tick_stride < q.ld))
+    throw std::invalid_argument("target_estimation_amd: innovation stream: nis_tick_stride must be 0 or >= ld");
+  if (q.innov_tick_stride < 0 || (q.innov_tick_stride > 0 && q.innov_tick_stride < m * q.ld))
+    throw std::invalid_argument("target_estimation_amd: innovation stream: innov_tick_stride must be 0 or >= " + std::to_string(m) + " * ld");
+  if (q.ring < 0) throw std::invalid_argument("target_estimation_amd: innovation stream: negative ring_ticks");
+}
+
 void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                          const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks, const PoseStream& poses) {
+                          const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks, const PoseStream& poses,
+                          const InnovStream& innov) {
   check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
+  check_innov_stream(innov);
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
   const size_t es = elem_size();
@@ -659,10 +672,11 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     p.dt = dt;
     p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
     p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
+    p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld;
     return p;
   };
   if (!use_graph) {
-    const bool ab = pingpong();
+    const bool ab = pingpong() && !innov.on();   // (a tick with an innovation stream runs in place: same bits)
     for (long s = 0; s < n_ticks; ++s) {
       StepParams p = params(s);
       if (ab) p.rec_out = alt_records();
@@ -676,7 +690,8 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     for (auto& g : graphs_)
       if (g.n_ticks == n_ticks && g.tick_stride == tick_stride && g.ld == ld && g.has_stride == has_stride && g.n == n_ &&
           g.dt == dt && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks &&
-          g.poses.dev == poses.dev && g.poses.ld == poses.ld && g.poses.tick_stride == poses.tick_stride && g.poses.ring == poses.ring) hit = &g;
+          g.poses.dev == poses.dev && g.poses.ld == poses.ld && g.poses.tick_stride == poses.tick_stride && g.poses.ring == poses.ring &&
+          g.innov.same(innov)) hit = &g;
     if (!hit) {
       if (graphs_.size() >= 64) {   // e.g. a ring of 4096 ticks replayed in 64-tick blocks: evict the least recently used one
         size_t victim = 0;
@@ -690,6 +705,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
       if (!cap_stream_) TE_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
       GraphEntry e{n_ticks, tick_stride, ld, has_stride, n_, dt, meas_base, has_base, d_rec_, nullptr, nullptr, ring_ticks};
       e.poses = poses;
+      e.innov = innov;
       TE_HIP_CHECK(hipStreamBeginCapture(cap_stream_, hipStreamCaptureModeThreadLocal));
       recording_ = true;   // (a recording is a dense streak: its ticks promote)
       try {
@@ -731,11 +747,16 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
                          bool reverse, bool ab) {
   if (n_ == 0) return;
   double* pose_block = q.poses.block(s);   // (tick s of the call: the pose stream's own ring)
+  double* nis_row = q.innov.nis_row(s);    // (... and the innovation stream's)
+  double* innov_block = q.innov.innov_block(s);
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
-  const bool fused_q = ops_->fused_query && n_classes_ == 1;
+  // (a tick with an innovation stream runs in place and without the fused query: the query follows as intersect_kernel)
+  const bool fused_q = ops_->fused_query && n_classes_ == 1 && !q.innov.on();
+  if (q.innov.on()) ab = false;
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
+  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
@@ -761,12 +782,33 @@ bool Batch::population_ready() const {
   return ops_->L.layout == LAYOUT_SEPARABLE_PACKED && n_classes_ == 1 && !keep_meas_ && ops_->fused_query;
 }
 
+void Batch::enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& q, bool query, const double* origin, double radius) {
+  if (n_ == 0) return;
+  if (q.poses.dev) {
+    OutArgs o;
+    o.rec = records_as_stored(); o.idx = nullptr; o.n = n_; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
+    o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = d_tbase_;
+    o.pose_soa = q.poses.block(s); o.pose_ld = q.poses.ld;
+    ops_->outputs(o, st);
+  }
+  if (query) {
+    IntersectArgs a;
+    a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
+    a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
+    a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
+    ops_->intersect(a, st);
+  }
+}
+
 StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius, bool ab) {
   double* pose_block = q.poses.block(s);
+  double* nis_row = q.innov.nis_row(s);
+  double* innov_block = q.innov.innov_block(s);
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
+  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;

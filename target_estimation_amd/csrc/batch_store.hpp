@@ -28,6 +28,25 @@ struct PoseStream {
   double* block(long s) const { return dev ? dev + (ring > 0 ? s % ring : s) * tick_stride : nullptr; }
 };
 
+// A per-tick innovation stream (target_innov_stream_c): after tick s of a call, for every slot (column), the tick's normalised
+// innovation squared nu^T S^-1 nu in row b = (ring > 0 ? s % ring : s) of nis (rows nis_tick_stride apart) and, unless innov is null,
+// its innovation nu = y - x^-[0:m] in block b of innov, SoA [m][ld] (blocks innov_tick_stride apart); a stride of 0 overwrites one
+// row / block every tick.  A slot without a measurement on the tick: NIS = -1, nu = 0.  nis == null: no stream.
+struct InnovStream {
+  double* nis = nullptr;
+  double* innov = nullptr;
+  long ld = 0;
+  long nis_tick_stride = 0;
+  long innov_tick_stride = 0;
+  long ring = 0;
+  bool on() const { return nis != nullptr; }
+  double* nis_row(long s) const { return nis ? nis + (ring > 0 ? s % ring : s) * nis_tick_stride : nullptr; }
+  double* innov_block(long s) const { return (nis && innov) ? innov + (ring > 0 ? s % ring : s) * innov_tick_stride : nullptr; }
+  bool same(const InnovStream& o) const {
+    return nis == o.nis && innov == o.innov && ld == o.ld && nis_tick_stride == o.nis_tick_stride && innov_tick_stride == o.innov_tick_stride && ring == o.ring;
+  }
+};
+
 class Batch {
  public:
   // `owner_lock`: the one mutex of the manager whose shard owns the batch (TargetManager::target_lock_, whatever the number
@@ -112,9 +131,12 @@ class Batch {
   // per-launch host cost when a recorded stream is replayed; 2: record only, launch nothing).
   // poses: the per-tick pose stream of the call (PoseStream; by default none), written by the step kernel where the layout has a
   // POSE variant, by a pose-writer launch behind every tick otherwise (OpsImpl::step)
+  // innov: the per-tick innovation stream of the call (InnovStream; by default none), written by the step kernel where the layout
+  // has an INNOV variant, by an innovation-writer launch ahead of every tick otherwise (OpsImpl::step).  Its ticks run in place
+  // (no A -> B variant) -- same bits.
   void step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                      const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks = 0,
-                     const PoseStream& poses = PoseStream{});
+                     const PoseStream& poses = PoseStream{}, const InnovStream& innov = InnovStream{});
   // n_ticks ticks in ONE launch: every target's state stays in registers across the ticks and only
   // the measurements are read per tick.  Same results as n_ticks single ticks; a different
   // ("effective", temporally fused) cost model -- for replaying recorded streams.
@@ -123,6 +145,8 @@ class Batch {
   // throws std::invalid_argument unless `poses` is none or a valid stream for this batch (ld >= size, tick_stride 0 or >= 7 ld,
   // ring >= 0): checked before a call enqueues anything
   void check_pose_stream(const PoseStream& poses) const;
+  // the same for an innovation stream: ld >= size, nis_tick_stride 0 or >= ld, innov_tick_stride 0 or >= m ld, nothing negative
+  void check_innov_stream(const InnovStream& innov) const;
   // RESIDENT ("live") mode for small batches: ONE launch stays on the device with the batch's state in registers and serves
   // tick after tick as the host posts them -- no per-tick dispatch (a dependent launch costs 1.5-2 us, more than the tick of a
   // 10^4-target batch itself).  Protocol:
@@ -216,6 +240,7 @@ class Batch {
     double* delta_dev; double* pose_dev;                // query outputs [size] / [size][7] (overwritten every tick)
     long ring_ticks;                                    // > 0: the measurements are a ring, tick s reads entry s % ring_ticks
     PoseStream poses{};                                 // the per-tick pose stream of the batch (tick s: poses.block(s)), or none
+    InnovStream innov{};                                // the per-tick innovation stream of the batch, or none
   };
   // tick s of the spec on `st`, without touching the batch clock.  With query: the own-time sphere
   // query of every slot runs inside the step kernel (one launch).
@@ -228,6 +253,9 @@ class Batch {
   // caller calls swap_records() once the launch is queued (and only if the returned parameters carry rec_out).
   bool population_ready() const;
   StepParams tick_params(long s, double dt, const SeqSpec& spec, bool query, const double* origin, double radius, bool ab);
+  // What follows a population tick that carried an innovation stream (whose kernel has neither the fused query nor the pose
+  // output) for this batch: the pose-writer launch into tick s's pose block and / or the own-time sphere query, as launches.
+  void enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& spec, bool query, const double* origin, double radius);
   void swap_records() { std::swap(d_rec_, d_rec_alt_); }
   void account_sequence(long n_ticks, double dt, bool all_measured);
   // identity of everything a recorded launch sequence refers to
@@ -348,6 +376,7 @@ class Batch {
     long ring_ticks;
     unsigned long last_use = 0;
     PoseStream poses{};   // (recorded graphs write into the pose buffers they were recorded with)
+    InnovStream innov{};  // (... and into the innovation buffers)
   };
   std::vector<GraphEntry> graphs_;
   unsigned long graph_clock_ = 0;   // recorded sequences are evicted least-recently-used first (64 kept)

@@ -397,6 +397,160 @@ __global__ __launch_bounds__(kOutputsBlock) void outputs_rows_kernel(const OutAr
   }
 }
 
+// ---- the innovation writer -------------------------------------------------------------------------------------------------
+// The innovation stream of a tick (kf_step.hpp StepArgs::nis) for the layouts whose step kernel does not write it itself: the
+// dense kf_step_kernel layouts, the symmetric-packed EKF, batches with several (Q, R) classes.  One launch BEFORE the step,
+// records read-only: what the step is about to form.
+struct InnovArgs {
+  char* rec;                       // read, never written (nor is the unwrap memory)
+  const void* qr;                  // the batch's [Q | R] row, or (cls != null) its table of rows
+  const int* cls;                  // per-slot parameter class, or null
+  long n;
+  const void* meas;                // SoA [7][meas_ld] in the batch precision, or null (a predict-only tick: sentinels)
+  long meas_ld;
+  const unsigned char* has_meas;   // per-slot mask or null
+  double dt;
+  const double* tile_blk;          // the batch's uniform tiles, honoured read-only (null: none)
+  const int* tile_uni;
+  double* nis;                     // [n]
+  double* innov;                   // SoA [m][innov_ld], or null
+  long innov_ld;
+};
+
+// Thread per target: x^-[0:m] = (A x | f(x))[0:m], S = (A P A^T + Q)[0:m,0:m] + R from the rows of A that reach a measured state
+// (src/kalman.cpp:84-92 | :129-137; the EKF's Jacobians at the stored posterior, as the step takes them), S^-1 by unpivoted
+// Gauss-Jordan as the step does, y with the unwrapped angles of the angular models, nu = y - x^-[0:m], NIS = nu^T S^-1 nu.  P is
+// read element by element through the layout's accessors (state_get, as get_state_kernel): nothing is expanded in memory.
+// Off the hot path: correct, not fast.  A target without a measurement gets NIS = -1 and nu = 0.
+template <class M, typename T, int G, int LAYOUT>
+__global__ void innov_kernel(const InnovArgs a) {
+#pragma clang fp contract(off)
+  using C = Cfg<M, T, G, LAYOUT>;
+  using F = Mth<T>;
+  constexpr int N = C::N, K = C::K;   // K = m: the measured states are rows 0..K-1
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.n) return;
+  const T* meas = static_cast<const T*>(a.meas);
+  const bool has = meas != nullptr && (a.has_meas == nullptr || a.has_meas[e] != 0);
+  if (!has) {
+    a.nis[e] = -1.0;
+    if (a.innov != nullptr) for (int c = 0; c < K; ++c) a.innov[(long)c * a.innov_ld + e] = 0.0;
+    return;
+  }
+  const T dt = (T)a.dt, hdt = (T)0.5 * dt * dt;
+  const T* qr = static_cast<const T*>(a.qr) + (a.cls ? (long)a.cls[e] * C::QR_WORDS : 0L);
+  bool uni = false;
+  if constexpr (C::UT) uni = a.tile_uni != nullptr && a.tile_uni[e / C::TPW] != 0;
+  auto Pget = [&](int r, int c) -> T {
+    if constexpr (C::UT) {
+      const int w = C::PWORD.v[r][c];
+      if (uni && w >= 0 && C::LIN.idx[w] >= 0) return (T)a.tile_blk[(e / C::TPW) * C::LW + C::LIN.idx[w]];
+    }
+    return state_get<C, T>(a.rec, e, r, c);
+  };
+  T x[N];
+  for (int r = 0; r < N; ++r) x[r] = state_get<C, T>(a.rec, e, r, N);
+  // row r < K of A, sparse: A[r][col[r][j]] = cf[r][j]
+  int col[K][6], cnt[K];
+  T cf[K][6], xm[K];
+  if constexpr (!M::EKF) {
+    for (int r = 0; r < K; ++r) {
+      col[r][0] = r; cf[r][0] = (T)1;
+      col[r][1] = r + K; cf[r][1] = dt;
+      cnt[r] = 2;
+      xm[r] = F::fma(dt, x[r + K], x[r]);
+      if (C::NB == 3) {
+        col[r][2] = r + 2 * K; cf[r][2] = hdt;
+        cnt[r] = 3;
+        xm[r] = F::fma(hdt, x[r + 2 * K], xm[r]);
+      }
+    }
+  } else {
+    for (int r = 0; r < 3; ++r) {   // x, y, z: [p v] chains, rows {r, r + 6}
+      col[r][0] = r; cf[r][0] = (T)1;
+      col[r][1] = r + 6; cf[r][1] = dt;
+      cnt[r] = 2;
+      xm[r] = F::fma(dt, x[r + 6], x[r]);
+    }
+    // the attitude rows: geometry.hpp:394-426 (Jacobians at the stored posterior), :359-374 (EarBaseInv), angular_velocities.cpp:137
+    T s_r, c_r, s_p, c_p;
+    F::sincos(x[3], &s_r, &c_r);
+    F::sincos(x[4], &s_p, &c_p);
+    const T wy = x[10], wz = x[11];
+    T Jr[3][3], Jw[3][3], Ei[3][3];
+    Jr[0][0] = (dt * (wy * c_r * s_p - wz * s_p * s_r)) / c_p + 1;
+    Jr[0][1] = (dt * (wz * c_r + wy * s_r)) / (c_p * c_p);
+    Jr[0][2] = 0;
+    Jr[1][0] = -dt * (wz * c_r + wy * s_r);
+    Jr[1][1] = 1;
+    Jr[1][2] = 0;
+    Jr[2][0] = (dt * (wy * c_r - wz * s_r)) / c_p;
+    Jr[2][1] = (dt * s_p * (wz * c_r + wy * s_r)) / (c_p * c_p);
+    Jr[2][2] = 1;
+    Jw[0][0] = dt; Jw[0][1] = (dt * s_p * s_r) / c_p; Jw[0][2] = (dt * c_r * s_p) / c_p;
+    Jw[1][0] = 0;  Jw[1][1] = dt * c_r;               Jw[1][2] = -dt * s_r;
+    Jw[2][0] = 0;  Jw[2][1] = (dt * s_r) / c_p;       Jw[2][2] = (dt * c_r) / c_p;
+    Ei[0][0] = 1; Ei[0][1] = (s_p * s_r) / c_p; Ei[0][2] = (c_r * s_p) / c_p;
+    Ei[1][0] = 0; Ei[1][1] = c_r;               Ei[1][2] = -s_r;
+    Ei[2][0] = 0; Ei[2][1] = s_r / c_p;         Ei[2][2] = c_r / c_p;
+    for (int r = 0; r < 3; ++r) {
+      for (int j = 0; j < 3; ++j) {
+        col[3 + r][j] = 3 + j; cf[3 + r][j] = Jr[r][j];
+        col[3 + r][3 + j] = 9 + j; cf[3 + r][3 + j] = Jw[r][j];
+      }
+      cnt[3 + r] = 6;
+      T acc = (dt * Ei[r][0]) * x[9];
+      acc = F::fma(dt * Ei[r][1], x[10], acc);
+      acc = F::fma(dt * Ei[r][2], x[11], acc);
+      xm[3 + r] = x[3 + r] + acc;
+    }
+  }
+  // S = ((A P) A^T + Q)[0:K,0:K] + R
+  T S[K][K];
+  for (int r = 0; r < K; ++r)
+    for (int c = 0; c < K; ++c) {
+      T v = 0;
+      for (int j = 0; j < cnt[c]; ++j) {
+        T t = 0;   // (A P)[r][col[c][j]]
+        for (int i = 0; i < cnt[r]; ++i) t = F::fma(cf[r][i], Pget(col[r][i], col[c][j]), t);
+        v = F::fma(t, cf[c][j], v);
+      }
+      const int qw = C::QWORD.v[r][c], rw = C::RWORD.v[r][c];   // (negative: a structural zero of the separable layouts)
+      S[r][c] = (v + (qw >= 0 ? qr[qw] : (T)0)) + (rw >= 0 ? qr[rw] : (T)0);
+    }
+  // the measurement as the update takes it
+  T y[K];
+  for (int c = 0; c < 3; ++c) y[c] = meas[(long)c * a.meas_ld + e];
+  if constexpr (M::ANGULAR) {
+    T q[4], mrpy[3];
+    for (int c = 0; c < 4; ++c) q[c] = meas[(long)(3 + c) * a.meas_ld + e];
+    quat_normalize(q);
+    quat_to_rpy(q, mrpy);
+    for (int c = 0; c < 3; ++c) y[3 + c] = unwrap_angle(*unwrap_ptr<C, T>(a.rec, e, c), mrpy[c]);   // (read only)
+  }
+  T nu[K];
+  for (int c = 0; c < K; ++c) nu[c] = y[c] - xm[c];
+  for (int p = 0; p < K; ++p) {   // unpivoted Gauss-Jordan (S is SPD), as the step kernels
+    const T inv = (T)1 / S[p][p];
+    S[p][p] = 1;
+    for (int c = 0; c < K; ++c) S[p][c] *= inv;
+    for (int r = 0; r < K; ++r) {
+      if (r == p) continue;
+      const T f = S[r][p];
+      S[r][p] = 0;
+      for (int c = 0; c < K; ++c) S[r][c] = F::fma(-f, S[p][c], S[r][c]);
+    }
+  }
+  T nis = 0;
+  for (int r = 0; r < K; ++r) {
+    T w = 0;
+    for (int c = 0; c < K; ++c) w = F::fma(S[r][c], nu[c], w);
+    nis = F::fma(nu[r], w, nis);
+  }
+  a.nis[e] = (double)nis;
+  if (a.innov != nullptr) for (int c = 0; c < K; ++c) a.innov[(long)c * a.innov_ld + e] = (double)nu[c];
+}
+
 struct IntersectArgs {
   char* rec;
   const int* idx;     // null: dense slots 0..n-1

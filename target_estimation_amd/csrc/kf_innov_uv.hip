@@ -1,0 +1,9 @@
+// kf_innov_uv.hip -- the uniform_velocity step kernels that also write the innovation stream (kf_innov_impl.hpp): a translation
+// unit of its own so that the build stays parallel.
+#include "kf_innov_impl.hpp"
+
+namespace te {
+
+TE_INNOV_INSTANCES(ModelUV)
+
+}  // namespace te

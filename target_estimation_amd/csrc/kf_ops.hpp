@@ -63,6 +63,12 @@ struct StepParams {
   double* tile_blk = nullptr;
   int* tile_uni = nullptr;
   int promote = 0;
+  // innovation stream of a dense single tick (StepArgs::nis): this tick's NIS row [n] and, or null, its innovation block
+  // [m][innov_ld].  The separable layouts of one-class batches write it from the step kernel (INNOV variants, in place, no fused
+  // query); every other layout gets one innovation-writer launch (innov_kernel) BEFORE the step (OpsImpl::step).
+  double* nis = nullptr;
+  double* innov = nullptr;
+  long innov_ld = 0;
 };
 
 struct Ops {
@@ -82,6 +88,7 @@ struct Ops {
   void (*pack_meas)(const double* aos, long n, void* soa, long ld, hipStream_t);
   void (*intersect)(const IntersectArgs&, hipStream_t);
   void (*outputs_rows)(const OutArgs&, hipStream_t);   // outputs_rows_kernel: poses at OutArgs::row_of_slot
+  void (*innov)(const InnovArgs&, hipStream_t);       // innov_kernel: the innovations a tick WOULD see, records read-only
   // shared-axes storage form only (L.shared_axes; null otherwise): write the n records of `rec` as plain LAYOUT_SEPARABLE_PACKED
   // records into `rec_plain` (a zero-filled buffer of the plain form's tiles), every kind's block copied to each of its axes
   void (*expand)(char* rec, char* rec_plain, long n, hipStream_t) = nullptr;

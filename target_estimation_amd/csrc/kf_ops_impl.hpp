@@ -28,8 +28,15 @@ inline StepArgs<T> make_step_args(const StepParams& p) {
   a.live_spin_limit = p.live_spin_limit; a.live_idle_ticks = p.live_idle_ticks; a.live_flags = p.live_flags; a.live_pose = p.live_pose; a.live_pose_ld = p.live_pose_ld;
   a.pose = p.pose; a.pose_ld = p.pose_ld; a.pose_tick_stride = p.pose_tick_stride; a.pose_ring = p.pose_ring;
   a.tile_blk = p.tile_blk; a.tile_uni = p.tile_uni; a.promote = p.promote;
+  a.nis = p.nis; a.innov = p.innov; a.innov_ld = p.innov_ld;
   return a;
 }
+
+// The INNOV step kernels (kf_step_sep.hpp; dense single ticks of the separable layouts) are instantiated in translation units of
+// their own, kf_innov_{uv,ua,ar,av}.hip (kf_innov_impl.hpp), so that the build stays parallel and the kf_model_* / kf_shared_*
+// objects hold the instantiations they always held; OpsImpl::step reaches them through this declaration.
+template <class M, typename T, int LAYOUT>
+void launch_sep_innov_step(const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s);
 
 template <class M, typename T, int G, int LAYOUT = LAYOUT_FULL>
 struct OpsImpl {
@@ -61,6 +68,15 @@ struct OpsImpl {
   // request with poses is served tick by tick by the single-tick POSE kernel -- same results, one launch per tick.
   static constexpr bool kFusedPoseTickByTick = sizeof(T) == 4 && LAYOUT == LAYOUT_SEPARABLE_PACKED &&
                                                (M::TYPE == ANGULAR_RATES || M::TYPE == UNIFORM_ACCELERATION);
+  // the pose-writer launch behind a tick whose kernel has no pose output: outputs_kernel into the tick's block
+  static void write_pose_block(const StepParams& p, hipStream_t s) {
+    OutArgs o;
+    o.rec = p.rec_out ? p.rec_out : p.rec;   // (an A -> B tick has written the new records there)
+    o.idx = nullptr; o.n = p.n; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
+    o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = p.t_base;
+    o.pose_soa = p.pose; o.pose_ld = p.pose_ld;
+    outputs(o, s);
+  }
   static void step(const StepParams& p, hipStream_t s) {
     if (p.n <= 0) return;
     if constexpr (C::SHARED) {   // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
@@ -87,6 +103,31 @@ struct OpsImpl {
     }
     if (p.o_pose && (!p.idx || (p.n > C::TPW && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))
       throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
+    if (p.nis) {
+      // The innovation stream.  The separable layouts of one-class batches write it from the step kernel itself (INNOV variants:
+      // one launch, in place); with a pose stream in the same tick the existing pose-writer launch follows it.  Every other
+      // layout -- the dense kf_step_kernel ones, the symmetric-packed EKF, several (Q, R) classes -- gets one innovation-writer
+      // launch on the records BEFORE the step, then steps as without the stream.
+      if (p.idx || p.o_pose || p.n_ticks > 1 || p.rec_out || p.q_delta)
+        throw std::runtime_error("target_estimation_amd: the innovation stream is an output of dense single ticks in place, without the fused query");
+      if (!(C::SEP && !p.cls)) {
+        InnovArgs w;
+        w.rec = p.rec; w.qr = p.qr; w.cls = p.cls; w.n = p.n; w.meas = p.meas; w.meas_ld = p.meas_ld; w.has_meas = p.has_meas; w.dt = p.dt;
+        w.tile_blk = p.tile_blk; w.tile_uni = p.tile_uni; w.nis = p.nis; w.innov = p.innov; w.innov_ld = p.innov_ld;
+        innov(w, s);
+        StepParams q = p;
+        q.nis = nullptr; q.innov = nullptr;
+        step(q, s);
+        return;
+      }
+      if (p.pose) {
+        StepParams q = p;
+        q.pose = nullptr;
+        step(q, s);
+        write_pose_block(p, s);
+        return;
+      }
+    }
     if (p.pose) {
       // The pose stream.  The separable layouts of one-class batches write it from the step kernel itself (POSE variants); a
       // temporally fused request is one launch where that variant fits the register file, tick by tick where it does not
@@ -112,12 +153,7 @@ struct OpsImpl {
         StepParams q = p;
         q.pose = nullptr;
         step(q, s);
-        OutArgs o;
-        o.rec = p.rec_out ? p.rec_out : p.rec;   // (an A -> B tick has written the new records there)
-        o.idx = nullptr; o.n = p.n; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
-        o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = p.t_base;
-        o.pose_soa = p.pose; o.pose_ld = p.pose_ld;
-        outputs(o, s);
+        write_pose_block(p, s);
         return;
       }
     }
@@ -167,6 +203,8 @@ struct OpsImpl {
             hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true>), dim3(b4), blk, 0, s, a);
         }
       }
+      else if (p.nis)
+        launch_sep_innov_step<M, T, LAYOUT>(a, b4, 64u * (unsigned)wpb, s);
       else if (p.pose && p.rec_out)
         hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, true, true>), dim3(b4), blk, 0, s, a);
       else if (p.pose && p.n_ticks > 1) {
@@ -246,6 +284,10 @@ struct OpsImpl {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((outputs_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
   }
+  static void innov(const InnovArgs& a, hipStream_t s) {
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL((innov_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + 127) / 128)), dim3(128), 0, s, a);
+  }
   static void outputs_rows(const OutArgs& a, hipStream_t s) {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((outputs_rows_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
@@ -269,7 +311,7 @@ struct OpsImpl {
     static const Ops ops = {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
-        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows,
+        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov,
         C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr};
     return &ops;
   }

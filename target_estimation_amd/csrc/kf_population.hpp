@@ -14,6 +14,8 @@ namespace te {
 // in every present part; not together with the query).  reverse: walk the whole population last to first (zig-zag).
 // A part with StepParams::pose set also writes the tick's poses (one block, pose_ring / pose_tick_stride unused); other parts may
 // have none.
+// A part with StepParams::nis set also writes the tick's innovation stream; then the launch is a plain tick in place: no query, no
+// A -> B, no pose in any part (the caller adds the query and the poses as launches of their own).
 // shared: every present batch is in the shared-axes storage form (te_layout.hpp; fp64 only) instead of the plain one.
 void launch_population_step(int dtype, const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s, bool shared = false);
 

@@ -16,6 +16,14 @@ void launch_population_grid(const PopulationArgs<T>& p, unsigned blocks, unsigne
   else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
   else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
 }
+// the INNOV variant (in place, no fused query, no pose output): kf_population_f{64,32}_innov.hip, kf_population_f64_shared_innov.hip
+template <typename T, bool SHARED>
+void launch_population_grid_innov_t(const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
+  hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, false, SHARED, true>), dim3(blocks), dim3(64 * wpb), 0, s, p);
+}
+void launch_population_grid_innov_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_innov(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_innov(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_pose_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
 void launch_population_grid_pose(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
 void launch_population_grid_pose(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
@@ -26,9 +34,11 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   PopulationArgs<T> p;
   long waves_max = 0;
   bool pose = false;   // some part writes the pose stream (StepParams::pose, one block: a population launch is one tick)
+  bool innov = false;  // some part writes the innovation stream (StepParams::nis)
   for (int k = 0; k < 4; ++k) {
     const StepParams& q = parts[k];
     if (q.n > 0 && q.pose) pose = true;
+    if (q.n > 0 && q.nis) innov = true;
     if (q.n > 0 && (q.idx || q.cls || q.n_ticks != 1 || q.live_posted || q.o_pose || (query && !q.q_delta) || (ab && !q.rec_out) || (query && ab)))
       throw std::runtime_error("target_estimation_amd: a population launch takes dense single ticks of one-class batches");
     waves_max = std::max(waves_max, (q.n + TPW - 1) / TPW);
@@ -49,6 +59,13 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   }
   if (end == 0) return;
   p.reverse_blocks = reverse ? 1 : 0;
+  if (innov) {
+    if (query || ab || pose)
+      throw std::runtime_error("target_estimation_amd: a population launch with an innovation stream is a plain tick in place (the query and the poses follow as launches of their own)");
+    if constexpr (SHARED) launch_population_grid_innov_shared(p, end, (unsigned)wpb, s);
+    else launch_population_grid_innov(p, end, (unsigned)wpb, s);
+    return;
+  }
   if constexpr (SHARED) {
     if (pose) launch_population_grid_pose_shared(p, end, (unsigned)wpb, query, ab, s);
     else launch_population_grid<T, false, true>(p, end, (unsigned)wpb, query, ab, s);

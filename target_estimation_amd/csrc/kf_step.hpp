@@ -125,6 +125,14 @@ struct StepArgs {
   double* tile_blk;
   int* tile_uni;
   int promote;
+  // nis (or null): the innovation stream of a launched tick, next to the pose stream (INNOV variants of the separable kernels,
+  // innov_kernel for every other layout): nis[entry] = nu^T S^-1 nu of the tick, innov (or null: NIS only) SoA [m][innov_ld]
+  // doubles with row c = nu_c = y_c - x^-_c, column = entry; a target without a measurement on the tick gets NIS = -1 and nu = 0.
+  // One block: the host hands every tick its own (Batch: InnovStream).  Plain stores, like the pose stream's.  The last fields
+  // of the block: every other field keeps its offset.
+  double* nis;
+  double* innov;
+  long innov_ld;
 };
 
 __device__ __forceinline__ long long wave_uniform_ll(long long v) {

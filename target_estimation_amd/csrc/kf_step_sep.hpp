@@ -22,8 +22,11 @@
 namespace te {
 
 // one [p v (a)] chain with a scalar position measurement: rows r0, r0+K, r0+2K of the model
-template <int NB, typename T>
-__device__ __forceinline__ void sep_linear_axis(T* x, T (&P)[NB][NB], const T (&Q)[NB][NB], T r_meas, T dt, bool has, T y) {
+// INNOV: also hands out what the innovation stream needs, the chain's 1 / S (inv_out) and its innovation y - x^-_0 (nu_out): the
+// values the gain and the state update use, not second ones.  Untouched without a measurement.
+template <int NB, typename T, bool INNOV = false>
+__device__ __forceinline__ void sep_linear_axis(T* x, T (&P)[NB][NB], const T (&Q)[NB][NB], T r_meas, T dt, bool has, T y,
+                                                T* inv_out = nullptr, T* nu_out = nullptr) {
 #pragma clang fp contract(off)  // only the explicit fma calls fuse: same roundings as the dense kernel
   using F = Mth<T>;
   const T hdt = (T)0.5 * dt * dt;
@@ -58,6 +61,7 @@ __device__ __forceinline__ void sep_linear_axis(T* x, T (&P)[NB][NB], const T (&
 #pragma unroll
   for (int b = 0; b < NB; ++b) Kg[b] = P[b][0] * inv;
   const T nu = y - x[0];
+  if constexpr (INNOV) { *inv_out = inv; *nu_out = nu; }
 #pragma unroll
   for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
   T top[NB];
@@ -84,8 +88,9 @@ __device__ __forceinline__ void sep_linear_axis(T* x, T (&P)[NB][NB], const T (&
 // allocation of the kernels that sit at an occupancy limit follows its statement order (built from the halves, the per-class
 // angular_rates fp64 kernels spilled 116 B per lane and the resident ones lost a wavefront per SIMD).  tests/test_gpu_shared_axes.py
 // holds the two forms to the same bits.
-template <int NB, typename T>
-__device__ __forceinline__ void sep_linear_cov(T (&P)[NB][NB], const T (&Q)[NB][NB], T r_meas, T dt, bool has, T (&Kg)[NB]) {
+// INNOV: sep_linear_cov hands out its 1 / S (one per kind of axis), sep_linear_state its innovation (one per axis), as above.
+template <int NB, typename T, bool INNOV = false>
+__device__ __forceinline__ void sep_linear_cov(T (&P)[NB][NB], const T (&Q)[NB][NB], T r_meas, T dt, bool has, T (&Kg)[NB], T* inv_out = nullptr) {
 #pragma clang fp contract(off)  // only the explicit fma calls fuse: same roundings as the dense kernel
   using F = Mth<T>;
   const T hdt = (T)0.5 * dt * dt;
@@ -116,6 +121,7 @@ __device__ __forceinline__ void sep_linear_cov(T (&P)[NB][NB], const T (&Q)[NB][
   if (!has) return;
   // S = P00 + R ; K = P[:,0] / S ; P = (I - K C) P
   const T inv = (T)1 / (P[0][0] + r_meas);
+  if constexpr (INNOV) *inv_out = inv;
 #pragma unroll
   for (int b = 0; b < NB; ++b) Kg[b] = P[b][0] * inv;
   T top[NB];
@@ -133,8 +139,8 @@ __device__ __forceinline__ void sep_linear_cov(T (&P)[NB][NB], const T (&Q)[NB][
   }
 }
 
-template <int NB, typename T>
-__device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, const T (&Kg)[NB]) {
+template <int NB, typename T, bool INNOV = false>
+__device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, const T (&Kg)[NB], T* nu_out = nullptr) {
 #pragma clang fp contract(off)
   using F = Mth<T>;
   const T hdt = (T)0.5 * dt * dt;
@@ -147,6 +153,7 @@ __device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, cons
   if (!has) return;
   // x += K (y - x0)
   const T nu = y - x[0];
+  if constexpr (INNOV) *nu_out = nu;
 #pragma unroll
   for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
 }
@@ -250,11 +257,16 @@ template <class C, class M, typename T> struct LivePark {
 // POSE: the per-tick pose stream (StepArgs::pose): after each tick, derive_outputs on the posterior still in registers, the 7
 // components stored as SoA rows -- a wavefront's 64 lanes write 64 consecutive doubles per row, i.e. whole 512-byte lines.  A
 // single tick writes its block behind store_record (most of P is dead by then); FUSED writes tick s's block inside the tick loop.
+// INNOV: the innovation stream (StepArgs::nis): the tick's innovation nu = y - x^-[0:m] and NIS = nu^T S^-1 nu, from the values the
+// update itself forms -- every chain adds nu^2 / S as it runs, axis-ascending, the EKF's attitude group adds its 3 x 3 form last --
+// stored behind store_record like the pose block: lane = column, 64 consecutive doubles per row.  Without a measurement: -1 and
+// zeros.  Dense single ticks in place, without the fused query or the pose output (the host adds those as launches of their own).
 // The step of one wavefront's targets: `wg` = index of the wavefront among those of the launch (of the BATCH, in a population
 // launch: kf_step_population_kernel below), lane = its lane.
 template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
-          bool POSE = false>
+          bool POSE = false, bool INNOV = false>
 __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane) {
+  static_assert(!INNOV || (!INDEXED && !FUSED && !QUERY && !PERQR && !LIVE && !AB && !POSE), "the innovation stream is an output of dense single ticks in place of one-class batches");
   static_assert(!POSE || (!INDEXED && !PERQR && !LIVE), "the pose stream is an output of dense launches of one-class batches");
   static_assert(!AB || (!INDEXED && !FUSED && !QUERY && !LIVE), "A -> B ticks are dense single-tick launches without the fused query");
   static_assert(!(QUERY && (INDEXED || FUSED)), "the fused query is for dense single-tick launches");
@@ -375,6 +387,15 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     for (int c = 0; c < 7; ++c) dst[(long)c * a.pose_ld] = (double)pose7[c];
   };
   if constexpr (!POSE) (void)write_pose;
+  // INNOV: the tick's NIS row and innovation block (uniform branches: a population part may have no stream, a stream no block)
+  auto write_innov = [&](bool has, T nis, const T* nu, int m) {
+    if (a.nis == nullptr || !valid) return;
+    a.nis[entry] = has ? (double)nis : -1.0;
+    if (a.innov != nullptr) {
+      for (int c = 0; c < m; ++c) a.innov[(long)c * a.innov_ld + entry] = has ? (double)nu[c] : 0.0;
+    }
+  };
+  if constexpr (!INNOV) (void)write_innov;
   double dtd = a.dt;
   if constexpr (INDEXED) {
     if (a.dt_per && valid) dtd = a.dt_per[entry];
@@ -442,6 +463,12 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         for (int c = 0; c < 3; ++c) Ratt[r][c] = Qm[C::RWORD.v[3 + r][3 + c]];
     }
   }
+  // INNOV: the tick's innovations (measurement order = state rows 0..m-1) and the NIS sum (one tick per launch)
+  constexpr int MI = INNOV ? (M::ANGULAR ? 6 : 3) : 1;
+  T nu_all[MI], nis = T(0);
+#pragma unroll
+  for (int c = 0; c < MI; ++c) nu_all[c] = T(0);
+  if constexpr (!INNOV) { (void)nu_all; (void)nis; }
   int n_has = 0;
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
@@ -534,6 +561,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   if constexpr (C::SHARED) {
     // one covariance half per kind of axis (its lead axis i % 3 == 0 owns the kind's block), one state half per axis
     T Kg[LB];
+    T inv_kind = T(0);   // (INNOV) 1 / S of the kind of axis, from its lead axis
+    if constexpr (!INNOV) (void)inv_kind;
 #pragma unroll
     for (int b = 0; b < LB; ++b) Kg[b] = T(0);
 #pragma unroll
@@ -551,7 +580,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         T r_meas;
         if constexpr (HOIST_QR) r_meas = Rlin[i];
         else r_meas = Qm[C::RWORD.v[i][i]];
-        sep_linear_cov<LB, T>(Pb, Qb, r_meas, dt, has, Kg);
+        sep_linear_cov<LB, T, INNOV>(Pb, Qb, r_meas, dt, has, Kg, &inv_kind);
 #pragma unroll
         for (int b = 0; b < LB; ++b)
 #pragma unroll
@@ -569,7 +598,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
           UWW_(i - 3) = y;
         }
       }
-      sep_linear_state<LB, T>(xs, dt, has, y, Kg);
+      sep_linear_state<LB, T, INNOV>(xs, dt, has, y, Kg, &nu_all[INNOV ? i : 0]);
+      if constexpr (INNOV) {
+#pragma clang fp contract(off)
+        if (has) nis = nis + (nu_all[i] * nu_all[i]) * inv_kind;
+      }
 #pragma unroll
       for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
     }
@@ -625,7 +658,14 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
           UWW_(i - 3) = y;
         }
       }
-      sep_linear_axis<LB, T>(xs, Pb, Qb, r_meas, dt, has, y);
+      if constexpr (INNOV) {
+#pragma clang fp contract(off)
+        T inv_i = T(0);
+        sep_linear_axis<LB, T, true>(xs, Pb, Qb, r_meas, dt, has, y, &inv_i, &nu_all[i]);
+        if (has) nis = nis + (nu_all[i] * nu_all[i]) * inv_i;
+      } else {
+        sep_linear_axis<LB, T>(xs, Pb, Qb, r_meas, dt, has, y);
+      }
 #pragma unroll
       for (int b = 0; b < LB; ++b) {
         XS_(i + STRIDE * b, xs[b]);
@@ -769,6 +809,17 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         const T y = unwrap_angle(UWW_(c), mrpy[c]);   // angular_velocities.cpp:93-96
         UWW_(c) = y;
         nu[c] = y - xr[c];
+      }
+      if constexpr (INNOV) {   // the attitude group's term, last: sum_r sum_c nu_r S^-1[r][c] nu_c with the inverse the gain uses
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          nu_all[3 + r] = nu[r];
+          T w = S[r][0] * nu[0];
+          w = F::fma(S[r][1], nu[1], w);
+          w = F::fma(S[r][2], nu[2], w);
+          nis = F::fma(nu[r], w, nis);
+        }
       }
       T Kg[6][3];
 #pragma unroll
@@ -924,6 +975,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     else if constexpr (AB) store_record<C, T, false, true>(a.rec_out + tile * C::TILE_BYTES, lt, mem);   // A -> B tick (StepArgs::rec_out)
     else store_record<C, T>(tb, lt, mem);
     if constexpr (POSE && !FUSED) write_pose(0);
+    if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
     if constexpr (QUERY) {
       T xq[N];
 #pragma unroll
@@ -970,9 +1022,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 }
 
 template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
-          bool POSE = false>
+          bool POSE = false, bool INNOV = false>
 __global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, PERQR, LIVE>())) kf_step_sep_kernel(const StepArgs<T> a) {
-  sep_step_wave<M, T, LAYOUT, INDEXED, FUSED, QUERY, PERQR, LIVE, AB, POSE>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
+  sep_step_wave<M, T, LAYOUT, INDEXED, FUSED, QUERY, PERQR, LIVE, AB, POSE, INNOV>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------
@@ -994,17 +1046,19 @@ struct PopulationArgs {
 };
 
 // SHARED: every part is a batch in the shared-axes storage form (te_layout.hpp LAYOUT_SEPARABLE_SHARED; fp64 only).
-template <typename T, bool QUERY, bool AB, bool POSE = false, bool SHARED = false>
+// INNOV: every part with a non-null StepArgs::nis also writes the tick's innovation stream (sep_step_wave, INNOV); in place, without
+// the fused query or the pose output.  Instantiated in kf_population_f{64,32}_innov.hip and kf_population_f64_shared_innov.hip.
+template <typename T, bool QUERY, bool AB, bool POSE = false, bool SHARED = false, bool INNOV = false>
 __global__ void __launch_bounds__(256) kf_step_population_kernel(const PopulationArgs<T> p) {
   const int lane = (int)(threadIdx.x & 63);
   const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
   unsigned b = blockIdx.x;
   if (p.reverse_blocks) b = gridDim.x - 1 - b;
   constexpr int L = SHARED ? LAYOUT_SEPARABLE_SHARED : LAYOUT_SEPARABLE_PACKED;
-  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[0], (long)b * wpb + wave, lane);
-  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
-  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
-  else sep_step_wave<ModelUV, T, L, false, false, QUERY, false, 0, AB, POSE>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
+  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[0], (long)b * wpb + wave, lane);
+  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
+  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
+  else sep_step_wave<ModelUV, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
 }
 
 }  // namespace te

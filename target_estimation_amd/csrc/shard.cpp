@@ -748,6 +748,23 @@ void Shard::enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch
   StepParams parts[4];
   for (auto& q : parts) { q = StepParams{}; q.n = 0; q.idx = nullptr; }
   Batch* swap[4] = {nullptr, nullptr, nullptr, nullptr};
+  // An innovation stream on any batch: the tick is the INNOV population kernel -- a plain tick in place -- and what that kernel
+  // does not carry follows per batch as the launches that exist for it: the pose writer, intersect_kernel (same results).
+  bool innov = false;
+  for (size_t b = 0; b < batches_.size(); ++b) innov = innov || (batches_[b]->size() > 0 && specs[b].innov.on());
+  if (innov) {
+    bool shared_form = false;
+    for (size_t b = 0; b < batches_.size(); ++b) {
+      if (batches_[b]->size() == 0) continue;
+      const int t = batches_[b]->type();
+      parts[t] = batches_[b]->tick_params(s, dt, specs[b], false, origin, radius, false);
+      parts[t].pose = nullptr;
+      shared_form = batches_[b]->shared_axes();
+    }
+    launch_population_step(set_.dtype, parts, false, false, reverse, st, shared_form);
+    for (size_t b = 0; b < batches_.size(); ++b) batches_[b]->enqueue_after_innov_tick(st, s, specs[b], query, origin, radius);
+    return;
+  }
   bool ab_all = ab, shared = false;
   for (int pass = 0; pass < 2; ++pass) {   // (a batch without room for its second record buffer puts the whole tick in place)
     for (size_t b = 0; b < batches_.size(); ++b) {
@@ -769,7 +786,10 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
                                     const double* origin, double radius, int use_graph) {
   const size_t nb = batches_.size();
   if ((size_t)n_specs != nb) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
-  for (size_t b = 0; b < nb; ++b) batches_[b]->check_pose_stream(specs[b].poses);   // (before anything is enqueued)
+  for (size_t b = 0; b < nb; ++b) {   // (before anything is enqueued)
+    batches_[b]->check_pose_stream(specs[b].poses);
+    batches_[b]->check_innov_stream(specs[b].innov);
+  }
   if (n_ticks <= 0 || nb == 0) return;
   if (query && !origin) throw std::runtime_error("target_estimation_amd: stepSequenceAll: query without an origin");
   for (size_t b = 0; b < nb; ++b) {
@@ -806,7 +826,8 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     auto same_spec = [](const Batch::SeqSpec& x, const Batch::SeqSpec& y) {
       return x.meas_base == y.meas_base && x.tick_stride == y.tick_stride && x.ld == y.ld && x.has_base == y.has_base &&
              x.has_stride == y.has_stride && x.delta_dev == y.delta_dev && x.pose_dev == y.pose_dev && x.ring_ticks == y.ring_ticks &&
-             x.poses.dev == y.poses.dev && x.poses.ld == y.poses.ld && x.poses.tick_stride == y.poses.tick_stride && x.poses.ring == y.poses.ring;
+             x.poses.dev == y.poses.dev && x.poses.ld == y.poses.ld && x.poses.tick_stride == y.poses.tick_stride && x.poses.ring == y.poses.ring &&
+             x.innov.same(y.innov);
     };
     auto same_id = [](const Batch::DevIdentity& x, const Batch::DevIdentity& y) {
       return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n && x.ops == y.ops;

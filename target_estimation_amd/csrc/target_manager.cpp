@@ -614,12 +614,13 @@ bool TargetManager::populationTickNow() {
 }
 
 void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
-                                    const double* origin, double radius, int use_graph) {
+                                    const double* origin, double radius, int use_graph, const InnovStream* innov) {
   if (n_specs < 0) throw std::invalid_argument("target_estimation_amd: stepSequenceAll: negative number of batches");
   std::vector<Batch::SeqSpec> with((size_t)n_specs);
   for (long b = 0; b < n_specs; ++b) {
     with[(size_t)b] = specs[b];
     with[(size_t)b].poses = poses ? poses[b] : PoseStream{};
+    with[(size_t)b].innov = innov ? innov[b] : InnovStream{};
   }
   stepSequenceAll(n_ticks, dt, with.data(), n_specs, query, origin, radius, use_graph);
 }
@@ -633,6 +634,7 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
     for (auto& s : shards_)
       for (auto& b : s->batches()) {
         b->check_pose_stream(specs[off].poses);
+        b->check_innov_stream(specs[off].innov);
         if (n_ticks > 0 && query && b->size() > 0 && (!origin || !specs[off].delta_dev))
           throw std::runtime_error("target_estimation_amd: stepSequenceAll: query without an origin or a delta output");
         ++off;

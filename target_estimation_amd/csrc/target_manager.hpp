@@ -167,8 +167,11 @@ class TargetManager {
   // The same with a per-tick pose stream per batch (poses[b], PoseStream; one with a null dev writes nothing for that batch):
   // written by the step kernels -- the population kernel's POSE variant where the tick is one launch -- or by a pose-writer
   // launch behind each tick of a batch whose layout has no POSE kernel.  Every stream is checked before anything is enqueued.
+  // innov (or null): a per-tick innovation stream per batch as well (innov[b], InnovStream; one with a null nis writes nothing for
+  // that batch), routed like the pose streams: the step kernels' INNOV variants -- the population kernel's where the tick is one
+  // launch -- or an innovation-writer launch ahead of each tick of a batch whose layout has none.
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
-                       const double* origin, double radius, int use_graph);
+                       const double* origin, double radius, int use_graph, const InnovStream* innov = nullptr);
 
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and

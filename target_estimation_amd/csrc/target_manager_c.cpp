@@ -76,6 +76,15 @@ te::PoseStream pose_stream(const target_pose_stream_c* p) {
   if (p && p->pose_dev) { q.dev = p->pose_dev; q.ld = p->ld; q.tick_stride = p->tick_stride; q.ring = p->ring_ticks; }
   return q;
 }
+// the innovation stream of a ..._innov call (target_innov_stream_c; NULL or a NULL nis_dev: none)
+te::InnovStream innov_stream(const target_innov_stream_c* p) {
+  te::InnovStream q;
+  if (p && p->nis_dev) {
+    q.nis = p->nis_dev; q.innov = p->innov_dev; q.ld = p->ld; q.nis_tick_stride = p->nis_tick_stride;
+    q.innov_tick_stride = p->innov_tick_stride; q.ring = p->ring_ticks;
+  }
+  return q;
+}
 }  // namespace
 
 extern "C" {
@@ -467,6 +476,36 @@ int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, do
       poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
     }
     M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph);
+  });
+}
+
+// ---- per-tick innovation streams of launched ticks
+int target_batch_step_sequence_innov(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, const target_innov_stream_c* innov, int use_graph) {
+  return guarded("target_batch_step_sequence_innov", [&] { BatchLock lk(B(b));
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses),
+                        innov_stream(innov));
+  });
+}
+
+int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           const target_innov_stream_c* per_batch_innov, long n_batches,
+                                           int query, const double* origin, double radius, int use_graph) {
+  return guarded("target_manager_step_sequence_all_innov", [&] {
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    std::vector<te::InnovStream> innov(nb);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+      innov[i] = innov_stream(per_batch_innov ? &per_batch_innov[i] : nullptr);
+    }
+    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
   });
 }
 

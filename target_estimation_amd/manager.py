@@ -57,6 +57,32 @@ def _pose_stream(poses, size, n_ticks):
     return ps
 
 
+def _innov_stream(innov, size, m, n_ticks):
+    """(nis, nu): float64 CUDA tensors [blocks, ld] (or [ld]) and [blocks, m, ld] (or [m, ld]), nu may be None (NIS only) ->
+    capi.InnovStream.  One block: every tick overwrites it; fewer blocks than ticks make a ring, as for poses."""
+    import torch
+    nis, nu = innov
+    assert nis.is_cuda and nis.dtype == torch.float64, "innov: nis is a float64 CUDA tensor"
+    if nis.dim() == 1:
+        nis = nis.unsqueeze(0)
+    assert nis.dim() == 2 and nis.stride(1) == 1, "innov: nis is [ticks_or_ring, ld] with unit stride along the slots"
+    if nis.shape[1] < size:
+        raise RuntimeError("innovation stream: %d columns for a batch of %d targets" % (nis.shape[1], size))
+    s = capi.InnovStream()
+    s.nis_dev, s.ld = nis.data_ptr(), nis.shape[1]
+    s.nis_tick_stride = nis.stride(0) if nis.shape[0] > 1 else 0
+    s.ring_ticks = nis.shape[0] if nis.shape[0] < n_ticks else 0
+    if nu is not None:
+        assert nu.is_cuda and nu.dtype == torch.float64, "innov: nu is a float64 CUDA tensor"
+        if nu.dim() == 2:
+            nu = nu.unsqueeze(0)
+        assert nu.dim() == 3 and nu.shape[0] == nis.shape[0] and nu.shape[1] == m and nu.stride(2) == 1 and nu.stride(1) == s.ld, \
+            "innov: nu is [blocks, m, ld] with as many blocks and the same ld as nis"
+        s.innov_dev = nu.data_ptr()
+        s.innov_tick_stride = nu.stride(0) if nu.shape[0] > 1 else 0
+    return s
+
+
 class Batch:
     """All targets of one (model, Q, R) of a manager: the device-resident dense path."""
 
@@ -120,17 +146,28 @@ class Batch:
             hp = h.data_ptr()
         _check(self._lib.target_batch_step_host(self._h, float(dt), t.data_ptr(), t.stride(0), hp), "target_batch_step_host")
 
-    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None):
+    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None):
         """meas: CUDA tensor [ticks, 7, ld]: one launch per tick, all enqueued by one C call.  n_ticks > ticks
         treats meas (and has_meas) as a ring: tick s reads entry s % ticks.  poses: float64 CUDA tensor
         [ticks_or_ring, 7, ld] (or [7, ld]) that receives every target's pose after every tick (column = slot;
-        target_batch_step_sequence_poses); fewer blocks than ticks make it a ring."""
+        target_batch_step_sequence_poses); fewer blocks than ticks make it a ring.  innov = (nis, nu_or_None): float64 CUDA
+        tensors [ticks_or_ring, ld] and [ticks_or_ring, m, ld] that receive every tick's NIS and innovations
+        (target_batch_step_sequence_innov; -1 and zeros for a target without a measurement on the tick)."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if innov is not None:
+            ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
+            ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
+            ins = _innov_stream(innov, self.size, self.meas_dim, ticks)
+            _check(self._lib.target_batch_step_sequence_innov(self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1),
+                                                               hp, hs, meas.shape[0] if ticks != meas.shape[0] else 0,
+                                                               None if ps is None else C.byref(ps), C.byref(ins), int(use_graph)),
+                   "target_batch_step_sequence_innov")
+            return
         if poses is not None:
             ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
             ps = _pose_stream(poses, self.size, ticks)
@@ -598,14 +635,16 @@ class TargetManager:
             "target_manager_intersect_sphere_converged_batch")
         return conv.astype(bool), pose, delta, filt
 
-    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None):
+    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None):
         """meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order): `ticks` ticks of every batch -- ONE launch per
         tick for all of them where population_tick() holds, otherwise a launch per batch (recorded: one graph branch per
         batch) -- replayed from a recorded hipGraph (use_graph) or eagerly.  query =
         (origin[3], radius, deltas, poses) adds the own-time sphere query of every target after every step;
         deltas[i] [size] and poses[i] [size, 7] (or None) are CUDA double tensors, overwritten every tick.
         poses: one pose stream per batch (a tensor as for Batch.step_sequence, or None for a batch without one): every
-        target's pose after every tick (target_manager_step_sequence_all_poses)."""
+        target's pose after every tick (target_manager_step_sequence_all_poses).
+        innov: one innovation stream per batch ((nis, nu_or_None) as for Batch.step_sequence, or None for a batch without one):
+        every target's NIS and innovations of every tick (target_manager_step_sequence_all_innov)."""
         nb = len(meas)          # the library checks it against the number of batches
         ring = meas[0].shape[0] if nb else 0
         ticks = ring if n_ticks is None else int(n_ticks)      # n_ticks > ring: the tensors are rings (tick s reads s % ring)
@@ -625,6 +664,21 @@ class TargetManager:
             for i in range(nb):
                 specs[i].delta_dev = deltas[i].data_ptr()
                 specs[i].pose_dev = None if qposes is None or qposes[i] is None else qposes[i].data_ptr()
+        if innov is not None:
+            assert len(innov) == nb and (poses is None or len(poses) == nb), "one stream (or None) per batch"
+            bs = self.batches()
+            pss = (capi.PoseStream * max(nb, 1))()
+            iss = (capi.InnovStream * max(nb, 1))()
+            for i in range(nb):
+                size = bs[i].size if i < len(bs) else 0
+                if poses is not None and poses[i] is not None:
+                    pss[i] = _pose_stream(poses[i], size, ticks)
+                if innov[i] is not None:
+                    iss[i] = _innov_stream(innov[i], size, bs[i].meas_dim if i < len(bs) else 3, ticks)
+            _check(self._lib.target_manager_step_sequence_all_innov(
+                self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, nb, 0 if query is None else 1,
+                None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all_innov")
+            return
         if poses is not None:
             assert len(poses) == nb, "one pose stream (or None) per batch"
             bs = self.batches()
