@@ -308,8 +308,10 @@ class Batch {
   void* d_qr_ = nullptr;           // [qr_cap_][N*N + K*K] in the batch precision
   int* d_cls_ = nullptr;           // [cap_] class of every slot
   bool flip_ = false;              // the next dense tick walks the tiles backwards (zig-zag, kf_step.hpp StepArgs::reverse)
-  // Zig-zag only pays when the state does not fit the Infinity Cache, and it costs when the state is L2-resident: a tile
-  // walked backwards lands on another XCD, whose L2 does not hold it (10^5 UA fp32: 4.7 -> 8.2 us per tick).
+  // Zig-zag only pays when the state does not fit the Infinity Cache.  With the plain mirror b -> n - 1 - b it cost when the
+  // state is L2-resident: a tile walked backwards landed on another XCD, whose L2 does not hold it (10^5 UA fp32: 4.7 ->
+  // 8.2 us per tick), hence the threshold.  The kernels now mirror the workgroups inside each class b % 8 (zigzag_map.hpp),
+  // which keeps a tile on its XCD; the threshold has not been measured again with that order and stays where it was.
   bool zigzag() const { return state_bytes() >= zigzag_min_bytes(); }
   StepParams base_params();          // launches that need plain records (indexed, fused, live): behind settle_tiles()
   StepParams dense_params();         // a dense single tick: the records as stored, with the batch's tile arrays

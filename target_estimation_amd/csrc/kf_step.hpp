@@ -27,6 +27,7 @@
 #include "kf_aux.hpp"
 #include "te_device_math.hpp"
 #include "te_layout.hpp"
+#include "zigzag_map.hpp"
 
 namespace te {
 
@@ -65,7 +66,9 @@ struct StepArgs {
   // Zig-zag traversal: reverse != 0 walks the tiles from the last to the first.  Alternating the direction between
   // consecutive ticks leaves the part of the state touched last in the 256 MB Infinity Cache for the start of the next
   // tick (tools/zigzag_ceiling.hip: 480 MB of state in place 5.3 -> 6.6 TB/s, 960 MB 5.4 -> 6.0); results are
-  // independent of the order (targets are independent).
+  // independent of the order (targets are independent).  Dense single-tick launches only (no batch reverses an indexed,
+  // fused or live one).  The kernels reverse the WORKGROUPS, inside each class b % 8 (zigzag_map.hpp zz_block), so that a
+  // tile is stepped by the same class of workgroup -- by observation on the same XCD, next to the same L2 -- both ways.
   int reverse;
   // measurements are read once per tick: nt_meas != 0 loads them with the nontemporal policy so that they do not push
   // state out of the Infinity Cache (set for batches large enough to zig-zag; TE_NT_MEAS overrides)
@@ -439,9 +442,13 @@ kf_step_kernel(const StepArgs<T> a) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   // the launcher may use fewer wavefronts per workgroup than the LDS arrays are sized for (small grids)
-  long wg = (long)blockIdx.x * (blockDim.x >> 6) + wave;  // wavefront-global index
+  unsigned blk = blockIdx.x;
+  if constexpr (!INDEXED && !FUSED) {   // zig-zag traversal: the workgroups, class by class (zigzag_map.hpp); a select (kf_step_sep_kernel)
+    const unsigned zz = zz_block(blk, gridDim.x);
+    blk = a.reverse ? zz : blk;
+  }
+  const long wg = (long)blk * (blockDim.x >> 6) + wave;  // wavefront-global index
   if (wg * TPW >= a.n) return;                           // wave-uniform
-  if (a.reverse) wg = (a.n + TPW - 1) / TPW - 1 - wg;
   const int g = lane / G;
   const int i = (G == 1) ? 0 : lane % G;
   const long entry = wg * TPW + g;

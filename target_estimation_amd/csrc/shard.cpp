@@ -804,7 +804,9 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     // backwards, so that what the Infinity Cache still holds at the end of a tick is what the next tick reads first.
     long state = 0;
     for (size_t b = 0; b < nb; ++b) state += batches_[b]->state_bytes();
-    const bool zz = state >= Batch::zigzag_min_bytes();   // L2-resident populations keep their tile -> XCD affinity
+    // (backwards = the workgroups mirrored inside each class b % 8, zigzag_map.hpp: a tile keeps its XCD both ways.  The
+    // threshold dates from the plain mirror, which moved L2-resident populations' tiles to another XCD; not measured again.)
+    const bool zz = state >= Batch::zigzag_min_bytes();
     // A -> B ticks (Batch::pingpong_min_bytes) by the size of the WHOLE population: what decides is how much is streamed
     // between two uses of a record, not which batch it belongs to
     const bool ab = Batch::pingpong_min_bytes() >= 0 && state >= Batch::pingpong_min_bytes();
