@@ -752,7 +752,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   // (a tick with an innovation stream runs in place and without the fused query: the query follows as intersect_kernel)
-  const bool fused_q = ops_->fused_query && n_classes_ == 1 && !q.innov.on();
+  const bool fused_q = n_classes_ == 1 && !q.innov.on();
   if (q.innov.on()) ab = false;
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
@@ -779,7 +779,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
 }
 
 bool Batch::population_ready() const {
-  return ops_->L.layout == LAYOUT_SEPARABLE_PACKED && n_classes_ == 1 && !keep_meas_ && ops_->fused_query;
+  return ops_->L.layout == LAYOUT_SEPARABLE_PACKED && n_classes_ == 1 && !keep_meas_;
 }
 
 void Batch::enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& q, bool query, const double* origin, double radius) {

@@ -9,7 +9,7 @@ namespace te {
 
 template <class M, typename T, int LAYOUT>
 void launch_sep_innov_step(const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s) {
-  hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, false, false, true>), dim3(blocks), dim3(threads), 0, s, a);
+  hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, kInnov>), dim3(blocks), dim3(threads), 0, s, a);
 }
 
 #define TE_INNOV_INSTANCES(M)                                                                                                  \

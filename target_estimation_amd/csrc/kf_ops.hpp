@@ -74,7 +74,6 @@ struct StepParams {
 struct Ops {
   LayoutInfo L;
   int wpb;  // wavefronts per workgroup of the step kernel
-  bool fused_query;  // step() honours StepParams::q_delta
   void (*step)(const StepParams&, hipStream_t);
   // wavefronts of the live kernel the device can hold at once (0: this (model, precision, layout) has no live kernel)
   long (*live_capacity)(int with_outputs);   // resident wavefronts of the plain / the query-and-pose-output variant

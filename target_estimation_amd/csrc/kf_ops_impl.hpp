@@ -7,7 +7,9 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <iterator>
 #include <stdexcept>
+#include <utility>
 
 namespace te {
 
@@ -43,13 +45,13 @@ struct OpsImpl {
   using C = Cfg<M, T, G, LAYOUT>;
 
   static constexpr bool kHasLive = LAYOUT == LAYOUT_SEPARABLE_PACKED;
-  static long live_capacity(int with_outputs) {   // with_outputs: the variant with the per-tick query / pose output (LIVE == 2)
+  static long live_capacity(int with_outputs) {   // with_outputs: the variant with the per-tick query / pose output (kLive2)
     if constexpr (kHasLive) {
       int per_cu = 0, dev = 0;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-      const void* kernel = with_outputs ? (const void*)kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 2>
-                                        : (const void*)kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 1>;
+      const void* kernel = with_outputs ? (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive2>
+                                        : (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive1>;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) return 0;
       // Measured on an MI355X with the relay's start word (tools/live_capacity.py --probe, profiles/r03_live_capacity.txt): the
       // largest grid that becomes resident is the query's figure for every kernel at up to 6 wavefronts per SIMD, but 28 per CU
@@ -68,184 +70,83 @@ struct OpsImpl {
   // request with poses is served tick by tick by the single-tick POSE kernel -- same results, one launch per tick.
   static constexpr bool kFusedPoseTickByTick = sizeof(T) == 4 && LAYOUT == LAYOUT_SEPARABLE_PACKED &&
                                                (M::TYPE == ANGULAR_RATES || M::TYPE == UNIFORM_ACCELERATION);
+  // A few temporally fused instantiations of the dense kernel do not fit the register file and would spill hundreds of bytes
+  // per lane to scratch (228 / 116 / 340 / 352 B).  Not instantiated: a fused request is served tick by tick -- same results.
+  static constexpr bool kFusedSpills = (M::TYPE == ANGULAR_RATES && sizeof(T) == 8 && G == 3 && LAYOUT == LAYOUT_PACKED) ||
+                                       (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 4 && G == 1 && LAYOUT == LAYOUT_FULL) ||
+                                       (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 8 && G == 1 && LAYOUT == LAYOUT_PACKED) ||
+                                       (M::TYPE == ANGULAR_RATES && sizeof(T) == 8 && G == 6 && LAYOUT == LAYOUT_PACKED);
+  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW};
   // the pose-writer launch behind a tick whose kernel has no pose output: outputs_kernel into the tick's block
-  static void write_pose_block(const StepParams& p, hipStream_t s) {
+  static void write_pose_block(const StepParams& p, double* pose, hipStream_t s) {
     OutArgs o;
     o.rec = p.rec_out ? p.rec_out : p.rec;   // (an A -> B tick has written the new records there)
     o.idx = nullptr; o.n = p.n; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
     o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = p.t_base;
-    o.pose_soa = p.pose; o.pose_ld = p.pose_ld;
+    o.pose_soa = pose; o.pose_ld = p.pose_ld;
     outputs(o, s);
   }
+  // One launch of the step kernel of variant V.  A variant this OpsImpl does not ship (variant_shipped) is not instantiated; the
+  // kInnov kernels live in translation units of their own (launch_sep_innov_step above).
+  template <unsigned V>
+  static bool launch_if(unsigned v, const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (variant_shipped(V, kTraits)) {
+      if (v != V) return false;
+      if constexpr (V == kInnov) launch_sep_innov_step<M, T, LAYOUT>(a, blocks, threads, s);
+      else if constexpr (C::SEP) hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, V>), dim3(blocks), dim3(threads), 0, s, a);
+      else hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, V>), dim3(blocks), dim3(threads), 0, s, a);
+      return true;
+    } else {
+      return false;
+    }
+  }
+  template <const auto& LIST, size_t... I>
+  static void launch_variant(std::index_sequence<I...>, unsigned v, const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s) {
+    if (!(launch_if<LIST[I]>(v, a, blocks, threads, s) || ...)) throw std::runtime_error("target_estimation_amd: no step kernel for this request");
+  }
+  static void launch_variant(unsigned v, const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (C::SEP) launch_variant<kSepVariants>(std::make_index_sequence<std::size(kSepVariants)>{}, v, a, blocks, threads, s);
+    else launch_variant<kDenseVariants>(std::make_index_sequence<std::size(kDenseVariants)>{}, v, a, blocks, threads, s);
+  }
+  // The launches of a request are plan_step's (step_variant.hpp): [innovation writer,] then once, or once per tick, the step
+  // kernel [and the pose writer].
   static void step(const StepParams& p, hipStream_t s) {
     if (p.n <= 0) return;
-    if constexpr (C::SHARED) {   // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
-      if (p.live_posted || p.cls || p.n_ticks > 1)
-        throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
-    }
-    if (p.tile_uni && (!C::UT || p.idx || !p.tile_blk))
-      throw std::runtime_error("target_estimation_amd: uniform tiles are a property of dense ticks of the shared-axes storage form");
-    StepArgs<T> a = make_step_args<T>(p);
-    if (p.live_posted) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
-      if constexpr (kHasLive) {
-        if (p.idx || p.cls || p.rec_out || !p.live_progress || !p.live_mirror || !p.live_done || p.live_ring <= 0 || p.n_ticks < 1)
-          throw std::runtime_error("target_estimation_amd: a live launch is a dense launch of a one-class batch over a measurement ring");
-        const long waves_live = (p.n + C::TPW - 1) / C::TPW;
-        // + 1: the relay wavefront (kf_step.hpp live_relay)
-        if (p.q_delta || p.live_pose)
-          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 2>), dim3((unsigned)waves_live + 1), dim3(64), 0, s, a);
-        else
-          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 1>), dim3((unsigned)waves_live + 1), dim3(64), 0, s, a);
-        return;
-      } else {
-        throw std::runtime_error("target_estimation_amd: live mode needs the axis-separable layout with packed groups (the automatic choice for the shipped models)");
-      }
-    }
-    if (p.o_pose && (!p.idx || (p.n > C::TPW && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))
-      throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
-    if (p.nis) {
-      // The innovation stream.  The separable layouts of one-class batches write it from the step kernel itself (INNOV variants:
-      // one launch, in place); with a pose stream in the same tick the existing pose-writer launch follows it.  Every other
-      // layout -- the dense kf_step_kernel ones, the symmetric-packed EKF, several (Q, R) classes -- gets one innovation-writer
-      // launch on the records BEFORE the step, then steps as without the stream.
-      if (p.idx || p.o_pose || p.n_ticks > 1 || p.rec_out || p.q_delta)
-        throw std::runtime_error("target_estimation_amd: the innovation stream is an output of dense single ticks in place, without the fused query");
-      if (!(C::SEP && !p.cls)) {
-        InnovArgs w;
-        w.rec = p.rec; w.qr = p.qr; w.cls = p.cls; w.n = p.n; w.meas = p.meas; w.meas_ld = p.meas_ld; w.has_meas = p.has_meas; w.dt = p.dt;
-        w.tile_blk = p.tile_blk; w.tile_uni = p.tile_uni; w.nis = p.nis; w.innov = p.innov; w.innov_ld = p.innov_ld;
-        innov(w, s);
-        StepParams q = p;
-        q.nis = nullptr; q.innov = nullptr;
-        step(q, s);
-        return;
-      }
-      if (p.pose) {
-        StepParams q = p;
-        q.pose = nullptr;
-        step(q, s);
-        write_pose_block(p, s);
-        return;
-      }
-    }
-    if (p.pose) {
-      // The pose stream.  The separable layouts of one-class batches write it from the step kernel itself (POSE variants); a
-      // temporally fused request is one launch where that variant fits the register file, tick by tick where it does not
-      // (kFusedPoseTickByTick).
-      // Every other layout -- the dense kf_step_kernel ones, several (Q, R) classes -- steps as without poses and then runs one
-      // pose-writer launch per tick (outputs_kernel into the tick's block: the same derive_outputs, the same bits).
-      if (p.idx || p.o_pose) throw std::runtime_error("target_estimation_amd: the pose stream is an output of dense launches");
-      const bool pose_kernel = C::SEP && !p.cls;
-      if (p.n_ticks > 1 && (!pose_kernel || kFusedPoseTickByTick)) {
-        StepParams q = p;
-        q.n_ticks = 1;
-        q.pose_tick_stride = 0;
-        q.pose_ring = 0;
-        for (int t = 0; t < p.n_ticks; ++t) {
-          q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
-          q.has_meas = p.has_meas ? p.has_meas + (long)t * p.has_stride : nullptr;
-          q.pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
-          step(q, s);
-        }
-        return;
-      }
-      if (!pose_kernel) {
-        StepParams q = p;
-        q.pose = nullptr;
-        step(q, s);
-        write_pose_block(p, s);
-        return;
-      }
-    }
-    static const int nt_env = [] { const char* e = std::getenv("TE_NT_MEAS"); return e ? std::atoi(e) : -1; }();
-    a.nt_meas = nt_env >= 0 ? nt_env : p.nt_meas;
-    if (p.q_delta && (p.idx || p.n_ticks > 1))
-      throw std::runtime_error("target_estimation_amd: the fused query needs a dense single-tick launch");
+    const StepPlan plan = plan_step(kTraits, p);
     const long waves = (p.n + C::TPW - 1) / C::TPW;
-    static const long small_grid = [] { const char* e = std::getenv("TE_SMALL_GRID_WAVES"); return e ? std::atol(e) : 1024L; }();
-    // small (latency-bound) grids: one wavefront per workgroup spreads the waves over more CUs
-    const int wpb_dense = waves <= small_grid ? 1 : C::WPB;
-    const unsigned blocks = (unsigned)((waves + wpb_dense - 1) / wpb_dense);
-    if (p.n_ticks > 1 && p.idx) throw std::runtime_error("target_estimation_amd: fused multi-tick launches are dense only");
-    if (p.rec_out && (p.idx || p.n_ticks > 1 || p.q_delta))
-      throw std::runtime_error("target_estimation_amd: A -> B ticks are dense single-tick launches without the fused query");
-    // A few temporally fused instantiations do not fit the register file and would spill hundreds of bytes per lane to
-    // scratch (228 / 116 / 340 / 352 B): for them a fused request is served tick by tick -- same results.
-    constexpr bool kFusedSpills = (M::TYPE == ANGULAR_RATES && sizeof(T) == 8 && G == 3 && LAYOUT == LAYOUT_PACKED) ||
-                                  (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 4 && G == 1 && LAYOUT == LAYOUT_FULL) ||
-                                  (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 8 && G == 1 && LAYOUT == LAYOUT_PACKED) ||
-                                  (M::TYPE == ANGULAR_RATES && sizeof(T) == 8 && G == 6 && LAYOUT == LAYOUT_PACKED);
-    // A batch with several (Q, R) classes has no temporally fused kernel either: same tick-by-tick service (same results).
-    if ((kFusedSpills || p.cls) && p.n_ticks > 1) {
-      StepParams q = p;
-      q.n_ticks = 1;
-      for (int t = 0; t < p.n_ticks; ++t) {
-        q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
-        q.has_meas = p.has_meas ? p.has_meas + (long)t * p.has_stride : nullptr;
-        step(q, s);
-      }
+    if (sv_live(plan.variant)) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
+      // + 1: the relay wavefront (kf_step.hpp live_relay)
+      launch_variant(plan.variant, make_step_args<T>(p), (unsigned)waves + 1, 64, s);
       return;
     }
-    if (p.cls && p.q_delta)
-      throw std::runtime_error("target_estimation_amd: a batch with several (Q, R) classes has no fused sphere query (step, then target_batch_intersect_sphere_dev)");
-    if constexpr (C::SEP) {
-      // small (latency-bound) grids: one wavefront per workgroup spreads the waves over more CUs
-      const int wpb = waves <= small_grid ? 1 : 4;
-      const unsigned b4 = (unsigned)((waves + wpb - 1) / wpb);
-      const dim3 blk(64 * wpb);
-      if (p.cls) {
-        if constexpr (!C::SHARED) {
-          if (p.idx)
-            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, true, false, false, true>), dim3(b4), blk, 0, s, a);
-          else if (p.rec_out)
-            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true, false, true>), dim3(b4), blk, 0, s, a);
-          else
-            hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, true>), dim3(b4), blk, 0, s, a);
-        }
+    StepParams q = p;
+    if (plan.innov_writer_first) {
+      InnovArgs w;
+      w.rec = p.rec; w.qr = p.qr; w.cls = p.cls; w.n = p.n; w.meas = p.meas; w.meas_ld = p.meas_ld; w.has_meas = p.has_meas; w.dt = p.dt;
+      w.tile_blk = p.tile_blk; w.tile_uni = p.tile_uni; w.nis = p.nis; w.innov = p.innov; w.innov_ld = p.innov_ld;
+      innov(w, s);
+      q.nis = nullptr; q.innov = nullptr;
+    }
+    static const int nt_env = [] { const char* e = std::getenv("TE_NT_MEAS"); return e ? std::atoi(e) : -1; }();
+    if (nt_env >= 0) q.nt_meas = nt_env;
+    static const long small_grid = [] { const char* e = std::getenv("TE_SMALL_GRID_WAVES"); return e ? std::atol(e) : 1024L; }();
+    // small (latency-bound) grids: one wavefront per workgroup spreads the waves over more CUs
+    const int wpb = waves <= small_grid ? 1 : C::SEP ? 4 : C::WPB;
+    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
+    if (plan.tick_by_tick) {
+      q.n_ticks = 1;
+      if (p.pose) { q.pose_tick_stride = 0; q.pose_ring = 0; }
+    }
+    for (int t = 0, launches = plan.tick_by_tick ? p.n_ticks : 1; t < launches; ++t) {
+      double* pose = p.pose;
+      if (plan.tick_by_tick) {   // tick t's measurement block, mask row and pose block
+        q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
+        q.has_meas = p.has_meas ? p.has_meas + (long)t * p.has_stride : nullptr;
+        if (p.pose) pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
       }
-      else if (p.nis)
-        launch_sep_innov_step<M, T, LAYOUT>(a, b4, 64u * (unsigned)wpb, s);
-      else if (p.pose && p.rec_out)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, true, true>), dim3(b4), blk, 0, s, a);
-      else if (p.pose && p.n_ticks > 1) {
-        if constexpr (!kFusedPoseTickByTick && !C::SHARED)
-          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
-      }
-      else if (p.pose && p.q_delta)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, true, false, 0, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.pose)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, 0, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.rec_out)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, false, false, false, true>), dim3(b4), blk, 0, s, a);
-      else if (p.n_ticks > 1) {
-        if constexpr (!C::SHARED)
-          hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, true>), dim3(b4), blk, 0, s, a);
-      }
-      else if (p.idx)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, true>), dim3(b4), blk, 0, s, a);
-      else if (p.q_delta)
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false, false, true>), dim3(b4), blk, 0, s, a);
-      else
-        hipLaunchKernelGGL((kf_step_sep_kernel<M, T, LAYOUT, false>), dim3(b4), blk, 0, s, a);
-    } else {
-      if (p.cls && p.idx)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, true, false, false, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else if (p.cls && p.rec_out)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false, false, false, true, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else if (p.cls)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false, false, false, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else if (p.rec_out)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false, false, false, false, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else if (p.n_ticks > 1) {
-        if constexpr (!kFusedSpills)
-          hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      }
-      else if (p.idx)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else if (p.q_delta)
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false, false, true>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
-      else
-        hipLaunchKernelGGL((kf_step_kernel<M, T, G, LAYOUT, false>), dim3(blocks), dim3(wpb_dense * 64), 0, s, a);
+      q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
+      launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
+      if (plan.pose_writer_after_each_tick) write_pose_block(q, pose, s);
     }
   }
   static void init(const InitArgs& a, hipStream_t s) {
@@ -311,7 +212,7 @@ struct OpsImpl {
     static const Ops ops = {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
-        C::WPB, true, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov,
+        C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov,
         C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr};
     return &ops;
   }

@@ -1,12 +1,12 @@
 // kf_population_f64_innov.hip -- the one-launch population tick in fp64 with the per-tick innovation stream
-// (kf_population_impl.hpp, kf_step_population_kernel<T, 0, 0, 0, SHARED, INNOV = true>): a translation unit of its own so that
+// (kf_population_impl.hpp, kf_step_population_kernel, the kInnov variant): a translation unit of its own so that
 // the build stays parallel.
 #include "kf_population_impl.hpp"
 
 namespace te {
 
-void launch_population_grid_innov(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
-  launch_population_grid_innov_t<double, false>(p, blocks, wpb, s);
+void launch_population_grid_innov(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
+  launch_population_grid<double, false, kInnov>(v, p, blocks, wpb, s);
 }
 
 }  // namespace te

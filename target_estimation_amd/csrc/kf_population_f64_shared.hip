@@ -1,5 +1,5 @@
 // kf_population_f64_shared.hip -- the one-launch population tick in fp64 for managers whose batches are all in the shared-axes
-// storage form (kf_step_population_kernel<T, QUERY, AB, POSE, SHARED = true>): a translation unit of its own so that the build
+// storage form (kf_step_population_kernel<T, SHARED = true, VAR>): a translation unit of its own so that the build
 // stays parallel.
 #include "kf_population_impl.hpp"
 

@@ -3,8 +3,8 @@
 
 namespace te {
 
-void launch_population_grid_pose_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s) {
-  launch_population_grid<double, true, true>(p, blocks, wpb, query, ab, s);
+void launch_population_grid_pose_shared(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
+  launch_population_grid<double, true, kPose, kQuery | kPose, kAB | kPose>(v, p, blocks, wpb, s);
 }
 
 }  // namespace te

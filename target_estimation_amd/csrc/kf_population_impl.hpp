@@ -6,41 +6,37 @@
 
 namespace te {
 
-// the grid of a population tick, POSE or not (the POSE variants are instantiated in kf_population_f{64,32}_pose.hip: one
-// population translation unit already takes a minute to compile, so the pose stream's three kernels per precision get their own)
-// SHARED: the parts are batches in the shared-axes storage form (fp64; kf_population_f64_shared{,_pose}.hip)
-template <typename T, bool POSE, bool SHARED = false>
-void launch_population_grid(const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s) {
-  const dim3 blk(64 * wpb);
-  if (query) hipLaunchKernelGGL((kf_step_population_kernel<T, true, false, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
-  else if (ab) hipLaunchKernelGGL((kf_step_population_kernel<T, false, true, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
-  else hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, POSE, SHARED>), dim3(blocks), blk, 0, s, p);
+// One launch of the population kernel of variant `v`, one of the V... this translation unit instantiates: the plain ticks
+// (0, kQuery, kAB) with launch_population_step_t; the kPose variants in kf_population_f{64,32}_pose.hip and the kInnov one in
+// kf_population_f{64,32}_innov.hip (one population translation unit already takes a minute to compile, so each stream's kernels
+// get their own); SHARED -- the parts are batches in the shared-axes storage form, fp64 -- in kf_population_f64_shared{,_pose,_innov}.hip.
+template <typename T, bool SHARED, unsigned... V>
+void launch_population_grid(unsigned v, const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
+  const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * wpb), 0, s, p); return true; };
+  if (!((v == V && launch(kf_step_population_kernel<T, SHARED, V>)) || ...)) throw std::runtime_error("target_estimation_amd: no population kernel for this request");
 }
-// the INNOV variant (in place, no fused query, no pose output): kf_population_f{64,32}_innov.hip, kf_population_f64_shared_innov.hip
-template <typename T, bool SHARED>
-void launch_population_grid_innov_t(const PopulationArgs<T>& p, unsigned blocks, unsigned wpb, hipStream_t s) {
-  hipLaunchKernelGGL((kf_step_population_kernel<T, false, false, false, SHARED, true>), dim3(blocks), dim3(64 * wpb), 0, s, p);
-}
-void launch_population_grid_innov_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
-void launch_population_grid_innov(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
-void launch_population_grid_innov(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
-void launch_population_grid_pose_shared(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
-void launch_population_grid_pose(const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
-void launch_population_grid_pose(const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, bool query, bool ab, hipStream_t s);
+void launch_population_grid_innov_shared(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_innov(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_innov(unsigned v, const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_pose_shared(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_pose(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_pose(unsigned v, const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 
 template <typename T, bool SHARED = false>
 void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s) {
   constexpr int TPW = 64;   // thread per target in every separable layout
   PopulationArgs<T> p;
   long waves_max = 0;
-  bool pose = false;   // some part writes the pose stream (StepParams::pose, one block: a population launch is one tick)
-  bool innov = false;  // some part writes the innovation stream (StepParams::nis)
+  // the variant of the launch: the caller's query / ab, kPose / kInnov when some part writes that stream (StepParams::pose, one
+  // block: a population launch is one tick; StepParams::nis)
+  unsigned variant = (query ? kQuery : 0u) | (ab ? kAB : 0u);
   for (int k = 0; k < 4; ++k) {
     const StepParams& q = parts[k];
-    if (q.n > 0 && q.pose) pose = true;
-    if (q.n > 0 && q.nis) innov = true;
-    if (q.n > 0 && (q.idx || q.cls || q.n_ticks != 1 || q.live_posted || q.o_pose || (query && !q.q_delta) || (ab && !q.rec_out) || (query && ab)))
+    if (q.n <= 0) continue;
+    const unsigned asked = requested_variant(q);
+    if ((asked & ~(kQuery | kAB | kPose | kInnov)) || q.n_ticks != 1 || q.o_pose || (query && !q.q_delta) || (ab && !q.rec_out))
       throw std::runtime_error("target_estimation_amd: a population launch takes dense single ticks of one-class batches");
+    variant |= asked & (kPose | kInnov);
     waves_max = std::max(waves_max, (q.n + TPW - 1) / TPW);
   }
   static const long small_grid = [] { const char* e = std::getenv("TE_SMALL_GRID_WAVES"); return e ? std::atol(e) : 1024L; }();
@@ -59,19 +55,18 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   }
   if (end == 0) return;
   p.reverse_blocks = reverse ? 1 : 0;
-  if (innov) {
-    if (query || ab || pose)
-      throw std::runtime_error("target_estimation_amd: a population launch with an innovation stream is a plain tick in place (the query and the poses follow as launches of their own)");
-    if constexpr (SHARED) launch_population_grid_innov_shared(p, end, (unsigned)wpb, s);
-    else launch_population_grid_innov(p, end, (unsigned)wpb, s);
-    return;
-  }
-  if constexpr (SHARED) {
-    if (pose) launch_population_grid_pose_shared(p, end, (unsigned)wpb, query, ab, s);
-    else launch_population_grid<T, false, true>(p, end, (unsigned)wpb, query, ab, s);
+  if (!population_variant_ok(variant, SHARED))
+    throw std::runtime_error(sv_has(variant, kInnov)
+                                 ? "target_estimation_amd: a population launch with an innovation stream is a plain tick in place (the query and the poses follow as launches of their own)"
+                                 : "target_estimation_amd: a population launch takes dense single ticks of one-class batches");
+  if (sv_has(variant, kInnov)) {
+    if constexpr (SHARED) launch_population_grid_innov_shared(variant, p, end, (unsigned)wpb, s);
+    else launch_population_grid_innov(variant, p, end, (unsigned)wpb, s);
+  } else if (sv_has(variant, kPose)) {
+    if constexpr (SHARED) launch_population_grid_pose_shared(variant, p, end, (unsigned)wpb, s);
+    else launch_population_grid_pose(variant, p, end, (unsigned)wpb, s);
   } else {
-    if (pose) launch_population_grid_pose(p, end, (unsigned)wpb, query, ab, s);
-    else launch_population_grid<T, false>(p, end, (unsigned)wpb, query, ab, s);
+    launch_population_grid<T, SHARED, 0u, kQuery, kAB>(variant, p, end, (unsigned)wpb, s);
   }
 }
 

@@ -25,6 +25,7 @@
 
 #include "ekf_sym.hpp"
 #include "kf_aux.hpp"
+#include "step_variant.hpp"
 #include "te_device_math.hpp"
 #include "te_layout.hpp"
 #include "zigzag_map.hpp"
@@ -419,16 +420,17 @@ constexpr int step_min_waves() { return (M::TYPE == ANGULAR_RATES && LAYOUT == L
 // AB: an A -> B tick (StepArgs::rec_out).  Its own instantiation, not a run-time branch around the record stores: with the
 // branch some kernels kept both store sequences' operands alive and fell to one wavefront per SIMD (angular_rates fp32 on
 // the upper triangle, 3 lanes per target: 242 -> 299 registers, 304 -> 513 us per 10^6-target tick).
-template <class M, typename T, int G, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, bool AB = false>
+// VAR: the variant word (step_variant.hpp), unpacked here into the names the body uses.
+template <class M, typename T, int G, int LAYOUT, unsigned VAR>
 __global__ void __launch_bounds__((Cfg<M, T, G, LAYOUT>::WPB * 64), (step_min_waves<M, T, G, LAYOUT>()))
 kf_step_kernel(const StepArgs<T> a) {
-  static_assert(!AB || (!INDEXED && !FUSED && !QUERY), "A -> B ticks are dense single-tick launches without the fused query");
+  constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
+                 AB = sv_has(VAR, kAB);
+  static_assert(dense_variant_ok(VAR), "no such variant of the dense step (step_variant.hpp)");
   using C = Cfg<M, T, G, LAYOUT>;
   constexpr bool PK = C::PK;
   // the EKF on a symmetric-packed covariance, thread per target: works on the triangle in place (ekf_sym.hpp)
   constexpr bool EKF_SYM = M::EKF && PK && G == 1;
-  static_assert(!(QUERY && (INDEXED || FUSED)), "the fused query is for dense single-tick launches");
-  static_assert(!(PERQR && (FUSED || QUERY)), "per-class Q/R: single-tick launches without the fused query");
   static_assert(!C::SEP, "the separable layout has its own kernel (kf_step_sep.hpp)");
   constexpr int N = C::N, K = C::K, RPL = C::RPL, KPL = C::KPL, TPW = C::TPW, GS = C::GS;
   constexpr int kStepWaves = C::WPB, kStepThreads = C::WPB * 64;

@@ -263,18 +263,15 @@ template <class C, class M, typename T> struct LivePark {
 // zeros.  Dense single ticks in place, without the fused query or the pose output (the host adds those as launches of their own).
 // The step of one wavefront's targets: `wg` = index of the wavefront among those of the launch (of the BATCH, in a population
 // launch: kf_step_population_kernel below), lane = its lane.
-template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
-          bool POSE = false, bool INNOV = false>
+// VAR: the variant word (step_variant.hpp), unpacked here into the names the body uses.
+template <class M, typename T, int LAYOUT, unsigned VAR>
 __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane) {
-  static_assert(!INNOV || (!INDEXED && !FUSED && !QUERY && !PERQR && !LIVE && !AB && !POSE), "the innovation stream is an output of dense single ticks in place of one-class batches");
-  static_assert(!POSE || (!INDEXED && !PERQR && !LIVE), "the pose stream is an output of dense launches of one-class batches");
-  static_assert(!AB || (!INDEXED && !FUSED && !QUERY && !LIVE), "A -> B ticks are dense single-tick launches without the fused query");
-  static_assert(!(QUERY && (INDEXED || FUSED)), "the fused query is for dense single-tick launches");
-  static_assert(!(PERQR && (FUSED || QUERY)), "per-class Q/R: single-tick launches without the fused query");
-  static_assert(!LIVE || (FUSED && !INDEXED && !QUERY && !PERQR), "live launches are dense multi-tick launches");
+  constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
+                 AB = sv_has(VAR, kAB), POSE = sv_has(VAR, kPose), INNOV = sv_has(VAR, kInnov);
+  constexpr int LIVE = sv_live(VAR);
   using C = Cfg<M, T, 1, LAYOUT>;
   static_assert(C::SEP, "separable layouts only");
-  static_assert(!C::SHARED || (!FUSED && !PERQR && !LIVE), "the shared-axes storage form: single-tick launches of one-class batches (the host expands the batch first)");
+  static_assert(sep_variant_ok(VAR, C::SHARED), "no such variant of the separable step (step_variant.hpp)");
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -1020,17 +1017,16 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #undef XS_
 }
 
-template <class M, typename T, int LAYOUT, bool INDEXED, bool FUSED = false, bool QUERY = false, bool PERQR = false, int LIVE = 0, bool AB = false,
-          bool POSE = false, bool INNOV = false>
-__global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, PERQR, LIVE>())) kf_step_sep_kernel(const StepArgs<T> a) {
+template <class M, typename T, int LAYOUT, unsigned VAR>
+__global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, sv_has(VAR, kPerQR), sv_live(VAR)>())) kf_step_sep_kernel(const StepArgs<T> a) {
   unsigned b = blockIdx.x;
-  if constexpr (!INDEXED && !FUSED && !LIVE) {
+  if constexpr (!sv_has(VAR, kIndexed | kFused | kLiveMask)) {
     // zig-zag traversal (StepArgs::reverse): the workgroups, class by class (zigzag_map.hpp).  A select, not a branch: behind a
     // branch the load of the grid size waits for the one of `reverse` (10^5 UA fp32, never reversed: 5.7 -> 5.9 us per tick)
     const unsigned zz = zz_block(b, gridDim.x);
     b = a.reverse ? zz : b;
   }
-  sep_step_wave<M, T, LAYOUT, INDEXED, FUSED, QUERY, PERQR, LIVE, AB, POSE, INNOV>(a, (long)b * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
+  sep_step_wave<M, T, LAYOUT, VAR>(a, (long)b * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------
@@ -1054,17 +1050,19 @@ struct PopulationArgs {
 // SHARED: every part is a batch in the shared-axes storage form (te_layout.hpp LAYOUT_SEPARABLE_SHARED; fp64 only).
 // INNOV: every part with a non-null StepArgs::nis also writes the tick's innovation stream (sep_step_wave, INNOV); in place, without
 // the fused query or the pose output.  Instantiated in kf_population_f{64,32}_innov.hip and kf_population_f64_shared_innov.hip.
-template <typename T, bool QUERY, bool AB, bool POSE = false, bool SHARED = false, bool INNOV = false>
+// VAR: kQuery, kAB, kPose, kInnov of the variant word, handed to every part's sep_step_wave.
+template <typename T, bool SHARED, unsigned VAR>
 __global__ void __launch_bounds__(256) kf_step_population_kernel(const PopulationArgs<T> p) {
+  static_assert(population_variant_ok(VAR, SHARED), "no such variant of the population step (step_variant.hpp)");
   const int lane = (int)(threadIdx.x & 63);
   const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
   unsigned b = blockIdx.x;
   if (p.reverse_blocks) b = zz_block(b, gridDim.x);
   constexpr int L = SHARED ? LAYOUT_SEPARABLE_SHARED : LAYOUT_SEPARABLE_PACKED;
-  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[0], (long)b * wpb + wave, lane);
-  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
-  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
-  else sep_step_wave<ModelUV, T, L, false, false, QUERY, false, 0, AB, POSE, INNOV>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
+  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, VAR>(p.part[0], (long)b * wpb + wave, lane);
+  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, VAR>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
+  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, VAR>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
+  else sep_step_wave<ModelUV, T, L, VAR>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
 }
 
 }  // namespace te

@@ -1,0 +1,148 @@
+// step_variant.hpp -- which step kernels exist and which launches serve a request.  Plain C++17 without a HIP dependency
+// (tests/host/step_variant_host_test.cpp compiles it with g++).
+//
+// The three step kernels (kf_step_sep_kernel / sep_step_wave, kf_step_kernel, kf_step_population_kernel) take their variant as ONE
+// unsigned template argument made of the named bits below; kf_step.hpp and kf_step_sep.hpp say what each bit compiles in.
+// sep_variant_ok / dense_variant_ok are the single statement of which combinations make sense (each kernel static_asserts its
+// own), kSepVariants / kDenseVariants the ones the library ships, variant_shipped the per-layout exclusions, and plan_step the
+// launches of one OpsImpl::step request.  DESIGN.md ("Step-kernel variants") says how a new variant is added.
+#pragma once
+#include <stdexcept>
+
+namespace te {
+
+enum StepVariantBit : unsigned {
+  kIndexed = 1u << 0,   // StepParams::idx: the entries' slots come from a list
+  kFused = 1u << 1,     // n_ticks > 1 in one launch, the state stays in registers
+  kQuery = 1u << 2,     // the own-time sphere query behind the tick (q_delta)
+  kPerQR = 1u << 3,     // Q and R of the target's own parameter class (cls)
+  kAB = 1u << 4,        // an A -> B tick (rec_out)
+  kPose = 1u << 5,      // the per-tick pose stream from the step kernel (pose)
+  kInnov = 1u << 6,     // the innovation stream from the step kernel (nis)
+  kLive1 = 1u << 7,     // the live field (two bits): 1 = resident launch,
+  kLive2 = 2u << 7,     //                            2 = resident launch with the per-tick query / pose output
+};
+constexpr unsigned kLiveMask = 3u << 7, kVariantBits = 9;
+constexpr int sv_live(unsigned v) { return (int)((v & kLiveMask) >> 7); }
+constexpr bool sv_has(unsigned v, unsigned bit) { return (v & bit) != 0; }
+
+// kf_step_sep_kernel / sep_step_wave; shared_layout: the shared-axes storage form (LAYOUT_SEPARABLE_SHARED)
+constexpr bool sep_variant_ok(unsigned v, bool shared_layout) {
+  const bool INDEXED = sv_has(v, kIndexed), FUSED = sv_has(v, kFused), QUERY = sv_has(v, kQuery), PERQR = sv_has(v, kPerQR), AB = sv_has(v, kAB),
+             POSE = sv_has(v, kPose), INNOV = sv_has(v, kInnov);
+  const int LIVE = sv_live(v);
+  return v < (1u << kVariantBits) && LIVE != 3 &&
+         // the innovation stream is an output of dense single ticks in place of one-class batches
+         (!INNOV || (!INDEXED && !FUSED && !QUERY && !PERQR && !LIVE && !AB && !POSE)) &&
+         // the pose stream is an output of dense launches of one-class batches
+         (!POSE || (!INDEXED && !PERQR && !LIVE)) &&
+         // A -> B ticks are dense single-tick launches without the fused query
+         (!AB || (!INDEXED && !FUSED && !QUERY && !LIVE)) &&
+         // the fused query is for dense single-tick launches
+         !(QUERY && (INDEXED || FUSED)) &&
+         // per-class Q/R: single-tick launches without the fused query
+         !(PERQR && (FUSED || QUERY)) &&
+         // live launches are dense multi-tick launches
+         (!LIVE || (FUSED && !INDEXED && !QUERY && !PERQR)) &&
+         // the shared-axes storage form: single-tick launches of one-class batches (the host expands the batch first)
+         (!shared_layout || (!FUSED && !PERQR && !LIVE));
+}
+// kf_step_kernel: no resident launches and no output streams (pose-writer / innovation-writer launches serve those)
+constexpr bool dense_variant_ok(unsigned v) {
+  const bool INDEXED = sv_has(v, kIndexed), FUSED = sv_has(v, kFused), QUERY = sv_has(v, kQuery), PERQR = sv_has(v, kPerQR), AB = sv_has(v, kAB);
+  return (v & ~(kIndexed | kFused | kQuery | kPerQR | kAB)) == 0 && (!AB || (!INDEXED && !FUSED && !QUERY)) && !(QUERY && (INDEXED || FUSED)) &&
+         !(PERQR && (FUSED || QUERY));
+}
+// kf_step_population_kernel: dense single ticks of one-class batches
+constexpr bool population_variant_ok(unsigned v, bool shared_layout) {
+  return (v & ~(kQuery | kAB | kPose | kInnov)) == 0 && sep_variant_ok(v, shared_layout);
+}
+
+// The variants the library instantiates, before the per-layout exclusions of variant_shipped.
+constexpr unsigned kSepVariants[] = {0, kIndexed, kFused, kQuery, kAB, kPose, kAB | kPose, kFused | kPose, kQuery | kPose, kInnov,
+                                     kFused | kLive1, kFused | kLive2, kPerQR, kIndexed | kPerQR, kPerQR | kAB};
+constexpr unsigned kDenseVariants[] = {0, kIndexed, kFused, kQuery, kAB, kPerQR, kIndexed | kPerQR, kPerQR | kAB};
+
+// What OpsImpl<M, T, G, LAYOUT> knows about itself at compile time.
+struct StepTraits {
+  bool sep;                      // the axis-separable kernel (kf_step_sep_kernel), else the dense one (kf_step_kernel)
+  bool shared;                   // the shared-axes storage form
+  bool uniform_tiles;            // ... whose kernels carry uniform tiles
+  bool has_live;                 // resident kernels exist (packed groups)
+  bool fused_pose_tick_by_tick;  // no kFused | kPose kernel: it would cost a wavefront per SIMD or spill
+  bool fused_spills;             // no kFused kernel (dense): it would spill
+  int tpw;                       // targets per wavefront
+};
+
+template <unsigned N>
+constexpr bool variant_in(const unsigned (&list)[N], unsigned v) {
+  for (unsigned i = 0; i < N; ++i)
+    if (list[i] == v) return true;
+  return false;
+}
+constexpr bool variant_shipped(unsigned v, const StepTraits& t) {
+  if (!t.sep) return variant_in(kDenseVariants, v) && dense_variant_ok(v) && !(sv_has(v, kFused) && t.fused_spills);
+  return variant_in(kSepVariants, v) && sep_variant_ok(v, t.shared) && (sv_live(v) == 0 || t.has_live) &&
+         !(v == (kFused | kPose) && t.fused_pose_tick_by_tick);
+}
+
+// The launches of one step request, in order: [innovation writer] then, once or (tick_by_tick) once per tick of the request,
+// the step kernel `variant` [and the pose writer behind it].
+struct StepPlan {
+  bool innov_writer_first = false;
+  bool tick_by_tick = false;
+  unsigned variant = 0;
+  bool pose_writer_after_each_tick = false;
+};
+
+// P: StepParams (kf_ops.hpp), or anything with its member names.
+// Every bit a request asks for, before plan_step decides which launch serves it.
+template <class P>
+constexpr unsigned requested_variant(const P& p) {
+  return (p.idx ? kIndexed : 0u) | (p.n_ticks > 1 ? kFused : 0u) | (p.q_delta ? kQuery : 0u) | (p.cls ? kPerQR : 0u) | (p.rec_out ? kAB : 0u) |
+         (p.pose ? kPose : 0u) | (p.nis ? kInnov : 0u) | (p.live_posted ? kLive1 : 0u);
+}
+// Throws for the requests no launch sequence serves.
+template <class P>
+StepPlan plan_step(const StepTraits& t, const P& p) {
+  StepPlan plan;
+  // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
+  if (t.shared && (p.live_posted || p.cls || p.n_ticks > 1))
+    throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
+  if (p.tile_uni && (!t.uniform_tiles || p.idx || !p.tile_blk))
+    throw std::runtime_error("target_estimation_amd: uniform tiles are a property of dense ticks of the shared-axes storage form");
+  if (p.live_posted) {   // a resident launch serves its ticks, query and poses by itself
+    if (!t.has_live)
+      throw std::runtime_error("target_estimation_amd: live mode needs the axis-separable layout with packed groups (the automatic choice for the shipped models)");
+    if (p.idx || p.cls || p.rec_out || !p.live_progress || !p.live_mirror || !p.live_done || p.live_ring <= 0 || p.n_ticks < 1)
+      throw std::runtime_error("target_estimation_amd: a live launch is a dense launch of a one-class batch over a measurement ring");
+    plan.variant = kFused | ((p.q_delta || p.live_pose) ? kLive2 : kLive1);
+    return plan;
+  }
+  if (p.o_pose && (!p.idx || (p.n > t.tpw && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))
+    throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
+  if (p.nis && (p.idx || p.o_pose || p.n_ticks > 1 || p.rec_out || p.q_delta))
+    throw std::runtime_error("target_estimation_amd: the innovation stream is an output of dense single ticks in place, without the fused query");
+  if (p.pose && (p.idx || p.o_pose)) throw std::runtime_error("target_estimation_amd: the pose stream is an output of dense launches");
+  if (p.q_delta && (p.idx || p.n_ticks > 1)) throw std::runtime_error("target_estimation_amd: the fused query needs a dense single-tick launch");
+  if (p.n_ticks > 1 && p.idx) throw std::runtime_error("target_estimation_amd: fused multi-tick launches are dense only");
+  if (p.rec_out && (p.idx || p.n_ticks > 1 || p.q_delta))
+    throw std::runtime_error("target_estimation_amd: A -> B ticks are dense single-tick launches without the fused query");
+  if (p.cls && p.q_delta)
+    throw std::runtime_error("target_estimation_amd: a batch with several (Q, R) classes has no fused sphere query (step, then target_batch_intersect_sphere_dev)");
+  // The separable kernels of one-class batches write both output streams themselves (kPose; kInnov, with a pose stream in the
+  // same tick the pose writer follows it).  Every other kernel -- the dense ones, several (Q, R) classes -- steps as without the
+  // streams: one innovation-writer launch on the records BEFORE the step, one pose-writer launch behind every tick.
+  const bool streams_in_kernel = t.sep && !p.cls;
+  plan.innov_writer_first = p.nis && !streams_in_kernel;
+  plan.pose_writer_after_each_tick = p.pose && (!streams_in_kernel || p.nis);
+  // A fused request is served tick by tick -- same results, one launch per tick -- where its kernel does not exist: several
+  // (Q, R) classes, poses without a kFused | kPose kernel, the dense kernels that would spill.
+  plan.tick_by_tick = p.n_ticks > 1 && (p.cls || t.fused_spills || (p.pose && (!streams_in_kernel || t.fused_pose_tick_by_tick)));
+  plan.variant = requested_variant(p) & ~((plan.tick_by_tick ? kFused : 0u) | (plan.pose_writer_after_each_tick ? kPose : 0u) |
+                                          (plan.innov_writer_first ? kInnov : 0u));
+  if (!variant_shipped(plan.variant, t)) throw std::runtime_error("target_estimation_amd: no step kernel for this request");
+  return plan;
+}
+
+}  // namespace te

@@ -166,6 +166,32 @@ def test_temporally_fused_launch_equals_single_ticks(models, name, dtype, lanes)
     np.testing.assert_array_equal(out[0][1], out[1][1])
 
 
+@pytest.mark.parametrize("name,dtype,lanes", [("angular_velocities", "f64", 101), ("angular_rates", "f64", 103)])
+def test_fused_request_on_a_layout_without_a_fused_kernel(models, name, dtype, lanes):
+    """The dense layouts whose temporally fused kernel would spill serve target_batch_step_fused tick by tick, each tick from
+    its own measurement block and mask row.  65 targets (a wavefront and one lane), 3 ticks, target 7 without a measurement on
+    tick 2: within the parity tolerance of the oracle, the measurement counter and the clock as for single ticks."""
+    N, ticks, dt = 65, 3, 0.004
+    m = models[name]
+    p0, meas = synth_stream(name, N, ticks, seed=37)
+    mask = np.ones((ticks, N), np.uint8)
+    mask[1, 7] = 0
+    ids = np.arange(N, dtype=np.uint32)
+    mgr = te.TargetManager(model_path(name), dtype=dtype, lanes_per_target=lanes)
+    mgr.init_batch(ids, dt, 0.0, p0)
+    b = mgr.batches()[0]
+    assert b.layout == "symmetric_packed"
+    soa = torch.from_numpy(np.ascontiguousarray(meas.transpose(0, 2, 1))).cuda().to(b.torch_dtype()).contiguous()
+    b.step_fused(dt, soa, torch.from_numpy(mask).cuda())
+    orc = oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], p0, dt, dtype=dtype)
+    for s in range(ticks):
+        orc.step(dt, meas[s], mask[s])
+    print("worst x / P error", check_state(mgr, ids, orc, dtype, "%s %s %d" % (name, dtype, lanes)))
+    assert mgr.getNumberMeasurements(7) == ticks - 1 and mgr.getNumberMeasurements(8) == ticks
+    assert mgr.getTime(7) == pytest.approx(ticks * dt)
+    mgr.close()
+
+
 @pytest.mark.parametrize("name", HARNESS_ORDER)
 def test_reference_harness_in_fp32(models, harness_stream, name):
     """The reference integration test's stream through the fp32 dense path: the reference's own

@@ -14,8 +14,8 @@ import pytest
 
 import innov_stream_ref as ref
 import oracle
-from conftest import HARNESS_ORDER, model_path
-from test_gpu_parity import LANES, coupled
+from conftest import HARNESS_ORDER, model_path, synth_stream
+from test_gpu_parity import LANES, TOL, coupled
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -461,6 +461,58 @@ def test_fallback_layouts(models, kind, dtype):
     for s in states[:2]:
         np.testing.assert_array_equal(s[0], states[2][0])
         np.testing.assert_array_equal(s[1], states[2][1])
+
+
+def test_several_classes_with_poses_in_the_same_call(models):
+    """Test 8b: a 3-class batch of the separable layout with a pose stream AND an innovation stream in one eager call -- the
+    innovation writer ahead of each per-class step, the pose writer behind it.  65 targets (a wavefront and one lane), 3 ticks,
+    target 7 without a measurement on tick 2: every tick's innovations within test 8's bound against one twin per class, every
+    tick's poses within the pose stream's output tolerance against the oracle, the state as without the streams."""
+    name, dtype, N, ticks, m = "angular_rates", "f64", 65, 3, 6
+    mdl = models[name]
+    p0, meas = synth_stream(name, N, ticks, seed=23)
+    mask = np.ones((ticks, N), np.uint8)
+    mask[1, 7] = 0
+    soa, has = _soa(meas, dtype, N + 3), torch.from_numpy(mask.copy()).cuda()
+    ids = np.arange(N, dtype=np.uint32)
+    scale = np.array([1.0, 2.0, 0.5])
+    Q = np.stack([mdl["Q"] * s for s in scale]); R = np.stack([mdl["R"] * s for s in scale]); P0 = np.stack([mdl["P"]] * 3)
+    class_of = (np.arange(N) % 3).astype(np.uint32)
+    kw = dict(classes=(Q, R, P0, class_of, mdl["model"]))
+    want, want_pose = None, np.zeros((ticks, N, 7))
+    for k in range(3):
+        sel = class_of == k
+        w = ref.twin_innovations(mdl["model"], Q[k], R[k], P0[k], p0[sel], meas[:, sel], mask[:, sel], DT)
+        if want is None:
+            want = {key: np.zeros(v.shape[:1] + (N,) + v.shape[2:]) for key, v in w.items() if key not in ("x", "P")}
+        for key in want:
+            want[key][:, sel] = w[key]
+        orc = oracle.OracleBatch(mdl["model"], Q[k], R[k], P0[k], p0[sel], DT, dtype=dtype)
+        for s in range(ticks):
+            orc.step(DT, meas[s, sel], mask[s, sel])
+            want_pose[s, sel] = orc.pose()
+    states = []
+    for form in ("both", "plain"):
+        mgr = _manager(name, dtype, **kw)
+        _init(mgr, ids, p0, **kw)
+        b = mgr.batches()[0]
+        assert b.num_classes == 3 and b.layout.startswith("axis_separable")
+        poses = torch.full((ticks, 7, N + 3), NAN, dtype=torch.float64, device="cuda")
+        bufs = _bufs(ticks, m, N + 3)
+        b.step_sequence(DT, soa, has, use_graph=False, poses=poses if form == "both" else None, innov=bufs if form == "both" else None)
+        if form == "both":
+            nis, nu = _read(bufs, N)
+            ref.check(nu, nis, want, mask, dtype, "3 classes with poses")
+            h = poses.cpu().numpy()
+            assert np.isnan(h[:, :, N:]).all(), "a pose column beyond the batch size was written"
+            got = h[:, :, :N].transpose(0, 2, 1)
+            print("worst pose error %.3g (tolerance %.3g)" % (np.abs(got - want_pose).max(), TOL[dtype]["out_atol"]))
+            np.testing.assert_allclose(got, want_pose, atol=TOL[dtype]["out_atol"], rtol=0)
+        torch.cuda.synchronize()
+        states.append(mgr.get_state_batch(ids))
+        mgr.close()
+    np.testing.assert_array_equal(states[0][0], states[1][0])
+    np.testing.assert_array_equal(states[0][1], states[1][1])
 
 
 def test_columns_follow_slot_ids_after_erase():

@@ -297,6 +297,48 @@ def test_ab_ticks_forced_on_small_batches_match_oracle(case):
     assert p.returncode == 0 and "pingpong small case ok" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
 
 
+def _pingpong_coupled_classes_case():
+    """Child process with TE_PINGPONG_MIN_MB=0: a batch of the dense kernel with three (Q, R) classes of coupled matrices, every
+    eager tick an A -> B tick of the per-class kernel.  65 targets (a wavefront and one lane), 3 ticks, target 7 without a
+    measurement on tick 2; every class against its oracle."""
+    from conftest import model_path, synth_stream
+    from test_gpu_parity import coupled
+    assert os.environ.get("TE_PINGPONG_MIN_MB") == "0"
+    name, N, ticks, dt = "uniform_acceleration", 65, 3, 0.004
+    m = oracle.load_model_yaml(model_path(name))
+    p0, meas = synth_stream(name, N, ticks, seed=29)
+    mask = np.ones((ticks, N), np.uint8)
+    mask[1, 7] = 0
+    cs = [coupled(m, seed=k + 3) for k in range(3)]
+    Q, R, P0 = (np.stack([c[k] for c in cs]) for k in ("Q", "R", "P"))
+    class_of = (np.arange(N) % 3).astype(np.uint32)
+    ids = np.arange(N, dtype=np.uint32) + 10
+    for dtype in ("f64", "f32"):
+        mgr = te.TargetManager(dtype=dtype)
+        assert mgr.init_batch_classes(ids, dt, 0.0, p0, m["model"], Q, R, P0, class_of) == N
+        b = mgr.batches()[0]
+        assert b.num_classes == 3 and b.layout in ("full", "symmetric_packed")
+        soa = torch.from_numpy(np.ascontiguousarray(meas.transpose(0, 2, 1))).cuda().to(b.torch_dtype()).contiguous()
+        b.step_sequence(dt, soa, torch.from_numpy(mask).cuda(), use_graph=False)
+        torch.cuda.synchronize()
+        for k in range(3):
+            sel = class_of == k
+            orc = oracle.OracleBatch(m["model"], Q[k], R[k], P0[k], p0[sel], dt, dtype=dtype)
+            for s in range(ticks):
+                orc.step(dt, meas[s, sel], mask[s, sel])
+            print(dtype, "class", k, "worst x / P error", check_state(mgr, ids[sel], orc, dtype, "%s class %d" % (dtype, k)))
+        mgr.close()
+    print("pingpong coupled classes ok")
+
+
+def test_ab_ticks_forced_on_a_dense_batch_with_several_classes_match_oracle():
+    env = dict(os.environ, TE_PINGPONG_MIN_MB="0", PYTHONPATH=os.pathsep.join([os.path.dirname(__file__), os.path.dirname(os.path.dirname(__file__))]))
+    p = subprocess.run([sys.executable, "-c", "import test_gpu_mixed_configs as t; t._pingpong_coupled_classes_case()"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    print(p.stdout[-2000:])
+    assert p.returncode == 0 and "pingpong coupled classes ok" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
 def test_ab_ticks_equal_in_place_ticks_bit_for_bit():
     """The same 4 * 10^6-target batch stepped in place (policy off) and A -> B (policy on, the default at this size): the
     records must be the same bits.  Two child processes (the thresholds are read once per process), 20 000-target sample."""

@@ -13,7 +13,7 @@ import pytest
 
 import oracle
 from conftest import HARNESS_ORDER, model_path, synth_stream
-from test_gpu_parity import LANES, TOL, coupled
+from test_gpu_parity import LANES, TOL, check_state, coupled
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -369,6 +369,45 @@ def test_fallback_layouts(models, kind, dtype):
         np.testing.assert_array_equal(got, want, err_msg="%s %s %s" % (kind, dtype, form))
         _check_oracle(got, want_o, dtype, "%s %s %s" % (kind, dtype, form))
         mgr.close()
+
+
+@pytest.mark.parametrize("name,dtype,lanes", [("uniform_acceleration", "f64", 3), ("angular_velocities", "f32", 101)])
+def test_dense_layouts_with_poses_and_the_fused_query(models, name, dtype, lanes):
+    """Case 9b: a batch of the dense kernel in a step_sequence_all with the own-time sphere query and a pose stream -- the QUERY
+    step kernel, then the pose writer, per tick.  65 targets (a wavefront and one lane), 3 ticks, target 7 without a measurement
+    on tick 2: every tick's poses within the oracle's output tolerance, the state within the parity tolerance, the query results
+    the bits of the stand-alone query on the final state."""
+    m = models[name]
+    N, ticks = 65, 3
+    p0, meas = synth_stream(name, N, ticks, seed=41)
+    mask = np.ones((ticks, N), np.uint8)
+    mask[1, 7] = 0
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    soa = torch.zeros((ticks, 7, N + 3), dtype=tdt, device="cuda")
+    soa[:, :, :N] = torch.from_numpy(np.ascontiguousarray(meas.transpose(0, 2, 1))).to("cuda").to(tdt)
+    has = torch.from_numpy(mask).cuda()
+    origin, radius = np.array([0.5, -0.25, 0.1]), 6.0
+    ids = np.arange(N, dtype=np.uint32)
+    mgr = te.TargetManager(model_path(name), dtype=dtype, lanes_per_target=lanes)
+    _init(mgr, ids, p0)
+    b = mgr.batches()[0]
+    assert b.layout in ("full", "symmetric_packed") and not mgr.population_tick()
+    buf = torch.full((ticks, 7, N + 3), float("nan"), dtype=torch.float64, device="cuda")
+    delta = torch.full((N,), float("nan"), dtype=torch.float64, device="cuda")
+    qpose = torch.full((N, 7), float("nan"), dtype=torch.float64, device="cuda")
+    mgr.step_sequence_all(DT, [soa], has_meas=[has], query=(origin, radius, [delta], [qpose]), use_graph=0, poses=[buf])
+    torch.cuda.synchronize()
+    got = _soa_poses(buf, N)
+    orc = oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], p0, DT, dtype=dtype)
+    for s in range(ticks):
+        orc.step(DT, meas[s], mask[s])
+        print("tick %d: worst pose error %.3g (tolerance %.3g)" % (s + 1, np.abs(got[s] - orc.pose()).max(), TOL[dtype]["out_atol"]))
+        np.testing.assert_allclose(got[s], orc.pose(), atol=TOL[dtype]["out_atol"], rtol=0, err_msg="tick %d" % (s + 1))
+    check_state(mgr, ids, orc, dtype, "%s %s %d" % (name, dtype, lanes))
+    d1, p1 = b.intersect_sphere(origin, radius)
+    np.testing.assert_array_equal(delta.cpu().numpy(), d1.cpu().numpy())
+    np.testing.assert_array_equal(qpose.cpu().numpy(), p1.cpu().numpy())
+    mgr.close()
 
 
 def test_bad_pose_streams_are_refused_and_launch_nothing(models):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Join tools/sweep.py output (stdin) with the compiler's resource table (profiles/r02_kernel_resources.txt) and mark the
+"""Join tools/sweep.py output (stdin) with the compiler's resource table (tools/kres_all.sh > profiles/<TE_KRES_FILE>) and mark the
 lanes codes the library picks by itself (csrc/shard.cpp chooseLayout, kf_model_*.hip defaults).
     python tools/sweep.py --steps 100 --sizes 1000000 > gpurun_out/sweep.txt     (GPU box)
     python tools/annotate_sweep.py < gpurun_out/sweep.txt > profiles/r02_layout_sweep.txt"""
@@ -7,13 +7,19 @@ import os
 import re
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))   # tools/step_variant.py, wherever this module is loaded from
+from step_variant import variant_name  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHORT = {"uniform_velocity": "UV", "uniform_acceleration": "UA", "angular_rates": "AR", "angular_velocities": "AV"}
 res = {}
-for ln in open(os.path.join(ROOT, "profiles", os.environ.get("TE_KRES_FILE", "r04_kernel_resources.txt"))):
+for ln in open(os.path.join(ROOT, "profiles", os.environ.get("TE_KRES_FILE", "r11_kernel_resources.txt"))):
     m = re.match(r"(kf_step\w*<[^>]*>)\s+vgpr\s+(\d+) agpr\s+(\d+) \(\s*(\d+)\) sgpr\s+\d+ scratch\s+(\d+) waves/SIMD (\d)", ln)
     if m:
         res[m.group(1)] = (int(m.group(4)), int(m.group(5)), int(m.group(6)))
+if not any(k.startswith("kf_step_sep_kernel<") and k.count(",") == 3 for k in res):   # <model,T,layout,variant>
+    sys.exit("annotate_sweep.py: profiles/%s has no kernel named by variant (a record from before the variant word?  tools/kres_all.sh "
+             "makes a current one)" % os.environ.get("TE_KRES_FILE", "r11_kernel_resources.txt"))
 # (model, precision) -> {lanes code: note}
 AUTO = {}
 for mdl in SHORT:
@@ -29,7 +35,7 @@ for mdl in SHORT:
             a[101] = "coupled symmetric matrices (csrc/ekf_sym.hpp)"; a[6 if prec == "f64" else 3] = "non-symmetric matrices"
         AUTO[(mdl, prec)] = a
 print("# tools/sweep.py --steps 100 --sizes 1000000 on one MI355X (zig-zag traversal on), every (model, precision, lanes code) the library instantiates, joined by")
-print("# tools/annotate_sweep.py with the register budget of the kernel that runs (profiles/" + os.environ.get("TE_KRES_FILE", "r04_kernel_resources.txt") + ").  lanes code G: dense kernel, full P, G lanes per")
+print("# tools/annotate_sweep.py with the register budget of the kernel that runs (profiles/" + os.environ.get("TE_KRES_FILE", "r11_kernel_resources.txt") + ").  lanes code G: dense kernel, full P, G lanes per")
 print("# target; 100+G: dense kernel, symmetric-packed P; 201: axis-separable, full group blocks; 301: axis-separable, packed group blocks.")
 print("# frac = algorithmic GB/s / 8000 with the bytes the kernel reads + writes.  '<- auto' marks what the library picks by itself.")
 for ln in sys.stdin:
@@ -44,9 +50,9 @@ for ln in sys.stdin:
     mdl, prec, g = p[0], p[1], int(p[2])
     T = "double" if prec == "f64" else "float"
     if g >= 200:
-        key = "kf_step_sep_kernel<%s,%s,%d,0,0,0,0,0,0>" % (SHORT[mdl], T, 2 if g == 201 else 3)
+        key = "kf_step_sep_kernel<%s,%s,%d,%s>" % (SHORT[mdl], T, 2 if g == 201 else 3, variant_name(0))
     else:
-        key = "kf_step_kernel<%s,%s,%d,%d,0,0,0,0,0>" % (SHORT[mdl], T, g % 100, 1 if g >= 100 else 0)
+        key = "kf_step_kernel<%s,%s,%d,%d,%s>" % (SHORT[mdl], T, g % 100, 1 if g >= 100 else 0, variant_name(0))
     r = res.get(key)
     note = "regs %3d scratch %3d waves/SIMD %d" % r if r else "regs ?"
     auto = AUTO[(mdl, prec)].get(g)

@@ -24,14 +24,16 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))   # tools/step_variant.py, wherever this module is loaded from
+from step_variant import BITS  # noqa: E402
 
 
 def short_kernel(name):
-    """'void te::kf_step_sep_kernel<te::ModelAR, double, 3, false, ...>(...)' -> 'kf_step_sep_kernel<ModelAR,double,3>'
+    """'void te::kf_step_sep_kernel<te::ModelAR, double, 3, 0u>(...)' -> 'kf_step_sep_kernel<ModelAR,double,3>'
     (the form bench.py's kernel_name() prints): model, type, then LAYOUT (separable) or G, LAYOUT (dense)."""
-    pm = re.search(r"kf_step_population_kernel<(double|float), (true|false), (true|false)[^>]*>", name.replace("te::", ""))
-    if pm:   # the whole population of a manager in one launch: <T, QUERY, AB (, POSE, SHARED)>
-        return "kf_step_population_kernel<%s>" % pm.group(1) + ("+query" if pm.group(2) == "true" else "")
+    pm = re.search(r"kf_step_population_kernel<(double|float), (?:true|false), (\d+)u>", name.replace("te::", ""))
+    if pm:   # the whole population of a manager in one launch: <T, SHARED, variant>
+        return "kf_step_population_kernel<%s>" % pm.group(1) + ("+query" if int(pm.group(2)) & BITS["QUERY"] else "")
     m = re.search(r"(kf_step(?:_sep)?_kernel)<([^>]*)>", name.replace("te::", ""))
     if not m:
         return None

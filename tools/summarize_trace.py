@@ -9,11 +9,14 @@ import re
 import sys
 from collections import defaultdict
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))   # tools/step_variant.py, wherever this module is loaded from
+from step_variant import name_variants  # noqa: E402
+
 
 def short(name):
     name = name.replace("(anonymous namespace)::", "")
     name = re.sub(r"\(.*", "", name)
-    return name.replace("void ", "").replace("te::", "")
+    return name_variants(name.replace("void ", "").replace("te::", ""))
 
 
 def main():
@@ -25,8 +28,9 @@ def main():
             g = int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)
             groups[(short(r["Kernel_Name"]), g)].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     print("# rocprofv3 --kernel-trace --stats summary; template arguments of kf_step_sep_kernel: <model, precision, layout (2 = separable,")
-    print("# 3 = separable + packed, 4 = its shared-axes storage form), INDEXED, FUSED, QUERY, PERQR, LIVE (1 = resident, 2 = resident with per-tick query / pose output), AB>, of kf_step_kernel:")
-    print("# <model, precision, lanes per target, layout (0 = full, 1 = packed), INDEXED, FUSED, QUERY, PERQR, AB>; kf_step_population_kernel<precision, QUERY, AB, POSE, SHARED>:")
+    print("# 3 = separable + packed, 4 = its shared-axes storage form), variant (tools/step_variant.py; LIVE1 = resident, LIVE2 = resident with per-tick")
+    print("# query / pose output; 0 = the plain tick)>, of kf_step_kernel: <model, precision, lanes per target, layout (0 = full, 1 = packed), variant>;")
+    print("# kf_step_population_kernel<precision, shared-axes form, variant>:")
     print("# ONE launch for every batch of a manager (grid = the sum over the models of their targets, each rounded up to whole workgroups)")
     print("%-78s %9s %6s %10s %10s %10s" % ("kernel", "grid", "calls", "avg_us", "min_us", "max_us"))
     rows = sorted(groups.items(), key=lambda kv: -sum(kv[1]))
