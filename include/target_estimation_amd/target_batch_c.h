@@ -433,6 +433,39 @@ int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, do
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            const target_innov_stream_c* per_batch_innov, long n_batches,
                                            int query, const double* origin, double radius, int use_graph);
+/* ---- The NIS validation gate inside launched ticks.
+ * A chi-square gate around the Kalman update, decided INSIDE the tick, between prediction and update: the ..._innov calls with a
+ * threshold nis_max on NIS = nu^T S^-1 nu.  A launched dense tick with a gate treats a target as follows.
+ *   no measurement on the tick (mask 0): as without a gate -- predict only, NIS -1, zero innovations;
+ *   measurement present: x^-, P^-, the unwrapped angles, nu and S^-1 are formed as the update forms them and NIS is summed in the
+ *     ..._innov order (chains axis-ascending, the EKF attitude group last).  The measurement is ACCEPTED iff (double)NIS <= nis_max
+ *     evaluates true -- a NaN NIS (a NaN anywhere in the measurement) rejects; fp32 batches sum NIS in fp32 and compare the double
+ *     that the stream stores.  The NIS row and the innovation block report NIS and nu of the measurement whether or not it was
+ *     accepted: a consumer recovers the decision exactly as 0 <= nis <= nis_max;
+ *   accepted: the update -- bit for bit the ungated tick with mask 1;
+ *   rejected: bit for bit the ungated tick with mask 0 (the reference's update(dt)): state, covariance, the unwrap memory (not
+ *     advanced) and the target's measurement counter (not incremented) are those of a predict-only tick, and no NaN of the
+ *     rejected measurement reaches the record.
+ * So a gated call leaves every target in the bits the ungated call leaves with the mask has & (0 <= nis <= nis_max), nis read from
+ * the gated call's own stream.  chi-square 0.99 quantiles for the user's convenience: 11.345 for m = 3 (the uniform models),
+ * 16.812 for m = 6 (the angular models).
+ * nis_max == 0 (or a NULL per_batch_nis_max): no gate for that batch, exactly the ..._innov call.  nis_max > 0, +inf included:
+ * gated.  nis_max < 0 or NaN, or nis_max > 0 with a NULL `innov` / nis_dev (the NIS row reports the decisions; a stride of 0 keeps
+ * it to one line): a negative return code, target_manager_last_error set, nothing launched.
+ * One-class batches in the axis-separable layouts decide inside the step kernel (and inside the population kernel where the
+ * manager's tick is one launch); every other layout's innovation-writer launch is followed by a small launch that forms the effective
+ * mask from the NIS row just written, into a row the library owns, and the plain step takes that row -- three launches per tick,
+ * one more than ..._innov.  Poses and the fused query in the same
+ * call, use_graph (a recorded graph is keyed by the gate too) and every other argument: as for ..._innov.
+ * Not served: target_batch_step_fused, the resident mode, the by-id / indexed launches, the one-target symbols, the Eigen facade. */
+int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max, int use_graph);
+/* per_batch_nis_max[i]: the gate of batch i (NULL: none for any batch) */
+int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max, long n_batches,
+                                           int query, const double* origin, double radius, int use_graph);
 /* Resident ("live") mode (target_batch_live_* above) for EVERY batch of a manager at once (BASELINE.json configs[3] / configs[4]: two motion models per GPU, whose per-GPU
  * share is launch-bound): one resident kernel per batch, each on a stream of its own so that they are on the device together;
  * per_batch[i] describes batch i's ring as for target_manager_step_sequence_all (ring_ticks > 0); with query != 0 the own-time

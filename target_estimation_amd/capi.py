@@ -160,6 +160,11 @@ SIGNATURES = {
                                                    C.c_long, C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_int]),
     "target_manager_step_sequence_all_innov": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
                                                          C.POINTER(InnovStream), C.c_long, C.c_int, c_double_p, C.c_double, C.c_int]),
+    "target_batch_step_sequence_gated": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                   C.c_long, C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.c_int]),
+    "target_manager_step_sequence_all_gated": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
+                                                         C.POINTER(InnovStream), c_double_p, C.c_long, C.c_int, c_double_p, C.c_double,
+                                                         C.c_int]),
     "target_batch_live_start": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long,
                                           C.c_long, C.c_double]),
     "target_batch_live_set_pose_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -166,14 +166,23 @@ int Batch::add_class(const double* Q, const double* R) {
 }
 
 void Batch::launch_step(const StepParams& p, hipStream_t st, int meas_rows) {
-  ops_->step(p, st);
+  const bool gated_rows = keep_meas_ && p.gate > 0.0;
+  if (gated_rows) {   // the measured-pose rows keep ACCEPTED measurements: the gate's mask comes from the writer, for the row kernel too
+    StepParams q = p;
+    q.gate_by_writer = 1;
+    ops_->step(q, st);
+  } else {
+    ops_->step(p, st);
+  }
   if (!keep_meas_ || !p.meas || p.n <= 0) return;
+  const unsigned char* has = gated_rows ? p.gate_row : p.has_meas;
+  const long has_stride = gated_rows ? 0 : p.has_stride;
   const unsigned blocks = (unsigned)((p.n + 255) / 256);
   if (dtype_ == F64)
-    keep_measurement_kernel<double><<<blocks, 256, 0, st>>>(static_cast<const double*>(p.meas), p.meas_ld, p.tick_stride, p.has_meas, p.has_stride,
+    keep_measurement_kernel<double><<<blocks, 256, 0, st>>>(static_cast<const double*>(p.meas), p.meas_ld, p.tick_stride, has, has_stride,
                                                             p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_);
   else
-    keep_measurement_kernel<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(p.meas), p.meas_ld, p.tick_stride, p.has_meas, p.has_stride,
+    keep_measurement_kernel<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(p.meas), p.meas_ld, p.tick_stride, has, has_stride,
                                                            p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_);
 }
 
@@ -286,6 +295,7 @@ StepParams Batch::dense_params() {
   p.rec = d_rec_; p.qr = d_qr_; p.cls = n_classes_ > 1 ? d_cls_ : nullptr; p.n = n_; p.idx = nullptr;
   p.meas = nullptr; p.meas_ld = 0; p.has_meas = nullptr; p.dt_per = nullptr; p.dt = 0.0;
   p.t_base = d_tbase_; p.nm_base = d_nmbase_;
+  p.gate_row = d_has_eff_;
   if (uniform_tiles_enabled() && d_tile_uni_) {
     p.tile_blk = d_tile_blk_; p.tile_uni = d_tile_uni_;
     p.promote = (recording_ || dense_streak_ >= promote_after()) ? 1 : 0;
@@ -314,6 +324,7 @@ Batch::~Batch() {
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
   device_free(d_tile_blk_); device_free(d_tile_uni_);
   device_free(d_qr_); device_free(d_rec_); device_free(d_rec_alt_); device_free(d_tbase_); device_free(d_nmbase_); device_free(d_cls_);
+  device_free(d_has_eff_);
   device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
   device_free(d_dtper_); device_free(d_lastmeas_);
@@ -426,6 +437,9 @@ void Batch::reserve(long n) {
     d_lastmeas_ = lm;
   }
   d_rec_ = rec; d_tbase_ = tb; d_nmbase_ = nm; d_cls_ = cl; cap_ = want;
+  // (the gate's mask row is written whole by every launch that reads it: no contents to carry over)
+  device_free(d_has_eff_); d_has_eff_ = nullptr;
+  TE_HIP_CHECK(hipMalloc((void**)&d_has_eff_, (size_t)want));
   device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;
   if (uniform_tiles_enabled()) {   // about 1.5 B per target (angular_rates: 96 + 4 B per 64)
     const size_t tiles = (size_t)(want / tpw);
@@ -645,6 +659,8 @@ void Batch::check_pose_stream(const PoseStream& q) const {
 }
 
 void Batch::check_innov_stream(const InnovStream& q) const {
+  if (!(q.gate >= 0.0)) throw std::invalid_argument("target_estimation_amd: gate: nis_max must be 0 (no gate) or positive");
+  if (q.gated() && !q.nis) throw std::invalid_argument("target_estimation_amd: gate: nis_max > 0 needs an innovation stream with a NIS row (it reports the decisions)");
   if (!q.nis) return;
   const long m = ops_->L.m;
   if (q.ld < n_) throw std::invalid_argument("target_estimation_amd: innovation stream: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
@@ -672,7 +688,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     p.dt = dt;
     p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
     p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
-    p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld;
+    p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld; p.gate = innov.gate;
     return p;
   };
   if (!use_graph) {
@@ -740,7 +756,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
   t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
-  if (meas_base && !has_base) nm_acc_ += n_ticks;
+  if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
 }
 
 void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius,
@@ -756,7 +772,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   if (q.innov.on()) ab = false;
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
-  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld;
+  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
@@ -808,7 +824,7 @@ StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, c
   const size_t es = elem_size();
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
-  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld;
+  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;

@@ -39,11 +39,17 @@ struct InnovStream {
   long nis_tick_stride = 0;
   long innov_tick_stride = 0;
   long ring = 0;
+  // The validation gate that goes with the stream (StepParams::gate): > 0 (+inf included) = a measurement is folded in iff its
+  // (double)NIS <= gate, a rejected one leaves the target as a tick without a measurement would; the stream reports NIS and nu of
+  // every measured slot, so the decision is 0 <= nis <= gate.  0: none.  Needs the NIS row.
+  double gate = 0.0;
+  bool gated() const { return gate > 0.0; }
   bool on() const { return nis != nullptr; }
   double* nis_row(long s) const { return nis ? nis + (ring > 0 ? s % ring : s) * nis_tick_stride : nullptr; }
   double* innov_block(long s) const { return (nis && innov) ? innov + (ring > 0 ? s % ring : s) * innov_tick_stride : nullptr; }
   bool same(const InnovStream& o) const {
-    return nis == o.nis && innov == o.innov && ld == o.ld && nis_tick_stride == o.nis_tick_stride && innov_tick_stride == o.innov_tick_stride && ring == o.ring;
+    return nis == o.nis && innov == o.innov && ld == o.ld && nis_tick_stride == o.nis_tick_stride && innov_tick_stride == o.innov_tick_stride && ring == o.ring &&
+           gate == o.gate;   // (recorded graphs are keyed by the gate as well)
   }
 };
 
@@ -257,6 +263,7 @@ class Batch {
   // output) for this batch: the pose-writer launch into tick s's pose block and / or the own-time sphere query, as launches.
   void enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& spec, bool query, const double* origin, double radius);
   void swap_records() { std::swap(d_rec_, d_rec_alt_); }
+  // (all_measured: measurements without a mask and without a gate -- a gated tick counts its accepted ones on the device)
   void account_sequence(long n_ticks, double dt, bool all_measured);
   // identity of everything a recorded launch sequence refers to
   // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
@@ -344,6 +351,7 @@ class Batch {
   bool alt_failed_ = false;
   TClock* d_tbase_ = nullptr;
   int* d_nmbase_ = nullptr;
+  unsigned char* d_has_eff_ = nullptr;   // [cap_] the effective mask of a gated tick whose layout has no gated kernel (StepParams::gate_row)
   long cap_ = 0;  // slots
   long n_ = 0;
   std::vector<unsigned> slot_ids_;

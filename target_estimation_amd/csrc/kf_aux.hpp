@@ -551,6 +551,18 @@ __global__ void innov_kernel(const InnovArgs a) {
   if (a.innov != nullptr) for (int c = 0; c < K; ++c) a.innov[(long)c * a.innov_ld + e] = (double)nu[c];
 }
 
+// The effective mask of a gated tick whose layout has no gated step kernel (StepParams::gate_row), from the NIS row the writer
+// above has just written: has_eff[e] = has && nis[e] <= gate -- the double of the stream, so a NaN rejects.  The step that follows
+// takes the row as its has_meas.  A launch of its own behind the writer, which stays the code it was.  (A template only so that
+// every translation unit that launches it may hold it.)
+template <typename Tag = void>
+__global__ void gate_mask_kernel(const double* nis, const unsigned char* has_meas, int measured, long n, double gate, unsigned char* has_eff) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const bool has = measured != 0 && (has_meas == nullptr || has_meas[e] != 0);
+  has_eff[e] = (has && nis[e] <= gate) ? 1 : 0;
+}
+
 struct IntersectArgs {
   char* rec;
   const int* idx;     // null: dense slots 0..n-1

@@ -1,0 +1,9 @@
+// kf_gate_ua.hip -- the uniform_acceleration step kernels with the NIS validation gate (kf_gate_impl.hpp): a translation unit of its
+// own so that the build stays parallel.
+#include "kf_gate_impl.hpp"
+
+namespace te {
+
+TE_GATE_INSTANCES(ModelUA)
+
+}  // namespace te

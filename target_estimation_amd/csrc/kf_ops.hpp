@@ -69,6 +69,15 @@ struct StepParams {
   double* nis = nullptr;
   double* innov = nullptr;
   long innov_ld = 0;
+  // The validation gate of a dense single tick with an innovation stream: gate > 0 (+inf included) accepts a measurement iff
+  // (double)NIS <= gate; a rejected one is a tick without a measurement (state, covariance, unwrap memory, counter), its NIS and
+  // innovation still reported.  0: none.  The separable layouts of one-class batches decide inside the step kernel (GATE,
+  // kf_step_sep.hpp); every other layout's innovation writer is followed by the effective mask from its NIS row (gate_mask_kernel)
+  // in gate_row [n] (the batch's own row), which the plain step kernel then takes as its has_meas.  gate_by_writer: take that path whatever the layout.
+  // A gated tick always counts its accepted measurements in nm_base.
+  double gate = 0.0;
+  unsigned char* gate_row = nullptr;
+  int gate_by_writer = 0;
 };
 
 struct Ops {
@@ -88,6 +97,8 @@ struct Ops {
   void (*intersect)(const IntersectArgs&, hipStream_t);
   void (*outputs_rows)(const OutArgs&, hipStream_t);   // outputs_rows_kernel: poses at OutArgs::row_of_slot
   void (*innov)(const InnovArgs&, hipStream_t);       // innov_kernel: the innovations a tick WOULD see, records read-only
+  // the same, then gate_mask_kernel: has_eff[e] = has && nis[e] <= gate for the step that follows
+  void (*innov_gate)(const InnovArgs&, double gate, unsigned char* has_eff, hipStream_t);
   // shared-axes storage form only (L.shared_axes; null otherwise): write the n records of `rec` as plain LAYOUT_SEPARABLE_PACKED
   // records into `rec_plain` (a zero-filled buffer of the plain form's tiles), every kind's block copied to each of its axes
   void (*expand)(char* rec, char* rec_plain, long n, hipStream_t) = nullptr;

@@ -40,6 +40,10 @@ inline StepArgs<T> make_step_args(const StepParams& p) {
 template <class M, typename T, int LAYOUT>
 void launch_sep_innov_step(const StepArgs<T>& a, unsigned blocks, unsigned threads, hipStream_t s);
 
+// The gated kInnov kernels (kf_step_sep.hpp, kf_step_sep_gate_kernel), in kf_gate_{uv,ua,ar,av}.hip (kf_gate_impl.hpp) likewise.
+template <class M, typename T, int LAYOUT>
+void launch_sep_gate_step(const StepArgs<T>& a, double gate, unsigned blocks, unsigned threads, hipStream_t s);
+
 template <class M, typename T, int G, int LAYOUT = LAYOUT_FULL>
 struct OpsImpl {
   using C = Cfg<M, T, G, LAYOUT>;
@@ -76,7 +80,10 @@ struct OpsImpl {
                                        (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 4 && G == 1 && LAYOUT == LAYOUT_FULL) ||
                                        (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 8 && G == 1 && LAYOUT == LAYOUT_PACKED) ||
                                        (M::TYPE == ANGULAR_RATES && sizeof(T) == 8 && G == 6 && LAYOUT == LAYOUT_PACKED);
-  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW};
+  // Gated separable instantiations that would spill or need scratch are not shipped: their gate is the innovation writer's mask
+  // row and the plain step (profiles/r11_gate_kernel_resources.txt).  None does.
+  static constexpr bool kGateByWriter = false;
+  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW, kGateByWriter};
   // the pose-writer launch behind a tick whose kernel has no pose output: outputs_kernel into the tick's block
   static void write_pose_block(const StepParams& p, double* pose, hipStream_t s) {
     OutArgs o;
@@ -108,6 +115,10 @@ struct OpsImpl {
     if constexpr (C::SEP) launch_variant<kSepVariants>(std::make_index_sequence<std::size(kSepVariants)>{}, v, a, blocks, threads, s);
     else launch_variant<kDenseVariants>(std::make_index_sequence<std::size(kDenseVariants)>{}, v, a, blocks, threads, s);
   }
+  static void launch_gate(const StepArgs<T>& a, double gate, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (C::SEP && !kGateByWriter) launch_sep_gate_step<M, T, LAYOUT>(a, gate, blocks, threads, s);
+    else throw std::runtime_error("target_estimation_amd: no gated step kernel for this request");
+  }
   // The launches of a request are plan_step's (step_variant.hpp): [innovation writer,] then once, or once per tick, the step
   // kernel [and the pose writer].
   static void step(const StepParams& p, hipStream_t s) {
@@ -124,9 +135,16 @@ struct OpsImpl {
       InnovArgs w;
       w.rec = p.rec; w.qr = p.qr; w.cls = p.cls; w.n = p.n; w.meas = p.meas; w.meas_ld = p.meas_ld; w.has_meas = p.has_meas; w.dt = p.dt;
       w.tile_blk = p.tile_blk; w.tile_uni = p.tile_uni; w.nis = p.nis; w.innov = p.innov; w.innov_ld = p.innov_ld;
-      innov(w, s);
+      if (plan.gated) {   // the writer decides: its mask row is the step's has_meas
+        if (!p.gate_row) throw std::runtime_error("target_estimation_amd: a gated tick of this layout needs the batch's mask row");
+        innov_gate(w, p.gate, p.gate_row, s);
+        q.has_meas = p.gate_row; q.has_stride = 0;
+      } else {
+        innov(w, s);
+      }
       q.nis = nullptr; q.innov = nullptr;
     }
+    const bool gate_kernel = plan.gated && !plan.innov_writer_first;
     static const int nt_env = [] { const char* e = std::getenv("TE_NT_MEAS"); return e ? std::atoi(e) : -1; }();
     if (nt_env >= 0) q.nt_meas = nt_env;
     static const long small_grid = [] { const char* e = std::getenv("TE_SMALL_GRID_WAVES"); return e ? std::atol(e) : 1024L; }();
@@ -145,7 +163,8 @@ struct OpsImpl {
         if (p.pose) pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
       }
       q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
-      launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
+      if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
+      else launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
       if (plan.pose_writer_after_each_tick) write_pose_block(q, pose, s);
     }
   }
@@ -189,6 +208,12 @@ struct OpsImpl {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((innov_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + 127) / 128)), dim3(128), 0, s, a);
   }
+  static void innov_gate(const InnovArgs& a, double gate, unsigned char* has_eff, hipStream_t s) {
+    if (a.n <= 0) return;
+    innov(a, s);
+    hipLaunchKernelGGL((gate_mask_kernel<>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, (const double*)a.nis, a.has_meas, a.meas != nullptr ? 1 : 0,
+                       a.n, gate, has_eff);
+  }
   static void outputs_rows(const OutArgs& a, hipStream_t s) {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((outputs_rows_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
@@ -212,7 +237,7 @@ struct OpsImpl {
     static const Ops ops = {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
-        C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov,
+        C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov, &innov_gate,
         C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr};
     return &ops;
   }

@@ -18,6 +18,10 @@ void launch_population_grid(unsigned v, const PopulationArgs<T>& p, unsigned blo
 void launch_population_grid_innov_shared(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_innov(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_innov(unsigned v, const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
+// the gated population tick (kf_step_population_gate_kernel), in kf_population_f{64,32}_gate.hip / kf_population_f64_shared_gate.hip
+void launch_population_grid_gate_shared(const PopulationArgs<double>& p, const PopulationGate& g, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_gate(const PopulationArgs<double>& p, const PopulationGate& g, unsigned blocks, unsigned wpb, hipStream_t s);
+void launch_population_grid_gate(const PopulationArgs<float>& p, const PopulationGate& g, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_pose_shared(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_pose(unsigned v, const PopulationArgs<double>& p, unsigned blocks, unsigned wpb, hipStream_t s);
 void launch_population_grid_pose(unsigned v, const PopulationArgs<float>& p, unsigned blocks, unsigned wpb, hipStream_t s);
@@ -30,6 +34,9 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
   // the variant of the launch: the caller's query / ab, kPose / kInnov when some part writes that stream (StepParams::pose, one
   // block: a population launch is one tick; StepParams::nis)
   unsigned variant = (query ? kQuery : 0u) | (ab ? kAB : 0u);
+  // a part with StepParams::gate set makes the launch the gated kernel: the kInnov tick with every part's gate (0: none)
+  PopulationGate gates{{0.0, 0.0, 0.0, 0.0}};
+  bool gated = false;
   for (int k = 0; k < 4; ++k) {
     const StepParams& q = parts[k];
     if (q.n <= 0) continue;
@@ -37,6 +44,10 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
     if ((asked & ~(kQuery | kAB | kPose | kInnov)) || q.n_ticks != 1 || q.o_pose || (query && !q.q_delta) || (ab && !q.rec_out))
       throw std::runtime_error("target_estimation_amd: a population launch takes dense single ticks of one-class batches");
     variant |= asked & (kPose | kInnov);
+    if (!(q.gate >= 0.0) || (q.gate > 0.0 && !q.nis))
+      throw std::runtime_error("target_estimation_amd: the gate (nis_max) must be 0 (none) or positive, and needs the part's innovation stream");
+    gates.gate[k] = q.gate;
+    gated = gated || q.gate > 0.0;
     waves_max = std::max(waves_max, (q.n + TPW - 1) / TPW);
   }
   static const long small_grid = [] { const char* e = std::getenv("TE_SMALL_GRID_WAVES"); return e ? std::atol(e) : 1024L; }();
@@ -59,7 +70,10 @@ void launch_population_step_t(const StepParams parts[4], bool query, bool ab, bo
     throw std::runtime_error(sv_has(variant, kInnov)
                                  ? "target_estimation_amd: a population launch with an innovation stream is a plain tick in place (the query and the poses follow as launches of their own)"
                                  : "target_estimation_amd: a population launch takes dense single ticks of one-class batches");
-  if (sv_has(variant, kInnov)) {
+  if (gated) {   // (variant == kInnov: population_variant_ok above)
+    if constexpr (SHARED) launch_population_grid_gate_shared(p, gates, end, (unsigned)wpb, s);
+    else launch_population_grid_gate(p, gates, end, (unsigned)wpb, s);
+  } else if (sv_has(variant, kInnov)) {
     if constexpr (SHARED) launch_population_grid_innov_shared(variant, p, end, (unsigned)wpb, s);
     else launch_population_grid_innov(variant, p, end, (unsigned)wpb, s);
   } else if (sv_has(variant, kPose)) {

@@ -158,6 +158,87 @@ __device__ __forceinline__ void sep_linear_state(T* x, T dt, bool has, T y, cons
   for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
 }
 
+// GATE (sep_step_wave): the same statements once more, cut where the validation gate decides -- between the prediction and the
+// update, for ALL chains of a target.  Statement for statement the halves of sep_linear_axis (and of sep_linear_cov /
+// sep_linear_state, whose statements are the same ones): the gated kernels are held to the bits of the plain ones
+// (tests/test_gpu_gate.py).
+//   sep_gate_predict_x / sep_gate_predict_P : x^- = A x / P^- = A P A^T + Q -- what precedes `if (!has) return`
+//   sep_gate_gain, sep_gate_update_x / _P   : what follows it, with the 1 / S and nu formed at the decision: the gain from the
+//                                             column P^-[:,0] as predicted (P^-[b][0] and P^-[0][b] round differently, and a
+//                                             packed record keeps the upper triangle only), then the state half (per axis) and
+//                                             the covariance half (per chain; per kind of axis in the shared-axes form).
+template <int NB, typename T>
+__device__ __forceinline__ void sep_gate_predict_x(T* x, T dt) {
+#pragma clang fp contract(off)
+  using F = Mth<T>;
+  const T hdt = (T)0.5 * dt * dt;
+#pragma unroll
+  for (int b = 0; b + 1 < NB; ++b) {
+    x[b] = F::fma(dt, x[b + 1], x[b]);
+    if (NB == 3 && b == 0) x[b] = F::fma(hdt, x[b + 2], x[b]);
+  }
+}
+template <int NB, typename T>
+__device__ __forceinline__ void sep_gate_predict_P(T (&P)[NB][NB], const T (&Q)[NB][NB], T dt) {
+#pragma clang fp contract(off)
+  using F = Mth<T>;
+  const T hdt = (T)0.5 * dt * dt;
+  // AP = A P (rows)
+#pragma unroll
+  for (int b = 0; b + 1 < NB; ++b) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      T v = F::fma(dt, P[b + 1][c], P[b][c]);
+      if (NB == 3 && b == 0) v = F::fma(hdt, P[b + 2][c], v);
+      P[b][c] = v;
+    }
+  }
+  // (AP) A^T (columns), + Q
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      T v = P[b][c];
+      if (c + 1 < NB) {
+        v = F::fma(dt, P[b][c + 1], v);
+        if (NB == 3 && c == 0) v = F::fma(hdt, P[b][c + 2], v);
+      }
+      P[b][c] = v + Q[b][c];
+    }
+}
+template <int NB, typename T>
+__device__ __forceinline__ void sep_gate_gain(const T (&pcol)[NB], T inv, T (&Kg)[NB]) {
+#pragma clang fp contract(off)
+  // K = P^-[:,0] / S
+#pragma unroll
+  for (int b = 0; b < NB; ++b) Kg[b] = pcol[b] * inv;
+}
+template <int NB, typename T>
+__device__ __forceinline__ void sep_gate_update_x(T* x, const T (&Kg)[NB], T nu) {
+#pragma clang fp contract(off)
+  // x += K (y - x0)
+#pragma unroll
+  for (int b = 0; b < NB; ++b) x[b] += Kg[b] * nu;
+}
+template <int NB, typename T>
+__device__ __forceinline__ void sep_gate_update_P(T (&P)[NB][NB], const T (&Kg)[NB]) {
+#pragma clang fp contract(off)
+  // P = (I - K C) P
+  T top[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) top[c] = P[0][c];
+  const T d0 = (T)1 - Kg[0];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) {
+    P[0][c] = d0 * top[c];
+#pragma unroll
+    for (int b = 1; b < NB; ++b) {
+      const T t = ((T)0 - Kg[b]) * top[c];
+      P[b][c] = t + P[b][c];
+    }
+  }
+}
+
 // Uniform tiles (te_layout.hpp Cfg::UT): a record in two parts -- its linear-covariance chunks (LIN), which a uniform tile neither
 // loads nor stores, and everything else (the other chunks and the tail row).
 template <class C, typename T, bool LIN>
@@ -264,14 +345,23 @@ template <class C, class M, typename T> struct LivePark {
 // The step of one wavefront's targets: `wg` = index of the wavefront among those of the launch (of the BATCH, in a population
 // launch: kf_step_population_kernel below), lane = its lane.
 // VAR: the variant word (step_variant.hpp), unpacked here into the names the body uses.
-template <class M, typename T, int LAYOUT, unsigned VAR>
-__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane) {
+// GATE: the validation gate of a launched tick (StepParams::gate), with INNOV only.  The tick in two phases.  A: every chain's
+// prediction and, with a measurement, its innovation, 1 / S and NIS term -- the unwrapped angles in temporaries, the unwrap
+// memory untouched.  The decision: acc = has && (double)nis <= gate, so a NaN rejects.  B, under acc: the unwrap memory and every
+// chain's update from the SAME 1 / S and nu.  An accepted target leaves in the bits of the plain tick with mask 1, a rejected one
+// in those of the plain tick with mask 0; the stream reports NIS and nu of every measured target either way.  acc replaces the
+// has-bit in everything behind it: the measurement counter (always added to nm_base) and the uniform-tile agreement (always
+// tested).  `gate` is an argument of its own, not a field of StepArgs, whose size is part of every existing kernel's descriptor;
+// 0 = no gate (a part of a gated population launch without one): acc = has.
+template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false>
+__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0) {
   constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
                  AB = sv_has(VAR, kAB), POSE = sv_has(VAR, kPose), INNOV = sv_has(VAR, kInnov);
   constexpr int LIVE = sv_live(VAR);
   using C = Cfg<M, T, 1, LAYOUT>;
   static_assert(C::SEP, "separable layouts only");
   static_assert(sep_variant_ok(VAR, C::SHARED), "no such variant of the separable step (step_variant.hpp)");
+  static_assert(!GATE || INNOV, "the gate decides on the NIS of the innovation stream's kernels");
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -465,6 +555,13 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
   for (int c = 0; c < MI; ++c) nu_all[c] = T(0);
   if constexpr (!INNOV) { (void)nu_all; (void)nis; }
+  // GATE: what the update behind the decision takes from the prediction -- per chain 1 / S and the column P^-[1:,0] (the packed
+  // records keep the upper triangle only), the unwrapped angles -- and the two masks: the tick's has-bit for the stream, acc for the rest
+  constexpr int NGATE = GATE ? NCOV : 1;            // one entry per chain whose covariance half runs
+  auto cov_of = [](int i) constexpr { return C::SHARED ? i / 3 : i; };
+  T g_inv[NGATE], g_pcol[NGATE][LB], g_uw[3] = {0, 0, 0};
+  bool g_has = false, acc = false;
+  if constexpr (!GATE) { (void)g_inv; (void)g_pcol; (void)g_uw; (void)g_has; (void)acc; (void)gate; (void)cov_of; }
   int n_has = 0;
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
@@ -497,7 +594,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
   const bool has = valid && meas_t != nullptr && hmask != 0;
-  n_has += has ? 1 : 0;
+  if constexpr (!GATE) n_has += has ? 1 : 0;
   if constexpr (UT) {
     uni = __builtin_amdgcn_readfirstlane(uni_flag) != 0;
     if (uni) {   // (wave-uniform) every lane takes the tile's block
@@ -554,7 +651,59 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #define XS_(r, v) WR(C::X_OFF + (r), (v))
 
   // ---- the [p v (a)] chains
-  if constexpr (C::SHARED) {
+  if constexpr (GATE) {
+    // phase A (sep_gate_predict_*): every chain's prediction into the record's words; with a measurement, nu, 1 / S, the NIS term
+    g_has = has;
+#pragma unroll
+    for (int i = 0; i < NLIN; ++i) {
+      const int ic = cov_of(i);   // the covariance chain this axis takes its 1 / S from
+      if (lead(i)) {   // (a constant once the loop is unrolled)
+        T Pb[LB][LB], Qb[LB][LB];
+#pragma unroll
+        for (int b = 0; b < LB; ++b)
+#pragma unroll
+          for (int c = 0; c < LB; ++c) {
+            Pb[b][c] = mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            if constexpr (HOIST_QR) Qb[b][c] = Qlin[i][b][c];
+            else Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+          }
+        T r_meas;
+        if constexpr (HOIST_QR) r_meas = Rlin[i];
+        else r_meas = Qm[C::RWORD.v[i][i]];
+        sep_gate_predict_P<LB, T>(Pb, Qb, dt);
+        g_inv[ic] = T(0);
+        if (has) g_inv[ic] = (T)1 / (Pb[0][0] + r_meas);
+#pragma unroll
+        for (int b = 0; b < LB; ++b) {
+          g_pcol[ic][b] = Pb[b][0];
+#pragma unroll
+          for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]] = Pb[b][c];
+        }
+      }
+      T xs[LB];
+#pragma unroll
+      for (int b = 0; b < LB; ++b) xs[b] = XW_(i + STRIDE * b);
+      T y = 0;
+      if (has) {
+        if (!M::ANGULAR || i < 3) {
+          y = ymeas[i];
+        } else {
+          y = unwrap_angle(UWW_(i - 3), mrpy[i - 3]);   // angular_rates.cpp:85-88; stored in phase B
+          g_uw[i - 3] = y;
+        }
+      }
+      sep_gate_predict_x<LB, T>(xs, dt);
+      {
+#pragma clang fp contract(off)
+        if (has) {
+          nu_all[i] = y - xs[0];
+          nis = nis + (nu_all[i] * nu_all[i]) * g_inv[ic];
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
+    }
+  } else if constexpr (C::SHARED) {
     // one covariance half per kind of axis (its lead axis i % 3 == 0 owns the kind's block), one state half per axis
     T Kg[LB];
     T inv_kind = T(0);   // (INNOV) 1 / S of the kind of axis, from its lead axis
@@ -772,7 +921,88 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
       for (int c = 0; c < 6; ++c) Pr[r][c] = (c < 3 ? nw[c < 3 ? c : 0] : Pr[r][c]) + qrow[c];
     }
-    if (has) {
+    if constexpr (GATE) {
+      // phase A of the group: S, its inverse, nu and the NIS term; the decision (the group is the last term of the sum); phase B
+      T S[3][3], nu[3] = {0, 0, 0};
+      if (has) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            T rrc;
+            if constexpr (HOIST_QR) rrc = Ratt[r][c];
+            else rrc = Qm[C::RWORD.v[3 + r][3 + c]];
+            S[r][c] = Pr[r][c] + rrc;
+          }
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          const T inv = (T)1 / S[p][p];
+          S[p][p] = 1;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) S[p][c] *= inv;
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            if (r == p) continue;
+            const T f = S[r][p];
+            S[r][p] = 0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) S[r][c] = F::fma(-f, S[p][c], S[r][c]);
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const T y = unwrap_angle(UWW_(c), mrpy[c]);   // angular_velocities.cpp:93-96; stored under acc
+          g_uw[c] = y;
+          nu[c] = y - xr[c];
+        }
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            nu_all[3 + r] = nu[r];
+            T w = S[r][0] * nu[0];
+            w = F::fma(S[r][1], nu[1], w);
+            w = F::fma(S[r][2], nu[2], w);
+            nis = F::fma(nu[r], w, nis);
+          }
+        }
+      }
+      acc = has && (gate == 0.0 || (double)nis <= gate);
+      if (acc) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) UWW_(c) = g_uw[c];
+        T Kg[6][3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < 6; ++r) Kg[r][l] = (c == 0) ? Pr[r][0] * S[0][l] : F::fma(Pr[r][c], S[c][l], Kg[r][l]);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          T ac = Kg[r][0] * nu[0];
+          ac = F::fma(Kg[r][1], nu[1], ac);
+          ac = F::fma(Kg[r][2], nu[2], ac);
+          xr[r] += ac;
+        }
+        T D[6][3];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) D[r][j] = ((r == j) ? (T)1 : (T)0) - Kg[r][j];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          const T t0 = Pr[0][c], t1 = Pr[1][c], t2 = Pr[2][c];
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            T ac = D[r][0] * t0;
+            ac = F::fma(D[r][1], t1, ac);
+            ac = F::fma(D[r][2], t2, ac);
+            Pr[r][c] = (r < 3) ? ac : ac + Pr[r][c];
+          }
+        }
+      }
+    } else if (has) {
       T S[3][3];
 #pragma unroll
       for (int r = 0; r < 3; ++r)
@@ -856,6 +1086,44 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
 
+  if constexpr (GATE) {
+    if constexpr (!M::EKF) acc = has && (gate == 0.0 || (double)nis <= gate);
+    n_has += acc ? 1 : 0;
+    // phase B: the unwrap memory and every chain's update, from the 1 / S, P^-[:,0] and nu of phase A.  As in the shared form's
+    // plain loop, a lead axis forms the gain and runs the covariance half; every axis runs its state half with that gain.
+    if (acc) {
+      if constexpr (M::ANGULAR && !M::EKF) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) UWW_(c) = g_uw[c];
+      }
+      T Kg[LB];
+#pragma unroll
+      for (int b = 0; b < LB; ++b) Kg[b] = T(0);
+#pragma unroll
+      for (int i = 0; i < NLIN; ++i) {
+        if (lead(i)) {   // (a constant once the loop is unrolled; every axis outside the shared form)
+          const int ic = cov_of(i);
+          sep_gate_gain<LB, T>(g_pcol[ic], g_inv[ic], Kg);
+          T Pb[LB][LB];
+#pragma unroll
+          for (int b = 0; b < LB; ++b)
+#pragma unroll
+            for (int c = 0; c < LB; ++c) Pb[b][c] = (c == 0) ? g_pcol[ic][b] : mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]];
+          sep_gate_update_P<LB, T>(Pb, Kg);
+#pragma unroll
+          for (int b = 0; b < LB; ++b)
+#pragma unroll
+            for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]] = Pb[b][c];
+        }
+        T xs[LB];
+#pragma unroll
+        for (int b = 0; b < LB; ++b) xs[b] = XW_(i + STRIDE * b);
+        sep_gate_update_x<LB, T>(xs, Kg, nu_all[i]);
+#pragma unroll
+        for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
+      }
+    }
+  }
   if constexpr (LIVE == 2) {
     // the own-time sphere query of every target after every tick (BASELINE configs[4]), on the posterior still in registers,
     // and / or the tick's poses for a consumer outside the kernel.  Run-time choices inside the LIVE == 2 variant only: the
@@ -919,7 +1187,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     // launch that asks for it, if its valid lanes are found to agree on every linear P word, bit for bit.
     if (a.tile_uni != nullptr) {
       bool agree = true;
-      if (a.has_meas != nullptr) agree = __all(!valid || n_has == __builtin_amdgcn_readfirstlane(n_has)) != 0;
+      if (a.has_meas != nullptr || (GATE && gate != 0.0)) agree = __all(!valid || n_has == __builtin_amdgcn_readfirstlane(n_has)) != 0;
       if (uni) {
         uni_out = agree;
       } else if (a.promote != 0 && agree) {
@@ -971,7 +1239,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     else if constexpr (AB) store_record<C, T, false, true>(a.rec_out + tile * C::TILE_BYTES, lt, mem);   // A -> B tick (StepArgs::rec_out)
     else store_record<C, T>(tb, lt, mem);
     if constexpr (POSE && !FUSED) write_pose(0);
-    if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
+    if constexpr (GATE) write_innov(g_has, nis, nu_all, MI);
+    else if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
     if constexpr (QUERY) {
       T xq[N];
 #pragma unroll
@@ -997,7 +1266,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       a.t_base[slot] = te_clock_add_ticks(a.t_base[slot], dtd, (double)n_ticks);
       a.nm_base[slot] += n_has;
     } else {
-      if (a.has_meas != nullptr) a.nm_base[entry] += n_has;
+      if (a.has_meas != nullptr || (GATE && gate != 0.0)) a.nm_base[entry] += n_has;
     }
   }
   if constexpr (INDEXED) {
@@ -1027,6 +1296,16 @@ __global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, sv_has(VAR, 
     b = a.reverse ? zz : b;
   }
   sep_step_wave<M, T, LAYOUT, VAR>(a, (long)b * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63));
+}
+
+// The gated tick (sep_step_wave, GATE): the kInnov kernel with the two-phase body and the gate as an argument of its own.
+// Instantiated in kf_gate_{uv,ua,ar,av}.hip (kf_gate_impl.hpp).
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256) kf_step_sep_gate_kernel(const StepArgs<T> a, const double gate) {
+  unsigned b = blockIdx.x;
+  const unsigned zz = zz_block(b, gridDim.x);
+  b = a.reverse ? zz : b;
+  sep_step_wave<M, T, LAYOUT, kInnov, true>(a, (long)b * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), gate);
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------
@@ -1063,6 +1342,24 @@ __global__ void __launch_bounds__(256) kf_step_population_kernel(const Populatio
   else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, VAR>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane);
   else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, VAR>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane);
   else sep_step_wave<ModelUV, T, L, VAR>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane);
+}
+
+// The population tick with the gated body (sep_step_wave, GATE): gate[k] is part k's nis_max, 0 = that part has no gate and
+// leaves in the bits of the kInnov tick.  Instantiated in kf_population_f{64,32}_gate.hip and kf_population_f64_shared_gate.hip.
+struct PopulationGate {
+  double gate[4];   // indexed by ModelType, like PopulationArgs::part
+};
+template <typename T, bool SHARED>
+__global__ void __launch_bounds__(256) kf_step_population_gate_kernel(const PopulationArgs<T> p, const PopulationGate g) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  unsigned b = blockIdx.x;
+  if (p.reverse_blocks) b = zz_block(b, gridDim.x);
+  constexpr int L = SHARED ? LAYOUT_SEPARABLE_SHARED : LAYOUT_SEPARABLE_PACKED;
+  if (b < p.end[0]) sep_step_wave<ModelAR, T, L, kInnov, true>(p.part[0], (long)b * wpb + wave, lane, g.gate[0]);
+  else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, kInnov, true>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane, g.gate[1]);
+  else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, kInnov, true>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane, g.gate[2]);
+  else sep_step_wave<ModelUV, T, L, kInnov, true>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane, g.gate[3]);
 }
 
 }  // namespace te

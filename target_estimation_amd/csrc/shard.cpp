@@ -915,7 +915,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     for (size_t b = 0; b < nb; ++b) batches_[b]->note_replay(n_ticks);
   }
   for (size_t b = 0; b < nb; ++b)
-    if (batches_[b]->size() > 0) batches_[b]->account_sequence(n_ticks, dt, specs[b].meas_base && !specs[b].has_base);
+    if (batches_[b]->size() > 0) batches_[b]->account_sequence(n_ticks, dt, specs[b].meas_base && !specs[b].has_base && !specs[b].innov.gated());
 }
 
 void Shard::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s,

@@ -8,6 +8,8 @@
 // launches of one OpsImpl::step request.  DESIGN.md ("Step-kernel variants") says how a new variant is added.
 #pragma once
 #include <stdexcept>
+#include <type_traits>
+#include <utility>
 
 namespace te {
 
@@ -72,6 +74,7 @@ struct StepTraits {
   bool fused_pose_tick_by_tick;  // no kFused | kPose kernel: it would cost a wavefront per SIMD or spill
   bool fused_spills;             // no kFused kernel (dense): it would spill
   int tpw;                       // targets per wavefront
+  bool gate_by_writer = false;   // no gated kernel (it would spill or need scratch): the gate's mask comes from the innovation writer
 };
 
 template <unsigned N>
@@ -93,7 +96,29 @@ struct StepPlan {
   bool tick_by_tick = false;
   unsigned variant = 0;
   bool pose_writer_after_each_tick = false;
+  // the request carries a validation gate.  Without innov_writer_first the step is the gated kInnov kernel (kf_step_sep.hpp,
+  // GATE: a template argument next to the variant word, not a bit of it); with it the innovation writer is followed by the mask
+  // launch (gate_mask_kernel: has && nis <= gate from the NIS row just written), and the plain step kernel behind the two takes
+  // that row as its has_meas: three launches per tick.
+  bool gated = false;
 };
+
+// The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
+// request type has them; a request type without them plans as it always did.
+template <class P, class = void> struct has_gate_member : std::false_type {};
+template <class P> struct has_gate_member<P, std::void_t<decltype(std::declval<const P&>().gate)>> : std::true_type {};
+template <class P, class = void> struct has_gate_by_writer_member : std::false_type {};
+template <class P> struct has_gate_by_writer_member<P, std::void_t<decltype(std::declval<const P&>().gate_by_writer)>> : std::true_type {};
+template <class P>
+constexpr double requested_gate(const P& p) {
+  if constexpr (has_gate_member<P>::value) return (double)p.gate;
+  else return 0.0;
+}
+template <class P>
+constexpr bool requested_gate_by_writer(const P& p) {
+  if constexpr (has_gate_by_writer_member<P>::value) return p.gate_by_writer != 0;
+  else return false;
+}
 
 // P: StepParams (kf_ops.hpp), or anything with its member names.
 // Every bit a request asks for, before plan_step decides which launch serves it.
@@ -106,6 +131,11 @@ constexpr unsigned requested_variant(const P& p) {
 template <class P>
 StepPlan plan_step(const StepTraits& t, const P& p) {
   StepPlan plan;
+  const double gate = requested_gate(p);
+  if (!(gate >= 0.0)) throw std::runtime_error("target_estimation_amd: the gate (nis_max) must be 0 (none) or positive");
+  plan.gated = gate > 0.0;
+  if (plan.gated && (!p.nis || p.idx || p.n_ticks > 1 || p.live_posted || p.o_pose))
+    throw std::runtime_error("target_estimation_amd: the gate acts in dense single ticks with an innovation stream (its NIS row reports the decisions)");
   // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
   if (t.shared && (p.live_posted || p.cls || p.n_ticks > 1))
     throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
@@ -134,7 +164,7 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
   // same tick the pose writer follows it).  Every other kernel -- the dense ones, several (Q, R) classes -- steps as without the
   // streams: one innovation-writer launch on the records BEFORE the step, one pose-writer launch behind every tick.
   const bool streams_in_kernel = t.sep && !p.cls;
-  plan.innov_writer_first = p.nis && !streams_in_kernel;
+  plan.innov_writer_first = p.nis && (!streams_in_kernel || (plan.gated && (t.gate_by_writer || requested_gate_by_writer(p))));
   plan.pose_writer_after_each_tick = p.pose && (!streams_in_kernel || p.nis);
   // A fused request is served tick by tick -- same results, one launch per tick -- where its kernel does not exist: several
   // (Q, R) classes, poses without a kFused | kPose kernel, the dense kernels that would spill.

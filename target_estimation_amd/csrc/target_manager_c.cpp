@@ -85,6 +85,15 @@ te::InnovStream innov_stream(const target_innov_stream_c* p) {
   }
   return q;
 }
+// the same with the gate of a ..._gated call: nis_max 0 = none, > 0 (+inf included) = gated; anything else, or a gate without a
+// NIS row, is refused before a handle is looked at
+te::InnovStream gated_stream(const target_innov_stream_c* p, double nis_max) {
+  if (!(nis_max >= 0.0)) throw std::invalid_argument("gate: nis_max must be 0 (no gate) or positive, got " + std::to_string(nis_max));
+  te::InnovStream q = innov_stream(p);
+  if (nis_max > 0.0 && !q.nis) throw std::invalid_argument("gate: nis_max > 0 needs an innovation stream with a NIS row (nis_dev): it reports the decisions");
+  q.gate = nis_max > 0.0 ? nis_max : 0.0;
+  return q;
+}
 }  // namespace
 
 extern "C" {
@@ -504,6 +513,38 @@ int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, do
       specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
       poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
       innov[i] = innov_stream(per_batch_innov ? &per_batch_innov[i] : nullptr);
+    }
+    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
+  });
+}
+
+// ---- the NIS validation gate inside launched ticks
+int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                     long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                     const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max, int use_graph) {
+  return guarded("target_batch_step_sequence_gated", [&] {
+    const te::InnovStream stream = gated_stream(innov, nis_max);
+    BatchLock lk(B(b));
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream);
+  });
+}
+
+int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, double dt,
+                                           const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                           const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max, long n_batches,
+                                           int query, const double* origin, double radius, int use_graph) {
+  return guarded("target_manager_step_sequence_all_gated", [&] {
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    std::vector<te::InnovStream> innov(nb);
+    for (size_t i = 0; i < nb; ++i)   // (every gate is looked at before anything else is)
+      innov[i] = gated_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
     }
     M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
   });

@@ -146,27 +146,32 @@ class Batch:
             hp = h.data_ptr()
         _check(self._lib.target_batch_step_host(self._h, float(dt), t.data_ptr(), t.stride(0), hp), "target_batch_step_host")
 
-    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None):
+    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None, gate=None):
         """meas: CUDA tensor [ticks, 7, ld]: one launch per tick, all enqueued by one C call.  n_ticks > ticks
         treats meas (and has_meas) as a ring: tick s reads entry s % ticks.  poses: float64 CUDA tensor
         [ticks_or_ring, 7, ld] (or [7, ld]) that receives every target's pose after every tick (column = slot;
         target_batch_step_sequence_poses); fewer blocks than ticks make it a ring.  innov = (nis, nu_or_None): float64 CUDA
         tensors [ticks_or_ring, ld] and [ticks_or_ring, m, ld] that receive every tick's NIS and innovations
-        (target_batch_step_sequence_innov; -1 and zeros for a target without a measurement on the tick)."""
+        (target_batch_step_sequence_innov; -1 and zeros for a target without a measurement on the tick).  gate = nis_max: the
+        NIS validation gate inside the ticks (target_batch_step_sequence_gated): a measurement with NIS > nis_max, or a NaN one,
+        is not folded in -- the target is stepped as without a measurement -- and the stream still reports its NIS and nu, so the
+        decision is 0 <= nis <= nis_max.  Needs innov; 0 or None: no gate."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
-        if innov is not None:
+        if innov is not None or gate is not None:   # (a gate without a stream is the library's to refuse)
             ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
             ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
-            ins = _innov_stream(innov, self.size, self.meas_dim, ticks)
-            _check(self._lib.target_batch_step_sequence_innov(self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1),
-                                                               hp, hs, meas.shape[0] if ticks != meas.shape[0] else 0,
-                                                               None if ps is None else C.byref(ps), C.byref(ins), int(use_graph)),
-                   "target_batch_step_sequence_innov")
+            ins = _innov_stream(innov, self.size, self.meas_dim, ticks) if innov is not None else None
+            args = (self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1), hp, hs,
+                    meas.shape[0] if ticks != meas.shape[0] else 0, None if ps is None else C.byref(ps), None if ins is None else C.byref(ins))
+            if gate is not None:
+                _check(self._lib.target_batch_step_sequence_gated(*args, float(gate), int(use_graph)), "target_batch_step_sequence_gated")
+            else:
+                _check(self._lib.target_batch_step_sequence_innov(*args, int(use_graph)), "target_batch_step_sequence_innov")
             return
         if poses is not None:
             ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
@@ -635,7 +640,7 @@ class TargetManager:
             "target_manager_intersect_sphere_converged_batch")
         return conv.astype(bool), pose, delta, filt
 
-    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None):
+    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None, gate=None):
         """meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order): `ticks` ticks of every batch -- ONE launch per
         tick for all of them where population_tick() holds, otherwise a launch per batch (recorded: one graph branch per
         batch) -- replayed from a recorded hipGraph (use_graph) or eagerly.  query =
@@ -644,7 +649,9 @@ class TargetManager:
         poses: one pose stream per batch (a tensor as for Batch.step_sequence, or None for a batch without one): every
         target's pose after every tick (target_manager_step_sequence_all_poses).
         innov: one innovation stream per batch ((nis, nu_or_None) as for Batch.step_sequence, or None for a batch without one):
-        every target's NIS and innovations of every tick (target_manager_step_sequence_all_innov)."""
+        every target's NIS and innovations of every tick (target_manager_step_sequence_all_innov).
+        gate: the NIS validation gate of every batch (a number) or one per batch (a list; 0 or None: that batch has none), as for
+        Batch.step_sequence (target_manager_step_sequence_all_gated)."""
         nb = len(meas)          # the library checks it against the number of batches
         ring = meas[0].shape[0] if nb else 0
         ticks = ring if n_ticks is None else int(n_ticks)      # n_ticks > ring: the tensors are rings (tick s reads s % ring)
@@ -664,6 +671,13 @@ class TargetManager:
             for i in range(nb):
                 specs[i].delta_dev = deltas[i].data_ptr()
                 specs[i].pose_dev = None if qposes is None or qposes[i] is None else qposes[i].data_ptr()
+        gates = None
+        if gate is not None:
+            per = list(gate) if isinstance(gate, (list, tuple)) else [gate] * nb
+            assert len(per) == nb, "one gate (or None) per batch"
+            gates = (C.c_double * max(nb, 1))(*[0.0 if g is None else float(g) for g in per])
+            if innov is None:
+                innov = [None] * nb
         if innov is not None:
             assert len(innov) == nb and (poses is None or len(poses) == nb), "one stream (or None) per batch"
             bs = self.batches()
@@ -675,6 +689,11 @@ class TargetManager:
                     pss[i] = _pose_stream(poses[i], size, ticks)
                 if innov[i] is not None:
                     iss[i] = _innov_stream(innov[i], size, bs[i].meas_dim if i < len(bs) else 3, ticks)
+            if gates is not None:
+                _check(self._lib.target_manager_step_sequence_all_gated(
+                    self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, gates, nb, 0 if query is None else 1,
+                    None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all_gated")
+                return
             _check(self._lib.target_manager_step_sequence_all_innov(
                 self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, nb, 0 if query is None else 1,
                 None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all_innov")
