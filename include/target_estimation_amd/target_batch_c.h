@@ -466,6 +466,64 @@ int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, do
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max, long n_batches,
                                            int query, const double* origin, double radius, int use_graph);
+/* ---- Re-acquisition of lost tracks inside the gated ticks.
+ * A bare validation gate locks out: a target whose measurements move off its prediction for good is rejected on every tick from
+ * then on.  The ..._reacquire calls are the ..._gated calls with a policy K = max_rejects on consecutive rejections, kept and
+ * acted on inside the launched ticks.
+ * Every slot has a REJECTION RUN c: one unsigned byte the library owns, 0 at creation.  It follows its target through erase
+ * compaction and capacity growth.  Only the calls of this section read or write it; every other call, the plain ..._gated ones
+ * included, leaves it alone.  A gated tick run through these calls with a policy treats a slot as follows.
+ *   no measurement on the tick (mask 0, or a predict-only tick)   c unchanged                          event byte 0
+ *   measured and accepted (0 <= nis <= nis_max, nis being the
+ *     double the stream stores -- the step's own decision)         c = 0                                event byte 0
+ *   measured and rejected, not re-initialised                     c' = min(c + 1, 127), stored c = c'  event byte c'
+ *   measured and rejected, re-initialised                         c' = min(c + 1, 127), stored c = 0   event byte 0x80 | c'
+ * A rejected slot is RE-INITIALISED iff K > 0 and c' >= K and the initial state formed from this tick's measurement is finite in
+ * every component -- for the angular models after the quaternion has become roll, pitch, yaw, so a NaN measurement or a zero
+ * quaternion never re-initialises.
+ * Re-initialisation: behind the tick's step the slot's record becomes, bit for bit, what the creation of a fresh target writes
+ * with p0 = this tick's measurement in the batch precision as the tick read it, v0 = a0 = 0, P0 = the slot's own initial
+ * covariance (the P0 that target_manager_get_model_matrices returns for it) and unwrap memory 0.  The target keeps its slot, its id,
+ * its class, its clock (advanced by dt like every other slot) and its measurement counter: the rejected tick did not increment
+ * it and the re-initialisation does not touch it.  State, covariance, unwrap memory and counters of every slot that is not
+ * re-initialised are those of the ..._gated call, bit for bit; K = 0 counts only.  Poses and the query in the same call see the
+ * re-initialised state.  The convergence gates' moving averages of a re-initialised target are not reset.
+ * event_dev (or NULL): after tick s, row b = (ring_ticks > 0 ? s % ring_ticks : s) at event_dev + b * tick_stride holds the event
+ * byte of every slot (column = slot); columns >= batch size are not written.
+ * Refused with a negative code, target_manager_last_error set and nothing launched: a policy without a gate (nis_max == 0);
+ * max_rejects outside 0..127; event rows with ld < batch size, tick_stride in (0, ld), a negative tick_stride or ring_ticks; a batch
+ * that keeps measured poses (target_manager_set_keep_measurement); a batch that no longer keeps its initial covariances (more than
+ * 4096 distinct ones); everything ..._gated refuses.  A NULL policy (or NULL per_batch_reacq) is exactly the ..._gated call.
+ * How: one small launch per batch behind each measured tick's step (behind the population launch where the manager's tick is
+ * one launch) and ahead of that tick's pose-writer and query launches, recorded with the tick; a recorded graph is keyed by the
+ * policy too.  It streams about 11 B per target and tick (NIS, mask byte, run, event) and touches records only in wavefronts
+ * that re-initialise.  A tile of a shared-axes batch that is re-initialised while flagged uniform is settled first; the batch
+ * stays in the form.
+ * A gate at a chi-square quantile re-initialises often on a stream that is not chi-square consistent:
+ * choose nis_max for the outliers to be kept out, K for the time a lost target may coast.
+ * Not served: target_batch_step_fused, the resident mode, the by-id / indexed launches, the one-target symbols, the Eigen
+ * facade; M-of-N logic other than K consecutive; a velocity from two measurements. */
+typedef struct target_reacquire_c {
+  int max_rejects;           /* K: 1..127 re-initialise on the K-th consecutive rejection; 0 count only */
+  unsigned char* event_dev;  /* device memory or NULL: per tick, row [ld] of the bytes defined above */
+  long ld;                   /* >= batch size (ignored when event_dev is NULL) */
+  long tick_stride;          /* bytes between rows of consecutive ticks (>= ld); 0 = every tick overwrites one row */
+  long ring_ticks;           /* as for the innovation stream */
+} target_reacquire_c;
+int target_batch_step_sequence_reacquire(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                         long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                         const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                         const target_reacquire_c* reacq, int use_graph);
+/* per_batch_reacq[i]: the policy of batch i (NULL: none for any batch); a batch without one passes max_rejects = -1 */
+int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks, double dt,
+                                               const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                               const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                                               const target_reacquire_c* per_batch_reacq, long n_batches,
+                                               int query, const double* origin, double radius, int use_graph);
+/* the rejection run of every slot, slot order, into runs_host [size]; synchronises */
+int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host);
+/* the rejection run of one target: >= 0, or negative: unknown id */
+int target_manager_get_rejection_run(target_manager_c* m, unsigned int id);
 /* Resident ("live") mode (target_batch_live_* above) for EVERY batch of a manager at once (BASELINE.json configs[3] / configs[4]: two motion models per GPU, whose per-GPU
  * share is launch-bound): one resident kernel per batch, each on a stream of its own so that they are on the device together;
  * per_batch[i] describes batch i's ring as for target_manager_step_sequence_all (ring_ticks > 0); with query != 0 the own-time

@@ -32,6 +32,12 @@ class InnovStream(C.Structure):
                 ("innov_tick_stride", C.c_long), ("ring_ticks", C.c_long)]
 
 
+class Reacquire(C.Structure):
+    """target_reacquire_c of target_batch_c.h: the re-acquisition policy of a gated call (max_rejects = -1 in a per-batch array:
+    no policy for that batch)"""
+    _fields_ = [("max_rejects", C.c_int), ("event_dev", C.c_void_p), ("ld", C.c_long), ("tick_stride", C.c_long), ("ring_ticks", C.c_long)]
+
+
 class StreamSpec(C.Structure):
     """target_stream_c of target_batch_c.h"""
     _fields_ = [("model", C.c_int), ("seed", C.c_ulonglong), ("first_target", C.c_long), ("dt", C.c_double),
@@ -165,6 +171,14 @@ SIGNATURES = {
     "target_manager_step_sequence_all_gated": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
                                                          C.POINTER(InnovStream), c_double_p, C.c_long, C.c_int, c_double_p, C.c_double,
                                                          C.c_int]),
+    "target_batch_step_sequence_reacquire": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                       C.c_long, C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.POINTER(Reacquire),
+                                                       C.c_int]),
+    "target_manager_step_sequence_all_reacquire": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
+                                                             C.POINTER(InnovStream), c_double_p, C.POINTER(Reacquire), C.c_long, C.c_int,
+                                                             c_double_p, C.c_double, C.c_int]),
+    "target_batch_rejection_runs": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "target_manager_get_rejection_run": (C.c_int, [C.c_void_p, C.c_uint]),
     "target_batch_live_start": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long,
                                           C.c_long, C.c_double]),
     "target_batch_live_set_pose_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -165,6 +165,67 @@ int Batch::add_class(const double* Q, const double* R) {
   return n_classes_++;
 }
 
+namespace {
+// batched erase: the rejection runs of the survivors that fill the holes (sources lie above every destination)
+__global__ void run_moves_kernel(unsigned char* run, const int* src, const int* dst, long m) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) run[dst[i]] = run[src[i]];
+}
+}  // namespace
+
+void Batch::run_move(long src, long dst) {
+  if (d_run_) TE_HIP_CHECK(hipMemcpyAsync(d_run_ + dst, d_run_ + src, 1, hipMemcpyDeviceToDevice, stream_));
+  p0idx_dirty_.mark(dst, 1);
+}
+
+void Batch::prepare_reacquire(const InnovStream& innov) {
+  if (!innov.reacq.on || n_ == 0) return;
+  const size_t nn = (size_t)ops_->L.n * (size_t)ops_->L.n;
+  if (!p0_kept_ || slot_p0_.size() < (size_t)n_) throw std::runtime_error("target_estimation_amd: re-acquisition: the batch does not keep its initial covariances");
+  const P0TableMirror::Upload u = p0tab_dev_.plan((long)p0_tab_.size());
+  if (u.grow) {   // recorded sequences hold the old table
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+    drop_graphs();
+    device_free(d_p0tab_); d_p0tab_ = nullptr;
+    TE_HIP_CHECK(hipMalloc((void**)&d_p0tab_, sizeof(double) * nn * (size_t)u.new_cap));
+  }
+  if (u.count > 0) {
+    std::vector<double> rows(nn * (size_t)u.count);
+    for (long r = 0; r < u.count; ++r) std::copy(p0_tab_[(size_t)(u.first + r)].begin(), p0_tab_[(size_t)(u.first + r)].end(), rows.begin() + (size_t)r * nn);
+    TE_HIP_CHECK(hipMemcpyAsync(d_p0tab_ + (size_t)u.first * nn, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, stream_));
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));   // (rows goes out of scope)
+  }
+  p0idx_dirty_.clip(n_);
+  if (!p0idx_dirty_.empty()) {
+    TE_HIP_CHECK(hipMemcpyAsync(d_p0idx_ + p0idx_dirty_.lo, slot_p0_.data() + p0idx_dirty_.lo, sizeof(int) * (size_t)(p0idx_dirty_.hi - p0idx_dirty_.lo),
+                                hipMemcpyHostToDevice, stream_));
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));   // (slot_p0_ may change before the copy has run)
+    p0idx_dirty_.clear();
+  }
+}
+
+void Batch::fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const {
+  if (!innov.reacq.on) return;
+  p.reacq = 1; p.reacq_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_event = innov.reacq.row(s_call);
+  p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+}
+
+void Batch::rejection_runs(unsigned char* out) {
+  flush();
+  if (n_ <= 0) return;
+  TE_HIP_CHECK(hipMemcpyAsync(out, d_run_, (size_t)n_, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+int Batch::rejection_run(long slot) {
+  flush();
+  if (slot < 0 || slot >= n_) throw std::runtime_error("target_estimation_amd: rejection_run: bad slot");
+  unsigned char c = 0;
+  TE_HIP_CHECK(hipMemcpyAsync(&c, d_run_ + slot, 1, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  return (int)c;
+}
+
 void Batch::launch_step(const StepParams& p, hipStream_t st, int meas_rows) {
   const bool gated_rows = keep_meas_ && p.gate > 0.0;
   if (gated_rows) {   // the measured-pose rows keep ACCEPTED measurements: the gate's mask comes from the writer, for the row kernel too
@@ -324,7 +385,7 @@ Batch::~Batch() {
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
   device_free(d_tile_blk_); device_free(d_tile_uni_);
   device_free(d_qr_); device_free(d_rec_); device_free(d_rec_alt_); device_free(d_tbase_); device_free(d_nmbase_); device_free(d_cls_);
-  device_free(d_has_eff_);
+  device_free(d_has_eff_); device_free(d_run_); device_free(d_p0idx_); device_free(d_p0tab_);
   device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
   device_free(d_dtper_); device_free(d_lastmeas_);
@@ -440,6 +501,17 @@ void Batch::reserve(long n) {
   // (the gate's mask row is written whole by every launch that reads it: no contents to carry over)
   device_free(d_has_eff_); d_has_eff_ = nullptr;
   TE_HIP_CHECK(hipMalloc((void**)&d_has_eff_, (size_t)want));
+  {   // the rejection runs follow their targets; the slot -> row index is uploaded again from the host's (prepare_reacquire)
+    unsigned char* run = nullptr;
+    TE_HIP_CHECK(hipMalloc((void**)&run, (size_t)want));
+    TE_HIP_CHECK(hipMemsetAsync(run, 0, (size_t)want, stream_));
+    if (d_run_ && n_ > 0) TE_HIP_CHECK(hipMemcpyAsync(run, d_run_, (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+    device_free(d_run_); d_run_ = run;
+    device_free(d_p0idx_); d_p0idx_ = nullptr;
+    TE_HIP_CHECK(hipMalloc((void**)&d_p0idx_, sizeof(int) * (size_t)want));
+    p0idx_dirty_.clear(); p0idx_dirty_.mark(0, want);
+  }
   device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;
   if (uniform_tiles_enabled()) {   // about 1.5 B per target (angular_rates: 96 + 4 B per 64)
     const size_t tiles = (size_t)(want / tpw);
@@ -545,6 +617,8 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
   a.t_base = d_tbase_; a.nm_base = d_nmbase_;
   ops_->init(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
+  TE_HIP_CHECK(hipMemsetAsync(d_run_ + first, 0, (size_t)count, stream_));   // a new target has no rejections behind it
+  p0idx_dirty_.mark(first, count);
   if (d_gate_ring_) { if (gate_cap_ < cap_) gate_reserve(gate_window_); gate_reset(first, count); }
   if (keep_meas_) {
     init_measured_rows_kernel<<<(unsigned)((count * 7 + 255) / 256), 256, 0, stream_>>>(d_lastmeas_, first, count);
@@ -579,6 +653,7 @@ unsigned Batch::erase_slot(long slot) {
     ops_->move_record(records(), last, slot, d_tbase_, d_nmbase_, d_cls_, stream_);
     TE_HIP_CHECK(hipGetLastError());
     gate_move(last, slot);
+    run_move(last, slot);
     if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_ + 7 * slot, d_lastmeas_ + 7 * last, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
     if (p0_kept_) slot_p0_[(size_t)slot] = slot_p0_[(size_t)last];
     moved = slot_ids_[(size_t)last];
@@ -616,7 +691,10 @@ void Batch::erase_slots(const int* slots, long k, std::vector<std::pair<unsigned
     TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + m, dst.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
     ops_->move_records(records(), d_idx_, d_idx_ + m, m, d_tbase_, d_nmbase_, d_cls_, stream_);
     TE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(run_moves_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream_, d_run_, d_idx_, d_idx_ + m, m);
+    TE_HIP_CHECK(hipGetLastError());
     for (long j = 0; j < m; ++j) {
+      p0idx_dirty_.mark(dst[(size_t)j], 1);
       gate_move(src[(size_t)j], dst[(size_t)j]);
       if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_ + 7 * (long)dst[(size_t)j], d_lastmeas_ + 7 * (long)src[(size_t)j], sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
       if (p0_kept_) slot_p0_[(size_t)dst[(size_t)j]] = slot_p0_[(size_t)src[(size_t)j]];
@@ -661,7 +739,7 @@ void Batch::check_pose_stream(const PoseStream& q) const {
 void Batch::check_innov_stream(const InnovStream& q) const {
   if (!(q.gate >= 0.0)) throw std::invalid_argument("target_estimation_amd: gate: nis_max must be 0 (no gate) or positive");
   if (q.gated() && !q.nis) throw std::invalid_argument("target_estimation_amd: gate: nis_max > 0 needs an innovation stream with a NIS row (it reports the decisions)");
-  if (!q.nis) return;
+  if (!q.nis) { check_reacquire(q.reacq, q.gate, n_, keep_meas_, p0_kept_); return; }
   const long m = ops_->L.m;
   if (q.ld < n_) throw std::invalid_argument("target_estimation_amd: innovation stream: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
   if (q.nis_tick_stride < 0 || (q.nis_tick_stride > 0 && q.nis_tick_stride < q.ld))
@@ -669,6 +747,7 @@ void Batch::check_innov_stream(const InnovStream& q) const {
   if (q.innov_tick_stride < 0 || (q.innov_tick_stride > 0 && q.innov_tick_stride < m * q.ld))
     throw std::invalid_argument("target_estimation_amd: innovation stream: innov_tick_stride must be 0 or >= " + std::to_string(m) + " * ld");
   if (q.ring < 0) throw std::invalid_argument("target_estimation_amd: innovation stream: negative ring_ticks");
+  check_reacquire(q.reacq, q.gate, n_, keep_meas_, p0_kept_);
 }
 
 void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
@@ -678,6 +757,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
   check_innov_stream(innov);
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
+  prepare_reacquire(innov);   // (before anything is enqueued or recorded)
   const size_t es = elem_size();
   auto params = [&](long s0) {
     const long s = ring_ticks > 0 ? s0 % ring_ticks : s0;   // the measurements form a ring of ring_ticks ticks
@@ -689,6 +769,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
     p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
     p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld; p.gate = innov.gate;
+    fill_reacquire(p, innov, s0);
     return p;
   };
   if (!use_graph) {
@@ -765,6 +846,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   double* pose_block = q.poses.block(s);   // (tick s of the call: the pose stream's own ring)
   double* nis_row = q.innov.nis_row(s);    // (... and the innovation stream's)
   double* innov_block = q.innov.innov_block(s);
+  const long s_call = s;
   if (q.ring_ticks > 0) s %= q.ring_ticks;
   const size_t es = elem_size();
   // (a tick with an innovation stream runs in place and without the fused query: the query follows as intersect_kernel)
@@ -773,6 +855,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   StepParams p = dense_params();
   p.pose = pose_block; p.pose_ld = q.poses.ld;
   p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
+  fill_reacquire(p, q.innov, s_call);
   p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
   p.meas_ld = q.ld;
   p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
@@ -800,6 +883,17 @@ bool Batch::population_ready() const {
 
 void Batch::enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& q, bool query, const double* origin, double radius) {
   if (n_ == 0) return;
+  if (q.innov.reacq.on && q.meas_base) {   // behind the population tick's step, ahead of the poses and the query
+    const long sm = q.ring_ticks > 0 ? s % q.ring_ticks : s;
+    StepParams p;
+    p.rec = records_as_stored(); p.n = n_;
+    p.meas = static_cast<const char*>(q.meas_base) + (size_t)(sm * q.tick_stride) * elem_size(); p.meas_ld = q.ld;
+    p.has_meas = q.has_base ? q.has_base + sm * q.has_stride : nullptr;
+    p.nis = q.innov.nis_row(s); p.gate = q.innov.gate;
+    if (uniform_tiles_enabled() && d_tile_uni_) { p.tile_blk = d_tile_blk_; p.tile_uni = d_tile_uni_; }
+    fill_reacquire(p, q.innov, s);
+    ops_->reacquire(make_reacquire_args(p), st);
+  }
   if (q.poses.dev) {
     OutArgs o;
     o.rec = records_as_stored(); o.idx = nullptr; o.n = n_; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "kf_ops.hpp"
+#include "reacquire_plan.hpp"
 
 namespace te {
 
@@ -44,12 +45,15 @@ struct InnovStream {
   // every measured slot, so the decision is 0 <= nis <= gate.  0: none.  Needs the NIS row.
   double gate = 0.0;
   bool gated() const { return gate > 0.0; }
+  // The re-acquisition policy that goes with the gate (reacquire_plan.hpp; target_reacquire_c): rejection runs, event rows,
+  // re-initialisation on the K-th consecutive rejection.  Off by default.
+  Reacquire reacq{};
   bool on() const { return nis != nullptr; }
   double* nis_row(long s) const { return nis ? nis + (ring > 0 ? s % ring : s) * nis_tick_stride : nullptr; }
   double* innov_block(long s) const { return (nis && innov) ? innov + (ring > 0 ? s % ring : s) * innov_tick_stride : nullptr; }
   bool same(const InnovStream& o) const {
     return nis == o.nis && innov == o.innov && ld == o.ld && nis_tick_stride == o.nis_tick_stride && innov_tick_stride == o.innov_tick_stride && ring == o.ring &&
-           gate == o.gate;   // (recorded graphs are keyed by the gate as well)
+           gate == o.gate && reacq.same(o.reacq);   // (recorded graphs are keyed by the gate and the re-acquisition policy as well)
   }
 };
 
@@ -152,7 +156,14 @@ class Batch {
   // ring >= 0): checked before a call enqueues anything
   void check_pose_stream(const PoseStream& poses) const;
   // the same for an innovation stream: ld >= size, nis_tick_stride 0 or >= ld, innov_tick_stride 0 or >= m ld, nothing negative
+  // ... and, with it, the gate and the re-acquisition policy it carries (reacquire_plan.hpp, check_reacquire)
   void check_innov_stream(const InnovStream& innov) const;
+  // Before a call with a re-acquisition policy enqueues or records anything: bring the device copies of the initial-covariance
+  // table and of the slot -> row index up to date (a table that had to grow drops the recorded sequences; dev_identity() shows it).
+  void prepare_reacquire(const InnovStream& innov);
+  // the rejection run of every slot (host array [size()]); synchronises
+  void rejection_runs(unsigned char* out);
+  int rejection_run(long slot);
   // RESIDENT ("live") mode for small batches: ONE launch stays on the device with the batch's state in registers and serves
   // tick after tick as the host posts them -- no per-tick dispatch (a dependent launch costs 1.5-2 us, more than the tick of a
   // 10^4-target batch itself).  Protocol:
@@ -267,9 +278,9 @@ class Batch {
   void account_sequence(long n_ticks, double dt, bool all_measured);
   // identity of everything a recorded launch sequence refers to
   // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
-  struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; };
-  // (the tile arrays are allocated and freed with the records: rec identifies them too)
-  DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_}; }
+  struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; const void* p0tab; };
+  // (the tile arrays, the rejection runs and the slot -> row index are allocated and freed with the records: rec identifies them too)
+  DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_, d_p0tab_}; }
   void prepare() { touch(); }
 
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121), optional: see measured_pose.hpp
@@ -352,6 +363,15 @@ class Batch {
   TClock* d_tbase_ = nullptr;
   int* d_nmbase_ = nullptr;
   unsigned char* d_has_eff_ = nullptr;   // [cap_] the effective mask of a gated tick whose layout has no gated kernel (StepParams::gate_row)
+  // Re-acquisition (kf_reacquire_impl.hpp): the rejection run of every slot -- library-owned, 0 at creation, follows its target
+  // through erase and growth, read and written by the calls with a policy only -- and the device copies of p0_tab_ / slot_p0_.
+  unsigned char* d_run_ = nullptr;       // [cap_], allocated with the records
+  int* d_p0idx_ = nullptr;               // [cap_], allocated with the records; current behind prepare_reacquire()
+  DirtySlots p0idx_dirty_;
+  double* d_p0tab_ = nullptr;            // [p0tab_dev_.cap][N*N]
+  P0TableMirror p0tab_dev_;
+  void run_move(long src, long dst);
+  void fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const;   // the policy's launch parameters of tick s_call of a call
   long cap_ = 0;  // slots
   long n_ = 0;
   std::vector<unsigned> slot_ids_;

@@ -78,7 +78,44 @@ struct StepParams {
   double gate = 0.0;
   unsigned char* gate_row = nullptr;
   int gate_by_writer = 0;
+  // Re-acquisition behind a gated dense single tick (ReacquireArgs below; kf_reacquire_impl.hpp): reacq = 1 puts one
+  // reacquire_kernel launch behind the tick's step and ahead of its pose writer.  It keeps every slot's rejection run in
+  // reacq_run [n], writes the tick's event bytes to reacq_event [>= n] (or null) and, with reacq_k > 0, re-initialises a slot
+  // from this tick's measurement on its reacq_k-th consecutive rejection, P0 = reacq_p0 + reacq_p0_idx[slot] * N*N.  Needs the
+  // gate; a tick without measurements launches nothing.
+  int reacq = 0;
+  int reacq_k = 0;
+  unsigned char* reacq_run = nullptr;
+  unsigned char* reacq_event = nullptr;
+  const double* reacq_p0 = nullptr;
+  const int* reacq_p0_idx = nullptr;
 };
+
+// The launch behind a gated tick that keeps the rejection runs and re-initialises lost targets (kf_reacquire_impl.hpp).
+struct ReacquireArgs {
+  char* rec;                       // the records the tick's step has just written
+  long n;
+  const void* meas;                // the tick's SoA [7][meas_ld] block in the batch precision (never null: no launch without one)
+  long meas_ld;
+  const unsigned char* has_meas;   // the tick's per-slot mask as the caller gave it, or null
+  const double* nis;               // the tick's NIS row [n], just written
+  double gate;
+  int k;                           // 0: count only
+  unsigned char* run;              // [n] rejection runs
+  unsigned char* event;            // [>= n] this tick's event bytes, or null
+  const double* p0_tab;            // [rows][N*N] initial covariances
+  const int* p0_idx;               // [n] row of every slot
+  double* tile_blk;                // the batch's uniform tiles (null: none)
+  int* tile_uni;
+};
+
+inline ReacquireArgs make_reacquire_args(const StepParams& p) {
+  ReacquireArgs a;
+  a.rec = p.rec_out ? p.rec_out : p.rec; a.n = p.n; a.meas = p.meas; a.meas_ld = p.meas_ld; a.has_meas = p.has_meas;
+  a.nis = p.nis; a.gate = p.gate; a.k = p.reacq_k; a.run = p.reacq_run; a.event = p.reacq_event;
+  a.p0_tab = p.reacq_p0; a.p0_idx = p.reacq_p0_idx; a.tile_blk = p.tile_blk; a.tile_uni = p.tile_uni;
+  return a;
+}
 
 struct Ops {
   LayoutInfo L;
@@ -105,6 +142,8 @@ struct Ops {
   // uniform tiles (L.lin_words > 0; null otherwise): write every flagged tile's block back into the linear P words of its n-bounded
   // lanes -- an exact copy; the caller clears the flags behind it
   void (*settle)(char* rec, long n, const double* tile_blk, const int* tile_uni, hipStream_t) = nullptr;
+  // reacquire_kernel (kf_reacquire_impl.hpp) behind a gated tick: rejection runs, event bytes, re-initialisation
+  void (*reacquire)(const ReacquireArgs&, hipStream_t) = nullptr;
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported

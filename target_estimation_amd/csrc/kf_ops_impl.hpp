@@ -44,6 +44,10 @@ void launch_sep_innov_step(const StepArgs<T>& a, unsigned blocks, unsigned threa
 template <class M, typename T, int LAYOUT>
 void launch_sep_gate_step(const StepArgs<T>& a, double gate, unsigned blocks, unsigned threads, hipStream_t s);
 
+// reacquire_kernel (kf_reacquire_impl.hpp), in kf_reacquire_{uv,ua,ar,av}.hip likewise: one instance per OpsImpl.
+template <class M, typename T, int G, int LAYOUT>
+void launch_reacquire(const ReacquireArgs& a, hipStream_t s);
+
 template <class M, typename T, int G, int LAYOUT = LAYOUT_FULL>
 struct OpsImpl {
   using C = Cfg<M, T, G, LAYOUT>;
@@ -165,6 +169,7 @@ struct OpsImpl {
       q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
       if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
       else launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
+      if (plan.reacquire_after_step) reacquire(make_reacquire_args(p), s);   // (p: the caller's mask and NIS row; gated ticks are single)
       if (plan.pose_writer_after_each_tick) write_pose_block(q, pose, s);
     }
   }
@@ -214,6 +219,10 @@ struct OpsImpl {
     hipLaunchKernelGGL((gate_mask_kernel<>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, (const double*)a.nis, a.has_meas, a.meas != nullptr ? 1 : 0,
                        a.n, gate, has_eff);
   }
+  static void reacquire(const ReacquireArgs& a, hipStream_t s) {
+    if (a.n <= 0 || !a.meas) return;
+    launch_reacquire<M, T, G, LAYOUT>(a, s);
+  }
   static void outputs_rows(const OutArgs& a, hipStream_t s) {
     if (a.n <= 0) return;
     hipLaunchKernelGGL((outputs_rows_kernel<M, T, G, LAYOUT>), dim3((unsigned)((a.n + kOutputsBlock - 1) / kOutputsBlock)), dim3(kOutputsBlock), 0, s, a);
@@ -238,7 +247,7 @@ struct OpsImpl {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
         C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov, &innov_gate,
-        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr};
+        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr, &reacquire};
     return &ops;
   }
 };

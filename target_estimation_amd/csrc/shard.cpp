@@ -467,6 +467,12 @@ long long Shard::numberMeasurements(unsigned id) {
   return 0;
 }
 
+int Shard::rejectionRun(unsigned id) {
+  Loc loc;
+  if (find(id, loc)) return batches_[(size_t)loc.batch]->rejection_run(loc.slot);
+  return -1;
+}
+
 // Node-tick sizes (a few to a thousand targets per call) are a LATENCY path: staging copies and separate launches cost more than
 // the step itself (40 targets: 22 us for the dense host path below, 78 us with the getters behind it).  They go through the
 // one-target queue instead -- host table look-up per id, one indexed launch at the next read, the queue behind the PCIe BAR and the
@@ -796,6 +802,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     if (query && batches_[b]->size() > 0 && !specs[b].delta_dev)
       throw std::runtime_error("target_estimation_amd: stepSequenceAll: query without a delta output");
     batches_[b]->prepare();   // queued one-target steps run first
+    batches_[b]->prepare_reacquire(specs[b].innov);   // (the device tables of a re-acquisition policy, before anything is recorded)
   }
   const double zero3[3] = {0, 0, 0};
   const double* org = origin ? origin : zero3;
@@ -832,7 +839,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
              x.innov.same(y.innov);
     };
     auto same_id = [](const Batch::DevIdentity& x, const Batch::DevIdentity& y) {
-      return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n && x.ops == y.ops;
+      return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n && x.ops == y.ops && x.p0tab == y.p0tab;
     };
     SeqGraph* hit = nullptr;
     for (auto& g : seq_graphs_) {

@@ -96,6 +96,7 @@ class Shard {
   bool time(unsigned id, double& t);
   int state(unsigned id, double* x, double* P);
   long long numberMeasurements(unsigned id);
+  int rejectionRun(unsigned id);   // the target's run of consecutive gate rejections (Batch::rejection_run), -1: unknown id
   double intersectTime(unsigned id, double t1, const double* origin, double radius);
   bool intersectPose(unsigned id, double t1, const double* origin, double radius, double* pose7, double* delta);
 

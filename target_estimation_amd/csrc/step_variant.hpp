@@ -101,6 +101,9 @@ struct StepPlan {
   // launch (gate_mask_kernel: has && nis <= gate from the NIS row just written), and the plain step kernel behind the two takes
   // that row as its has_meas: three launches per tick.
   bool gated = false;
+  // the request keeps rejection runs / re-acquires (P::reacq): one reacquire launch behind the step of the (gated, measured) tick
+  // and ahead of its pose writer
+  bool reacquire_after_step = false;
 };
 
 // The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
@@ -113,6 +116,13 @@ template <class P>
 constexpr double requested_gate(const P& p) {
   if constexpr (has_gate_member<P>::value) return (double)p.gate;
   else return 0.0;
+}
+template <class P, class = void> struct has_reacq_member : std::false_type {};
+template <class P> struct has_reacq_member<P, std::void_t<decltype(std::declval<const P&>().reacq)>> : std::true_type {};
+template <class P>
+constexpr bool requested_reacquire(const P& p) {
+  if constexpr (has_reacq_member<P>::value) return p.reacq != 0;
+  else return false;
 }
 template <class P>
 constexpr bool requested_gate_by_writer(const P& p) {
@@ -136,6 +146,16 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
   plan.gated = gate > 0.0;
   if (plan.gated && (!p.nis || p.idx || p.n_ticks > 1 || p.live_posted || p.o_pose))
     throw std::runtime_error("target_estimation_amd: the gate acts in dense single ticks with an innovation stream (its NIS row reports the decisions)");
+  // (a request type with P::reacq has P::reacq_k, the pointers P::reacq_run / reacq_p0 / reacq_p0_idx and P::meas as well)
+  if constexpr (has_reacq_member<P>::value) {
+    if (requested_reacquire(p)) {
+      if (!plan.gated) throw std::runtime_error("target_estimation_amd: re-acquisition needs the gate (nis_max > 0): it counts the gate's rejections");
+      if (p.reacq_k < 0 || p.reacq_k > 127) throw std::runtime_error("target_estimation_amd: re-acquisition: max_rejects must be 0..127");
+      if (!p.reacq_run || !p.reacq_p0 || !p.reacq_p0_idx)
+        throw std::runtime_error("target_estimation_amd: re-acquisition needs the batch's rejection runs and its table of initial covariances");
+      plan.reacquire_after_step = p.meas ? true : false;   // (a tick without measurements changes no run: no launch)
+    }
+  }
   // (Batch expands a shared-axes batch to the plain form before any of these: batch_store.cpp, demote_shared)
   if (t.shared && (p.live_posted || p.cls || p.n_ticks > 1))
     throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");

@@ -428,6 +428,10 @@ long long TargetManager::getNumberMeasurements(unsigned id) {
   return routeId(id, [&](Shard& s) { return s.numberMeasurements(id); });
 }
 
+int TargetManager::getRejectionRun(unsigned id) {
+  return routeId(id, [&](Shard& s) { return s.rejectionRun(id); });
+}
+
 // Each shard gets its ids in the caller's order (a repeated id stays two steps in a row) and decides the path for its own slice.
 long TargetManager::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas) {
   lock_guard<mutex> lg(target_lock_);

@@ -69,6 +69,7 @@ class TargetManager {
   bool getTargetTwist(unsigned id, double* twist6);         // :263-272
   bool getTargetAcceleration(unsigned id, double* acc6);    // :274-283
   long long getNumberMeasurements(unsigned id);             // :285-295
+  int getRejectionRun(unsigned id);   // consecutive gate rejections kept by the ..._reacquire calls; -1: unknown id
   // :120-124.  The reference publishes five channels per target through rt_logger (an external ROS package):
   // measurement (measured_pose_), pose (pose_internal_ = [xyz rpy]), twist, acceleration, covariance (the full P),
   // target_interface.cpp:32-40,50-55.  Equivalent observability without ROS: with a log directory set (setLogDirectory

@@ -94,6 +94,20 @@ te::InnovStream gated_stream(const target_innov_stream_c* p, double nis_max) {
   q.gate = nis_max > 0.0 ? nis_max : 0.0;
   return q;
 }
+// the same with the re-acquisition policy of a ..._reacquire call (NULL, or max_rejects < 0 in a per-batch array: none)
+te::InnovStream reacquire_stream(const target_innov_stream_c* p, double nis_max, const target_reacquire_c* r, bool per_batch) {
+  te::InnovStream q = gated_stream(p, nis_max);
+  if (!r || (per_batch && r->max_rejects < 0)) return q;
+  if (r->max_rejects < 0 || r->max_rejects > 127) throw std::invalid_argument("re-acquisition: max_rejects must be 0..127, got " + std::to_string(r->max_rejects));
+  if (!q.gated()) throw std::invalid_argument("re-acquisition: a policy needs the gate (nis_max > 0): it counts the gate's rejections");
+  q.reacq.on = true; q.reacq.k = r->max_rejects; q.reacq.event = r->event_dev;
+  if (r->event_dev) {
+    if (r->ld <= 0 || r->tick_stride < 0 || (r->tick_stride > 0 && r->tick_stride < r->ld) || r->ring_ticks < 0)
+      throw std::invalid_argument("re-acquisition: event rows need ld > 0, tick_stride 0 or >= ld, ring_ticks >= 0");
+    q.reacq.ld = r->ld; q.reacq.tick_stride = r->tick_stride; q.reacq.ring = r->ring_ticks;
+  }
+  return q;
+}
 }  // namespace
 
 extern "C" {
@@ -548,6 +562,55 @@ int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, do
     }
     M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
   });
+}
+
+// ---- re-acquisition of lost tracks inside the gated ticks
+int target_batch_step_sequence_reacquire(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
+                                         long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                         const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                         const target_reacquire_c* reacq, int use_graph) {
+  return guarded("target_batch_step_sequence_reacquire", [&] {
+    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
+    BatchLock lk(B(b));
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream);
+  });
+}
+
+int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks, double dt,
+                                               const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                               const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                                               const target_reacquire_c* per_batch_reacq, long n_batches,
+                                               int query, const double* origin, double radius, int use_graph) {
+  return guarded("target_manager_step_sequence_all_reacquire", [&] {
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    std::vector<te::InnovStream> innov(nb);
+    for (size_t i = 0; i < nb; ++i)   // (every gate and policy is looked at before anything else is)
+      innov[i] = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
+                                  per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+    }
+    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
+  });
+}
+
+int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host) {
+  return guarded("target_batch_rejection_runs", [&] {
+    BatchLock lk(B(b));
+    if (!runs_host) throw std::invalid_argument("runs_host must not be NULL");
+    B(b)->rejection_runs(runs_host);
+  });
+}
+
+int target_manager_get_rejection_run(target_manager_c* m, unsigned int id) {
+  int run = -1;
+  const int rc = guarded("target_manager_get_rejection_run", [&] { run = M(m)->getRejectionRun(id); });
+  return rc < 0 ? rc : run;
 }
 
 // ---- resident ("live") mode

@@ -83,6 +83,27 @@ def _innov_stream(innov, size, m, n_ticks):
     return s
 
 
+def _reacquire(policy, size, n_ticks):
+    """(K, events_or_None) -> capi.Reacquire.  events: uint8 CUDA tensor [blocks, ld] (or [ld]): one block, every tick overwrites
+    it; fewer blocks than ticks make a ring, as for the innovation stream.  None: no policy (max_rejects = -1)."""
+    import torch
+    r = capi.Reacquire()
+    if policy is None:
+        r.max_rejects = -1
+        return r
+    k, ev = policy
+    r.max_rejects = int(k)
+    if ev is not None:
+        assert ev.is_cuda and ev.dtype == torch.uint8, "reacquire: events is a uint8 CUDA tensor"
+        if ev.dim() == 1:
+            ev = ev.unsqueeze(0)
+        assert ev.dim() == 2 and ev.stride(1) == 1, "reacquire: events is [ticks_or_ring, ld] with unit stride along the slots"
+        r.event_dev, r.ld = ev.data_ptr(), ev.shape[1]
+        r.tick_stride = ev.stride(0) if ev.shape[0] > 1 else 0
+        r.ring_ticks = ev.shape[0] if ev.shape[0] < n_ticks else 0
+    return r
+
+
 class Batch:
     """All targets of one (model, Q, R) of a manager: the device-resident dense path."""
 
@@ -146,7 +167,14 @@ class Batch:
             hp = h.data_ptr()
         _check(self._lib.target_batch_step_host(self._h, float(dt), t.data_ptr(), t.stride(0), hp), "target_batch_step_host")
 
-    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None, gate=None):
+    def rejection_runs(self):
+        """The run of consecutive gate rejections of every slot (uint8, slot order), as the calls with reacquire= keep it
+        (target_batch_rejection_runs); synchronises."""
+        out = np.zeros(max(self.size, 1), dtype=np.uint8)
+        _check(self._lib.target_batch_rejection_runs(self._h, out.ctypes.data), "target_batch_rejection_runs")
+        return out[:self.size]
+
+    def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None, gate=None, reacquire=None):
         """meas: CUDA tensor [ticks, 7, ld]: one launch per tick, all enqueued by one C call.  n_ticks > ticks
         treats meas (and has_meas) as a ring: tick s reads entry s % ticks.  poses: float64 CUDA tensor
         [ticks_or_ring, 7, ld] (or [7, ld]) that receives every target's pose after every tick (column = slot;
@@ -155,20 +183,28 @@ class Batch:
         (target_batch_step_sequence_innov; -1 and zeros for a target without a measurement on the tick).  gate = nis_max: the
         NIS validation gate inside the ticks (target_batch_step_sequence_gated): a measurement with NIS > nis_max, or a NaN one,
         is not folded in -- the target is stepped as without a measurement -- and the stream still reports its NIS and nu, so the
-        decision is 0 <= nis <= nis_max.  Needs innov; 0 or None: no gate."""
+        decision is 0 <= nis <= nis_max.  Needs innov; 0 or None: no gate.  reacquire = (K, events_or_None): re-acquisition
+        inside the gated ticks (target_batch_step_sequence_reacquire): every slot's run of consecutive rejections is kept on the
+        device (rejection_runs()), and on its K-th consecutive rejection a target is re-initialised from that tick's
+        measurement with its own initial covariance (K = 0: count only); events: uint8 CUDA tensor [ticks_or_ring, ld] (or
+        [ld]) that receives every tick's event bytes (0, the run c', or 0x80 | c' for a re-initialisation).  Needs gate."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
-        if innov is not None or gate is not None:   # (a gate without a stream is the library's to refuse)
+        if innov is not None or gate is not None or reacquire is not None:   # (a gate without a stream, a policy without a gate: the library's to refuse)
             ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
             ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
             ins = _innov_stream(innov, self.size, self.meas_dim, ticks) if innov is not None else None
             args = (self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1), hp, hs,
                     meas.shape[0] if ticks != meas.shape[0] else 0, None if ps is None else C.byref(ps), None if ins is None else C.byref(ins))
-            if gate is not None:
+            if reacquire is not None:
+                rq = _reacquire(reacquire, self.size, ticks)
+                _check(self._lib.target_batch_step_sequence_reacquire(*args, 0.0 if gate is None else float(gate), C.byref(rq), int(use_graph)),
+                       "target_batch_step_sequence_reacquire")
+            elif gate is not None:
                 _check(self._lib.target_batch_step_sequence_gated(*args, float(gate), int(use_graph)), "target_batch_step_sequence_gated")
             else:
                 _check(self._lib.target_batch_step_sequence_innov(*args, int(use_graph)), "target_batch_step_sequence_innov")
@@ -476,6 +512,11 @@ class TargetManager:
     def getNumberMeasurements(self, id):
         return self._lib.target_manager_get_n_measurements(self._h, int(id))
 
+    def getRejectionRun(self, id):
+        """The target's run of consecutive gate rejections (step_sequence(..., reacquire=)), or None for an unknown id."""
+        rc = self._lib.target_manager_get_rejection_run(self._h, int(id))
+        return rc if rc >= 0 else None
+
     def getAvailableTargets(self):
         n = self._lib.target_manager_size(self._h)
         out = np.empty(max(n, 1), dtype=np.uint32)
@@ -640,7 +681,8 @@ class TargetManager:
             "target_manager_intersect_sphere_converged_batch")
         return conv.astype(bool), pose, delta, filt
 
-    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None, gate=None):
+    def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None, gate=None,
+                          reacquire=None):
         """meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order): `ticks` ticks of every batch -- ONE launch per
         tick for all of them where population_tick() holds, otherwise a launch per batch (recorded: one graph branch per
         batch) -- replayed from a recorded hipGraph (use_graph) or eagerly.  query =
@@ -651,7 +693,9 @@ class TargetManager:
         innov: one innovation stream per batch ((nis, nu_or_None) as for Batch.step_sequence, or None for a batch without one):
         every target's NIS and innovations of every tick (target_manager_step_sequence_all_innov).
         gate: the NIS validation gate of every batch (a number) or one per batch (a list; 0 or None: that batch has none), as for
-        Batch.step_sequence (target_manager_step_sequence_all_gated)."""
+        Batch.step_sequence (target_manager_step_sequence_all_gated).
+        reacquire: the re-acquisition policy (K, events_or_None) of every batch (one tuple) or one per batch (a list; None: that
+        batch has none), as for Batch.step_sequence (target_manager_step_sequence_all_reacquire)."""
         nb = len(meas)          # the library checks it against the number of batches
         ring = meas[0].shape[0] if nb else 0
         ticks = ring if n_ticks is None else int(n_ticks)      # n_ticks > ring: the tensors are rings (tick s reads s % ring)
@@ -672,6 +716,8 @@ class TargetManager:
                 specs[i].delta_dev = deltas[i].data_ptr()
                 specs[i].pose_dev = None if qposes is None or qposes[i] is None else qposes[i].data_ptr()
         gates = None
+        if reacquire is not None and gate is None:
+            gate = 0.0   # (a policy without a gate is the library's to refuse)
         if gate is not None:
             per = list(gate) if isinstance(gate, (list, tuple)) else [gate] * nb
             assert len(per) == nb, "one gate (or None) per batch"
@@ -689,6 +735,16 @@ class TargetManager:
                     pss[i] = _pose_stream(poses[i], size, ticks)
                 if innov[i] is not None:
                     iss[i] = _innov_stream(innov[i], size, bs[i].meas_dim if i < len(bs) else 3, ticks)
+            if reacquire is not None:
+                per = list(reacquire) if isinstance(reacquire, list) else [reacquire] * nb
+                assert len(per) == nb, "one re-acquisition policy (or None) per batch"
+                rqs = (capi.Reacquire * max(nb, 1))()
+                for i in range(nb):
+                    rqs[i] = _reacquire(per[i], bs[i].size if i < len(bs) else 0, ticks)
+                _check(self._lib.target_manager_step_sequence_all_reacquire(
+                    self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, gates, rqs, nb, 0 if query is None else 1,
+                    None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all_reacquire")
+                return
             if gates is not None:
                 _check(self._lib.target_manager_step_sequence_all_gated(
                     self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, gates, nb, 0 if query is None else 1,
