@@ -415,8 +415,8 @@ int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, do
  * target_manager_last_error set, and nothing is launched.  A NULL `innov` (or per_batch_innov), or a NULL nis_dev, gives exactly
  * the ..._poses call.  target_batch_algorithmic_bytes keeps reporting the plain tick: the stream adds 8 B per target and tick
  * for NIS, plus 8 * m B for the innovations.
- * Not served (no innovation stream there): target_batch_step_fused, the resident mode (target_batch_live_*), the by-id / indexed
- * launches, the one-target symbols and the Eigen facade. */
+ * Not served (no innovation stream there): target_batch_step_fused, the resident mode (target_batch_live_*); by id only NIS is
+ * reported (target_manager_update_meas_batch_gated below), not nu. */
 typedef struct target_innov_stream_c {
   double* nis_dev;          /* device memory; NULL = no innovation stream for this batch */
   double* innov_dev;        /* device memory or NULL: NIS only */
@@ -457,7 +457,8 @@ int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, do
  * mask from the NIS row just written, into a row the library owns, and the plain step takes that row -- three launches per tick,
  * one more than ..._innov.  Poses and the fused query in the same
  * call, use_graph (a recorded graph is keyed by the gate too) and every other argument: as for ..._innov.
- * Not served: target_batch_step_fused, the resident mode, the by-id / indexed launches, the one-target symbols, the Eigen facade. */
+ * Not served: target_batch_step_fused, the resident mode.  The by-id / indexed launches, the one-target symbols and the Eigen
+ * facade are gated through the sticky policy of target_manager_set_update_gate below. */
 int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                      const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max, int use_graph);
@@ -501,8 +502,9 @@ int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, do
  * stays in the form.
  * A gate at a chi-square quantile re-initialises often on a stream that is not chi-square consistent:
  * choose nis_max for the outliers to be kept out, K for the time a lost target may coast.
- * Not served: target_batch_step_fused, the resident mode, the by-id / indexed launches, the one-target symbols, the Eigen
- * facade; M-of-N logic other than K consecutive; a velocity from two measurements. */
+ * Not served: target_batch_step_fused, the resident mode; M-of-N logic other than K consecutive; a velocity from two
+ * measurements.  The by-id / indexed launches, the one-target symbols and the Eigen facade re-acquire through the sticky policy
+ * of target_manager_set_update_gate below. */
 typedef struct target_reacquire_c {
   int max_rejects;           /* K: 1..127 re-initialise on the K-th consecutive rejection; 0 count only */
   unsigned char* event_dev;  /* device memory or NULL: per tick, row [ld] of the bytes defined above */
@@ -524,6 +526,48 @@ int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks
 int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host);
 /* the rejection run of one target: >= 0, or negative: unknown id */
 int target_manager_get_rejection_run(target_manager_c* m, unsigned int id);
+/* ---- The gate and the re-acquisition on the by-id and one-target paths: a sticky update policy.
+ * The calls above serve callers whose loop is built around device-resident buffers.  A caller of the reference's own symbols --
+ * target_manager_update_meas per target, or the two-call node tick target_manager_update_meas_batch + ..._get_est_batch of
+ * examples/node_tick.c, or target_ingest_tick -- sets a POLICY once and keeps its loop: per manager and per model, off by
+ * default, applied from then on to every call that steps targets BY ID WITH A MEASUREMENT: target_manager_update_meas,
+ * target_manager_update_meas_batch, ..._update_meas_batch_gated below, target_ingest_tick and the Eigen facade's update.
+ * target_batch_step*, the step_sequence* calls, target_batch_step_fused, the resident mode and target_manager_update_all keep
+ * their own arguments and ignore the policy; a by-id step without a measurement is the plain predict-only step.
+ * Per entry the semantics are exactly those of the dense calls: the decision is (double)NIS <= nis_max (a NaN rejects); an
+ * accepted entry leaves in the bits of the ungated by-id step with a measurement, a rejected one in the bits of the ungated
+ * by-id step without (state, covariance, unwrap memory, measurement counter); the clock advances by the entry's own dt either
+ * way.  With max_rejects >= 0 the slot's rejection run -- the byte of the ..._reacquire section -- follows that section's table,
+ * and a re-initialised slot's record is bit for bit the record a fresh target gets from this entry's measurement (v0 = a0 = 0,
+ * the slot's own P0, unwrap memory 0; clock and counter untouched).  An id named twice in one call is two consecutive gated
+ * steps; queued one-target steps with different dt are each gated with their own dt.
+ * How: ONE launch per flush / indexed call, as without a policy -- the gated indexed step kernel carries the rejection-run
+ * policy in its tail and still fills the getter table; a call that names exactly one batch's ids in slot order runs the dense
+ * gated kernel and the re-acquisition launch of the sections above.
+ * type: a model type (0 angular_rates, 1 angular_velocities, 2 uniform_acceleration, 3 uniform_velocity), or -1 = every model.
+ * nis_max: 0 = no gate (default), > 0 (+inf included) = gated.  max_rejects: -1 = gate only (rejection runs untouched), 0 = count
+ * only, 1..127 = re-initialise on the K-th consecutive rejection.  Flushes every queued one-target step first.  Applies to
+ * batches created later too.
+ * Refused with a negative code, target_manager_last_error set and NOTHING STEPPED IN THE WHOLE CALL: nis_max < 0 or NaN;
+ * max_rejects outside -1..127; max_rejects >= 0 with nis_max == 0; a by-id update with measurements under a policy that touches a
+ * batch with no gated indexed kernel (the dense layouts of coupled Q / R / P0 or an explicit lanes_per_target outside 201 / 301,
+ * the symmetric-packed EKF, several (Q, R) classes, a batch that keeps measured-pose rows); for max_rejects >= 0, a batch that no
+ * longer keeps its initial covariances.  target_manager_update_gate_served asks up front.  The void one-target symbol reports
+ * through target_manager_last_error, as its other failures do.
+ * Not served: the innovations nu by id (NIS only); per-class, dense-layout and keep-measurement batches by id;
+ * target_batch_step_fused; the resident mode. */
+int  target_manager_set_update_gate(target_manager_c* m, int type, double nis_max, int max_rejects);
+int  target_manager_get_update_gate(target_manager_c* m, int type, double* nis_max, int* max_rejects);
+/* 1 if by-id updates of this model's batch would be served under a policy, 0 if not (see "refused"), -1 unknown */
+int  target_manager_update_gate_served(target_manager_c* m, int type);
+/* target_manager_update_meas_batch under the manager's policy, reporting per ENTRY i (caller's order):
+ * nis_out[i] (or NULL): NIS of the measurement; -1 = no measurement on this entry (or no policy for its model: nothing was
+ *   judged); -2 = unknown id (not stepped)
+ * event_out[i] (or NULL): the event byte of target_reacquire_c's table (0 when max_rejects == -1)
+ * Returns the number of targets stepped, after the outputs are in the caller's arrays. */
+long target_manager_update_meas_batch_gated(target_manager_c* m, const unsigned int* ids, long n, double dt,
+                                            const double* meas, const unsigned char* has_meas,
+                                            double* nis_out, unsigned char* event_out);
 /* Resident ("live") mode (target_batch_live_* above) for EVERY batch of a manager at once (BASELINE.json configs[3] / configs[4]: two motion models per GPU, whose per-GPU
  * share is launch-bound): one resident kernel per batch, each on a stream of its own so that they are on the device together;
  * per_batch[i] describes batch i's ring as for target_manager_step_sequence_all (ring_ticks > 0); with query != 0 the own-time

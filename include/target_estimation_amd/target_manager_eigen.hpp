@@ -149,6 +149,10 @@ class TargetManager {
     return target_manager_update_meas_batch(m_, &id, 1, dt, nullptr, nullptr) == 1;
   }
   virtual void update(const double& dt) { target_manager_update_all(m_, dt); }          // :120
+  // The sticky update policy of the by-id paths (target_batch_c.h, target_manager_set_update_gate): update(id, dt, meas) then
+  // gates on NIS <= nis_max and, with max_rejects >= 0, keeps the rejection runs and re-acquires.  type: (int)target_t or -1 = all.
+  bool setUpdateGate(int type, double nis_max, int max_rejects = -1) { return target_manager_set_update_gate(m_, type, nis_max, max_rejects) == 0; }
+  bool getUpdateGate(int type, double& nis_max, int& max_rejects) { return target_manager_get_update_gate(m_, type, &nis_max, &max_rejects) == 0; }
   bool erase(const unsigned int& id) { return target_manager_erase(m_, id) == 1; }     // :127
   TargetHandle::Ptr getTarget(const unsigned int& id) {                                 // :134
     unsigned char found = 0;

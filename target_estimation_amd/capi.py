@@ -179,6 +179,11 @@ SIGNATURES = {
                                                              c_double_p, C.c_double, C.c_int]),
     "target_batch_rejection_runs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "target_manager_get_rejection_run": (C.c_int, [C.c_void_p, C.c_uint]),
+    "target_manager_set_update_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    "target_manager_get_update_gate": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.POINTER(C.c_int)]),
+    "target_manager_update_gate_served": (C.c_int, [C.c_void_p, C.c_int]),
+    "target_manager_update_meas_batch_gated": (C.c_long, [C.c_void_p, c_uint_p, C.c_long, C.c_double, c_double_p, c_ubyte_p, c_double_p,
+                                                         c_ubyte_p]),
     "target_batch_live_start": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long,
                                           C.c_long, C.c_double]),
     "target_batch_live_set_pose_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

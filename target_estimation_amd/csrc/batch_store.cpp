@@ -180,6 +180,10 @@ void Batch::run_move(long src, long dst) {
 
 void Batch::prepare_reacquire(const InnovStream& innov) {
   if (!innov.reacq.on || n_ == 0) return;
+  prepare_p0_tables();
+}
+
+void Batch::prepare_p0_tables() {
   const size_t nn = (size_t)ops_->L.n * (size_t)ops_->L.n;
   if (!p0_kept_ || slot_p0_.size() < (size_t)n_) throw std::runtime_error("target_estimation_amd: re-acquisition: the batch does not keep its initial covariances");
   const P0TableMirror::Upload u = p0tab_dev_.plan((long)p0_tab_.size());
@@ -208,6 +212,44 @@ void Batch::fill_reacquire(StepParams& p, const InnovStream& innov, long s_call)
   if (!innov.reacq.on) return;
   p.reacq = 1; p.reacq_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_event = innov.reacq.row(s_call);
   p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+}
+
+void Batch::set_update_gate(const UpdateGate& g) {
+  check_update_gate(g.nis_max, g.max_rejects);
+  touch();   // what is queued was queued under the policy it runs under
+  pol_ = g;
+}
+
+const char* Batch::update_gate_refusal(const UpdateGate& g) const {
+  if (!g.on()) return nullptr;
+  if (ops_->L.layout != LAYOUT_SEPARABLE && ops_->L.layout != LAYOUT_SEPARABLE_PACKED)
+    return "target_estimation_amd: update gate: not served by id for a batch of the dense layouts (coupled matrices): no gated indexed kernel";
+  if (n_classes_ > 1) return "target_estimation_amd: update gate: not served by id for a batch with several (Q, R) classes: no gated indexed kernel";
+  if (keep_meas_) return "target_estimation_amd: update gate: not served by id for a batch that keeps measured poses (set_keep_measurement)";
+  if (g.max_rejects >= 0 && !p0_kept_) return "target_estimation_amd: update gate: max_rejects >= 0: the batch no longer keeps its initial covariances";
+  return nullptr;
+}
+
+void Batch::pol_reserve(long k) {
+  if (k <= pol_cap_) return;
+  const long want = (std::max<long>(std::max<long>(k, 64), pol_cap_ * 2) + 15) / 16 * 16;
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (h_pol_) (void)hipHostFree(h_pol_);
+  h_pol_ = nullptr; d_pol_ = nullptr; pol_cap_ = 0;
+  TE_HIP_CHECK(hipHostMalloc((void**)&h_pol_, (size_t)want * (sizeof(double) + 1) + 64, hipHostMallocMapped | hipHostMallocCoherent));
+  TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d_pol_, h_pol_, 0));
+  pol_cap_ = want;
+}
+
+void Batch::fill_update_gate(StepParams& p, long k, double* nis_dev, unsigned char* event_dev) {
+  if (const char* why = update_gate_refusal()) throw std::runtime_error(why);
+  if (!nis_dev) { pol_reserve(k); nis_dev = pol_nis_dev(); event_dev = pol_event_dev(); }
+  p.gate = pol_.nis_max; p.gate_id = 1; p.gate_id_k = pol_.max_rejects;
+  p.nis = nis_dev; p.gate_id_event = event_dev;
+  if (pol_.max_rejects >= 0) {
+    prepare_p0_tables();
+    p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+  }
 }
 
 void Batch::rejection_runs(unsigned char* out) {
@@ -390,6 +432,7 @@ Batch::~Batch() {
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
   device_free(d_dtper_); device_free(d_lastmeas_);
   if (h_pin_) (void)hipHostFree(h_pin_);
+  if (h_pol_) (void)hipHostFree(h_pol_);
   device_free(bar_pin_);
   if (h_cache_) (void)hipHostFree(h_cache_);
   device_free(d_state_scratch_);
@@ -1155,9 +1198,15 @@ long Batch::live_stop() {
   return (long)mn;
 }
 
-void Batch::step_indexed(const int* slots, long n, double dt, const double* meas_aos, const unsigned char* has) {
+void Batch::step_indexed(const int* slots, long n, double dt, const double* meas_aos, const unsigned char* has, double* nis_out,
+                         unsigned char* event_out) {
   touch();
   if (n <= 0) return;
+  const bool pol = pol_.on() && meas_aos != nullptr;
+  if (!pol) {   // (the plain kernels report nothing: no measurement was judged)
+    if (nis_out) std::fill(nis_out, nis_out + n, -1.0);
+    if (event_out) std::fill(event_out, event_out + n, (unsigned char)0);
+  }
   stage_reserve(n);
   upload_slots(slots, n);
   if (meas_aos) {
@@ -1168,17 +1217,24 @@ void Batch::step_indexed(const int* slots, long n, double dt, const double* meas
   StepParams p = base_params();
   p.n = n; p.idx = d_idx_; p.meas = meas_aos ? d_meas_ : nullptr; p.meas_ld = n;
   p.has_meas = (meas_aos && has) ? d_mask_ : nullptr; p.dt = dt;
+  if (pol) fill_update_gate(p, n);
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));  // caller's host arrays may be reused after return
+  if (pol) {
+    if (nis_out) std::copy(pol_nis_host(), pol_nis_host() + n, nis_out);
+    if (event_out) std::copy(pol_event_host(), pol_event_host() + n, event_out);
+  }
 }
 
-void Batch::step_indexed_dev(const int* idx_dev, long n, double dt, const void* meas_soa_dev, long ld, const unsigned char* has_dev) {
+void Batch::step_indexed_dev(const int* idx_dev, long n, double dt, const void* meas_soa_dev, long ld, const unsigned char* has_dev,
+                             double* nis_dev, unsigned char* event_dev) {
   touch();
   if (n <= 0) return;
   StepParams p = base_params();
   p.n = n; p.idx = idx_dev; p.meas = meas_soa_dev; p.meas_ld = ld;
   p.has_meas = meas_soa_dev ? has_dev : nullptr; p.dt = dt;
+  if (pol_.on() && meas_soa_dev) fill_update_gate(p, n, nis_dev, event_dev);
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
@@ -1193,18 +1249,40 @@ void Batch::outputs_indexed_dev(const int* idx_dev, long n, double* pose_dev, do
   TE_HIP_CHECK(hipGetLastError());
 }
 
-void Batch::step_dense_host(double dt, const double* meas_aos, const unsigned char* has) {
+void Batch::step_dense_host(double dt, const double* meas_aos, const unsigned char* has, double* nis_out, unsigned char* event_out) {
   touch();   // before the staging buffers are filled: a pending flush uses them too
   if (n_ == 0) return;
+  const bool pol = pol_.on() && meas_aos != nullptr;
+  if (!pol) {
+    if (nis_out) std::fill(nis_out, nis_out + n_, -1.0);
+    if (event_out) std::fill(event_out, event_out + n_, (unsigned char)0);
+  } else if (const char* why = update_gate_refusal()) {
+    throw std::runtime_error(why);
+  }
   stage_reserve(n_);
   if (meas_aos) {
     TE_HIP_CHECK(hipMemcpyAsync(d_aos_, meas_aos, sizeof(double) * 7 * n_, hipMemcpyHostToDevice, stream_));
     ops_->pack_meas(d_aos_, n_, d_meas_, n_, stream_);
   }
   if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_, has, (size_t)n_, hipMemcpyHostToDevice, stream_));
-  step_dense(dt, meas_aos ? d_meas_ : nullptr, n_, (meas_aos && has) ? d_mask_ : nullptr);
+  if (pol) {
+    // the whole batch in slot order under the policy: the dense gated kernel and, with runs, reacquire_kernel (one tick of
+    // step_sequence with the policy as its stream), the NIS row and the event row by slot = by entry in the batch's own rows
+    pol_reserve(n_);
+    InnovStream is;
+    is.nis = pol_nis_dev(); is.ld = n_; is.gate = pol_.nis_max;
+    if (pol_.max_rejects >= 0) { is.reacq.on = true; is.reacq.k = pol_.max_rejects; is.reacq.event = pol_event_dev(); is.reacq.ld = n_; }
+    else std::fill(pol_event_host(), pol_event_host() + n_, (unsigned char)0);
+    step_sequence(1, dt, d_meas_, 0, n_, has ? d_mask_ : nullptr, 0, 0, 0, PoseStream{}, is);
+  } else {
+    step_dense(dt, meas_aos ? d_meas_ : nullptr, n_, (meas_aos && has) ? d_mask_ : nullptr);
+  }
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));  // caller's host arrays may be reused after return
+  if (pol) {
+    if (nis_out) std::copy(pol_nis_host(), pol_nis_host() + n_, nis_out);
+    if (event_out) std::copy(pol_event_host(), pol_event_host() + n_, event_out);
+  }
 }
 
 void Batch::step_dense_host_soa(double dt, const void* meas_soa, long ld_host, const unsigned char* has) {
@@ -1227,11 +1305,11 @@ void Batch::step_dense_host_soa(double dt, const void* meas_soa, long ld_host, c
   TE_HIP_CHECK(hipStreamSynchronize(stream_));  // caller's host arrays may be reused after return
 }
 
-void Batch::step_one(long slot, double dt, const double* meas7) {
+void Batch::step_one(long slot, double dt, const double* meas7, long out_pos) {
   if (pending_mark_.size() < (size_t)n_) pending_mark_.resize((size_t)n_, 0);
   if (pending_mark_[(size_t)slot]) flush();   // second step of the same target: keep the caller's order
   Pending p;
-  p.slot = (int)slot; p.has = meas7 ? 1 : 0; p.dt = dt;
+  p.slot = (int)slot; p.has = meas7 ? 1 : 0; p.dt = dt; p.out = out_pos;
   for (int c = 0; c < 7; ++c) p.meas[c] = meas7 ? meas7[c] : 0.0;
   pending_.push_back(p);
   pending_mark_[(size_t)slot] = 1;
@@ -1312,6 +1390,11 @@ void Batch::flush() {
   double* h_dt = reinterpret_cast<double*>(hq + off_dt);
   unsigned char* h_has = reinterpret_cast<unsigned char*>(hq + off_has);
   bool all_has = true, any_has = false;
+  std::vector<long> outs;   // the entries' positions in the gate sink
+  if (sink_nis_ || sink_event_) {
+    outs.resize((size_t)k);
+    for (long j = 0; j < k; ++j) outs[(size_t)j] = pending_[(size_t)j].out;
+  }
   for (long j = 0; j < k; ++j) {
     const Pending& p = pending_[(size_t)j];
     h_idx[j] = p.slot; h_dt[j] = p.dt; h_has[j] = p.has;
@@ -1329,6 +1412,10 @@ void Batch::flush() {
   p.meas = any_has ? dq + off_meas : nullptr; p.meas_ld = k;
   p.has_meas = (any_has && !all_has) ? reinterpret_cast<const unsigned char*>(dq + off_has) : nullptr;
   p.dt_per = reinterpret_cast<const double*>(dq + off_dt); p.dt = 0.0;
+  // the update policy: the gated indexed kernel in place of the plain one, still one launch (each entry gated with its own dt);
+  // its NIS row and event row are host-mapped rows of their own, not part of the (possibly write-combined) queue block
+  const bool pol = pol_.on() && any_has;
+  if (pol) fill_update_gate(p, k);
   // With a current getter table the flush reports its own completion through a flag in host-mapped memory and the host
   // spins on it instead of synchronising the stream (tools/launch_latency.hip: the runtime's completion path costs 4 us more
   // than a PCIe write).  Up to one wavefront of queued targets the step kernel itself writes the table rows and the flag --
@@ -1368,6 +1455,11 @@ void Batch::flush() {
   // the pinned block is rewritten by the next flush, and the getters read the table right after this call
   if (seq != 0) wait_done(seq);
   else TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  for (size_t j = 0; j < outs.size(); ++j) {
+    if (outs[j] < 0) continue;
+    if (sink_nis_) sink_nis_[outs[j]] = pol ? pol_nis_host()[j] : -1.0;
+    if (sink_event_) sink_event_[outs[j]] = pol ? pol_event_host()[j] : (unsigned char)0;
+  }
 }
 
 void Batch::wait_done(int seq) {

@@ -200,21 +200,41 @@ class Batch {
   }
   bool live_pose_output_set() const { return live_.pose_out != nullptr; }
   bool live_running() const { return live_.active && __atomic_load_n(live_.h_done + 2, __ATOMIC_ACQUIRE) == 0; }   // the relay has not left (its last store)
+  // THE UPDATE POLICY OF THE BY-ID PATHS (UpdateGate, reacquire_plan.hpp; target_manager_set_update_gate).  While it is on, every
+  // by-id step WITH measurements -- step_indexed, step_indexed_dev, the one-target queue (step_one / flush), step_dense_host -- is
+  // gated and, with max_rejects >= 0, keeps the rejection runs and re-acquires, with the semantics of the dense calls
+  // (InnovStream::gate / reacq): the indexed ones by ONE launch of the gated indexed kernel (kf_step_sep_gate_indexed_kernel; the
+  // flush keeps its fused getter-table form), step_dense_host by the dense gated kernel and reacquire_kernel.  NIS and event bytes
+  // come back by entry: nis -1 = no measurement on the entry, event as target_reacquire_c's table (0 without runs).  The rows the
+  // kernels write live in host-mapped memory owned by the batch.  step_dense, step_sequence, step_fused and the resident mode
+  // ignore the policy.  update_gate_refusal(): why this batch cannot serve a policy (no gated indexed kernel: the dense layouts,
+  // several (Q, R) classes, measured-pose rows; with runs, initial covariances no longer kept), or null.
+  void set_update_gate(const UpdateGate& g);   // flushes the queued one-target steps first
+  const UpdateGate& update_gate() const { return pol_; }
+  const char* update_gate_refusal(const UpdateGate& g) const;
+  const char* update_gate_refusal() const { return update_gate_refusal(pol_); }
+  // where the queued one-target steps that carry an output position (step_one, out_pos) report when they are flushed; the caller
+  // clears it (nulls) before the arrays go away
+  void set_gate_sink(double* nis, unsigned char* event) { sink_nis_ = nis; sink_event_ = event; }
   // One tick over the listed slots, host inputs (meas rows follow the order of `slots`).
-  void step_indexed(const int* slots, long n, double dt, const double* meas_aos, const unsigned char* has);
+  // nis_out / event_out [n] (or null): the policy's outputs by entry
+  void step_indexed(const int* slots, long n, double dt, const double* meas_aos, const unsigned char* has, double* nis_out = nullptr,
+                    unsigned char* event_out = nullptr);
   // The same with everything already on the device: idx_dev [n] = slot of entry e or a negative number (entry skipped);
   // meas_soa_dev SoA [7][ld] in the batch precision, rows in entry order.  Asynchronous.
-  void step_indexed_dev(const int* idx_dev, long n, double dt, const void* meas_soa_dev, long ld, const unsigned char* has_dev);
+  // nis_dev / event_dev [n] (or null: rows of the batch's own): where the policy's kernel writes, by entry -- device-visible memory
+  void step_indexed_dev(const int* idx_dev, long n, double dt, const void* meas_soa_dev, long ld, const unsigned char* has_dev,
+                        double* nis_dev = nullptr, unsigned char* event_dev = nullptr);
   // derived outputs of the listed entries into device arrays (row e; entries with a negative slot are left untouched)
   void outputs_indexed_dev(const int* idx_dev, long n, double* pose_dev, double* twist_dev, double* acc_dev, bool at_time, double t1);
   // One-target call of the reference's C ABI (target_manager_update / update_meas).  The step is
   // QUEUED: it runs, together with every other queued one-target step, as a single indexed launch
   // when anything reads or otherwise touches the batch (flush()).  A slot queued twice flushes first,
   // so the order of steps per target is the caller's order.
-  void step_one(long slot, double dt, const double* meas7);
+  void step_one(long slot, double dt, const double* meas7, long out_pos = -1);
   void flush();
   // One tick over every slot in slot order, host inputs (rows of meas_aos / has follow the slot order)
-  void step_dense_host(double dt, const double* meas_aos, const unsigned char* has);
+  void step_dense_host(double dt, const double* meas_aos, const unsigned char* has, double* nis_out = nullptr, unsigned char* event_out = nullptr);
   // The same from SoA host rows in the BATCH precision (row c of meas_soa = component c of every slot,
   // ld_host elements apart): only the rows the model reads cross PCIe (3 for the linear models, 7 for the
   // angular ones) and no conversion kernel runs.  Pinned host memory makes the copies asynchronous DMA.
@@ -372,6 +392,22 @@ class Batch {
   P0TableMirror p0tab_dev_;
   void run_move(long src, long dst);
   void fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const;   // the policy's launch parameters of tick s_call of a call
+  void prepare_p0_tables();              // the body of prepare_reacquire
+  // the by-id update policy: its by-entry NIS row and event row (host-mapped, sized with the staging and queue blocks; the host
+  // reads them as cached host memory, never through the write-combined BAR block)
+  UpdateGate pol_{};
+  char* h_pol_ = nullptr;                // nis double[pol_cap_] | event uchar[pol_cap_]
+  char* d_pol_ = nullptr;
+  long pol_cap_ = 0;
+  void pol_reserve(long k);
+  double* pol_nis_host() const { return reinterpret_cast<double*>(h_pol_); }
+  unsigned char* pol_event_host() const { return reinterpret_cast<unsigned char*>(h_pol_ + (size_t)pol_cap_ * sizeof(double)); }
+  double* pol_nis_dev() const { return reinterpret_cast<double*>(d_pol_); }
+  unsigned char* pol_event_dev() const { return reinterpret_cast<unsigned char*>(d_pol_ + (size_t)pol_cap_ * sizeof(double)); }
+  // an indexed launch of k entries under the policy: rows reserved (unless the caller brings its own), tables current, p filled
+  void fill_update_gate(StepParams& p, long k, double* nis_dev = nullptr, unsigned char* event_dev = nullptr);
+  double* sink_nis_ = nullptr;
+  unsigned char* sink_event_ = nullptr;
   long cap_ = 0;  // slots
   long n_ = 0;
   std::vector<unsigned> slot_ids_;
@@ -418,7 +454,7 @@ class Batch {
   long append_now(long first, long count, const unsigned* ids, double t0, const double* P0, bool per_target_P0, const double* p0,
                   const double* v0, const double* a0, int cls, const int* cls_of, const int* P0_index, long P0_count, bool bookkeeping);
   // queue of one-target steps (reference C ABI) and the cache that serves the one-target getters
-  struct Pending { int slot; unsigned char has; double dt; double meas[7]; };
+  struct Pending { int slot; unsigned char has; double dt; double meas[7]; long out = -1; };   // out: position in the gate sink, or -1
   std::vector<Pending> pending_;
   std::vector<unsigned char> pending_mark_;
   double* d_dtper_ = nullptr;

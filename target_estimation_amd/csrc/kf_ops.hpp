@@ -89,6 +89,14 @@ struct StepParams {
   unsigned char* reacq_event = nullptr;
   const double* reacq_p0 = nullptr;
   const int* reacq_p0_idx = nullptr;
+  // The by-id update policy (target_manager_set_update_gate) of an INDEXED single tick: gate_id = 1 with gate > 0 and a by-entry
+  // NIS row in `nis` selects the gated indexed kernel (kf_step_sep.hpp, kf_step_sep_gate_indexed_kernel) -- ONE launch, the getter
+  // table included when o_pose is set.  gate_id_k: -1 = gate only; 0..127 = the rejection runs in reacq_run (by slot) by
+  // target_reacquire_c's table, re-initialising on the k-th consecutive rejection (k > 0) with P0 = reacq_p0 + reacq_p0_idx[slot] * N*N;
+  // gate_id_event [n] (or null): this call's event bytes by entry.  reacq stays 0: no reacquire launch.
+  int gate_id = 0;
+  int gate_id_k = -1;
+  unsigned char* gate_id_event = nullptr;
 };
 
 // The launch behind a gated tick that keeps the rejection runs and re-initialises lost targets (kf_reacquire_impl.hpp).

@@ -44,6 +44,10 @@ void launch_sep_innov_step(const StepArgs<T>& a, unsigned blocks, unsigned threa
 template <class M, typename T, int LAYOUT>
 void launch_sep_gate_step(const StepArgs<T>& a, double gate, unsigned blocks, unsigned threads, hipStream_t s);
 
+// The gated by-id kernels (kf_step_sep.hpp, kf_step_sep_gate_indexed_kernel), in kf_gate_id_{uv,ua,ar,av}.hip (kf_gate_id_impl.hpp) likewise.
+template <class M, typename T, int LAYOUT>
+void launch_sep_gate_id_step(const StepArgs<T>& a, const GateById& g, unsigned blocks, unsigned threads, hipStream_t s);
+
 // reacquire_kernel (kf_reacquire_impl.hpp), in kf_reacquire_{uv,ua,ar,av}.hip likewise: one instance per OpsImpl.
 template <class M, typename T, int G, int LAYOUT>
 void launch_reacquire(const ReacquireArgs& a, hipStream_t s);
@@ -123,6 +127,15 @@ struct OpsImpl {
     if constexpr (C::SEP && !kGateByWriter) launch_sep_gate_step<M, T, LAYOUT>(a, gate, blocks, threads, s);
     else throw std::runtime_error("target_estimation_amd: no gated step kernel for this request");
   }
+  static void launch_gate_by_id(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (C::SEP && !kGateByWriter) {
+      GateById g;
+      g.gate = p.gate; g.k = p.gate_id_k; g.run = p.reacq_run; g.p0_tab = p.reacq_p0; g.p0_idx = p.reacq_p0_idx; g.event = p.gate_id_event;
+      launch_sep_gate_id_step<M, T, LAYOUT>(a, g, blocks, threads, s);
+    } else {
+      throw std::runtime_error("target_estimation_amd: the update gate by id: no gated indexed kernel for this batch");
+    }
+  }
   // The launches of a request are plan_step's (step_variant.hpp): [innovation writer,] then once, or once per tick, the step
   // kernel [and the pose writer].
   static void step(const StepParams& p, hipStream_t s) {
@@ -167,7 +180,8 @@ struct OpsImpl {
         if (p.pose) pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
       }
       q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
-      if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
+      if (plan.gate_by_id) launch_gate_by_id(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
+      else if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
       else launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
       if (plan.reacquire_after_step) reacquire(make_reacquire_args(p), s);   // (p: the caller's mask and NIS row; gated ticks are single)
       if (plan.pose_writer_after_each_tick) write_pose_block(q, pose, s);

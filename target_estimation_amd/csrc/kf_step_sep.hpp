@@ -353,8 +353,41 @@ template <class C, class M, typename T> struct LivePark {
 // has-bit in everything behind it: the measurement counter (always added to nm_base) and the uniform-tile agreement (always
 // tested).  `gate` is an argument of its own, not a field of StepArgs, whose size is part of every existing kernel's descriptor;
 // 0 = no gate (a part of a gated population launch without one): acc = has.
-template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false>
-__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0) {
+// BYID: the by-id update policy (target_manager_set_update_gate) in the gated INDEXED tick: GateById below, whose tail runs per
+// valid lane behind the decision and ahead of store_record -- the slot's rejection run by target_reacquire_c's table and, on the
+// K-th consecutive rejection, the record re-initialised IN REGISTERS from this entry's measurement exactly as init_kernel /
+// reacquire_kernel write it (x0 = the measured pose with v0 = a0 = 0, the slot's own P0 through the layout's p_word table, unwrap
+// memory 0; clock and counter untouched).  store_record, the getter-table row (o_pose) and signal_done then see the
+// re-initialised state: the flush stays ONE launch.  The NIS row and the event row are indexed by ENTRY; an entry with a negative
+// slot writes nothing.  An indexed launch sees settled tiles (Batch::records() settles them), so no uniform-tile code is needed
+// here, in contrast to reacquire_kernel.
+struct GateById {
+  double gate;              // nis_max (> 0)
+  int k;                    // -1: gate only (runs untouched); 0: count only; 1..127: re-initialise on the k-th consecutive rejection
+  unsigned char* run;       // [slots] rejection runs (Batch::d_run_, the byte the dense calls use); unread with k < 0
+  const double* p0_tab;     // [rows][N*N] initial covariances; unread with k <= 0
+  const int* p0_idx;        // [slots] row of every slot
+  unsigned char* event;     // [entries] this call's event bytes, or null
+};
+
+// The form of the re-initialisation per instantiation.  In registers (above) where that costs no wavefront per SIMD against the
+// same kernel without it; elsewhere the record is written once more BEHIND store_record, word by word through state_set /
+// unwrap_ptr with the rolled loops init_kernel has, and the state words in registers are refreshed from x0 for the getter-table
+// row -- still one launch.  profiles/r13_update_gate_kernel_resources.txt names the form each instantiation got.
+template <class M, typename T, int LAYOUT>
+constexpr bool gate_id_tail_in_registers() {
+#ifdef TE_GATE_ID_TAIL
+  return TE_GATE_ID_TAIL != 0;   // (experiments: one form for every instantiation, through tools/kres.py)
+#else
+  // the two instantiations whose register form costs a wavefront per SIMD (88 against 76 registers, 5 against 6 wavefronts; 132
+  // against 128, 3 against 4); the other 18 have the same occupancy in both forms
+  return !(sizeof(T) == 4 && ((M::TYPE == UNIFORM_ACCELERATION && LAYOUT == LAYOUT_SEPARABLE) ||
+                              (M::TYPE == ANGULAR_VELOCITIES && LAYOUT == LAYOUT_SEPARABLE_PACKED)));
+#endif
+}
+
+template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false>
+__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0, const GateById* gid = nullptr) {
   constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
                  AB = sv_has(VAR, kAB), POSE = sv_has(VAR, kPose), INNOV = sv_has(VAR, kInnov);
   constexpr int LIVE = sv_live(VAR);
@@ -362,6 +395,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   static_assert(C::SEP, "separable layouts only");
   static_assert(sep_variant_ok(VAR, C::SHARED), "no such variant of the separable step (step_variant.hpp)");
   static_assert(!GATE || INNOV, "the gate decides on the NIS of the innovation stream's kernels");
+  static_assert(BYID == (INNOV && INDEXED) && (!BYID || GATE), "kInnov | kIndexed is the gated by-id step and nothing else");
+  if constexpr (!BYID) (void)gid;
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -562,6 +597,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   T g_inv[NGATE], g_pcol[NGATE][LB], g_uw[3] = {0, 0, 0};
   bool g_has = false, acc = false;
   if constexpr (!GATE) { (void)g_inv; (void)g_pcol; (void)g_uw; (void)g_has; (void)acc; (void)gate; (void)cov_of; }
+  // BYID, the form behind store_record: the measurement of a re-initialising lane, kept past the tick loop
+  constexpr bool TAIL_REGS = !BYID || gate_id_tail_in_registers<M, T, LAYOUT>();
+  T by_y[(BYID && !TAIL_REGS) ? (M::ANGULAR ? 7 : 3) : 1];
+  bool by_reinit = false;
+  if constexpr (!BYID || TAIL_REGS) { (void)by_y; (void)by_reinit; }
   int n_has = 0;
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
@@ -1124,6 +1164,57 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       }
     }
   }
+  if constexpr (BYID) {
+    // the policy tail (GateById): run, event byte and -- rarely -- the record's words replaced in registers
+    unsigned char ev = 0;
+    if (gid->k >= 0 && g_has) {   // (g_has: a valid lane with a measurement)
+      unsigned char* const runp = gid->run + slot_of;
+      unsigned run = 0;
+      if (!acc) {   // rejected (a NaN rejects)
+        const unsigned c0 = *runp;
+        const unsigned c1 = c0 + 1 < 127u ? c0 + 1 : 127u;
+        ev = (unsigned char)c1; run = c1;
+        if (gid->k > 0 && c1 >= (unsigned)gid->k) {   // a candidate: x0 as init_kernel forms it, re-initialised iff finite
+          T x0[N];
+#pragma unroll
+          for (int r = 0; r < N; ++r) x0[r] = 0;
+          if constexpr (M::ANGULAR) {
+            T p6[6];
+            pose7_to_pose6(ymeas, p6);
+#pragma unroll
+            for (int c6 = 0; c6 < 6; ++c6) x0[c6] = p6[c6];
+          } else {
+#pragma unroll
+            for (int c3 = 0; c3 < 3; ++c3) x0[c3] = ymeas[c3];
+          }
+          bool reinit = true;
+#pragma unroll
+          for (int r = 0; r < K; ++r) reinit = reinit && (x0[r] - x0[r] == (T)0);   // finite
+          if (reinit) { ev = (unsigned char)(0x80u | c1); run = 0; }
+          if constexpr (!TAIL_REGS) {
+            by_reinit = reinit;
+#pragma unroll
+            for (int c7 = 0; c7 < (M::ANGULAR ? 7 : 3); ++c7) by_y[c7] = ymeas[c7];
+          } else if (reinit) {
+            const double* P0 = gid->p0_tab + (long)gid->p0_idx[slot_of] * N * N;
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+              XW_(r) = x0[r];
+#pragma unroll
+              for (int c = (C::SEPPK ? r : 0); c < N; ++c)
+                if (C::PWORD.v[r][c] >= 0) mem[C::PWORD.v[r][c]] = (T)P0[r * N + c];   // (state_set's words, in its order)
+            }
+            if constexpr (M::ANGULAR) {
+#pragma unroll
+              for (int cc = 0; cc < 3; ++cc) UWW_(cc) = 0;
+            }
+          }
+        }
+      }
+      *runp = (unsigned char)run;
+    }
+    if (valid && gid->event != nullptr) gid->event[entry] = ev;
+  }
   if constexpr (LIVE == 2) {
     // the own-time sphere query of every target after every tick (BASELINE configs[4]), on the posterior still in registers,
     // and / or the tick's poses for a consumer outside the kernel.  Run-time choices inside the LIVE == 2 variant only: the
@@ -1241,6 +1332,33 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     if constexpr (POSE && !FUSED) write_pose(0);
     if constexpr (GATE) write_innov(g_has, nis, nu_all, MI);
     else if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
+    if constexpr (BYID && !TAIL_REGS) {
+      if (by_reinit) {   // the record once more, behind store_record, as init_kernel / reacquire_kernel write it
+        T x0[N];
+#pragma unroll
+        for (int r = 0; r < N; ++r) x0[r] = 0;
+        if constexpr (M::ANGULAR) {
+          T p6[6];
+          pose7_to_pose6(by_y, p6);
+#pragma unroll
+          for (int c6 = 0; c6 < 6; ++c6) x0[c6] = p6[c6];
+        } else {
+#pragma unroll
+          for (int c3 = 0; c3 < 3; ++c3) x0[c3] = by_y[c3];
+        }
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+          state_set<C, T>(a.rec, slot_of, r, N, x0[r]);
+          XW_(r) = x0[r];   // (the getter-table row below reads the state words in registers)
+        }
+        const double* P0 = gid->p0_tab + (long)gid->p0_idx[slot_of] * N * N;
+        for (int r = 0; r < N; ++r)
+          for (int c = (C::SEPPK ? r : 0); c < N; ++c) state_set<C, T>(a.rec, slot_of, r, c, (T)P0[r * N + c]);
+        if constexpr (M::ANGULAR) {
+          for (int cc = 0; cc < 3; ++cc) *unwrap_ptr<C, T>(a.rec, slot_of, cc) = 0;
+        }
+      }
+    }
     if constexpr (QUERY) {
       T xq[N];
 #pragma unroll
@@ -1306,6 +1424,13 @@ __global__ void __launch_bounds__(256) kf_step_sep_gate_kernel(const StepArgs<T>
   const unsigned zz = zz_block(b, gridDim.x);
   b = a.reverse ? zz : b;
   sep_step_wave<M, T, LAYOUT, kInnov, true>(a, (long)b * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), gate);
+}
+
+// The gated by-id tick (sep_step_wave, GATE + BYID): the kInnov | kIndexed step with the policy tail, everything new in the second
+// argument -- StepArgs keeps its size.  Instantiated in kf_gate_id_{uv,ua,ar,av}.hip (kf_gate_id_impl.hpp).
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256) kf_step_sep_gate_indexed_kernel(const StepArgs<T> a, const GateById g) {
+  sep_step_wave<M, T, LAYOUT, kInnov | kIndexed, true, true>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate, &g);
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------

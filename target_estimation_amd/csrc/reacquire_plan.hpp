@@ -39,6 +39,24 @@ inline void check_reacquire(const Reacquire& q, double gate, long n, bool keeps_
   if (!p0_kept) throw std::invalid_argument(pre + "the batch no longer keeps its initial covariances (too many distinct ones)");
 }
 
+// The update policy of the by-id paths (target_manager_c.h, target_manager_set_update_gate): sticky, per manager and model, off
+// by default.  nis_max 0 = no gate, > 0 (+inf included) = a measurement is folded in iff (double)NIS <= nis_max.  max_rejects -1 =
+// gate only (the rejection runs are neither read nor written), 0 = count only, 1..127 = re-initialise on the K-th consecutive
+// rejection, by the table of Reacquire above.
+struct UpdateGate {
+  double nis_max = 0.0;
+  int max_rejects = -1;
+  bool on() const { return nis_max > 0.0; }
+  bool runs() const { return on() && max_rejects >= 0; }
+};
+// throws std::invalid_argument for the policies that are refused whatever the batch
+inline void check_update_gate(double nis_max, int max_rejects) {
+  const std::string pre = "target_estimation_amd: update gate: ";
+  if (!(nis_max >= 0.0)) throw std::invalid_argument(pre + "nis_max must be 0 (no gate) or positive");
+  if (max_rejects < -1 || max_rejects > 127) throw std::invalid_argument(pre + "max_rejects must be -1..127, got " + std::to_string(max_rejects));
+  if (max_rejects >= 0 && !(nis_max > 0.0)) throw std::invalid_argument(pre + "max_rejects >= 0 needs the gate (nis_max > 0): it counts the gate's rejections");
+}
+
 // The device copy of the host table of distinct initial covariances (rows are only ever appended): what to do before a launch
 // reads it.  grow: allocate new_cap rows, copy nothing over -- every row is uploaded again (first = 0).
 struct P0TableMirror {

@@ -34,7 +34,7 @@ void Shard::devIdsFree() {
   DevIds& d = dev_ids_;
   device_free(d.keys); device_free(d.vals); device_free(d.seen);
   device_free(d.ids); device_free(d.loc); device_free(d.idx); device_free(d.aos); device_free(d.soa);
-  device_free(d.mask); device_free(d.found); device_free(d.out); device_free(d.counters);
+  device_free(d.mask); device_free(d.found); device_free(d.out); device_free(d.counters); device_free(d.gnis); device_free(d.gev);
   if (d.h_counters) (void)hipHostFree(d.h_counters);
   d = DevIds();
 }
@@ -49,7 +49,9 @@ void Shard::devIdsReserve(long n) {
   const long want = std::max(n, d.cap * 2);
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   device_free(d.ids); device_free(d.loc); device_free(d.idx); device_free(d.aos); device_free(d.soa);
-  device_free(d.mask); device_free(d.found); device_free(d.out);
+  device_free(d.mask); device_free(d.found); device_free(d.out); device_free(d.gnis); device_free(d.gev);
+  TE_HIP_CHECK(hipMalloc((void**)&d.gnis, sizeof(double) * want));
+  TE_HIP_CHECK(hipMalloc((void**)&d.gev, (size_t)want));
   TE_HIP_CHECK(hipMalloc((void**)&d.ids, sizeof(unsigned) * want));
   TE_HIP_CHECK(hipMalloc((void**)&d.loc, sizeof(int) * want));
   TE_HIP_CHECK(hipMalloc((void**)&d.idx, sizeof(int) * want));
@@ -186,6 +188,7 @@ int Shard::findOrCreateBatch(int type, const double* Q, const double* R, int lan
   // (the batch itself decides from Q and R whether it starts in the shared-axes form, and from every P0 whether it stays in it)
   batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes, set_.uniform_tiles));
   if (set_.keep_meas) batches_.back()->set_keep_measurement(true);
+  if (type >= 0 && type < 4 && set_.gate[type].on()) batches_.back()->set_update_gate(set_.gate[type]);
   cls = 0;
   return (int)batches_.size() - 1;
 }
@@ -485,23 +488,74 @@ bool Shard::smallBatchPath(long n) const {
   return true;
 }
 
-long Shard::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas) {
+namespace {
+// the update policy's rows of a device-resolved call: -2 / 0 (an unknown id) everywhere ahead of the batches' launches, and -1
+// ("no measurement judged") at the entries of a batch that steps without a policy
+__global__ void gate_rows_fill_kernel(double* nis, unsigned char* ev, long n) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) { nis[e] = -2.0; ev[e] = 0; }
+}
+__global__ void gate_rows_unjudged_kernel(const int* idx, double* nis, long n) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n && idx[e] >= 0) nis[e] = -1.0;
+}
+}  // namespace
+
+void Shard::updateGateChanged(int type) {
+  for (auto& b : batches_)
+    if (b->type() == type) b->set_update_gate(set_.gate[type]);
+}
+
+void Shard::checkUpdateGate(const unsigned* ids, long n) const {
+  std::vector<const char*> why(batches_.size(), nullptr);
+  bool any = false;
+  for (size_t b = 0; b < batches_.size(); ++b) { why[b] = batches_[b]->update_gate_refusal(); any = any || why[b]; }
+  if (!any) return;
+  for (long i = 0; i < n; ++i) {
+    Loc loc;
+    if (find(ids[i], loc) && why[(size_t)loc.batch]) throw std::runtime_error(why[(size_t)loc.batch]);
+  }
+}
+
+int Shard::updateGateServed(int type) const {
+  int r = -1;
+  for (const auto& b : batches_)
+    if (b->type() == type) {
+      const bool ok = b->update_gate_refusal(set_.gate[type].on() ? set_.gate[type] : UpdateGate{1.0, -1}) == nullptr;
+      r = (r == 0 || !ok) ? 0 : 1;
+    }
+  return r;
+}
+
+long Shard::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas, double* nis_out,
+                        unsigned char* event_out) {
   const size_t nb = batches_.size();
+  const bool outs = nis_out || event_out;
+  if (nis_out) std::fill(nis_out, nis_out + (n > 0 ? n : 0), -2.0);
+  if (event_out) std::fill(event_out, event_out + (n > 0 ? n : 0), (unsigned char)0);
   if (smallBatchPath(n)) {
     long done = 0;
-    for (long i = 0; i < n; ++i) {
-      Loc loc;
-      if (!find(ids[i], loc)) {
-        if (set_.verbose) notFound(ids[i]);
-        continue;
+    if (outs) for (auto& b : batches_) b->set_gate_sink(nis_out, event_out);
+    try {
+      for (long i = 0; i < n; ++i) {
+        Loc loc;
+        if (!find(ids[i], loc)) {
+          if (set_.verbose) notFound(ids[i]);
+          continue;
+        }
+        batches_[(size_t)loc.batch]->step_one(loc.slot, dt, (meas && (!has_meas || has_meas[i])) ? meas + 7 * i : nullptr, outs ? i : -1);
+        ++done;
       }
-      batches_[(size_t)loc.batch]->step_one(loc.slot, dt, (meas && (!has_meas || has_meas[i])) ? meas + 7 * i : nullptr);
-      ++done;
+      if (outs) for (auto& b : batches_) b->flush();   // the outputs are in the caller's arrays when the call returns
+    } catch (...) {
+      for (auto& b : batches_) b->set_gate_sink(nullptr, nullptr);
+      throw;
     }
+    if (outs) for (auto& b : batches_) b->set_gate_sink(nullptr, nullptr);
     return done;
   }
   if (Batch* bt = wholeBatch(ids, n)) {   // no per-id lookup, dense kernel
-    bt->step_dense_host(dt, meas, has_meas);
+    bt->step_dense_host(dt, meas, has_meas, nis_out, event_out);
     return n;
   }
   // ids in any order, possibly several batches, possibly unknown ids: resolved on the device (id_resolve.hpp); a call
@@ -516,13 +570,21 @@ long Shard::updateBatch(const unsigned* ids, long n, double dt, const double* me
       }
       if (meas && has_meas) TE_HIP_CHECK(hipMemcpyAsync(d.mask, has_meas, (size_t)n, hipMemcpyHostToDevice, stream_));
       long total = 0;
+      bool rows = outs;   // the policy's rows by entry: for the caller, or as the kernel's NIS row alone
+      for (size_t b = 0; b < nb && !rows; ++b) rows = meas && rc.found[b] > 0 && batches_[b]->update_gate().on();
+      if (rows) hipLaunchKernelGGL(gate_rows_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.gnis, d.gev, n);
       for (size_t b = 0; b < nb; ++b) {
         if (rc.found[b] <= 0) continue;
         total += rc.found[b];
         hipLaunchKernelGGL(id_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.loc, n, (int)b, d.idx,
                            (unsigned char*)nullptr);
-        batches_[b]->step_indexed_dev(d.idx, n, dt, meas ? d.soa : nullptr, n, (meas && has_meas) ? d.mask : nullptr);
+        const bool pol = meas && batches_[b]->update_gate().on();
+        if (rows && !pol) hipLaunchKernelGGL(gate_rows_unjudged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.idx, d.gnis, n);
+        batches_[b]->step_indexed_dev(d.idx, n, dt, meas ? d.soa : nullptr, n, (meas && has_meas) ? d.mask : nullptr, rows ? d.gnis : nullptr,
+                                      rows ? d.gev : nullptr);
       }
+      if (nis_out) TE_HIP_CHECK(hipMemcpyAsync(nis_out, d.gnis, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+      if (event_out) TE_HIP_CHECK(hipMemcpyAsync(event_out, d.gev, (size_t)n, hipMemcpyDeviceToHost, stream_));
       TE_HIP_CHECK(hipStreamSynchronize(stream_));   // the caller's host arrays may be reused after return
       return total;
     }
@@ -535,7 +597,10 @@ long Shard::updateBatch(const unsigned* ids, long n, double dt, const double* me
   auto step = [&](size_t b, const std::vector<long>* pos) {   // (pos null: the caller's arrays are this batch's rows already)
     RowsIn<double> m2(meas, pos, 7);
     RowsIn<unsigned char> h2(has_meas, pos, 1);
-    batches_[b]->step_indexed(by.slots[b].data(), (long)by.slots[b].size(), dt, m2.get(), h2.get());
+    RowsOut<double> n2(nis_out, pos, 1);
+    RowsOut<unsigned char> e2(event_out, pos, 1);
+    batches_[b]->step_indexed(by.slots[b].data(), (long)by.slots[b].size(), dt, m2.get(), h2.get(), n2.get(), e2.get());
+    scatterAll(n2, e2);
   };
   splitBySlot(ids, n, by, [&](size_t b, const Loc& loc) {
     if (seen[b][(size_t)loc.slot]) {

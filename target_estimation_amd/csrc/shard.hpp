@@ -10,6 +10,7 @@
 
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -48,6 +49,7 @@ struct ShardSettings {
   bool population_tick = true;   // TE_POPULATION_TICK
   bool uniform_tiles = true;     // TE_UNIFORM_TILES / TargetManager::setUniformTiles: new shared-axes batches keep uniform tiles (Batch)
   bool shared_axes = true;       // TE_SHARED_AXES / TargetManager::setSharedAxes: new fp64 batches may use the shared-axes storage form (Batch)
+  UpdateGate gate[4];            // TargetManager::setUpdateGate: the by-id update policy per model type; batches created later inherit it
 };
 
 // one target's log rows, formatted per channel (TargetManager::log); batch: the shard's batch index as logCollect leaves it
@@ -80,7 +82,11 @@ class Shard {
   bool update(unsigned id, double dt, const double* meas) {   // meas null: prediction only
     Loc loc;
     if (!find(id, loc)) { notFound(id); return false; }
-    batches_[(size_t)loc.batch]->step_one(loc.slot, dt, meas);
+    Batch& b = *batches_[(size_t)loc.batch];
+    if (meas && b.update_gate().on()) {   // (off: one load and one compare on the latency path)
+      if (const char* why = b.update_gate_refusal()) throw std::runtime_error(why);
+    }
+    b.step_one(loc.slot, dt, meas);
     return true;
   }
   bool erase(unsigned id);
@@ -106,7 +112,17 @@ class Shard {
   long initBatchClasses(int type, const unsigned* ids, long n, double t0, long n_classes, const double* Q, const double* R, const double* P0,
                         const unsigned* class_of, const double* p0, const double* v0, const double* a0);
   void updateAll(double dt);
-  long updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas);
+  // nis_out / event_out [n] (or null): what the update policy reports per entry (Batch: "the update policy of the by-id paths");
+  // -2 / 0 for an unknown id.  With them the call flushes the one-target queue before it returns.
+  long updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas, double* nis_out = nullptr,
+                   unsigned char* event_out = nullptr);
+  // The policy of settings.gate[type] to every batch of the model (flushes their queues).
+  void updateGateChanged(int type);
+  // throws, before anything is stepped, if a by-id update with measurements of these ids touches a batch that has a policy and
+  // cannot serve it (Batch::update_gate_refusal)
+  void checkUpdateGate(const unsigned* ids, long n) const;
+  // 1 / 0: would by-id updates of the model's batch be served under settings.gate[type]; -1: no such batch
+  int updateGateServed(int type) const;
   long eraseBatch(const unsigned* ids, long n, std::vector<unsigned>& erased);   // appends the ids that went away
   long getPoseBatch(const unsigned* ids, long n, double* pose, double* twist, double* acc, unsigned char* found, bool at_time, double t1);
   long getStateBatch(const unsigned* ids, long n, double* x, double* P);
@@ -181,6 +197,7 @@ class Shard {
     unsigned* ids = nullptr; int* loc = nullptr; int* idx = nullptr;
     double* aos = nullptr; void* soa = nullptr; unsigned char* mask = nullptr; unsigned char* found = nullptr;
     double* out = nullptr;              // [cap][7 + 6 + 6] getter outputs
+    double* gnis = nullptr; unsigned char* gev = nullptr;   // [cap] the update policy's rows by entry
     ResolveCounters* counters = nullptr;
     ResolveCounters* h_counters = nullptr;   // pinned
   } dev_ids_;

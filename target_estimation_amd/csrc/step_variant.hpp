@@ -8,6 +8,7 @@
 // launches of one OpsImpl::step request.  DESIGN.md ("Step-kernel variants") says how a new variant is added.
 #pragma once
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -34,8 +35,10 @@ constexpr bool sep_variant_ok(unsigned v, bool shared_layout) {
              POSE = sv_has(v, kPose), INNOV = sv_has(v, kInnov);
   const int LIVE = sv_live(v);
   return v < (1u << kVariantBits) && LIVE != 3 &&
-         // the innovation stream is an output of dense single ticks in place of one-class batches
-         (!INNOV || (!INDEXED && !FUSED && !QUERY && !PERQR && !LIVE && !AB && !POSE)) &&
+         // the innovation stream is an output of single ticks in place of one-class batches: of the dense ones and, with kIndexed, of
+         // the gated by-id step (kf_step_sep_gate_indexed_kernel), whose NIS row is indexed by entry.  kSepVariants does not list the
+         // latter: no plain kInnov | kIndexed kernel is shipped, plan_step reaches the gated one through StepPlan::gate_by_id.
+         (!INNOV || (!FUSED && !QUERY && !PERQR && !LIVE && !AB && !POSE)) &&
          // the pose stream is an output of dense launches of one-class batches
          (!POSE || (!INDEXED && !PERQR && !LIVE)) &&
          // A -> B ticks are dense single-tick launches without the fused query
@@ -104,6 +107,10 @@ struct StepPlan {
   // the request keeps rejection runs / re-acquires (P::reacq): one reacquire launch behind the step of the (gated, measured) tick
   // and ahead of its pose writer
   bool reacquire_after_step = false;
+  // the request carries the by-id update policy (P::gate_id): an indexed single tick, gated, served by ONE launch of the gated
+  // indexed kernel (kf_step_sep_gate_indexed_kernel: variant kInnov | kIndexed, the rejection runs and the re-initialisation in
+  // its tail, the getter table too when the request has one).  Never together with innov_writer_first / reacquire_after_step.
+  bool gate_by_id = false;
 };
 
 // The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
@@ -122,6 +129,15 @@ template <class P> struct has_reacq_member<P, std::void_t<decltype(std::declval<
 template <class P>
 constexpr bool requested_reacquire(const P& p) {
   if constexpr (has_reacq_member<P>::value) return p.reacq != 0;
+  else return false;
+}
+// The by-id update policy of a request: P::gate_id (non-zero = the request is a by-id update under a manager's policy; it then
+// has P::gate_id_k, -1 = gate only, 0..127 as P::reacq_k, and the pointers P::reacq_run / reacq_p0 / reacq_p0_idx as well).
+template <class P, class = void> struct has_gate_id_member : std::false_type {};
+template <class P> struct has_gate_id_member<P, std::void_t<decltype(std::declval<const P&>().gate_id)>> : std::true_type {};
+template <class P>
+constexpr bool requested_gate_by_id(const P& p) {
+  if constexpr (has_gate_id_member<P>::value) return p.gate_id != 0;
   else return false;
 }
 template <class P>
@@ -144,6 +160,25 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
   const double gate = requested_gate(p);
   if (!(gate >= 0.0)) throw std::runtime_error("target_estimation_amd: the gate (nis_max) must be 0 (none) or positive");
   plan.gated = gate > 0.0;
+  if constexpr (has_gate_id_member<P>::value) {
+    if (requested_gate_by_id(p)) {   // the by-id policy: one launch of the gated indexed kernel, or refused
+      const char* pre = "target_estimation_amd: the update gate by id: ";
+      if (!plan.gated) throw std::runtime_error(std::string(pre) + "a policy needs the gate (nis_max > 0)");
+      if (!p.idx || !p.nis) throw std::runtime_error(std::string(pre) + "an indexed launch with a by-entry NIS row");
+      if (p.n_ticks > 1 || p.live_posted || p.rec_out || p.q_delta || p.pose || p.tile_uni || requested_reacquire(p) || requested_gate_by_writer(p))
+        throw std::runtime_error(std::string(pre) + "a single indexed tick in place, without the dense calls' streams");
+      if (p.gate_id_k < -1 || p.gate_id_k > 127) throw std::runtime_error(std::string(pre) + "max_rejects must be -1..127");
+      if (p.gate_id_k >= 0 && (!p.reacq_run || !p.reacq_p0 || !p.reacq_p0_idx))
+        throw std::runtime_error(std::string(pre) + "rejection runs need the batch's run row and its table of initial covariances");
+      if (!t.sep || p.cls || t.gate_by_writer)
+        throw std::runtime_error(std::string(pre) + "no gated indexed kernel for this batch (dense layouts, several (Q, R) classes)");
+      if (p.o_pose && ((p.n > t.tpw && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))
+        throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
+      plan.gate_by_id = true;
+      plan.variant = kInnov | kIndexed;
+      return plan;
+    }
+  }
   if (plan.gated && (!p.nis || p.idx || p.n_ticks > 1 || p.live_posted || p.o_pose))
     throw std::runtime_error("target_estimation_amd: the gate acts in dense single ticks with an innovation stream (its NIS row reports the decisions)");
   // (a request type with P::reacq has P::reacq_k, the pointers P::reacq_run / reacq_p0 / reacq_p0_idx and P::meas as well)

@@ -433,17 +433,59 @@ int TargetManager::getRejectionRun(unsigned id) {
 }
 
 // Each shard gets its ids in the caller's order (a repeated id stays two steps in a row) and decides the path for its own slice.
-long TargetManager::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas) {
+long TargetManager::updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas, double* nis_out,
+                                unsigned char* event_out) {
   lock_guard<mutex> lg(target_lock_);
   const Split sp = splitIds(ids, n);
   if (settings_.verbose) for (long i : sp.unknown) std::cout << "Target(" << ids[i] << ") does not exist!" << std::endl;
+  // the update policy: every touched batch of every shard must serve it before the first one steps
+  bool any_gate = false;
+  for (const UpdateGate& g : settings_.gate) any_gate = any_gate || g.on();
+  if (any_gate && meas)
+    forShards(sp, ids, n, [&](Shard& sh, size_t, const unsigned* ids2, long m, const std::vector<long>*) { sh.checkUpdateGate(ids2, m); });
+  for (long i : sp.unknown) {
+    if (nis_out) nis_out[i] = -2.0;
+    if (event_out) event_out[i] = 0;
+  }
   long done = 0;
   forShards(sp, ids, n, [&](Shard& sh, size_t, const unsigned* ids2, long m, const std::vector<long>* pos) {
     RowsIn<double> m2(meas, pos, 7);
     RowsIn<unsigned char> h2(has_meas, pos, 1);
-    done += sh.updateBatch(ids2, m, dt, m2.get(), h2.get());
+    RowsOut<double> n2(nis_out, pos, 1);
+    RowsOut<unsigned char> e2(event_out, pos, 1);
+    done += sh.updateBatch(ids2, m, dt, m2.get(), h2.get(), n2.get(), e2.get());
+    scatterAll(n2, e2);
   });
   return done;
+}
+
+void TargetManager::setUpdateGate(int type, double nis_max, int max_rejects) {
+  check_update_gate(nis_max, max_rejects);
+  if (type < -1 || type > 3) throw std::invalid_argument("target_estimation_amd: update gate: no such model type " + std::to_string(type));
+  lock_guard<mutex> lg(target_lock_);
+  for (int t = 0; t < 4; ++t) {
+    if (type >= 0 && t != type) continue;
+    settings_.gate[t] = UpdateGate{nis_max, max_rejects};
+    for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(guardDev(k)); shards_[k]->updateGateChanged(t); }
+  }
+}
+
+bool TargetManager::getUpdateGate(int type, double& nis_max, int& max_rejects) {
+  if (type < 0 || type > 3) return false;
+  lock_guard<mutex> lg(target_lock_);
+  nis_max = settings_.gate[type].nis_max; max_rejects = settings_.gate[type].max_rejects;
+  return true;
+}
+
+int TargetManager::updateGateServed(int type) {
+  if (type < 0 || type > 3) return -1;
+  lock_guard<mutex> lg(target_lock_);
+  int r = -1;
+  for (size_t k = 0; k < shards_.size(); ++k) {
+    const int s = shards_[k]->updateGateServed(type);
+    if (s >= 0) r = (r == 0 || s == 0) ? 0 : 1;
+  }
+  return r;
 }
 
 long TargetManager::getPoseBatch(const unsigned* ids, long n, double* pose, double* twist, double* acc,

@@ -131,7 +131,16 @@ class TargetManager {
   long initBatchClasses(target_t type, const unsigned* ids, long n, double dt0, double t0, long n_classes, const double* Q,
                         const double* R, const double* P0, const unsigned* class_of, const double* p0, const double* v0,
                         const double* a0);
-  long updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas);
+  // nis_out / event_out [n] (or null): the update policy's reports per entry, in the caller's order (target_manager_c.h,
+  // target_manager_update_meas_batch_gated); a policy that a touched batch cannot serve throws before anything is stepped
+  long updateBatch(const unsigned* ids, long n, double dt, const double* meas, const unsigned char* has_meas, double* nis_out = nullptr,
+                   unsigned char* event_out = nullptr);
+  // THE UPDATE POLICY of the by-id paths (reacquire_plan.hpp UpdateGate; Batch): sticky, per model type (-1: every model), off by
+  // default, inherited by the batches created later.  Setting it flushes every queued one-target step first.  Throws
+  // std::invalid_argument for a policy that is refused whatever the batch.
+  void setUpdateGate(int type, double nis_max, int max_rejects);
+  bool getUpdateGate(int type, double& nis_max, int& max_rejects);   // false: no such model type
+  int updateGateServed(int type);   // 1 / 0: by-id updates of the model's batches would be served under a policy; -1: unknown (no batch)
   // erase many targets in one call (one compaction launch per batch); unknown or repeated ids are reported
   // like erase() does and skipped; returns the number erased
   long eraseBatch(const unsigned* ids, long n);

@@ -613,6 +613,32 @@ int target_manager_get_rejection_run(target_manager_c* m, unsigned int id) {
   return rc < 0 ? rc : run;
 }
 
+// ---- the update policy of the by-id paths
+int target_manager_set_update_gate(target_manager_c* m, int type, double nis_max, int max_rejects) {
+  return guarded("target_manager_set_update_gate", [&] {
+    te::check_update_gate(nis_max, max_rejects);   // (a bad policy is refused before the handle is looked at)
+    M(m)->setUpdateGate(type, nis_max, max_rejects);
+  });
+}
+int target_manager_get_update_gate(target_manager_c* m, int type, double* nis_max, int* max_rejects) {
+  return guarded("target_manager_get_update_gate", [&] {
+    double g = 0.0;
+    int k = -1;
+    if (!M(m)->getUpdateGate(type, g, k)) throw std::invalid_argument("update gate: no such model type");
+    if (nis_max) *nis_max = g;
+    if (max_rejects) *max_rejects = k;
+  });
+}
+int target_manager_update_gate_served(target_manager_c* m, int type) {
+  return guarded_value<int>("target_manager_update_gate_served", -1, [&] { return M(m)->updateGateServed(type); });
+}
+long target_manager_update_meas_batch_gated(target_manager_c* m, const unsigned int* ids, long n, double dt, const double* meas,
+                                            const unsigned char* has_meas, double* nis_out, unsigned char* event_out) {
+  long k = -1;
+  guarded("target_manager_update_meas_batch_gated", [&] { k = M(m)->updateBatch(ids, n, dt, meas, has_meas, nis_out, event_out); });
+  return k;
+}
+
 // ---- resident ("live") mode
 int target_batch_live_start(target_batch_c* b, double dt, const void* meas_ring_dev, long tick_stride, long ld,
                             const unsigned char* has_ring_dev, long has_stride, long ring_ticks, long first_entry, long max_ticks,

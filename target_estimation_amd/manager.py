@@ -34,6 +34,10 @@ def _ids(ids):
     return ids, ids.ctypes.data_as(capi.c_uint_p)
 
 
+def _model_type(type):
+    return MODEL_TYPES[type] if isinstance(type, str) else int(type)
+
+
 def _check(rc, what):
     if rc is None or rc < 0:
         raise RuntimeError("%s failed: %s" % (what, capi.last_error()))
@@ -611,7 +615,33 @@ class TargetManager:
             self._h, int(type), idp, n, float(dt0), float(t0), nc, _dp(Q), _dp(R), _dp(P0), class_of.ctypes.data_as(capi.c_uint_p),
             _dp(p0), _dp(v0), _dp(a0)), "target_manager_init_batch_classes")
 
-    def update_batch(self, ids, dt, meas=None, has_meas=None):
+    def set_update_gate(self, nis_max, max_rejects=-1, type=-1):
+        """The sticky update policy of the by-id paths (target_manager_set_update_gate): from now on update(id, dt, meas),
+        update_batch and the ingest tick fold a measurement in iff its NIS <= nis_max (0: no gate, the default) and, with
+        max_rejects >= 0, keep every target's run of consecutive rejections (getRejectionRun) and re-initialise a target from
+        the measurement of its max_rejects-th consecutive rejection (0: count only; -1: gate only).  type: a model type (a name
+        of MODEL_TYPES or its number), or -1 = every model."""
+        _check(self._lib.target_manager_set_update_gate(self._h, _model_type(type), float(nis_max), int(max_rejects)),
+               "target_manager_set_update_gate")
+
+    setUpdateGate = set_update_gate
+
+    def get_update_gate(self, type):
+        """(nis_max, max_rejects) of a model type's policy."""
+        g, k = C.c_double(0.0), C.c_int(-1)
+        _check(self._lib.target_manager_get_update_gate(self._h, _model_type(type), C.byref(g), C.byref(k)), "target_manager_get_update_gate")
+        return g.value, k.value
+
+    getUpdateGate = get_update_gate
+
+    def update_gate_served(self, type):
+        """True / False: by-id updates of this model's batches would be served under a policy; None: no such batch yet."""
+        rc = self._lib.target_manager_update_gate_served(self._h, _model_type(type))
+        return None if rc < 0 else bool(rc)
+
+    def update_batch(self, ids, dt, meas=None, has_meas=None, gated=False):
+        """gated=True: target_manager_update_meas_batch_gated -> (done, nis [n] float64, event [n] uint8), per entry in the
+        caller's order: nis -1 = no measurement judged on the entry, -2 = unknown id; event as the re-acquisition table."""
         ids, idp = _ids(ids)
         n = len(ids)
         meas = _d(meas, (n, 7))
@@ -619,6 +649,13 @@ class TargetManager:
         if has_meas is not None:
             has_meas = np.ascontiguousarray(has_meas, dtype=np.uint8)
             hp = has_meas.ctypes.data_as(capi.c_ubyte_p)
+        if gated:
+            nis = np.zeros(max(n, 1), dtype=np.float64)
+            event = np.zeros(max(n, 1), dtype=np.uint8)
+            done = _check(self._lib.target_manager_update_meas_batch_gated(self._h, idp, n, float(dt), _dp(meas), hp, _dp(nis),
+                                                                           event.ctypes.data_as(capi.c_ubyte_p)),
+                          "target_manager_update_meas_batch_gated")
+            return done, nis[:n], event[:n]
         return _check(self._lib.target_manager_update_meas_batch(self._h, idp, n, float(dt), _dp(meas), hp),
                       "target_manager_update_meas_batch")
 
