@@ -320,6 +320,41 @@ int target_batch_live_start(target_batch_c* b, double dt, const void* meas_ring_
  * (src/target_manager_ros.cpp:78-87) -- through the caches and before the tick counts as done: copy the buffer on another stream
  * after ..._live_done reached tick k and it holds the poses of a tick >= k (exactly k when one tick is posted at a time). */
 int target_batch_live_set_pose_output(target_batch_c* b, double* pose_soa_dev, long ld);
+/* THE GATE INSIDE A RESIDENT SESSION.  Sticky like ..._live_set_pose_output: the sessions started AFTER this call (also through
+ * target_manager_live_start_all, for each batch it was set on) decide the NIS validation gate between prediction and update,
+ * keep the rejection runs and re-initialise a lost target INSIDE the resident kernel, tick after tick -- no launch per tick.
+ *   nis_max == 0 or nis == NULL   the gate is off: sessions are exactly the plain ones.
+ *   nis_max > 0 (+inf included)   the session is gated.  nis->nis_dev is required (it reports the decisions, as in the launched
+ *                                 calls; a stride of 0 keeps it to one row); nis->innov_dev must be NULL.
+ *   reacq (or NULL: gate only)    the policy of target_batch_step_sequence_reacquire: max_rejects 0..127, event rows or none.
+ * Per slot and tick the semantics are those of target_batch_step_sequence_gated / ..._reacquire, word for word: the decision is
+ * (double)NIS <= nis_max (a NaN rejects); an accepted slot leaves in the bits of the ungated tick with mask 1, a rejected one in
+ * those of the ungated tick with mask 0 (state, covariance, unwrap memory, measurement counter); NIS is reported either way, -1
+ * without a measurement; the rejection run follows target_reacquire_c's table, and a re-initialised slot becomes bit for bit
+ * what a fresh target created from this tick's measurement gets (v0 = a0 = 0, the slot's own P0, unwrap memory 0, clock and
+ * counter untouched; the finiteness rule unchanged).  The per-tick pose output and the per-tick query of the same session see
+ * the re-initialised state.
+ * ROWS.  Tick k of the session, counted from 0 at ..._live_start, writes NIS row b = (ring_ticks > 0 ? k % ring_ticks : k) at
+ * nis_dev + b * nis_tick_stride, and its event row likewise through reacq's ring_ticks / tick_stride.  Columns >= size are never
+ * written.  With ring_ticks == 0 and a non-zero stride the caller provides max_ticks rows.  Both rows leave the kernel as the
+ * pose output does -- written through the caches, before the tick counts as done -- so a consumer may copy them on another
+ * stream once ..._live_done has reached k + 1, without ending the session.
+ * RUNS.  The session reads every slot's rejection run (the byte the dense calls use) at its start, keeps it in a register and
+ * writes it back with the records when the kernel leaves -- at ..._live_stop, or by itself after the idle limit.  "Any other call
+ * on the batch ends the session first" covers target_batch_rejection_runs and target_manager_get_rejection_run as well.
+ * REFUSED (negative return, target_manager_last_error, nothing launched or changed): nis_max < 0 or NaN; a gate without nis_dev;
+ * innov_dev != NULL; ld < size; a stride in (0, ld) or negative; ring_ticks < 0; max_rejects outside 0..127; a policy without a
+ * gate; a batch that keeps measured poses; max_rejects > 0 on a batch that no longer keeps its initial covariances; a batch
+ * without resident kernels or with several (Q, R) classes.  A batch that grew past ld since the call is refused at ..._live_start.
+ * The gated session runs a kernel of its own (the pose / query session's tick loop with the gate inside; a plain and a pose /
+ * query session keep theirs): once a gate is set, ..._live_capacity reports THAT kernel's capacity, at most the ungated figure.
+ * ..._live_gate_served: 1 if this batch has a gated resident kernel, 0 if not (..._live_set_gate then refuses), -1 on error.  Every
+ * (model, precision) with resident kernels has one, at zero scratch (profiles/live_gate_kernel_resources.txt).
+ * Not served: the innovations nu (NIS only, as by id); target_batch_step_fused still has neither gate nor policy. */
+struct target_innov_stream_c;   /* (both defined below, with the launched calls they were made for) */
+struct target_reacquire_c;
+int target_batch_live_set_gate(target_batch_c* b, double nis_max, const struct target_innov_stream_c* nis, const struct target_reacquire_c* reacq);
+int target_batch_live_gate_served(target_batch_c* b);
 int target_batch_live_post(target_batch_c* b, long n_ticks);
 /* n_ticks doorbells of ONE tick each, back to back (what a caller's loop of ..._live_post(b, 1) does, without its call overhead) */
 int target_batch_live_post_each(target_batch_c* b, long n_ticks);
@@ -415,7 +450,8 @@ int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, do
  * target_manager_last_error set, and nothing is launched.  A NULL `innov` (or per_batch_innov), or a NULL nis_dev, gives exactly
  * the ..._poses call.  target_batch_algorithmic_bytes keeps reporting the plain tick: the stream adds 8 B per target and tick
  * for NIS, plus 8 * m B for the innovations.
- * Not served (no innovation stream there): target_batch_step_fused, the resident mode (target_batch_live_*); by id only NIS is
+ * Not served (no innovation stream there): target_batch_step_fused; the resident mode (target_batch_live_*) reports NIS rows only,
+ * through the gate of its sessions (target_batch_live_set_gate), not nu; by id only NIS is
  * reported (target_manager_update_meas_batch_gated below), not nu. */
 typedef struct target_innov_stream_c {
   double* nis_dev;          /* device memory; NULL = no innovation stream for this batch */
@@ -457,7 +493,7 @@ int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, do
  * mask from the NIS row just written, into a row the library owns, and the plain step takes that row -- three launches per tick,
  * one more than ..._innov.  Poses and the fused query in the same
  * call, use_graph (a recorded graph is keyed by the gate too) and every other argument: as for ..._innov.
- * Not served: target_batch_step_fused, the resident mode.  The by-id / indexed launches, the one-target symbols and the Eigen
+ * Not served: target_batch_step_fused.  The resident mode gates inside its sessions (target_batch_live_set_gate).  The by-id / indexed launches, the one-target symbols and the Eigen
  * facade are gated through the sticky policy of target_manager_set_update_gate below. */
 int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
@@ -502,7 +538,8 @@ int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, do
  * stays in the form.
  * A gate at a chi-square quantile re-initialises often on a stream that is not chi-square consistent:
  * choose nis_max for the outliers to be kept out, K for the time a lost target may coast.
- * Not served: target_batch_step_fused, the resident mode; M-of-N logic other than K consecutive; a velocity from two
+ * Not served: target_batch_step_fused (the resident mode keeps the runs and re-acquires inside its sessions:
+ * target_batch_live_set_gate); M-of-N logic other than K consecutive; a velocity from two
  * measurements.  The by-id / indexed launches, the one-target symbols and the Eigen facade re-acquire through the sticky policy
  * of target_manager_set_update_gate below. */
 typedef struct target_reacquire_c {
@@ -555,7 +592,7 @@ int target_manager_get_rejection_run(target_manager_c* m, unsigned int id);
  * longer keeps its initial covariances.  target_manager_update_gate_served asks up front.  The void one-target symbol reports
  * through target_manager_last_error, as its other failures do.
  * Not served: the innovations nu by id (NIS only); per-class, dense-layout and keep-measurement batches by id;
- * target_batch_step_fused; the resident mode. */
+ * target_batch_step_fused.  (The resident mode ignores this policy and has a gate of its own: target_batch_live_set_gate.) */
 int  target_manager_set_update_gate(target_manager_c* m, int type, double nis_max, int max_rejects);
 int  target_manager_get_update_gate(target_manager_c* m, int type, double* nis_max, int* max_rejects);
 /* 1 if by-id updates of this model's batch would be served under a policy, 0 if not (see "refused"), -1 unknown */

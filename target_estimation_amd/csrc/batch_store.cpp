@@ -1011,7 +1011,14 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     throw std::invalid_argument("target_estimation_amd: live_start: bad measurement ring");
   if (max_ticks > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: live_start: at most 2^31 - 1 ticks per session");
   if (n_classes_ > 1) throw std::runtime_error("target_estimation_amd: live mode serves batches with one (Q, R) class");
-  long cap = ops_->live_capacity ? ops_->live_capacity((q_delta_dev || live_.pose_out) ? 1 : 0) : 0;
+  const InnovStream& lgate = live_.gate;
+  if (lgate.gated()) {   // (what may have changed since live_set_gate)
+    if (const char* why = live_gate_refusal()) throw std::runtime_error(why);
+    if (lgate.ld < n_ || (lgate.reacq.event && lgate.reacq.ld < n_))
+      throw std::invalid_argument("target_estimation_amd: live gate: rows shorter than the batch (it grew since live_set_gate)");
+    if (lgate.reacq.on && lgate.reacq.k > 0) prepare_p0_tables();   // (throws if the batch no longer keeps its initial covariances)
+  }
+  long cap = ops_->live_capacity ? ops_->live_capacity(live_kernel_next(q_delta_dev != nullptr)) : 0;
   if (const char* e = std::getenv("TE_LIVE_CAPACITY_WAVES")) { if (cap > 0 && std::atol(e) > 0) cap = std::atol(e); }   // experiments only (tools/live_capacity.py --probe)
   if (cap <= 0) throw std::runtime_error("target_estimation_amd: live mode needs the axis-separable layout with packed groups");
   const long waves = (n_ + ops_->L.tpw - 1) / ops_->L.tpw;
@@ -1110,10 +1117,19 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     p.q_origin[0] = q_origin[0]; p.q_origin[1] = q_origin[1]; p.q_origin[2] = q_origin[2];
     p.q_radius = q_radius; p.q_delta = q_delta_dev; p.q_pose = q_pose_dev;
   }
+  if (lgate.gated()) {
+    p.live_gate = 1; p.live_gate_nis_max = lgate.gate;
+    p.live_gate_nis = lgate.nis; p.live_gate_nis_stride = lgate.nis_tick_stride; p.live_gate_nis_ring = lgate.ring;
+    p.live_gate_k = lgate.reacq.on ? lgate.reacq.k : -1;
+    if (lgate.reacq.on) {
+      p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+      p.live_gate_event = lgate.reacq.event; p.live_gate_event_stride = lgate.reacq.tick_stride; p.live_gate_event_ring = lgate.reacq.ring;
+    }
+  }
   ops_->step(p, live_.stream);   // (the measured-pose rows are not kept during a live session: see measured_pose.hpp)
   TE_HIP_CHECK(hipGetLastError());
   live_.waves = waves; live_.posted = 0; live_.max_ticks = max_ticks; live_.dt = dt;
-  live_.all_measured = has_ring == nullptr;
+  live_.all_measured = has_ring == nullptr && !lgate.gated();   // (a gated session counts its accepted measurements per slot)
   // The session exists once its LAST workgroup (the relay) says so: then every worker holds its wave slot.  A kernel that is
   // still queued after two seconds is not going to run next to whatever is ahead of it (its stream shares a hardware queue with
   // another endless kernel -- more live batches than GPU_MAX_HW_QUEUES, or a caller's own high-priority stream -- or the device
@@ -1152,6 +1168,43 @@ void Batch::live_set_pose_output(double* pose_soa_dev, long ld) {
   if (pose_soa_dev && ld < n_) throw std::invalid_argument("target_estimation_amd: live pose output: rows shorter than the batch");
   live_.pose_out = pose_soa_dev;
   live_.pose_ld = pose_soa_dev ? ld : 0;
+}
+
+const char* Batch::live_gate_refusal() const {
+  const Ops* o = shared_axes() ? get_ops(type_, dtype_, lanes_code_) : ops_;
+  if (!o || !o->live_capacity || o->L.layout != LAYOUT_SEPARABLE_PACKED)
+    return "target_estimation_amd: live gate: no gated resident kernel for this batch (live mode needs the axis-separable layout with packed groups)";
+  if (n_classes_ > 1) return "target_estimation_amd: live gate: live mode serves batches with one (Q, R) class";
+  if (keep_meas_) return "target_estimation_amd: live gate: not served for a batch that keeps measured poses (set_keep_measurement)";
+  return nullptr;
+}
+
+void Batch::live_set_gate(const InnovStream& g) {
+  const std::string pre = "target_estimation_amd: live gate: ";
+  if (!(g.gate >= 0.0)) throw std::invalid_argument(pre + "nis_max must be 0 (no gate) or positive");
+  if (!g.gated()) {
+    if (g.reacq.on) throw std::invalid_argument(pre + "a policy needs the gate (nis_max > 0): it counts the gate's rejections");
+    touch();   // (a session that runs keeps the gate it started with; the next one has none)
+    live_.gate = InnovStream{};
+    return;
+  }
+  if (!g.nis) throw std::invalid_argument(pre + "nis_max > 0 needs the NIS rows of the session (nis_dev): they report the decisions");
+  if (g.innov) throw std::invalid_argument(pre + "the innovations are not served in resident sessions (innov_dev must be NULL)");
+  if (g.ld < n_) throw std::invalid_argument(pre + "ld " + std::to_string(g.ld) + " < batch size " + std::to_string(n_));
+  if (g.nis_tick_stride < 0 || (g.nis_tick_stride > 0 && g.nis_tick_stride < g.ld)) throw std::invalid_argument(pre + "nis_tick_stride must be 0 or >= ld");
+  if (g.ring < 0) throw std::invalid_argument(pre + "negative ring_ticks");
+  if (g.reacq.on) {
+    if (g.reacq.k < 0 || g.reacq.k > 127) throw std::invalid_argument(pre + "max_rejects must be 0..127, got " + std::to_string(g.reacq.k));
+    if (g.reacq.event) {
+      if (g.reacq.ld < n_) throw std::invalid_argument(pre + "event rows: ld " + std::to_string(g.reacq.ld) + " < batch size " + std::to_string(n_));
+      if (g.reacq.tick_stride < 0 || (g.reacq.tick_stride > 0 && g.reacq.tick_stride < g.reacq.ld)) throw std::invalid_argument(pre + "event rows: tick_stride must be 0 or >= ld");
+      if (g.reacq.ring < 0) throw std::invalid_argument(pre + "event rows: negative ring_ticks");
+    }
+    if (g.reacq.k > 0 && !p0_kept_) throw std::invalid_argument(pre + "max_rejects > 0: the batch no longer keeps its initial covariances (too many distinct ones)");
+  }
+  if (const char* why = live_gate_refusal()) throw std::runtime_error(why);
+  touch();   // (ends a session that runs: it keeps the gate it started with)
+  live_.gate = g;
 }
 
 void Batch::live_post(long n_ticks) {

@@ -187,6 +187,15 @@ class Batch {
   // src/target_manager_ros.cpp:78-87), through the caches and before the tick counts as done -- a consumer that copies the
   // buffer on another stream after live_done() reached tick k reads the poses of a tick >= k (of tick k if it posts one tick at a time)
   void live_set_pose_output(double* pose_soa_dev, long ld);
+  // THE GATE INSIDE THE SESSIONS started AFTER this call (target_batch_live_set_gate; kf_step_sep.hpp, LiveGate): g.gate > 0 with
+  // the NIS rows of the session (g.nis; no innovation block) and, or not, the policy g.reacq -- the semantics per slot and tick of
+  // step_sequence with the same stream, decided inside the resident kernel.  Tick k of a session writes NIS row and event row
+  // k (or k % ring) through the caches, ahead of the tick's progress word.  The rejection runs are read when a session starts and
+  // written back with its records.  !g.gated(): off.  Refusals throw and change nothing; live_gate_refusal says why this batch
+  // cannot serve a gate at all (no resident kernel, several (Q, R) classes, measured-pose rows), or null.
+  void live_set_gate(const InnovStream& g);
+  const char* live_gate_refusal() const;
+  bool live_gate_set() const { return live_.gate.gated(); }
   void live_post(long n_ticks);
   long live_done() const;
   bool live_wait(long tick, double timeout_s) const;
@@ -194,10 +203,14 @@ class Batch {
   bool live_active() const { return live_.active; }
   // targets a session can hold; with_outputs: one with the per-tick query or pose output (a larger kernel: fewer)
   // (a shared-axes batch answers for the plain form, which is what live_start would run)
-  long live_capacity_targets(bool with_outputs = false) const {
+  // kernel: 0 plain, 1 with outputs, 2 the gated one (Ops::live_capacity)
+  long live_capacity_targets(int kernel = 0) const {
     const Ops* o = shared_axes() ? get_ops(type_, dtype_, lanes_code_) : ops_;
-    return o->live_capacity ? o->live_capacity(with_outputs ? 1 : 0) * o->L.tpw : 0;
+    return o->live_capacity ? o->live_capacity(kernel) * o->L.tpw : 0;
   }
+  // ... of the kernel the NEXT session would run (query: one with the per-tick query)
+  long live_capacity_next(bool query = false) const { return live_capacity_targets(live_kernel_next(query)); }
+  int live_kernel_next(bool query) const { return live_.gate.gated() ? 2 : (query || live_.pose_out) ? 1 : 0; }
   bool live_pose_output_set() const { return live_.pose_out != nullptr; }
   bool live_running() const { return live_.active && __atomic_load_n(live_.h_done + 2, __ATOMIC_ACQUIRE) == 0; }   // the relay has not left (its last store)
   // THE UPDATE POLICY OF THE BY-ID PATHS (UpdateGate, reacquire_plan.hpp; target_manager_set_update_gate).  While it is on, every
@@ -516,6 +529,7 @@ class Batch {
     char* d_block = nullptr;         // device memory: [mirror word, padded to 64 B][progress words of the wavefronts]
     double* pose_out = nullptr;      // per-tick pose output (live_set_pose_output)
     long pose_ld = 0;
+    InnovStream gate{};              // the gate of the sessions to come (live_set_gate); !gated(): none
     hipStream_t stream = nullptr;    // the resident kernel's own stream
     hipEvent_t ready = nullptr;
     long waves = 0, cap_waves = 0;

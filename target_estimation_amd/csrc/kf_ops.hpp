@@ -97,6 +97,18 @@ struct StepParams {
   int gate_id = 0;
   int gate_id_k = -1;
   unsigned char* gate_id_event = nullptr;
+  // The gate INSIDE a resident launch (target_batch_live_set_gate; kf_step_sep.hpp, LiveGate): live_gate = 1 with live_posted
+  // selects the gated resident kernel (kf_step_sep_live_gate_kernel).  Tick k of the session writes its NIS row at live_gate_nis +
+  // (ring > 0 ? k % ring : k) * stride and, with live_gate_event, its event row likewise.  live_gate_k: -1 = gate only; 0..127 = the
+  // rejection runs, read from reacq_run when the session starts and written back when its kernel leaves, re-initialising on the
+  // k-th consecutive rejection (k > 0) with P0 = reacq_p0 + reacq_p0_idx[slot] * N*N.  gate / nis / reacq / gate_id stay 0.
+  int live_gate = 0;
+  double live_gate_nis_max = 0.0;
+  double* live_gate_nis = nullptr;
+  long live_gate_nis_stride = 0, live_gate_nis_ring = 0;
+  int live_gate_k = -1;
+  unsigned char* live_gate_event = nullptr;
+  long live_gate_event_stride = 0, live_gate_event_ring = 0;
 };
 
 // The launch behind a gated tick that keeps the rejection runs and re-initialises lost targets (kf_reacquire_impl.hpp).
@@ -130,7 +142,8 @@ struct Ops {
   int wpb;  // wavefronts per workgroup of the step kernel
   void (*step)(const StepParams&, hipStream_t);
   // wavefronts of the live kernel the device can hold at once (0: this (model, precision, layout) has no live kernel)
-  long (*live_capacity)(int with_outputs);   // resident wavefronts of the plain / the query-and-pose-output variant
+  // resident wavefronts of the plain (0) / the query-and-pose-output (1) / the gated (2: kf_step_sep_live_gate_kernel) variant
+  long (*live_capacity)(int with_outputs);
   void (*init)(const InitArgs&, hipStream_t);
   // tile_blk / tile_uni: the batch's uniform tiles, honoured read-only (null: none)
   void (*get_state)(char* rec, const int* idx, long n, double* x, double* P, const double* tile_blk, const int* tile_uni, hipStream_t);

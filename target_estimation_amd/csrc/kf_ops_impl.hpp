@@ -48,6 +48,13 @@ void launch_sep_gate_step(const StepArgs<T>& a, double gate, unsigned blocks, un
 template <class M, typename T, int LAYOUT>
 void launch_sep_gate_id_step(const StepArgs<T>& a, const GateById& g, unsigned blocks, unsigned threads, hipStream_t s);
 
+// The gated resident kernels (kf_step_sep.hpp, kf_step_sep_live_gate_kernel), in kf_live_gate_{uv,ua,ar,av}.hip
+// (kf_live_gate_impl.hpp) likewise; live_gate_blocks_per_cu is the occupancy query about them, made where they are instantiated.
+template <class M, typename T, int LAYOUT>
+void launch_sep_live_gate_step(const StepArgs<T>& a, const LiveGate& g, unsigned blocks, unsigned threads, hipStream_t s);
+template <class M, typename T, int LAYOUT>
+int live_gate_blocks_per_cu();
+
 // reacquire_kernel (kf_reacquire_impl.hpp), in kf_reacquire_{uv,ua,ar,av}.hip likewise: one instance per OpsImpl.
 template <class M, typename T, int G, int LAYOUT>
 void launch_reacquire(const ReacquireArgs& a, hipStream_t s);
@@ -57,14 +64,20 @@ struct OpsImpl {
   using C = Cfg<M, T, G, LAYOUT>;
 
   static constexpr bool kHasLive = LAYOUT == LAYOUT_SEPARABLE_PACKED;
-  static long live_capacity(int with_outputs) {   // with_outputs: the variant with the per-tick query / pose output (kLive2)
+  // with_outputs: 1 = the variant with the per-tick query / pose output (kLive2), 2 = the gated one (kf_step_sep_live_gate_kernel)
+  static long live_capacity(int with_outputs) {
     if constexpr (kHasLive) {
       int per_cu = 0, dev = 0;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-      const void* kernel = with_outputs ? (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive2>
-                                        : (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive1>;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) return 0;
+      if (with_outputs == 2) {
+        per_cu = live_gate_blocks_per_cu<M, T, LAYOUT>();
+        if (per_cu <= 0) return 0;
+      } else {
+        const void* kernel = with_outputs ? (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive2>
+                                          : (const void*)kf_step_sep_kernel<M, T, LAYOUT, kFused | kLive1>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) return 0;
+      }
       // Measured on an MI355X with the relay's start word (tools/live_capacity.py --probe, profiles/r03_live_capacity.txt): the
       // largest grid that becomes resident is the query's figure for every kernel at up to 6 wavefronts per SIMD, but 28 per CU
       // where the query says 32 (8 per SIMD).  And a device that full starves everybody else: with 22 or more resident
@@ -136,6 +149,17 @@ struct OpsImpl {
       throw std::runtime_error("target_estimation_amd: the update gate by id: no gated indexed kernel for this batch");
     }
   }
+  static void launch_live_gate(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (kHasLive) {
+      LiveGate g;
+      g.gate = p.live_gate_nis_max; g.nis = p.live_gate_nis; g.nis_stride = p.live_gate_nis_stride; g.nis_ring = p.live_gate_nis_ring;
+      g.k = p.live_gate_k; g.run = p.reacq_run; g.p0_tab = p.reacq_p0; g.p0_idx = p.reacq_p0_idx;
+      g.event = p.live_gate_event; g.event_stride = p.live_gate_event_stride; g.event_ring = p.live_gate_event_ring;
+      launch_sep_live_gate_step<M, T, LAYOUT>(a, g, blocks, threads, s);
+    } else {
+      throw std::runtime_error("target_estimation_amd: the resident gate: no resident kernel for this batch");
+    }
+  }
   // The launches of a request are plan_step's (step_variant.hpp): [innovation writer,] then once, or once per tick, the step
   // kernel [and the pose writer].
   static void step(const StepParams& p, hipStream_t s) {
@@ -144,7 +168,8 @@ struct OpsImpl {
     const long waves = (p.n + C::TPW - 1) / C::TPW;
     if (sv_live(plan.variant)) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
       // + 1: the relay wavefront (kf_step.hpp live_relay)
-      launch_variant(plan.variant, make_step_args<T>(p), (unsigned)waves + 1, 64, s);
+      if (plan.live_gated) launch_live_gate(make_step_args<T>(p), p, (unsigned)waves + 1, 64, s);
+      else launch_variant(plan.variant, make_step_args<T>(p), (unsigned)waves + 1, 64, s);
       return;
     }
     StepParams q = p;

@@ -353,6 +353,7 @@ template <class C, class M, typename T> struct LivePark {
 // has-bit in everything behind it: the measurement counter (always added to nm_base) and the uniform-tile agreement (always
 // tested).  `gate` is an argument of its own, not a field of StepArgs, whose size is part of every existing kernel's descriptor;
 // 0 = no gate (a part of a gated population launch without one): acc = has.
+// GATE with LIVE == 2 (and without INNOV): the same two-phase body inside the resident tick loop, LiveGate below.
 // BYID: the by-id update policy (target_manager_set_update_gate) in the gated INDEXED tick: GateById below, whose tail runs per
 // valid lane behind the decision and ahead of store_record -- the slot's rejection run by target_reacquire_c's table and, on the
 // K-th consecutive rejection, the record re-initialised IN REGISTERS from this entry's measurement exactly as init_kernel /
@@ -369,6 +370,34 @@ struct GateById {
   const int* p0_idx;        // [slots] row of every slot
   unsigned char* event;     // [entries] this call's event bytes, or null
 };
+
+// LIVE GATE: the validation gate and the re-acquisition policy INSIDE a resident session (kf_step_sep_live_gate_kernel: VAR =
+// kFused | kLive2 with GATE; target_batch_live_set_gate).  The two-phase body runs in every tick of the resident loop, and the
+// policy tail behind it: no launch can follow a resident tick, so the rejection run lives in a register for the whole session
+// (read from LiveGate::run at its start, written back with the records when the kernel leaves) and a lost target is
+// re-initialised in registers -- and in the parked part of the record (LivePark) -- exactly as the by-id tail does it.  Tick k of
+// the session (0 at its start) writes NIS row b = (nis_ring > 0 ? k % nis_ring : k) and the event row likewise: lane = column, so
+// a wavefront writes 64 consecutive doubles / bytes, with system-scope stores issued ahead of the wait that precedes the tick's
+// progress word -- a consumer may copy them on another stream once `done` has reached k + 1.  Nothing here waits, and every
+// branch on a slot's decision is lane-predicated arithmetic and stores inside the tick: the protocol is the plain session's.
+struct LiveGate {
+  double gate;              // nis_max (> 0)
+  double* nis;              // NIS rows of the session
+  long nis_stride;          // doubles between consecutive rows (0: one row)
+  long nis_ring;            // > 0: the rows form a ring
+  int k;                    // -1: gate only (runs untouched); 0: count only; 1..127: re-initialise on the k-th consecutive rejection
+  unsigned char* run;       // [n] rejection runs (Batch::d_run_); unread with k < 0
+  const double* p0_tab;     // [rows][N*N] initial covariances; unread with k <= 0
+  const int* p0_idx;        // [n] row of every slot
+  unsigned char* event;     // event rows of the session, or null
+  long event_stride;        // bytes between consecutive rows (0: one row)
+  long event_ring;
+};
+
+// The resident kernel reads it where it arrived, in the kernel-argument segment (constant address space: scalar loads), and
+// afresh in every tick: the resident loops have no scalar register to spare (they hold Q and R there), and eleven words that stay
+// live across the whole loop are spilled -- which the compiler accounts as scratch, and a resident kernel must have none.
+typedef const LiveGate __attribute__((address_space(4))) LiveGateArg;
 
 // The form of the re-initialisation per instantiation.  In registers (above) where that costs no wavefront per SIMD against the
 // same kernel without it; elsewhere the record is written once more BEHIND store_record, word by word through state_set /
@@ -387,16 +416,19 @@ constexpr bool gate_id_tail_in_registers() {
 }
 
 template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false>
-__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0, const GateById* gid = nullptr) {
+__device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0, const GateById* gid = nullptr,
+                                              const LiveGateArg* lg = nullptr) {
   constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
                  AB = sv_has(VAR, kAB), POSE = sv_has(VAR, kPose), INNOV = sv_has(VAR, kInnov);
   constexpr int LIVE = sv_live(VAR);
   using C = Cfg<M, T, 1, LAYOUT>;
   static_assert(C::SEP, "separable layouts only");
   static_assert(sep_variant_ok(VAR, C::SHARED), "no such variant of the separable step (step_variant.hpp)");
-  static_assert(!GATE || INNOV, "the gate decides on the NIS of the innovation stream's kernels");
+  constexpr bool LGATE = GATE && LIVE != 0;   // the gate inside a resident session (LiveGate)
+  static_assert(!GATE || INNOV || LIVE == 2, "the gate decides on the NIS of the innovation stream's kernels, or inside the resident kLive2 loop");
   static_assert(BYID == (INNOV && INDEXED) && (!BYID || GATE), "kInnov | kIndexed is the gated by-id step and nothing else");
   if constexpr (!BYID) (void)gid;
+  if constexpr (!LGATE) (void)lg;
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -561,7 +593,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   auto lead = [](int i) constexpr { return !C::SHARED || i % 3 == 0; };
   constexpr int NCOV = C::SHARED ? NLIN / 3 : NLIN;   // chains whose covariance half runs
   constexpr int QR_NEED = NCOV * LB * LB + NCOV + (M::EKF ? 36 + 9 : 0);
-  constexpr bool HOIST_QR = !PERQR && QR_NEED * (int)sizeof(T) <= 256;
+  // (the gated resident angular-rates fp32 kernel: its 60 hoisted words next to the gate's own push scalar registers out to
+  // scratch -- 68 B, and a resident kernel must have none; it reads Q and R chain by chain instead)
+  constexpr bool HOIST_QR = !PERQR && QR_NEED * (int)sizeof(T) <= 256 && !(LGATE && M::TYPE == ANGULAR_RATES && sizeof(T) == 4);
   T Qlin[HOIST_QR ? NLIN : 1][LB][LB], Rlin[HOIST_QR ? NLIN : 1], Qatt[HOIST_QR && M::EKF ? 6 : 1][6], Ratt[HOIST_QR && M::EKF ? 3 : 1][3];
   if constexpr (HOIST_QR) {
 #pragma unroll
@@ -585,11 +619,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
   // INNOV: the tick's innovations (measurement order = state rows 0..m-1) and the NIS sum (one tick per launch)
-  constexpr int MI = INNOV ? (M::ANGULAR ? 6 : 3) : 1;
+  constexpr int MI = (INNOV || LGATE) ? (M::ANGULAR ? 6 : 3) : 1;
   T nu_all[MI], nis = T(0);
 #pragma unroll
   for (int c = 0; c < MI; ++c) nu_all[c] = T(0);
-  if constexpr (!INNOV) { (void)nu_all; (void)nis; }
+  if constexpr (!INNOV && !LGATE) { (void)nu_all; (void)nis; }
   // GATE: what the update behind the decision takes from the prediction -- per chain 1 / S and the column P^-[1:,0] (the packed
   // records keep the upper triangle only), the unwrapped angles -- and the two masks: the tick's has-bit for the stream, acc for the rest
   constexpr int NGATE = GATE ? NCOV : 1;            // one entry per chain whose covariance half runs
@@ -602,6 +636,14 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   T by_y[(BYID && !TAIL_REGS) ? (M::ANGULAR ? 7 : 3) : 1];
   bool by_reinit = false;
   if constexpr (!BYID || TAIL_REGS) { (void)by_y; (void)by_reinit; }
+  // LGATE: the slot's rejection run, in a register for the whole session
+  unsigned live_run = 0;
+  long live_nis_row = 0, live_event_row = 0;   // row of the tick at hand: k, or k % ring
+  if constexpr (LGATE) {
+    if (lg->k >= 0 && valid) live_run = lg->run[entry];
+  } else {
+    (void)live_run; (void)live_nis_row; (void)live_event_row;
+  }
   int n_has = 0;
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
@@ -611,7 +653,12 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     // (the worker's own limit is a backstop far behind the relay's: a relay round is a PCIe read + a scan, a worker poll an L2 hit)
     if (!live_wait_tick(a.live_mirror + (wave_id / kLiveGroup) * kLiveMirrorStride, a.live_posted, (long long)tick + 1, a.live_spin_limit < 0x07000000u ? 32u * a.live_spin_limit + 10000000u : 0xffffffffu, live_seen, lane, a.live_flags)) break;
     slot_tick = (a.live_first + tick) % a.live_ring;
+    if constexpr (LGATE) nis = T(0);   // (one sum per tick)
   }
+  LiveGateArg* lgt = lg;   // LGATE: this tick's view of the gate's arguments (see LiveGateArg)
+  if constexpr (LGATE) asm volatile("" : "+s"(lgt));
+  else (void)lgt;
+#define GATE_T_ (LGATE ? lgt->gate : gate)
   const T* meas_t = a.meas ? a.meas + slot_tick * a.tick_stride : nullptr;
   const unsigned char* has_t = a.has_meas ? a.has_meas + slot_tick * a.has_stride : nullptr;
   // Every measurement word of the tick is requested up front, right behind the record loads and regardless
@@ -686,6 +733,10 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
 #define XW_(r) mem[C::X_OFF + (r)]
+  // the GATE body's words: a register, or in a resident session (NPARK > 0) possibly a parked word.  Macros with the constant test
+  // in front, not RD / WR: the launched gated kernels must compile to what they were
+#define GR_(w_) (((NPARK > 0) && Park::SLOT.v[(w_)] >= 0) ? park_lds[Park::SLOT.v[(w_)] * 64 + lane] : mem[(w_)])
+#define GW_(w_, val_) do { if ((NPARK > 0) && Park::SLOT.v[(w_)] >= 0) park_lds[Park::SLOT.v[(w_)] * 64 + lane] = (val_); else mem[(w_)] = (val_); } while (0)
 #define UWW_(s) mem[C::UW_OFF + (s)]
 #define XR_(r) RD(C::X_OFF + (r))
 #define XS_(r, v) WR(C::X_OFF + (r), (v))
@@ -703,7 +754,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         for (int b = 0; b < LB; ++b)
 #pragma unroll
           for (int c = 0; c < LB; ++c) {
-            Pb[b][c] = mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            Pb[b][c] = GR_(C::PWORD.v[i + STRIDE * b][i + STRIDE * c]);   // (GR_ / GW_: a parked word in a resident session)
             if constexpr (HOIST_QR) Qb[b][c] = Qlin[i][b][c];
             else Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
           }
@@ -717,12 +768,12 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         for (int b = 0; b < LB; ++b) {
           g_pcol[ic][b] = Pb[b][0];
 #pragma unroll
-          for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]] = Pb[b][c];
+          for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) GW_(C::PWORD.v[i + STRIDE * b][i + STRIDE * c], Pb[b][c]);
         }
       }
       T xs[LB];
 #pragma unroll
-      for (int b = 0; b < LB; ++b) xs[b] = XW_(i + STRIDE * b);
+      for (int b = 0; b < LB; ++b) xs[b] = GR_(C::X_OFF + i + STRIDE * b);
       T y = 0;
       if (has) {
         if (!M::ANGULAR || i < 3) {
@@ -741,7 +792,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
         }
       }
 #pragma unroll
-      for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
+      for (int b = 0; b < LB; ++b) GW_(C::X_OFF + i + STRIDE * b, xs[b]);
+      if constexpr (NPARK > 0) __builtin_amdgcn_sched_barrier(0);   // a parked chain's words are read when its turn comes, not ahead of it
     }
   } else if constexpr (C::SHARED) {
     // one covariance half per kind of axis (its lead axis i % 3 == 0 owns the kind's block), one state half per axis
@@ -1007,7 +1059,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
           }
         }
       }
-      acc = has && (gate == 0.0 || (double)nis <= gate);
+      acc = has && (GATE_T_ == 0.0 || (double)nis <= GATE_T_);
       if (acc) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) UWW_(c) = g_uw[c];
@@ -1127,7 +1179,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   }
 
   if constexpr (GATE) {
-    if constexpr (!M::EKF) acc = has && (gate == 0.0 || (double)nis <= gate);
+    if constexpr (!M::EKF) acc = has && (GATE_T_ == 0.0 || (double)nis <= GATE_T_);
     n_has += acc ? 1 : 0;
     // phase B: the unwrap memory and every chain's update, from the 1 / S, P^-[:,0] and nu of phase A.  As in the shared form's
     // plain loop, a lead axis forms the gain and runs the covariance half; every axis runs its state half with that gain.
@@ -1148,21 +1200,79 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
           for (int b = 0; b < LB; ++b)
 #pragma unroll
-            for (int c = 0; c < LB; ++c) Pb[b][c] = (c == 0) ? g_pcol[ic][b] : mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            for (int c = 0; c < LB; ++c) Pb[b][c] = (c == 0) ? g_pcol[ic][b] : GR_(C::PWORD.v[i + STRIDE * b][i + STRIDE * c]);
           sep_gate_update_P<LB, T>(Pb, Kg);
 #pragma unroll
           for (int b = 0; b < LB; ++b)
 #pragma unroll
-            for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) mem[C::PWORD.v[i + STRIDE * b][i + STRIDE * c]] = Pb[b][c];
+            for (int c = ((C::SEPPK || C::SHARED) ? b : 0); c < LB; ++c) GW_(C::PWORD.v[i + STRIDE * b][i + STRIDE * c], Pb[b][c]);
         }
         T xs[LB];
 #pragma unroll
-        for (int b = 0; b < LB; ++b) xs[b] = XW_(i + STRIDE * b);
+        for (int b = 0; b < LB; ++b) xs[b] = GR_(C::X_OFF + i + STRIDE * b);
         sep_gate_update_x<LB, T>(xs, Kg, nu_all[i]);
 #pragma unroll
-        for (int b = 0; b < LB; ++b) XW_(i + STRIDE * b) = xs[b];
+        for (int b = 0; b < LB; ++b) GW_(C::X_OFF + i + STRIDE * b, xs[b]);
+        if constexpr (NPARK > 0) __builtin_amdgcn_sched_barrier(0);
       }
     }
+  }
+  if constexpr (LGATE) {
+    // the policy tail of the resident tick (LiveGate): the run in its register, the event byte and -- rarely -- the record's words
+    // replaced where they live, registers and parked words alike; then the tick's NIS and event rows, lane = column
+    unsigned char ev = 0;
+    if (lgt->k >= 0 && g_has) {   // (g_has: a valid lane with a measurement)
+      unsigned run = 0;
+      if (!acc) {   // rejected (a NaN rejects)
+        const unsigned c1 = live_run + 1 < 127u ? live_run + 1 : 127u;
+        ev = (unsigned char)c1; run = c1;
+        if (lgt->k > 0 && c1 >= (unsigned)lgt->k) {   // a candidate: x0 as init_kernel forms it, re-initialised iff finite
+          T x0[N];
+#pragma unroll
+          for (int r = 0; r < N; ++r) x0[r] = 0;
+          if constexpr (M::ANGULAR) {
+            T p6[6];
+            pose7_to_pose6(ymeas, p6);
+#pragma unroll
+            for (int c6 = 0; c6 < 6; ++c6) x0[c6] = p6[c6];
+          } else {
+#pragma unroll
+            for (int c3 = 0; c3 < 3; ++c3) x0[c3] = ymeas[c3];
+          }
+          bool reinit = true;
+#pragma unroll
+          for (int r = 0; r < K; ++r) reinit = reinit && (x0[r] - x0[r] == (T)0);   // finite
+          if (reinit) {
+            ev = (unsigned char)(0x80u | c1); run = 0;
+            const double* P0 = lgt->p0_tab + (long)lgt->p0_idx[entry] * N * N;
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+              XS_(r, x0[r]);
+#pragma unroll
+              for (int c = (C::SEPPK ? r : 0); c < N; ++c)
+                if (C::PWORD.v[r][c] >= 0) WR(C::PWORD.v[r][c], (T)P0[r * N + c]);   // (state_set's words, in its order)
+            }
+            if constexpr (M::ANGULAR) {
+#pragma unroll
+              for (int cc = 0; cc < 3; ++cc) UWW_(cc) = 0;
+            }
+          }
+        }
+      }
+      live_run = run;
+    }
+    if (valid) {
+      double* const nrow = lgt->nis + live_nis_row * lgt->nis_stride;
+      __hip_atomic_store(reinterpret_cast<unsigned long long*>(&nrow[entry]), (unsigned long long)__double_as_longlong(g_has ? (double)nis : -1.0),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (lgt->event != nullptr) {
+        unsigned char* const erow = lgt->event + live_event_row * lgt->event_stride;
+        __hip_atomic_store(&erow[entry], ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+    // the rows of the next tick: counted, not divided (k % ring of two 64-bit words costs the scalar registers a tick has none to spare of)
+    live_nis_row = live_nis_row + 1 == lgt->nis_ring ? 0 : live_nis_row + 1;
+    live_event_row = live_event_row + 1 == lgt->event_ring ? 0 : live_event_row + 1;
   }
   if constexpr (BYID) {
     // the policy tail (GateById): run, event byte and -- rarely -- the record's words replaced in registers
@@ -1330,7 +1440,10 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     else if constexpr (AB) store_record<C, T, false, true>(a.rec_out + tile * C::TILE_BYTES, lt, mem);   // A -> B tick (StepArgs::rec_out)
     else store_record<C, T>(tb, lt, mem);
     if constexpr (POSE && !FUSED) write_pose(0);
-    if constexpr (GATE) write_innov(g_has, nis, nu_all, MI);
+    if constexpr (LGATE) {   // the session's runs go back with its records
+      if (lg->k >= 0) lg->run[entry] = (unsigned char)live_run;
+    }
+    else if constexpr (GATE) write_innov(g_has, nis, nu_all, MI);
     else if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
     if constexpr (BYID && !TAIL_REGS) {
       if (by_reinit) {   // the record once more, behind store_record, as init_kernel / reacquire_kernel write it
@@ -1399,6 +1512,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
 #undef XW_
+#undef GR_
+#undef GATE_T_
+#undef GW_
 #undef UWW_
 #undef XR_
 #undef XS_
@@ -1431,6 +1547,21 @@ __global__ void __launch_bounds__(256) kf_step_sep_gate_kernel(const StepArgs<T>
 template <class M, typename T, int LAYOUT>
 __global__ void __launch_bounds__(256) kf_step_sep_gate_indexed_kernel(const StepArgs<T> a, const GateById g) {
   sep_step_wave<M, T, LAYOUT, kInnov | kIndexed, true, true>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate, &g);
+}
+
+// The gated resident session (sep_step_wave, GATE inside the kFused | kLive2 tick loop; LiveGate above): the third resident
+// instantiation.  Everything new travels in the second argument -- StepArgs keeps its size -- and the plain and pose / query
+// sessions keep their kernels.  Never held to a register limit (see sep_min_waves: a resident kernel must not spill); what the
+// gate's values between the two phases cost in wavefronts per SIMD is in profiles/live_gate_kernel_resources.txt, and
+// OpsImpl::live_capacity asks the occupancy query about THIS kernel.  Instantiated in kf_live_gate_{uv,ua,ar,av}.hip
+// (kf_live_gate_impl.hpp), packed groups only (the layout that has resident kernels).
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256) kf_step_sep_live_gate_kernel(const StepArgs<T> a, const LiveGate g) {
+  // `g` where the launch put it: explicit kernel arguments lie in the segment in order, each at its natural alignment
+  constexpr unsigned long G_OFF = (sizeof(StepArgs<T>) + alignof(LiveGate) - 1) / alignof(LiveGate) * alignof(LiveGate);
+  typedef const char __attribute__((address_space(4))) ArgByte;
+  LiveGateArg* gp = (LiveGateArg*)((ArgByte*)__builtin_amdgcn_kernarg_segment_ptr() + G_OFF);
+  sep_step_wave<M, T, LAYOUT, kFused | kLive2, true, false>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate, nullptr, gp);
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------

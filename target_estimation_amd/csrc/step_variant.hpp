@@ -111,6 +111,9 @@ struct StepPlan {
   // indexed kernel (kf_step_sep_gate_indexed_kernel: variant kInnov | kIndexed, the rejection runs and the re-initialisation in
   // its tail, the getter table too when the request has one).  Never together with innov_writer_first / reacquire_after_step.
   bool gate_by_id = false;
+  // the request is a resident launch with the gate inside the session (P::live_gate): the gated resident kernel
+  // (kf_step_sep_live_gate_kernel), the variant word kFused | kLive2 and the gate a template argument next to it
+  bool live_gated = false;
 };
 
 // The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
@@ -138,6 +141,17 @@ template <class P> struct has_gate_id_member<P, std::void_t<decltype(std::declva
 template <class P>
 constexpr bool requested_gate_by_id(const P& p) {
   if constexpr (has_gate_id_member<P>::value) return p.gate_id != 0;
+  else return false;
+}
+// The gate of a resident session: P::live_gate (non-zero = the launch is a resident one that gates inside its tick loop; the request
+// then has P::live_gate_nis_max (> 0), the NIS rows P::live_gate_nis / _nis_stride / _nis_ring, P::live_gate_k (-1 = gate only, 0..127
+// as P::reacq_k), the event rows P::live_gate_event / _event_stride / _event_ring and, for the runs, the pointers P::reacq_run /
+// reacq_p0 / reacq_p0_idx).  A request type without the member plans as it always did.
+template <class P, class = void> struct has_live_gate_member : std::false_type {};
+template <class P> struct has_live_gate_member<P, std::void_t<decltype(std::declval<const P&>().live_gate)>> : std::true_type {};
+template <class P>
+constexpr bool requested_live_gate(const P& p) {
+  if constexpr (has_live_gate_member<P>::value) return p.live_gate != 0;
   else return false;
 }
 template <class P>
@@ -196,12 +210,30 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
     throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
   if (p.tile_uni && (!t.uniform_tiles || p.idx || !p.tile_blk))
     throw std::runtime_error("target_estimation_amd: uniform tiles are a property of dense ticks of the shared-axes storage form");
+  if (requested_live_gate(p) && !p.live_posted)
+    throw std::runtime_error("target_estimation_amd: the resident gate belongs to a live launch (live_posted)");
   if (p.live_posted) {   // a resident launch serves its ticks, query and poses by itself
     if (!t.has_live)
       throw std::runtime_error("target_estimation_amd: live mode needs the axis-separable layout with packed groups (the automatic choice for the shipped models)");
     if (p.idx || p.cls || p.rec_out || !p.live_progress || !p.live_mirror || !p.live_done || p.live_ring <= 0 || p.n_ticks < 1)
       throw std::runtime_error("target_estimation_amd: a live launch is a dense launch of a one-class batch over a measurement ring");
     plan.variant = kFused | ((p.q_delta || p.live_pose) ? kLive2 : kLive1);
+    if constexpr (has_live_gate_member<P>::value) {
+      if (requested_live_gate(p)) {   // the gated resident kernel: the pose / query session's loop with the gate inside, or refused
+        const char* pre = "target_estimation_amd: the resident gate: ";
+        if (!(p.live_gate_nis_max > 0.0)) throw std::runtime_error(std::string(pre) + "nis_max must be positive");
+        if (!p.live_gate_nis || p.live_gate_nis_stride < 0 || p.live_gate_nis_ring < 0) throw std::runtime_error(std::string(pre) + "it reports its decisions in NIS rows");
+        if (p.live_gate_k < -1 || p.live_gate_k > 127) throw std::runtime_error(std::string(pre) + "max_rejects must be -1..127");
+        if (p.live_gate_k >= 0 && !p.reacq_run) throw std::runtime_error(std::string(pre) + "rejection runs need the batch's run row");
+        if (p.live_gate_k > 0 && (!p.reacq_p0 || !p.reacq_p0_idx)) throw std::runtime_error(std::string(pre) + "re-acquisition needs the batch's table of initial covariances");
+        if (p.live_gate_event && (p.live_gate_k < 0 || p.live_gate_event_stride < 0 || p.live_gate_event_ring < 0))
+          throw std::runtime_error(std::string(pre) + "event rows belong to a policy (max_rejects >= 0)");
+        if (p.nis || requested_reacquire(p) || requested_gate_by_id(p) || requested_gate_by_writer(p))
+          throw std::runtime_error(std::string(pre) + "not together with the launched calls' gate, streams or policies");
+        plan.variant = kFused | kLive2;
+        plan.live_gated = true;
+      }
+    }
     return plan;
   }
   if (p.o_pose && (!p.idx || (p.n > t.tpw && !p.done_count) || !p.o_twist || !p.o_acc || !p.done_flag))

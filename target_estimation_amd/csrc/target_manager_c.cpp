@@ -650,6 +650,25 @@ int target_batch_live_start(target_batch_c* b, double dt, const void* meas_ring_
 int target_batch_live_set_pose_output(target_batch_c* b, double* pose_soa_dev, long ld) {
   return guarded("target_batch_live_set_pose_output", [&] { BatchLock lk(B(b)); B(b)->live_set_pose_output(pose_soa_dev, ld); });
 }
+int target_batch_live_set_gate(target_batch_c* b, double nis_max, const target_innov_stream_c* nis, const target_reacquire_c* reacq) {
+  return guarded("target_batch_live_set_gate", [&] {
+    if (!(nis_max >= 0.0)) throw std::invalid_argument("live gate: nis_max must be 0 (no gate) or positive, got " + std::to_string(nis_max));
+    te::InnovStream g;
+    if (nis_max > 0.0 && nis) {
+      if (!nis->nis_dev) throw std::invalid_argument("live gate: nis_max > 0 needs the NIS rows of the session (nis_dev): they report the decisions");
+      if (nis->innov_dev) throw std::invalid_argument("live gate: the innovations are not served in resident sessions (innov_dev must be NULL)");
+      g = reacquire_stream(nis, nis_max, reacq, false);
+      if (reacq && reacq->event_dev == nullptr) { g.reacq.ld = 0; g.reacq.tick_stride = 0; g.reacq.ring = 0; }
+    } else if (reacq) {
+      throw std::invalid_argument("live gate: a policy needs the gate (nis_max > 0 and the NIS rows): it counts the gate's rejections");
+    }
+    BatchLock lk(B(b));
+    B(b)->live_set_gate(g);
+  });
+}
+int target_batch_live_gate_served(target_batch_c* b) {
+  return guarded_value<int>("target_batch_live_gate_served", -1, [&] { BatchLock lk(B(b)); return B(b)->live_gate_refusal() == nullptr ? 1 : 0; });
+}
 int target_batch_live_post(target_batch_c* b, long n_ticks) {
   return guarded("target_batch_live_post", [&] { BatchLock lk(B(b)); B(b)->live_post(n_ticks); });
 }
@@ -671,7 +690,7 @@ int target_batch_live_running(target_batch_c* b) {
   return guarded_value<int>("target_batch_live_running", -1, [&] { return B(b)->live_running() ? 1 : 0; });   // reads a host-mapped word: no lock
 }
 long target_batch_live_capacity(target_batch_c* b) {
-  return guarded_value<long>("target_batch_live_capacity", -1L, [&] { return B(b)->live_capacity_targets(B(b)->live_pose_output_set()); });
+  return guarded_value<long>("target_batch_live_capacity", -1L, [&] { return B(b)->live_capacity_next(); });
 }
 
 int target_manager_live_start_all(target_manager_c* m, double dt, const target_batch_sequence_c* per_batch, long n_batches, long first_entry,

@@ -267,6 +267,23 @@ class Batch:
         assert pose_soa.is_cuda and pose_soa.dtype == torch.float64 and pose_soa.dim() == 2 and pose_soa.shape[0] == 7 and pose_soa.stride(1) == 1
         _check(self._lib.target_batch_live_set_pose_output(self._h, pose_soa.data_ptr(), pose_soa.stride(0)), "target_batch_live_set_pose_output")
 
+    def live_set_gate(self, nis_max, nis_rows, reacquire=None):
+        """The NIS gate and, with reacquire=, the re-acquisition policy INSIDE the sessions started afterwards
+        (target_batch_live_set_gate), in the conventions of step_sequence(..., innov=, gate=, reacquire=).  nis_max: the gate (0 or
+        None: off; inf: gated, everything finite accepted).  nis_rows: float64 CUDA tensor [rows, ld] (or [ld]) that receives
+        tick k's NIS in row k % rows (one row: every tick overwrites it); None with nis_max off.  reacquire = (K, events_or_None),
+        events a uint8 CUDA tensor [rows, ld] (or [ld]) with its own ring of rows.  A consumer may copy row k % rows on another
+        stream once live_done() has reached k + 1.  live_capacity then reports the gated kernel's capacity."""
+        if not nis_max and nis_rows is None and reacquire is None:
+            _check(self._lib.target_batch_live_set_gate(self._h, 0.0, None, None), "target_batch_live_set_gate")
+            return
+        ins = _innov_stream((nis_rows, None), self.size, self.meas_dim, 1 << 62) if nis_rows is not None else None
+        rq = _reacquire(reacquire, self.size, 1 << 62) if reacquire is not None else None
+        _check(self._lib.target_batch_live_set_gate(self._h, 0.0 if nis_max is None else float(nis_max), None if ins is None else C.byref(ins),
+                                                    None if rq is None else C.byref(rq)), "target_batch_live_set_gate")
+
+    live_gate_served = property(lambda s: s._lib.target_batch_live_gate_served(s._h))
+
     def live_post(self, n_ticks=1):
         _check(self._lib.target_batch_live_post(self._h, int(n_ticks)), "target_batch_live_post")
 
