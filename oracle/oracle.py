@@ -61,6 +61,8 @@ def load(fast=False):
         g("orc_batch_step").argtypes = [C.c_void_p, C.c_long, C.c_double, dp,
                                         C.POINTER(C.c_ubyte), C.c_int]
         g("orc_batch_get_state").argtypes = [C.c_void_p, C.c_long, dp, dp]
+        g("orc_batch_innovations").argtypes = [C.c_void_p, C.c_long, C.c_double, dp, C.POINTER(C.c_ubyte), C.c_int,
+                                               dp, dp, dp]
         for nm in ("orc_constrain_angle", "orc_angle_conv"):
             g(nm).restype = real
             g(nm).argtypes = [real]
@@ -168,6 +170,22 @@ class OracleBatch:
             has_meas = np.ascontiguousarray(has_meas, dtype=np.uint8)
             hp = has_meas.ctypes.data_as(C.POINTER(C.c_ubyte))
         self._f("orc_batch_step")(self._at(0), self.N, float(dt), mp, hp, int(nthreads))
+
+    def innovations(self, dt, meas, has_meas=None, nthreads=1, with_pred=False):
+        """(nu [N,m], nis [N]) that step(dt, meas, has_meas) would form, in the batch's precision, rounded to
+        double; 0 and -1 where a target has no measurement.  The batch is left bit-identical (the unwrap memory
+        is read, not advanced).  with_pred=True adds hx [N,m] = C x^- (h(x^-)), what y is subtracted from."""
+        meas = _d(meas, (self.N, 7))
+        hp = C.POINTER(C.c_ubyte)()
+        if has_meas is not None:
+            has_meas = np.ascontiguousarray(has_meas, dtype=np.uint8)
+            assert has_meas.shape == (self.N,)
+            hp = has_meas.ctypes.data_as(C.POINTER(C.c_ubyte))
+        nu = np.empty((self.N, self.m)); nis = np.empty(self.N)
+        hx = np.empty((self.N, self.m)) if with_pred else None
+        self._f("orc_batch_innovations")(self._at(0), self.N, float(dt), _dp(meas), hp, int(nthreads), _dp(nu), _dp(nis),
+                                         _dp(hx) if with_pred else C.POINTER(C.c_double)())
+        return (nu, nis, hx) if with_pred else (nu, nis)
 
     def state(self):
         x = np.empty((self.N, self.n)); P = np.empty((self.N, self.n, self.n))

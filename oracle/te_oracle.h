@@ -88,6 +88,13 @@ enum {
   void orc_batch_step_##SFX(orc_target_##SFX* tgs, long n, double dt, const double* meas,         \
                             const unsigned char* has_meas, int nthreads);                         \
   void orc_batch_get_state_##SFX(const orc_target_##SFX* tgs, long n, double* x, double* P);      \
+  /* not in the reference: nu = y - C x^- and NIS = nu^T S^-1 nu as add_measurement would form    \
+   * them, in REAL, on a copy (the target is left bit-identical); hx (C x^-) may be NULL */       \
+  void orc_target_innovation_##SFX(const orc_target_##SFX* tg, double dt, const double* meas,     \
+                                   double* nu, double* nis, double* hx);                          \
+  void orc_batch_innovations_##SFX(const orc_target_##SFX* tgs, long n, double dt,                \
+                                   const double* meas, const unsigned char* has_meas,            \
+                                   int nthreads, double* nu, double* nis, double* hx);            \
   /* geometry (include/target_estimation/geometry.hpp), exported for unit tests */                \
   REAL orc_constrain_angle_##SFX(REAL x);                                                         \
   REAL orc_angle_conv_##SFX(REAL a);                                                              \

@@ -655,6 +655,69 @@ void FN(orc_batch_step)(TGT* tgs, long n, double dt, const double* meas, const u
   }
 }
 
+/* Not in the reference: the innovation and NIS that orc_target_add_measurement(tg, dt, meas) would form,
+ * computed on a copy so that the target (its unwrap memory included) is left as it was.  The steps are
+ * those of addMeasurement up to kalman.cpp:93 (update_A, predict, y with the unwrap against the stored
+ * memory, nu = y - C x^- / y - h(x^-), S = C P^- C^T + R), then NIS = nu^T (S^-1 nu), all in REAL.
+ * nu [m], *nis and the optional hx [m] (C x^- resp. h(x^-), the quantity y is subtracted from) are
+ * rounded to double on the way out. */
+void FN(orc_target_innovation)(const TGT* tg_in, double dt_d, const double* meas, double* nu, double* nis,
+                               double* hx) {
+  TGT cp = *tg_in;
+  TGT* tg = &cp;
+  const int n = tg->n, m = tg->m;
+  const REAL dt = (REAL)dt_d;
+  REAL y[ORC_MMAX], mp[7];
+  REAL CP[ORC_MMAX * ORC_NMAX], S[ORC_MMAX * ORC_MMAX] = {0}, Sinv[ORC_MMAX * ORC_MMAX];
+  REAL Cx[ORC_MMAX], innov[ORC_MMAX], w[ORC_MMAX], acc;
+  FN(update_A)(tg, dt);
+  for (int i = 0; i < 7; ++i) mp[i] = (REAL)meas[i];
+  y[0] = mp[0]; y[1] = mp[1]; y[2] = mp[2];
+  if (tg->model == ORC_ANGULAR_RATES || tg->model == ORC_ANGULAR_VELOCITIES) {
+    REAL q[4] = {mp[3], mp[4], mp[5], mp[6]};
+    REAL rpy[3];
+    FN(orc_quat_normalize)(q);
+    FN(orc_quat_to_rpy)(q, rpy);
+    for (int i = 0; i < 3; ++i) y[3 + i] = FN(orc_unwrap)(tg->meas_rpy_internal[i], rpy[i]);
+  }
+  tg->f_dt = dt;
+  FN(kf_predict)(tg);
+  FN(mm)(CP, tg->C, tg->P, m, n, n);
+  FN(mmt)(S, CP, tg->C, m, n, m);
+  for (int i = 0; i < m * m; ++i) S[i] += tg->R[i];
+  FN(orc_inverse)(m, S, Sinv);
+  if (tg->model == ORC_ANGULAR_VELOCITIES) {
+    for (int i = 0; i < m; ++i) Cx[i] = tg->x_hat_new[i];
+  } else {
+    FN(mm)(Cx, tg->C, tg->x_hat_new, m, n, 1);
+  }
+  for (int i = 0; i < m; ++i) innov[i] = y[i] - Cx[i];
+  FN(mm)(w, Sinv, innov, m, m, 1);
+  acc = innov[0] * w[0];
+  for (int i = 1; i < m; ++i) acc += innov[i] * w[i];
+  for (int i = 0; i < m; ++i) nu[i] = (double)innov[i];
+  *nis = (double)acc;
+  if (hx) for (int i = 0; i < m; ++i) hx[i] = (double)Cx[i];
+}
+
+/* orc_target_innovation over a batch; a target without a measurement gets nu = 0, nis = -1 (the
+ * stream sentinels of the product) and hx = 0.  nu [n][m], nis [n], hx [n][m] or NULL. */
+void FN(orc_batch_innovations)(const TGT* tgs, long n, double dt, const double* meas,
+                               const unsigned char* has_meas, int nthreads, double* nu, double* nis,
+                               double* hx) {
+  if (nthreads <= 0) nthreads = orc_max_threads();
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+  for (long i = 0; i < n; ++i) {
+    const int m = tgs[i].m;
+    if (meas && (!has_meas || has_meas[i])) {
+      FN(orc_target_innovation)(&tgs[i], dt, meas + 7 * i, nu + i * m, nis + i, hx ? hx + i * m : 0);
+    } else {
+      for (int j = 0; j < m; ++j) { nu[i * m + j] = 0; if (hx) hx[i * m + j] = 0; }
+      nis[i] = -1;
+    }
+  }
+}
+
 void FN(orc_batch_get_state)(const TGT* tgs, long n, double* x, double* P) {
   for (long i = 0; i < n; ++i) {
     const int nn = tgs[i].n;

@@ -16,6 +16,8 @@ What is evaluated, with the reference lines it follows:
   measurement (angular models): quaternion normalised, quatToRpy, unwrap against the previous unwrapped angles
                                                                                      angular_rates.cpp:81-88, geometry.hpp:31-76, :154-176
   initial state: position and rpy of p0, zero rates; P = P0                           src/types/*.cpp constructors, geometry.hpp:619-628
+  innovation (measured ticks): nu = y - C x- (h(x-) for the EKF), S = C P- C^T + R, w = S^-1 nu, NIS = nu^T w
+                                                                                     src/kalman.cpp:92-93, :137-138 (what a gate decides on)
 The reference never initialises the unwrap memory (meas_rpy_internal_); zero is used here, as everywhere in this
 repository.  Inputs are doubles (the YAML matrices as parsed to double, dt = 1/250, the poses below); every operation after that
 is carried out in 50 digits and the results are rounded once, to double, at the end.
@@ -229,6 +231,7 @@ def run(model, Q, R, P0, p0, dt, stream):
         C[i, i] = 1
     I = mp.eye(n)
     xs, Ps, outs = [], [], []
+    inn = dict(nu=[], nis=[], w=[], Sinv=[], pmax=[])    # the innovation stream of the measured ticks (0 / -1 / zeros on the others)
     for meas in stream:
         if model == "angular_velocities":
             A = ekf_transition(x, dt)
@@ -245,14 +248,26 @@ def run(model, Q, R, P0, p0, dt, stream):
             S = C * P * C.T + R
             K = P * C.T * (S ** -1)
             innov = matrix([y[i] - xp[i] for i in range(m)])
+            # nu = y - C x^- (h(x^-) = x^-[0:6] for the EKF), w = S^-1 nu, NIS = nu^T w: what a validation gate decides on, with
+            # what a test needs to propagate a bound on nu and P through it (S^-1, max|P^-|)
+            Sinv = S ** -1
+            w = Sinv * innov
+            inn["nu"].append([float(v) for v in innov])
+            inn["nis"].append(float((innov.T * w)[0, 0]))
+            inn["w"].append([float(v) for v in w])
+            inn["Sinv"].append([[float(Sinv[i, j]) for j in range(m)] for i in range(m)])
+            inn["pmax"].append(float(max(abs(P[i, j]) for i in range(n) for j in range(n))))
             xp = list(matrix(xp) + K * innov)
             P = (I - K * C) * P
+        else:
+            inn["nu"].append([0.0] * m); inn["nis"].append(-1.0); inn["w"].append([0.0] * m)
+            inn["Sinv"].append([[0.0] * m] * m); inn["pmax"].append(0.0)
         x = xp
         xs.append([float(v) for v in x])
         Ps.append([[float(P[i, j]) for j in range(n)] for i in range(n)])
         now, later = outputs(model, x, mpf(AHEAD))
         outs.append([float(v) for v in now[0] + now[1] + now[2] + later[0] + later[1]])    # pose7 twist6 acc6 | pose7 twist6 at t + AHEAD
-    return np.array(xs), np.array(Ps), np.array(outs)
+    return np.array(xs), np.array(Ps), np.array(outs), {k: np.array(v) for k, v in inn.items()}
 
 
 def rpy_quat(r, p, y):      # only to WRITE test inputs (plain double arithmetic; the result is the input)
@@ -337,7 +352,10 @@ def main():
         for i in range(m):
             for j in range(m):
                 R[i, j] = mpf(float(y["R"][i * m + j]))
-        xs, Ps, outs = run(model, Q, R, P0, p0, mpf(dt), stream)
+        xs, Ps, outs, inn = run(model, Q, R, P0, p0, mpf(dt), stream)
+        # nu_ [tick][m], nis_ [tick] (0 and -1 on the predict-only tick), and w_ = S^-1 nu, Sinv_, pmax_ = max|P^-| for the bounds
+        for k, v in inn.items():
+            out[k + "_" + model] = v
         out["x_" + model] = xs
         out["P_" + model] = Ps
         out["out_" + model] = outs      # [tick][pose7 twist6 acc6 | pose7 twist6 extrapolated by `ahead`]
@@ -358,8 +376,9 @@ def main():
     for i in range(6):
         for j in range(6):
             R[i, j] = mpf(float(y["R"][i * 6 + j]))
-    xs, Ps, outs = run("angular_rates", Q, R, P0, p0, mpf(dt), gstream)
+    xs, Ps, outs, inn = run("angular_rates", Q, R, P0, p0, mpf(dt), gstream)
     out.update(gimbal_meas=np.array(gstream), gimbal_x=xs, gimbal_P=Ps, gimbal_out=outs)
+    out.update({"gimbal_" + k: v for k, v in inn.items()})
     print("gimbal branches: rpy after the three ticks", xs[:, 3:6])
     ix = intersection_cases()
     out.update(ix)

@@ -7,7 +7,9 @@ The bounds come from TOL[dtype] of tests/test_gpu_parity.py, the tolerance every
 no new constant.  With e_c = x_atol + x_rtol |x^-_c| the innovation may differ by |d nu_c| <= e_c (y is exact, x^- is a state
 within the state tolerance), and to first order plus the quadratic remainder
     |d NIS| <= 2 |w|^T e + e^T |S^-1| e + P_rel max|P^-| (sum_c |w_c|)^2,
-the last term being w^T dS w with every |dS_ij| <= P_rel max|P^-| (the tolerance on P, relative to the matrix's largest entry)."""
+the last term being w^T dS w with every |dS_ij| <= P_rel max|P^-| (the tolerance on P, relative to the matrix's largest entry).
+This bound is coarse (a tenth of the NIS in fp32); tests/test_gpu_precision_streams.py holds nu and the NIS of every path to the
+extended-precision oracle within 8 x the same-precision oracle's own error, on harder inputs."""
 import functools
 
 import numpy as np

@@ -5,7 +5,11 @@ only rounds differently is off by a few ulp amplified by the update's conditioni
 loses three digits).  Bounds, all fp64:
     x:  |dx| <= 1e-13 * max(1, |x|_inf)
     P:  |dP| <= 1e-13 * max|P|  and, entry by entry, |dP_ij| <= 2e-12 * |P_ij| + 1e-13 * sqrt(P_ii P_jj)
-(the measured worst cases are printed by `pytest -s`).  The same fixture holds 48 sphere intersections with the quartic's roots to
+(the measured worst cases are printed by `pytest -s`).  The innovation nu = y - C x^- and NIS = nu^T S^-1 nu of the measured ticks
+(oracle.OracleBatch.innovations) are held to the same fixture, with a bound that follows from the two above:
+    nu:   |d nu_c| <= e = 1e-13 * max(1, |x|_inf)                      (y is exact; x^- is a state)
+    NIS:  |d NIS| <= 2 |w|^T e + e^T |S^-1| e + 1e-13 max|P^-| (sum_c |w_c|)^2     w = S^-1 nu, S^-1, max|P^-| from the 50 digits
+(first order in d nu and dS = dP^-[0:m,0:m], plus the quadratic remainder in d nu).  The same fixture holds 48 sphere intersections with the quartic's roots to
 50 digits and the reference's selection rule (further down)."""
 import os
 
@@ -86,6 +90,55 @@ def test_numpy_twin_matches_the_high_precision_answers(models, kat, name):
         else:
             t.update(dt)
         check("twin %s tick %d" % (name, s + 1), t.x, t.P, kat["x_" + name][s], kat["P_" + name][s])
+
+
+def innov_check(tag, nu, nis, kat, key, s, x_scale, rel=1e-13, ulps=0):
+    """nu [m], nis of tick s against the fixture's `key` rows (nu_<key> ...; module docstring).  rel: the bound on x and P the
+    NIS bound is propagated from; ulps: double roundings granted on top (the f80 entry returns doubles, as the fixture holds)."""
+    nk, sk, w, Sinv, pmax = (kat["gimbal_" + f if key == "gimbal" else f + "_" + key][s] for f in ("nu", "nis", "w", "Sinv", "pmax"))
+    e = rel * max(1.0, x_scale)
+    b_nu = e + ulps * np.spacing(np.abs(nk))
+    b_nis = 2.0 * np.abs(w).sum() * e + e * e * np.abs(Sinv).sum() + rel * pmax * np.abs(w).sum() ** 2 + ulps * np.spacing(abs(sk))
+    r_nu, r_nis = (np.abs(nu - nk) / b_nu).max(), abs(nis - sk) / b_nis
+    print("%-44s NIS %.6g  |d nu| %.2e (%.3f of its bound)  |d NIS| %.2e (%.3f of its bound %.2e)"
+          % (tag, sk, np.abs(nu - nk).max(), r_nu, abs(nis - sk), r_nis, b_nis))
+    assert np.isfinite(nu).all() and np.isfinite(nis), tag
+    assert r_nu <= 1.0, (tag, "nu", r_nu)
+    assert r_nis <= 1.0, (tag, "NIS", r_nis)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f80"])
+@pytest.mark.parametrize("name", MODELS)
+def test_oracle_innovations_match_the_high_precision_answers(models, kat, name, dtype):
+    """OracleBatch.innovations before every step of the four-tick cases: fp64 within the bound of the module docstring; f80 within
+    that bound at 1e-18 (what its x and P are held to below) plus one rounding to double of the value itself.  The
+    predict-only tick gives the sentinels, asked with the mask."""
+    m = models[name]
+    dt = float(kat["dt"])
+    orc = oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], kat["p0"][None], dt, dtype=dtype)
+    rel, ulps = (1e-13, 0) if dtype == "f64" else (1e-18, 1)
+    for s, has in enumerate(kat["has"]):
+        mask = np.array([1 if has else 0], dtype=np.uint8)
+        nu, nis = orc.innovations(dt, kat["meas"][s][None], mask)
+        if has:
+            innov_check("%s oracle %s tick %d" % (dtype, name, s + 1), nu[0], nis[0], kat, name, s, np.abs(kat["x_" + name][s]).max(), rel, ulps)
+        else:
+            assert nis[0] == -1.0 and (nu[0] == 0.0).all()
+            assert kat["nis_" + name][s] == -1.0
+        orc.step(dt, kat["meas"][s][None], mask)
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f80"])
+def test_oracle_innovations_through_the_gimbal_branches(models, kat, dtype):
+    """The same through the gimbal branches of quatToRpy (angular rates; NIS of order 1e3: the measured attitude jumps)."""
+    m = models["angular_rates"]
+    dt = float(kat["dt"])
+    orc = oracle.OracleBatch(m["model"], m["Q"], m["R"], m["P"], kat["p0"][None], dt, dtype=dtype)
+    rel, ulps = (1e-13, 0) if dtype == "f64" else (1e-18, 1)
+    for s in range(3):
+        nu, nis = orc.innovations(dt, kat["gimbal_meas"][s][None])
+        innov_check("%s oracle gimbal tick %d" % (dtype, s + 1), nu[0], nis[0], kat, "gimbal", s, np.abs(kat["gimbal_x"][s]).max(), rel, ulps)
+        orc.step(dt, kat["gimbal_meas"][s][None])
 
 
 @pytest.mark.gpu
