@@ -350,7 +350,8 @@ int target_batch_live_set_pose_output(target_batch_c* b, double* pose_soa_dev, l
  * query session keep theirs): once a gate is set, ..._live_capacity reports THAT kernel's capacity, at most the ungated figure.
  * ..._live_gate_served: 1 if this batch has a gated resident kernel, 0 if not (..._live_set_gate then refuses), -1 on error.  Every
  * (model, precision) with resident kernels has one, at zero scratch (profiles/live_gate_kernel_resources.txt).
- * Not served: the innovations nu (NIS only, as by id); target_batch_step_fused still has neither gate nor policy. */
+ * Not served: the innovations nu (NIS only, as by id).  (A launched fused call gates and re-acquires through
+ * target_batch_step_fused_gated below.) */
 struct target_innov_stream_c;   /* (both defined below, with the launched calls they were made for) */
 struct target_reacquire_c;
 int target_batch_live_set_gate(target_batch_c* b, double nis_max, const struct target_innov_stream_c* nis, const struct target_reacquire_c* reacq);
@@ -450,7 +451,8 @@ int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, do
  * target_manager_last_error set, and nothing is launched.  A NULL `innov` (or per_batch_innov), or a NULL nis_dev, gives exactly
  * the ..._poses call.  target_batch_algorithmic_bytes keeps reporting the plain tick: the stream adds 8 B per target and tick
  * for NIS, plus 8 * m B for the innovations.
- * Not served (no innovation stream there): target_batch_step_fused; the resident mode (target_batch_live_*) reports NIS rows only,
+ * target_batch_step_fused has its innovation stream in target_batch_step_fused_gated below (nis_max 0).
+ * Not served: the resident mode (target_batch_live_*) reports NIS rows only,
  * through the gate of its sessions (target_batch_live_set_gate), not nu; by id only NIS is
  * reported (target_manager_update_meas_batch_gated below), not nu. */
 typedef struct target_innov_stream_c {
@@ -493,7 +495,7 @@ int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, do
  * mask from the NIS row just written, into a row the library owns, and the plain step takes that row -- three launches per tick,
  * one more than ..._innov.  Poses and the fused query in the same
  * call, use_graph (a recorded graph is keyed by the gate too) and every other argument: as for ..._innov.
- * Not served: target_batch_step_fused.  The resident mode gates inside its sessions (target_batch_live_set_gate).  The by-id / indexed launches, the one-target symbols and the Eigen
+ * A temporally fused call gates through target_batch_step_fused_gated below.  The resident mode gates inside its sessions (target_batch_live_set_gate).  The by-id / indexed launches, the one-target symbols and the Eigen
  * facade are gated through the sticky policy of target_manager_set_update_gate below. */
 int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
@@ -538,8 +540,8 @@ int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, do
  * stays in the form.
  * A gate at a chi-square quantile re-initialises often on a stream that is not chi-square consistent:
  * choose nis_max for the outliers to be kept out, K for the time a lost target may coast.
- * Not served: target_batch_step_fused (the resident mode keeps the runs and re-acquires inside its sessions:
- * target_batch_live_set_gate); M-of-N logic other than K consecutive; a velocity from two
+ * A temporally fused call keeps the runs and re-acquires through target_batch_step_fused_gated below, the resident mode inside
+ * its sessions (target_batch_live_set_gate).  Not served: M-of-N logic other than K consecutive; a velocity from two
  * measurements.  The by-id / indexed launches, the one-target symbols and the Eigen facade re-acquire through the sticky policy
  * of target_manager_set_update_gate below. */
 typedef struct target_reacquire_c {
@@ -559,6 +561,41 @@ int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks
                                                const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
                                                const target_reacquire_c* per_batch_reacq, long n_batches,
                                                int query, const double* origin, double radius, int use_graph);
+/* ---- The innovation stream, the gate and the re-acquisition INSIDE a temporally fused call.
+ * target_batch_step_fused[_poses] with the streams and policies of the sections above: n_ticks ticks in ONE launch, each target's
+ * state in registers across the ticks, and in every tick the two-phase gated body and the policy of ..._reacquire -- the
+ * rejection run of a slot lives in a register from the call's first tick to its last (read once at the start, written back with
+ * the records), and a lost target is re-initialised in registers.  For replaying a recorded stream WITH outliers.
+ * EQUALITY.  For every slot and every tick the call equals target_batch_step_sequence_reacquire called with the same arguments,
+ * ring_ticks = 0 for the measurements and use_graph = 0, bit for bit: state, covariance, unwrap memory, measurement counter,
+ * clock, rejection runs, every NIS row, innovation block, event row and pose block.  `innov` and `reacq` keep their own
+ * ring_ticks and their zero strides, with the meaning they have there; columns >= size are never written.
+ *   reacq == NULL                      the semantics of ..._gated; the rejection runs are neither read nor written.
+ *   nis_max == 0 with an innov         the plain innovation stream of ..._innov, from a fused call.
+ *   nis_max == 0 and innov == NULL     exactly target_batch_step_fused_poses: the same kernels.
+ *   meas_dev == NULL                   a predict-only call: NIS -1, zero innovations, runs unchanged; as in the ..._reacquire call
+ *                                      (which launches no policy for such a tick) the event rows are not written.
+ * REFUSED (negative return, target_manager_last_error, nothing launched or changed): what ..._reacquire, ..._gated and ..._innov
+ * refuse -- a policy without a gate; a gate without the NIS row; max_rejects outside 0..127; nis_max < 0 or NaN; ld < size, a
+ * stride in (0, ld) or negative, ring_ticks < 0 in either stream; a policy on a batch that keeps measured poses or that no longer
+ * keeps its initial covariances -- and, for the call itself, n_ticks beyond an int, a negative tick_stride or has_stride, and
+ * ld < size with measurements.
+ * WHO SERVES IT.  One-class batches in the axis-separable layouts (lanes 201 and 301: the automatic layout of the shipped models),
+ * fp64 and fp32, every model: one launch for the whole call (kf_step_sep_fused_gate_kernel), every instantiation at zero scratch
+ * (profiles/fused_gate_kernel_resources.txt); none had to be routed tick by tick.  ..._step_fused_gate_served says 1 for these.
+ * A shared-axes batch is expanded to the plain form first, as target_batch_step_fused does.  Served TICK BY TICK INSIDE THE CALL,
+ * by the launches ..._reacquire makes for each tick -- same results, its launch counts -- and reported as 0: the dense layouts
+ * (coupled Q / R / P0, an explicit lanes_per_target outside 201 / 301, the symmetric-packed EKF), batches with several (Q, R)
+ * classes, batches that keep measured-pose rows.  A call WITH `poses` is served tick by tick as well, whatever ..._served says:
+ * the fused gated kernels carry no pose block (chosen over a second set of instantiations; the bits are the same either way).
+ * target_batch_step_fused and target_batch_step_fused_poses stay exactly as they are.
+ * ..._step_fused_gate_served: 1 = one launch for the whole call (without `poses`); 0 = served tick by tick inside the call; -1 on error.
+ * Not served: a manager-level fused call; per-axis gates; M-of-N logic. */
+int target_batch_step_fused_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
+                                  const unsigned char* has_meas_dev, long has_stride,
+                                  const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                  const target_reacquire_c* reacq);
+int target_batch_step_fused_gate_served(target_batch_c* b);   /* 1: one launch for the whole call; 0: served tick by tick inside the call */
 /* the rejection run of every slot, slot order, into runs_host [size]; synchronises */
 int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host);
 /* the rejection run of one target: >= 0, or negative: unknown id */
@@ -591,8 +628,9 @@ int target_manager_get_rejection_run(target_manager_c* m, unsigned int id);
  * the symmetric-packed EKF, several (Q, R) classes, a batch that keeps measured-pose rows); for max_rejects >= 0, a batch that no
  * longer keeps its initial covariances.  target_manager_update_gate_served asks up front.  The void one-target symbol reports
  * through target_manager_last_error, as its other failures do.
- * Not served: the innovations nu by id (NIS only); per-class, dense-layout and keep-measurement batches by id;
- * target_batch_step_fused.  (The resident mode ignores this policy and has a gate of its own: target_batch_live_set_gate.) */
+ * Not served: the innovations nu by id (NIS only); per-class, dense-layout and keep-measurement batches by id.
+ * (The resident mode and the fused calls ignore this policy and have gates of their own: target_batch_live_set_gate,
+ * target_batch_step_fused_gated.) */
 int  target_manager_set_update_gate(target_manager_c* m, int type, double nis_max, int max_rejects);
 int  target_manager_get_update_gate(target_manager_c* m, int type, double* nis_max, int* max_rejects);
 /* 1 if by-id updates of this model's batch would be served under a policy, 0 if not (see "refused"), -1 unknown */

@@ -177,6 +177,9 @@ SIGNATURES = {
     "target_manager_step_sequence_all_reacquire": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream),
                                                              C.POINTER(InnovStream), c_double_p, C.POINTER(Reacquire), C.c_long, C.c_int,
                                                              c_double_p, C.c_double, C.c_int]),
+    "target_batch_step_fused_gated": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.POINTER(Reacquire)]),
+    "target_batch_step_fused_gate_served": (C.c_int, [C.c_void_p]),
     "target_batch_rejection_runs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "target_manager_get_rejection_run": (C.c_int, [C.c_void_p, C.c_uint]),
     "target_manager_set_update_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),

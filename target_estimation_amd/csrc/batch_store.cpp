@@ -779,7 +779,8 @@ void Batch::check_pose_stream(const PoseStream& q) const {
   if (q.ring < 0) throw std::invalid_argument("target_estimation_amd: pose stream: negative ring_ticks");
 }
 
-void Batch::check_innov_stream(const InnovStream& q) const {
+void Batch::check_innov_stream(const InnovStream& q, bool count_only_needs_no_p0) const {
+  const bool p0_kept_ = this->p0_kept_ || (count_only_needs_no_p0 && q.reacq.on && q.reacq.k == 0);   // (K = 0 never reads a P0)
   if (!(q.gate >= 0.0)) throw std::invalid_argument("target_estimation_amd: gate: nis_max must be 0 (no gate) or positive");
   if (q.gated() && !q.nis) throw std::invalid_argument("target_estimation_amd: gate: nis_max > 0 needs an innovation stream with a NIS row (it reports the decisions)");
   if (!q.nis) { check_reacquire(q.reacq, q.gate, n_, keep_meas_, p0_kept_); return; }
@@ -993,6 +994,44 @@ void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick
   TE_HIP_CHECK(hipGetLastError());
   t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (meas_base && !has_base) nm_acc_ += n_ticks;
+}
+
+void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
+                             long has_stride, const PoseStream& poses, const InnovStream& innov) {
+  if (!innov.on() && !innov.gated() && !innov.reacq.on) {   // no stream, no gate: the plain fused call, the same kernels
+    step_fused(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses);
+    return;
+  }
+  const bool one_launch = fused_gate_served() && !poses.dev;
+  check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
+  check_innov_stream(innov, one_launch);   // (the kernel's K = 0 reads no initial covariance; the single ticks' launch is given the table)
+  if (n_ticks > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: step_fused_gated: n_ticks does not fit an int");
+  if (tick_stride < 0 || has_stride < 0) throw std::invalid_argument("target_estimation_amd: step_fused_gated: negative stride");
+  if (meas_base && ld < n_) throw std::invalid_argument("target_estimation_amd: step_fused_gated: ld " + std::to_string(ld) + " < batch size " + std::to_string(n_));
+  touch();
+  demote_shared();   // (the temporally fused kernels exist for the plain form only)
+  if (n_ == 0 || n_ticks <= 0) return;
+  if (keep_meas_) {   // measured-pose rows keep ACCEPTED measurements, tick by tick: the sequence's launches
+    step_sequence(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, 0, 0, poses, innov);
+    return;
+  }
+  if (innov.reacq.on && (innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
+  StepParams p = base_params();
+  p.gate_row = d_has_eff_;   // (the dense layouts' single gated ticks take their mask from the writer's row)
+  p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
+  p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
+  p.pose = poses.dev; p.pose_ld = poses.ld; p.pose_tick_stride = poses.tick_stride; p.pose_ring = poses.ring;
+  p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
+  p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
+  p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
+  if (innov.reacq.on) {
+    p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+    p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
+  }
+  launch_step(p, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
+  if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
 }
 
 // device block of a live session: [one mirror word per kLiveGroup wavefronts, 128 bytes apart][progress words]

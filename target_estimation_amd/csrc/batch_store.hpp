@@ -152,12 +152,29 @@ class Batch {
   // ("effective", temporally fused) cost model -- for replaying recorded streams.
   void step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                   const unsigned char* has_base, long has_stride, const PoseStream& poses = PoseStream{});
+  // step_fused with the innovation stream, the validation gate and the re-acquisition policy of step_sequence INSIDE the fused call
+  // (target_batch_step_fused_gated): per slot and tick, bit for bit, what step_sequence(..., use_graph 0, ring_ticks 0, poses, innov)
+  // leaves -- state, covariance, unwrap memory, counter, clock, rejection runs, every NIS row, innovation block, event row and pose
+  // block.  ONE launch for the whole call (kf_step_sep_fused_gate_kernel: the run in a register across the ticks, lost targets
+  // re-initialised in registers) where fused_gate_served(); every other batch, and a call with a pose stream, runs the sequence's
+  // ticks -- same results, its launch counts.  !innov.on(): exactly step_fused.  Refusals (invalid_argument, nothing launched): those
+  // of step_sequence's streams, n_ticks beyond an int, negative strides, ld < size.  A shared-axes batch is expanded first.
+  void step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
+                        long has_stride, const PoseStream& poses, const InnovStream& innov);
+  // one launch per fused gated call (without a pose stream): the plain form of this batch has the kernel, one (Q, R) class, no
+  // measured-pose rows
+  bool fused_gate_served() const {
+    const Ops* o = shared_axes() ? get_ops(type_, dtype_, lanes_code_) : ops_;
+    return o && o->fused_gate != 0 && n_classes_ == 1 && !keep_meas_;
+  }
   // throws std::invalid_argument unless `poses` is none or a valid stream for this batch (ld >= size, tick_stride 0 or >= 7 ld,
   // ring >= 0): checked before a call enqueues anything
   void check_pose_stream(const PoseStream& poses) const;
   // the same for an innovation stream: ld >= size, nis_tick_stride 0 or >= ld, innov_tick_stride 0 or >= m ld, nothing negative
   // ... and, with it, the gate and the re-acquisition policy it carries (reacquire_plan.hpp, check_reacquire)
-  void check_innov_stream(const InnovStream& innov) const;
+  // count_only_needs_no_p0: a policy with K = 0 is not refused on a batch that no longer keeps its initial covariances (the fused
+  // gated kernel, like the resident one, reads none for it)
+  void check_innov_stream(const InnovStream& innov, bool count_only_needs_no_p0 = false) const;
   // Before a call with a re-acquisition policy enqueues or records anything: bring the device copies of the initial-covariance
   // table and of the slot -> row index up to date (a table that had to grow drops the recorded sequences; dev_identity() shows it).
   void prepare_reacquire(const InnovStream& innov);

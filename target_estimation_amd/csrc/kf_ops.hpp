@@ -109,6 +109,23 @@ struct StepParams {
   int live_gate_k = -1;
   unsigned char* live_gate_event = nullptr;
   long live_gate_event_stride = 0, live_gate_event_ring = 0;
+  // The gate INSIDE a launched fused call (target_batch_step_fused_gated; kf_step_sep.hpp, FusedGate): fused_gate = 1 on a dense
+  // request in place of n_ticks >= 1 ticks.  Tick s of the call writes its NIS row at fused_gate_nis + (ring > 0 ? s % ring : s) *
+  // stride, with fused_gate_innov its innovation block [m][fused_gate_innov_ld] likewise (the rows' ring) and with fused_gate_event its
+  // event row (its own ring).  fused_gate_nis_max: 0 = no gate (the plain innovation stream), > 0 = gated.  fused_gate_k: -1 = no
+  // policy; 0..127 = the rejection runs in reacq_run, re-initialising on the k-th consecutive rejection (k > 0) with P0 = reacq_p0 +
+  // reacq_p0_idx[slot] * N*N.  gate / nis / reacq / gate_id / live_gate stay 0.  One launch where the layout has the kernel
+  // (Ops::fused_gate and one (Q, R) class, no pose stream in the call); otherwise OpsImpl::step runs the ticks as single gated
+  // requests (gate_row as for those) -- same results.
+  int fused_gate = 0;
+  double fused_gate_nis_max = 0.0;
+  double* fused_gate_nis = nullptr;
+  long fused_gate_nis_stride = 0, fused_gate_nis_ring = 0;
+  double* fused_gate_innov = nullptr;
+  long fused_gate_innov_ld = 0, fused_gate_innov_stride = 0;
+  int fused_gate_k = -1;
+  unsigned char* fused_gate_event = nullptr;
+  long fused_gate_event_stride = 0, fused_gate_event_ring = 0;
 };
 
 // The launch behind a gated tick that keeps the rejection runs and re-initialises lost targets (kf_reacquire_impl.hpp).
@@ -165,6 +182,9 @@ struct Ops {
   void (*settle)(char* rec, long n, const double* tile_blk, const int* tile_uni, hipStream_t) = nullptr;
   // reacquire_kernel (kf_reacquire_impl.hpp) behind a gated tick: rejection runs, event bytes, re-initialisation
   void (*reacquire)(const ReacquireArgs&, hipStream_t) = nullptr;
+  // 1: this (model, precision, layout) has a launched fused gated kernel (kf_step_sep_fused_gate_kernel); 0: a fused gated request
+  // is served tick by tick
+  int fused_gate = 0;
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported

@@ -55,6 +55,11 @@ void launch_sep_live_gate_step(const StepArgs<T>& a, const LiveGate& g, unsigned
 template <class M, typename T, int LAYOUT>
 int live_gate_blocks_per_cu();
 
+// The launched fused gated kernels (kf_step_sep.hpp, kf_step_sep_fused_gate_kernel), in kf_fused_gate_{uv,ua,ar,av}.hip
+// (kf_fused_gate_impl.hpp) likewise.
+template <class M, typename T, int LAYOUT>
+void launch_sep_fused_gate_step(const StepArgs<T>& a, const FusedGate& g, unsigned blocks, unsigned threads, hipStream_t s);
+
 // reacquire_kernel (kf_reacquire_impl.hpp), in kf_reacquire_{uv,ua,ar,av}.hip likewise: one instance per OpsImpl.
 template <class M, typename T, int G, int LAYOUT>
 void launch_reacquire(const ReacquireArgs& a, hipStream_t s);
@@ -104,7 +109,11 @@ struct OpsImpl {
   // Gated separable instantiations that would spill or need scratch are not shipped: their gate is the innovation writer's mask
   // row and the plain step (profiles/r11_gate_kernel_resources.txt).  None does.
   static constexpr bool kGateByWriter = false;
-  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW, kGateByWriter};
+  // Launched fused gated instantiations that would need scratch are not shipped: such a batch's fused gated call is served tick
+  // by tick (profiles/fused_gate_kernel_resources.txt).  None does.
+  static constexpr bool kFusedGateTickByTick = false;
+  static constexpr bool kHasFusedGate = C::SEP && !C::SHARED && !kGateByWriter && !kFusedGateTickByTick;
+  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW, kGateByWriter, kFusedGateTickByTick};
   // the pose-writer launch behind a tick whose kernel has no pose output: outputs_kernel into the tick's block
   static void write_pose_block(const StepParams& p, double* pose, hipStream_t s) {
     OutArgs o;
@@ -160,12 +169,46 @@ struct OpsImpl {
       throw std::runtime_error("target_estimation_amd: the resident gate: no resident kernel for this batch");
     }
   }
+  static void launch_fused_gate(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (kHasFusedGate) {
+      FusedGate g;
+      g.gate = p.fused_gate_nis_max; g.nis = p.fused_gate_nis; g.nis_stride = p.fused_gate_nis_stride; g.nis_ring = p.fused_gate_nis_ring;
+      g.innov = p.fused_gate_innov; g.innov_ld = p.fused_gate_innov_ld; g.innov_stride = p.fused_gate_innov_stride;
+      g.k = p.fused_gate_k; g.run = p.reacq_run; g.p0_tab = p.reacq_p0; g.p0_idx = p.reacq_p0_idx;
+      // (a predict-only call changes no run and, like the single ticks, writes no event row)
+      g.event = p.meas ? p.fused_gate_event : nullptr; g.event_stride = p.fused_gate_event_stride; g.event_ring = p.fused_gate_event_ring;
+      launch_sep_fused_gate_step<M, T, LAYOUT>(a, g, blocks, threads, s);
+    } else {
+      throw std::runtime_error("target_estimation_amd: the fused gate: no fused gated kernel for this batch");
+    }
+  }
+  // A fused gated request without a kernel of its own: tick s of the call as the single gated request target_batch_step_sequence_reacquire
+  // makes for it, planned and launched on its own.
+  static void step_fused_gate_tick_by_tick(const StepParams& p, hipStream_t s) {
+    for (long t = 0; t < (long)p.n_ticks; ++t) {
+      StepParams q = p;
+      q.fused_gate = 0; q.n_ticks = 1; q.tick_stride = 0; q.has_stride = 0;
+      q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
+      q.has_meas = p.has_meas ? p.has_meas + t * p.has_stride : nullptr;
+      const long b = p.fused_gate_nis_ring > 0 ? t % p.fused_gate_nis_ring : t;
+      q.nis = p.fused_gate_nis + b * p.fused_gate_nis_stride;
+      q.innov = p.fused_gate_innov ? p.fused_gate_innov + b * p.fused_gate_innov_stride : nullptr; q.innov_ld = p.fused_gate_innov_ld;
+      q.gate = p.fused_gate_nis_max;
+      if (p.fused_gate_k >= 0) {
+        q.reacq = 1; q.reacq_k = p.fused_gate_k;
+        q.reacq_event = p.fused_gate_event ? p.fused_gate_event + (p.fused_gate_event_ring > 0 ? t % p.fused_gate_event_ring : t) * p.fused_gate_event_stride : nullptr;
+      }
+      if (p.pose) { q.pose = p.pose + (p.pose_ring > 0 ? t % p.pose_ring : t) * p.pose_tick_stride; q.pose_tick_stride = 0; q.pose_ring = 0; }
+      step(q, s);
+    }
+  }
   // The launches of a request are plan_step's (step_variant.hpp): [innovation writer,] then once, or once per tick, the step
   // kernel [and the pose writer].
   static void step(const StepParams& p, hipStream_t s) {
     if (p.n <= 0) return;
     const StepPlan plan = plan_step(kTraits, p);
     const long waves = (p.n + C::TPW - 1) / C::TPW;
+    if (plan.fused_gated && plan.tick_by_tick) { step_fused_gate_tick_by_tick(p, s); return; }
     if (sv_live(plan.variant)) {   // resident launch: one wavefront per workgroup, every workgroup resident (Batch::live_start checked the capacity)
       // + 1: the relay wavefront (kf_step.hpp live_relay)
       if (plan.live_gated) launch_live_gate(make_step_args<T>(p), p, (unsigned)waves + 1, 64, s);
@@ -206,6 +249,7 @@ struct OpsImpl {
       }
       q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
       if (plan.gate_by_id) launch_gate_by_id(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
+      else if (plan.fused_gated) launch_fused_gate(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
       else if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
       else launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
       if (plan.reacquire_after_step) reacquire(make_reacquire_args(p), s);   // (p: the caller's mask and NIS row; gated ticks are single)
@@ -286,7 +330,7 @@ struct OpsImpl {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
         C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov, &innov_gate,
-        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr, &reacquire};
+        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr, &reacquire, kHasFusedGate ? 1 : 0};
     return &ops;
   }
 };

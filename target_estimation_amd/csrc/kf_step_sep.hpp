@@ -354,6 +354,8 @@ template <class C, class M, typename T> struct LivePark {
 // tested).  `gate` is an argument of its own, not a field of StepArgs, whose size is part of every existing kernel's descriptor;
 // 0 = no gate (a part of a gated population launch without one): acc = has.
 // GATE with LIVE == 2 (and without INNOV): the same two-phase body inside the resident tick loop, LiveGate below.
+// GATE with VAR == kFused (no live field, no INNOV): the same body and the resident policy tail inside the LAUNCHED fused tick loop,
+// with the NIS rows, innovation blocks and event rows of every tick as plain stores: FusedGate below (kf_step_sep_fused_gate_kernel).
 // BYID: the by-id update policy (target_manager_set_update_gate) in the gated INDEXED tick: GateById below, whose tail runs per
 // valid lane behind the decision and ahead of store_record -- the slot's rejection run by target_reacquire_c's table and, on the
 // K-th consecutive rejection, the record re-initialised IN REGISTERS from this entry's measurement exactly as init_kernel /
@@ -399,6 +401,37 @@ struct LiveGate {
 // live across the whole loop are spilled -- which the compiler accounts as scratch, and a resident kernel must have none.
 typedef const LiveGate __attribute__((address_space(4))) LiveGateArg;
 
+// FUSED GATE: the validation gate, the innovation stream and the re-acquisition policy inside a LAUNCHED temporally fused call
+// (kf_step_sep_fused_gate_kernel: VAR = kFused with GATE and without a live field; target_batch_step_fused_gated).  The resident
+// kernel's loop as an ordinary launch: no relay, doorbell or progress word, a finite StepArgs::n_ticks, and nothing leaves through
+// system-scope stores -- the end of the kernel orders the rows for a consumer on the stream, as for the pose stream.  Every tick
+// runs the two-phase body and the policy tail; the run lives in a register from the first tick to the last (read from
+// FusedGate::run ahead of the loop, written back with the records behind it) and a lost target is re-initialised in registers.
+// Tick s of the call writes NIS row b = (nis_ring > 0 ? s % nis_ring : s), its innovation block b (SoA [m][innov_ld], unless innov
+// is null) and its event row (its own ring): plain stores, lane = column, so a wavefront writes 64 consecutive doubles / bytes per
+// row; columns >= n are never written.  gate == 0: no gate (acc = has), the plain innovation stream from a fused call.
+struct FusedGate {
+  double gate;              // nis_max (0: none)
+  double* nis;              // NIS rows of the call
+  long nis_stride;          // doubles between consecutive rows (0: one row)
+  long nis_ring;            // > 0: the rows and the innovation blocks form a ring
+  double* innov;            // innovation blocks [m][innov_ld] of the call, or null
+  long innov_ld;
+  long innov_stride;        // doubles between consecutive blocks (0: one block)
+  int k;                    // -1: no policy (runs untouched); 0: count only; 1..127: re-initialise on the k-th consecutive rejection
+  unsigned char* run;       // [n] rejection runs (Batch::d_run_); unread with k < 0
+  const double* p0_tab;     // [rows][N*N] initial covariances; unread with k <= 0
+  const int* p0_idx;        // [n] row of every slot
+  unsigned char* event;     // event rows of the call, or null
+  long event_stride;        // bytes between consecutive rows (0: one row)
+  long event_ring;
+};
+// Read per tick from the kernel-argument segment, like LiveGateArg and for its reason: fourteen words held in scalar registers
+// across the tick loop next to the hoisted Q and R would be spilled, and no shipped kernel has scratch.
+// Both kernel arguments as they lie in the segment (explicit arguments in order, each at its natural alignment): every read is then
+// a scalar load at a constant offset from the segment pointer, which a kernel holds anyway -- no second pointer to keep.
+template <typename T> struct FusedGateSegment { StepArgs<T> a; FusedGate g; };
+
 // The form of the re-initialisation per instantiation.  In registers (above) where that costs no wavefront per SIMD against the
 // same kernel without it; elsewhere the record is written once more BEHIND store_record, word by word through state_set /
 // unwrap_ptr with the rolled loops init_kernel has, and the state words in registers are refreshed from x0 for the getter-table
@@ -425,10 +458,16 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   static_assert(C::SEP, "separable layouts only");
   static_assert(sep_variant_ok(VAR, C::SHARED), "no such variant of the separable step (step_variant.hpp)");
   constexpr bool LGATE = GATE && LIVE != 0;   // the gate inside a resident session (LiveGate)
-  static_assert(!GATE || INNOV || LIVE == 2, "the gate decides on the NIS of the innovation stream's kernels, or inside the resident kLive2 loop");
+  constexpr bool FGATE = GATE && FUSED && LIVE == 0;   // the gate inside a launched fused call (FusedGate)
+  static_assert(!GATE || INNOV || LIVE == 2 || FGATE,
+                "the gate decides on the NIS of the innovation stream's kernels, inside the resident kLive2 loop, or inside the launched kFused loop");
+  static_assert(!FGATE || VAR == kFused, "the launched fused gate is kFused with GATE and nothing else (its streams travel in FusedGate)");
   static_assert(BYID == (INNOV && INDEXED) && (!BYID || GATE), "kInnov | kIndexed is the gated by-id step and nothing else");
   if constexpr (!BYID) (void)gid;
   if constexpr (!LGATE) (void)lg;
+  // FGATE: the kernel's two arguments where they arrived (FusedGateSegment)
+  typedef const FusedGateSegment<T> __attribute__((address_space(4))) FusedSeg;
+#define FG0_ (((FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr())->g)
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -596,6 +635,14 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   // (the gated resident angular-rates fp32 kernel: its 60 hoisted words next to the gate's own push scalar registers out to
   // scratch -- 68 B, and a resident kernel must have none; it reads Q and R chain by chain instead)
   constexpr bool HOIST_QR = !PERQR && QR_NEED * (int)sizeof(T) <= 256 && !(LGATE && M::TYPE == ANGULAR_RATES && sizeof(T) == 4);
+  // The launched fused gate's fp64 angular kernels read Q and R from memory every tick (480 B: not hoisted), and the compiler merges
+  // the scalar loads of neighbouring chains / rows into sixteen-register requests.  In two instantiations the allocator then sets
+  // up spill slots for scalar tuples -- 68 B that the compiler accounts as scratch although nothing is stored there.  Those two
+  // read every chain (angular-rates on full groups) / every row of the EKF group's Q (angular-velocities on packed groups) through
+  // a base pointer of its own, which keeps the requests apart; the other instantiations have no scratch as they are (and
+  // angular-velocities on full groups gets 100 B WITH the separate bases).
+  constexpr bool FGATE_Q_CHAIN_BASE = FGATE && sizeof(T) == 8 && M::TYPE == ANGULAR_RATES && LAYOUT == LAYOUT_SEPARABLE;
+  constexpr bool FGATE_Q_ROW_BASE = FGATE && sizeof(T) == 8 && M::TYPE == ANGULAR_VELOCITIES && LAYOUT == LAYOUT_SEPARABLE_PACKED;
   T Qlin[HOIST_QR ? NLIN : 1][LB][LB], Rlin[HOIST_QR ? NLIN : 1], Qatt[HOIST_QR && M::EKF ? 6 : 1][6], Ratt[HOIST_QR && M::EKF ? 3 : 1][3];
   if constexpr (HOIST_QR) {
 #pragma unroll
@@ -619,11 +666,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
   // INNOV: the tick's innovations (measurement order = state rows 0..m-1) and the NIS sum (one tick per launch)
-  constexpr int MI = (INNOV || LGATE) ? (M::ANGULAR ? 6 : 3) : 1;
+  constexpr int MI = (INNOV || LGATE || FGATE) ? (M::ANGULAR ? 6 : 3) : 1;
   T nu_all[MI], nis = T(0);
 #pragma unroll
   for (int c = 0; c < MI; ++c) nu_all[c] = T(0);
-  if constexpr (!INNOV && !LGATE) { (void)nu_all; (void)nis; }
+  if constexpr (!INNOV && !LGATE && !FGATE) { (void)nu_all; (void)nis; }
   // GATE: what the update behind the decision takes from the prediction -- per chain 1 / S and the column P^-[1:,0] (the packed
   // records keep the upper triangle only), the unwrapped angles -- and the two masks: the tick's has-bit for the stream, acc for the rest
   constexpr int NGATE = GATE ? NCOV : 1;            // one entry per chain whose covariance half runs
@@ -641,13 +688,19 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   long live_nis_row = 0, live_event_row = 0;   // row of the tick at hand: k, or k % ring
   if constexpr (LGATE) {
     if (lg->k >= 0 && valid) live_run = lg->run[entry];
+  } else if constexpr (FGATE) {   // the same register for the launched fused call
+    if (FG0_.k >= 0 && valid) live_run = FG0_.run[entry];
+    (void)live_nis_row; (void)live_event_row;
   } else {
     (void)live_run; (void)live_nis_row; (void)live_event_row;
   }
+  int fused_nis_row = 0, fused_event_row = 0;   // FGATE: row of the tick at hand
+  if constexpr (!FGATE) { (void)fused_nis_row; (void)fused_event_row; }
   int n_has = 0;
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
-  for (int tick = 0; tick < n_ticks; ++tick) {
+  // (FGATE: the bound read per tick as well -- FusedGateSegment)
+  for (int tick = 0; tick < (FGATE ? ((FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr())->a.n_ticks : n_ticks); ++tick) {
   long slot_tick = tick;
   if constexpr (LIVE) {
     // (the worker's own limit is a backstop far behind the relay's: a relay round is a PCIe read + a scan, a worker poll an L2 hit)
@@ -658,9 +711,24 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   LiveGateArg* lgt = lg;   // LGATE: this tick's view of the gate's arguments (see LiveGateArg)
   if constexpr (LGATE) asm volatile("" : "+s"(lgt));
   else (void)lgt;
-#define GATE_T_ (LGATE ? lgt->gate : gate)
-  const T* meas_t = a.meas ? a.meas + slot_tick * a.tick_stride : nullptr;
-  const unsigned char* has_t = a.has_meas ? a.has_meas + slot_tick * a.has_stride : nullptr;
+  // FGATE: likewise, and the tick's view of StepArgs as well (FusedGateSegment): the fp64 angular kernels spilled scalar
+  // registers otherwise, which the compiler accounts as scratch
+  FusedSeg* kt = FGATE ? (FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+  if constexpr (FGATE) {
+    asm volatile("" : "+s"(kt));
+    nis = T(0);   // (one sum per tick)
+  } else {
+    (void)kt;
+  }
+  const auto* const fgt = &kt->g;
+  const auto* const at = &kt->a;
+  (void)fgt; (void)at;
+#define GATE_T_ (LGATE ? lgt->gate : FGATE ? fgt->gate : gate)
+  // the policy's arguments of a gate that lives inside a tick loop (constant condition: only the live arm is compiled)
+#define PG_(f_) (LGATE ? lgt->f_ : fgt->f_)
+#define A_(f_) (FGATE ? at->f_ : a.f_)
+  const T* meas_t = A_(meas) ? A_(meas) + slot_tick * A_(tick_stride) : nullptr;
+  const unsigned char* has_t = A_(has_meas) ? A_(has_meas) + slot_tick * A_(has_stride) : nullptr;
   // Every measurement word of the tick is requested up front, right behind the record loads and regardless
   // of the mask: with a cache-resident state they are the only operands that come from HBM itself, and one
   // round trip for all of them replaces one per axis.
@@ -673,7 +741,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
     for (int c = 0; c < MW; ++c) {
       if constexpr (LIVE) ymeas[c] = load_meas_live(&meas_t[(long)c * a.meas_ld + entry]);   // (no per-load run-time choice here: it would get a branch and a wait per word)
-      else ymeas[c] = load_meas(&meas_t[(long)c * a.meas_ld + entry], a.nt_meas);
+      else ymeas[c] = load_meas(&meas_t[(long)c * A_(meas_ld) + entry], A_(nt_meas));
     }
     if (has_t != nullptr) {
       if constexpr (LIVE) hmask = (unsigned char)__hip_atomic_load(&has_t[entry], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -750,17 +818,19 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       const int ic = cov_of(i);   // the covariance chain this axis takes its 1 / S from
       if (lead(i)) {   // (a constant once the loop is unrolled)
         T Pb[LB][LB], Qb[LB][LB];
+        ConstT* Qc = Qm;   // (FGATE_Q_CHAIN_BASE: a base of its own per chain)
+        if constexpr (FGATE_Q_CHAIN_BASE) asm volatile("" : "+s"(Qc));
 #pragma unroll
         for (int b = 0; b < LB; ++b)
 #pragma unroll
           for (int c = 0; c < LB; ++c) {
             Pb[b][c] = GR_(C::PWORD.v[i + STRIDE * b][i + STRIDE * c]);   // (GR_ / GW_: a parked word in a resident session)
             if constexpr (HOIST_QR) Qb[b][c] = Qlin[i][b][c];
-            else Qb[b][c] = Qm[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
+            else Qb[b][c] = Qc[C::QWORD.v[i + STRIDE * b][i + STRIDE * c]];
           }
         T r_meas;
         if constexpr (HOIST_QR) r_meas = Rlin[i];
-        else r_meas = Qm[C::RWORD.v[i][i]];
+        else r_meas = Qc[C::RWORD.v[i][i]];
         sep_gate_predict_P<LB, T>(Pb, Qb, dt);
         g_inv[ic] = T(0);
         if (has) g_inv[ic] = (T)1 / (Pb[0][0] + r_meas);
@@ -1005,6 +1075,11 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
             for (int c = 0; c < 6; ++c) qrow[c] = Qsrc[C::QWORD.v[GR[r]][GR[c]]];
           }
+        } else if constexpr (FGATE_Q_ROW_BASE) {
+          ConstT* Qr = Qm;   // (a base of its own per row: see FGATE_Q_ROW_BASE)
+          asm volatile("" : "+s"(Qr));
+#pragma unroll
+          for (int c = 0; c < 6; ++c) qrow[c] = Qr[C::QWORD.v[GR[r]][GR[c]]];
         } else {
 #pragma unroll
           for (int c = 0; c < 6; ++c) qrow[c] = Qm[C::QWORD.v[GR[r]][GR[c]]];
@@ -1217,16 +1292,17 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       }
     }
   }
-  if constexpr (LGATE) {
-    // the policy tail of the resident tick (LiveGate): the run in its register, the event byte and -- rarely -- the record's words
-    // replaced where they live, registers and parked words alike; then the tick's NIS and event rows, lane = column
+  if constexpr (LGATE || FGATE) {
+    // the policy tail of the resident tick (LiveGate) and of a tick of the launched fused call (FusedGate): the run in its register,
+    // the event byte and -- rarely -- the record's words replaced where they live, registers and parked words alike; then the tick's
+    // NIS and event rows (FGATE: and its innovation block), lane = column
     unsigned char ev = 0;
-    if (lgt->k >= 0 && g_has) {   // (g_has: a valid lane with a measurement)
+    if (PG_(k) >= 0 && g_has) {   // (g_has: a valid lane with a measurement)
       unsigned run = 0;
       if (!acc) {   // rejected (a NaN rejects)
         const unsigned c1 = live_run + 1 < 127u ? live_run + 1 : 127u;
         ev = (unsigned char)c1; run = c1;
-        if (lgt->k > 0 && c1 >= (unsigned)lgt->k) {   // a candidate: x0 as init_kernel forms it, re-initialised iff finite
+        if (PG_(k) > 0 && c1 >= (unsigned)PG_(k)) {   // a candidate: x0 as init_kernel forms it, re-initialised iff finite
           T x0[N];
 #pragma unroll
           for (int r = 0; r < N; ++r) x0[r] = 0;
@@ -1244,7 +1320,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
           for (int r = 0; r < K; ++r) reinit = reinit && (x0[r] - x0[r] == (T)0);   // finite
           if (reinit) {
             ev = (unsigned char)(0x80u | c1); run = 0;
-            const double* P0 = lgt->p0_tab + (long)lgt->p0_idx[entry] * N * N;
+            const double* P0 = PG_(p0_tab) + (long)PG_(p0_idx)[entry] * N * N;
 #pragma unroll
             for (int r = 0; r < N; ++r) {
               XS_(r, x0[r]);
@@ -1261,18 +1337,33 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       }
       live_run = run;
     }
-    if (valid) {
-      double* const nrow = lgt->nis + live_nis_row * lgt->nis_stride;
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(&nrow[entry]), (unsigned long long)__double_as_longlong(g_has ? (double)nis : -1.0),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (lgt->event != nullptr) {
-        unsigned char* const erow = lgt->event + live_event_row * lgt->event_stride;
-        __hip_atomic_store(&erow[entry], ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if constexpr (LGATE) {
+      if (valid) {
+        double* const nrow = lgt->nis + live_nis_row * lgt->nis_stride;
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(&nrow[entry]), (unsigned long long)__double_as_longlong(g_has ? (double)nis : -1.0),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (lgt->event != nullptr) {
+          unsigned char* const erow = lgt->event + live_event_row * lgt->event_stride;
+          __hip_atomic_store(&erow[entry], ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
       }
+      // the rows of the next tick: counted, not divided (k % ring of two 64-bit words costs the scalar registers a tick has none to spare of)
+      live_nis_row = live_nis_row + 1 == lgt->nis_ring ? 0 : live_nis_row + 1;
+      live_event_row = live_event_row + 1 == lgt->event_ring ? 0 : live_event_row + 1;
+    } else {
+      if (valid) {   // plain stores: the end of the kernel orders them for a consumer on the stream
+        fgt->nis[(long)fused_nis_row * fgt->nis_stride + entry] = g_has ? (double)nis : -1.0;
+        if (fgt->innov != nullptr) {
+          double* const nublk = fgt->innov + (long)fused_nis_row * fgt->innov_stride + entry;
+#pragma unroll
+          for (int c = 0; c < MI; ++c) nublk[(long)c * fgt->innov_ld] = g_has ? (double)nu_all[c] : 0.0;
+        }
+        if (fgt->event != nullptr) fgt->event[(long)fused_event_row * fgt->event_stride + entry] = ev;
+      }
+      // (n_ticks is an int, so the rows are: one scalar register each)
+      fused_nis_row = (long)fused_nis_row + 1 == fgt->nis_ring ? 0 : fused_nis_row + 1;
+      fused_event_row = (long)fused_event_row + 1 == fgt->event_ring ? 0 : fused_event_row + 1;
     }
-    // the rows of the next tick: counted, not divided (k % ring of two 64-bit words costs the scalar registers a tick has none to spare of)
-    live_nis_row = live_nis_row + 1 == lgt->nis_ring ? 0 : live_nis_row + 1;
-    live_event_row = live_event_row + 1 == lgt->event_ring ? 0 : live_event_row + 1;
   }
   if constexpr (BYID) {
     // the policy tail (GateById): run, event byte and -- rarely -- the record's words replaced in registers
@@ -1382,6 +1473,10 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
   }  // tick loop
+  // FGATE: what follows the loop reads its arguments afresh as well (behind the loop: nothing of it is held across)
+  FusedSeg* ke = FGATE ? (FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+  if constexpr (FGATE) asm volatile("" : "+s"(ke));
+  else (void)ke;
   if constexpr (UT) {
     // Does the tile leave this tick uniform?  Its lanes must have taken the same has-bit (dt is the launch's).  A uniform tile
     // then stays one -- every lane has computed the same block from the same block -- and a tile that is not becomes one, in a
@@ -1443,6 +1538,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     if constexpr (LGATE) {   // the session's runs go back with its records
       if (lg->k >= 0) lg->run[entry] = (unsigned char)live_run;
     }
+    else if constexpr (FGATE) {   // ... and the fused call's (its rows were written tick by tick)
+      if (ke->g.k >= 0) ke->g.run[entry] = (unsigned char)live_run;
+    }
     else if constexpr (GATE) write_innov(g_has, nis, nu_all, MI);
     else if constexpr (INNOV) write_innov(n_has != 0, nis, nu_all, MI);
     if constexpr (BYID && !TAIL_REGS) {
@@ -1497,7 +1595,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       a.t_base[slot] = te_clock_add_ticks(a.t_base[slot], dtd, (double)n_ticks);
       a.nm_base[slot] += n_has;
     } else {
-      if (a.has_meas != nullptr || (GATE && gate != 0.0)) a.nm_base[entry] += n_has;
+      if constexpr (FGATE) {   // (the gate read where it arrived: not a scalar register pair held across the tick loop)
+        if (ke->a.has_meas != nullptr || ke->g.gate != 0.0) ke->a.nm_base[entry] += n_has;
+      } else if (a.has_meas != nullptr || (GATE && gate != 0.0)) a.nm_base[entry] += n_has;
     }
   }
   if constexpr (INDEXED) {
@@ -1514,6 +1614,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #undef XW_
 #undef GR_
 #undef GATE_T_
+#undef PG_
+#undef A_
+#undef FG0_
 #undef GW_
 #undef UWW_
 #undef XR_
@@ -1562,6 +1665,19 @@ __global__ void __launch_bounds__(256) kf_step_sep_live_gate_kernel(const StepAr
   typedef const char __attribute__((address_space(4))) ArgByte;
   LiveGateArg* gp = (LiveGateArg*)((ArgByte*)__builtin_amdgcn_kernarg_segment_ptr() + G_OFF);
   sep_step_wave<M, T, LAYOUT, kFused | kLive2, true, false>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate, nullptr, gp);
+}
+
+// The launched fused call with the gate inside (sep_step_wave, GATE inside the plain kFused tick loop; FusedGate above):
+// target_batch_step_fused_gated.  Everything new travels in the second argument -- StepArgs keeps its size -- and the plain kFused
+// kernels stay what they were.  Nothing here waits: no atomic read-modify-write, no word shared between wavefronts.  Instantiated in
+// kf_fused_gate_{uv,ua,ar,av}.hip (kf_fused_gate_impl.hpp) for the two separable layouts in both precisions; the grid is the
+// plain fused launch's.
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256) kf_step_sep_fused_gate_kernel(const StepArgs<T> a, const FusedGate g) {
+  // sep_step_wave reads `g` where the launch put it (FusedGateSegment; see kf_step_sep_live_gate_kernel)
+  static_assert(offsetof(FusedGateSegment<T>, g) == (sizeof(StepArgs<T>) + alignof(FusedGate) - 1) / alignof(FusedGate) * alignof(FusedGate),
+                "explicit kernel arguments lie in the segment in order, each at its natural alignment");
+  sep_step_wave<M, T, LAYOUT, kFused, true, false>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate);
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------

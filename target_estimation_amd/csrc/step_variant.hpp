@@ -78,6 +78,7 @@ struct StepTraits {
   bool fused_spills;             // no kFused kernel (dense): it would spill
   int tpw;                       // targets per wavefront
   bool gate_by_writer = false;   // no gated kernel (it would spill or need scratch): the gate's mask comes from the innovation writer
+  bool fused_gate_tick_by_tick = false;   // no launched fused gated kernel (it would need scratch): a fused gated request is served tick by tick
 };
 
 template <unsigned N>
@@ -114,6 +115,12 @@ struct StepPlan {
   // the request is a resident launch with the gate inside the session (P::live_gate): the gated resident kernel
   // (kf_step_sep_live_gate_kernel), the variant word kFused | kLive2 and the gate a template argument next to it
   bool live_gated = false;
+  // the request is a launched fused call with the gate, the innovation stream and the policy inside it (P::fused_gate).  Without
+  // tick_by_tick: ONE launch of kf_step_sep_fused_gate_kernel for the whole call, the variant word kFused and the gate a template
+  // argument next to it.  With tick_by_tick no such kernel serves the batch (the dense layouts, several (Q, R) classes, a pose
+  // stream in the same call, StepTraits::fused_gate_tick_by_tick): the caller runs the call's ticks as single gated requests, each
+  // planned on its own -- `variant` is then 0 and says nothing.
+  bool fused_gated = false;
 };
 
 // The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
@@ -154,6 +161,18 @@ constexpr bool requested_live_gate(const P& p) {
   if constexpr (has_live_gate_member<P>::value) return p.live_gate != 0;
   else return false;
 }
+// The gate of a launched fused call: P::fused_gate (non-zero = the request is target_batch_step_fused_gated's; it then has
+// P::fused_gate_nis_max (>= 0; 0 = the plain innovation stream), the NIS rows P::fused_gate_nis / _nis_stride / _nis_ring, the innovation
+// blocks P::fused_gate_innov / _innov_ld / _innov_stride (the rows' ring), P::fused_gate_k (-1 = no policy, 0..127 as P::reacq_k), the
+// event rows P::fused_gate_event / _event_stride / _event_ring and, for the runs, the pointers P::reacq_run / reacq_p0 /
+// reacq_p0_idx).  A request type without the member plans as it always did.
+template <class P, class = void> struct has_fused_gate_member : std::false_type {};
+template <class P> struct has_fused_gate_member<P, std::void_t<decltype(std::declval<const P&>().fused_gate)>> : std::true_type {};
+template <class P>
+constexpr bool requested_fused_gate(const P& p) {
+  if constexpr (has_fused_gate_member<P>::value) return p.fused_gate != 0;
+  else return false;
+}
 template <class P>
 constexpr bool requested_gate_by_writer(const P& p) {
   if constexpr (has_gate_by_writer_member<P>::value) return p.gate_by_writer != 0;
@@ -190,6 +209,29 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
         throw std::runtime_error("target_estimation_amd: the fused getter table needs an indexed launch (and a wavefront counter beyond one wavefront of entries)");
       plan.gate_by_id = true;
       plan.variant = kInnov | kIndexed;
+      return plan;
+    }
+  }
+  if constexpr (has_fused_gate_member<P>::value) {
+    if (requested_fused_gate(p)) {   // the launched fused call with the gate inside: one launch, or tick by tick, or refused
+      const char* pre = "target_estimation_amd: the fused gate: ";
+      if (!(p.fused_gate_nis_max >= 0.0)) throw std::runtime_error(std::string(pre) + "nis_max must be 0 (none) or positive");
+      if (!p.fused_gate_nis || p.fused_gate_nis_stride < 0 || p.fused_gate_nis_ring < 0)
+        throw std::runtime_error(std::string(pre) + "it reports its decisions in NIS rows");
+      if (p.fused_gate_innov && (p.fused_gate_innov_ld < p.n || p.fused_gate_innov_stride < 0)) throw std::runtime_error(std::string(pre) + "malformed innovation blocks");
+      if (p.fused_gate_k < -1 || p.fused_gate_k > 127) throw std::runtime_error(std::string(pre) + "max_rejects must be -1..127");
+      if (p.fused_gate_k >= 0 && !(p.fused_gate_nis_max > 0.0)) throw std::runtime_error(std::string(pre) + "a policy needs the gate (nis_max > 0)");
+      if (p.fused_gate_k >= 0 && !p.reacq_run) throw std::runtime_error(std::string(pre) + "rejection runs need the batch's run row");
+      if (p.fused_gate_k > 0 && (!p.reacq_p0 || !p.reacq_p0_idx)) throw std::runtime_error(std::string(pre) + "re-acquisition needs the batch's table of initial covariances");
+      if (p.fused_gate_event && (p.fused_gate_k < 0 || p.fused_gate_event_stride < 0 || p.fused_gate_event_ring < 0))
+        throw std::runtime_error(std::string(pre) + "event rows belong to a policy (max_rejects >= 0)");
+      if (p.n_ticks < 1 || p.idx || p.live_posted || p.rec_out || p.q_delta || p.o_pose || p.tile_uni || t.shared)
+        throw std::runtime_error(std::string(pre) + "a dense fused launch in place of a batch in the plain form");
+      if (plan.gated || p.nis || requested_reacquire(p) || requested_gate_by_id(p) || requested_live_gate(p) || requested_gate_by_writer(p))
+        throw std::runtime_error(std::string(pre) + "not together with the single ticks' gate, streams or policies");
+      plan.fused_gated = true;
+      plan.tick_by_tick = !t.sep || p.cls || p.pose || t.fused_gate_tick_by_tick || t.gate_by_writer;
+      plan.variant = plan.tick_by_tick ? 0u : (unsigned)kFused;
       return plan;
     }
   }

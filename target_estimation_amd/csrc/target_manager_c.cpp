@@ -577,6 +577,22 @@ int target_batch_step_sequence_reacquire(target_batch_c* b, long n_ticks, double
   });
 }
 
+// ---- the gate, the innovation stream and the re-acquisition inside a launched fused call
+int target_batch_step_fused_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
+                                  const unsigned char* has_meas_dev, long has_stride,
+                                  const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                  const target_reacquire_c* reacq) {
+  return guarded("target_batch_step_fused_gated", [&] {
+    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
+    BatchLock lk(B(b));
+    B(b)->step_fused_gated(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, pose_stream(poses), stream);
+  });
+}
+
+int target_batch_step_fused_gate_served(target_batch_c* b) {
+  return guarded_value<int>("target_batch_step_fused_gate_served", -1, [&] { BatchLock lk(B(b)); return B(b)->fused_gate_served() ? 1 : 0; });
+}
+
 int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks, double dt,
                                                const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                                const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,

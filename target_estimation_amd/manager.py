@@ -229,15 +229,28 @@ class Batch:
                                                               meas.stride(1), hp, hs, meas.shape[0], int(use_graph)),
                    "target_batch_step_sequence_ring")
 
-    def step_fused(self, dt, meas, has_meas=None, poses=None):
+    def step_fused(self, dt, meas, has_meas=None, poses=None, innov=None, gate=None, reacquire=None):
         """meas: CUDA tensor [ticks, 7, ld]: all ticks in ONE launch (state stays in registers).  poses: as for
-        step_sequence (target_batch_step_fused_poses)."""
+        step_sequence (target_batch_step_fused_poses).  innov, gate, reacquire: the keywords of step_sequence with their
+        meanings there, served inside the fused call (target_batch_step_fused_gated): per slot and tick the results of
+        step_sequence(dt, meas, has_meas, poses=, innov=, gate=, reacquire=) bit for bit -- one launch for the whole call where
+        fused_gate_served is 1 and no poses are asked for, tick by tick inside the call otherwise."""
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if innov is not None or gate is not None or reacquire is not None:   # (a gate without a stream, a policy without a gate: the library's to refuse)
+            ticks = meas.shape[0]
+            ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
+            ins = _innov_stream(innov, self.size, self.meas_dim, ticks) if innov is not None else None
+            rq = _reacquire(reacquire, self.size, ticks) if reacquire is not None else None
+            _check(self._lib.target_batch_step_fused_gated(self._h, ticks, float(dt), meas.data_ptr(), meas.stride(0), meas.stride(1), hp, hs,
+                                                            None if ps is None else C.byref(ps), None if ins is None else C.byref(ins),
+                                                            0.0 if gate is None else float(gate), None if rq is None else C.byref(rq)),
+                   "target_batch_step_fused_gated")
+            return
         if poses is not None:
             ps = _pose_stream(poses, self.size, meas.shape[0])
             _check(self._lib.target_batch_step_fused_poses(self._h, meas.shape[0], float(dt), meas.data_ptr(), meas.stride(0),
@@ -245,6 +258,9 @@ class Batch:
             return
         _check(self._lib.target_batch_step_fused(self._h, meas.shape[0], float(dt), meas.data_ptr(), meas.stride(0),
                                                   meas.stride(1), hp, hs), "target_batch_step_fused")
+
+    # 1: a fused call with innov= / gate= / reacquire= (and without poses=) is one launch; 0: served tick by tick inside the call
+    fused_gate_served = property(lambda s: s._lib.target_batch_step_fused_gate_served(s._h))
 
     # ---- resident ("live") mode: one launch serves tick after tick as the host posts them (target_batch_c.h)
     def live_start(self, dt, meas_ring, has_ring=None, first_entry=0, max_ticks=1 << 30, idle_limit_s=10.0):
