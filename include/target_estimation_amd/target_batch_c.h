@@ -596,6 +596,57 @@ int target_batch_step_fused_gated(target_batch_c* b, long n_ticks, double dt, co
                                   const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
                                   const target_reacquire_c* reacq);
 int target_batch_step_fused_gate_served(target_batch_c* b);   /* 1: one launch for the whole call; 0: served tick by tick inside the call */
+/* ---- Step sequences and fused replays with a TIME STEP PER TICK (a time-step schedule).
+ * A recorded stream has the stamps it has: jitter, a late frame, a dropped frame.  The calls below are the most general form of
+ * each multi-tick family with `double dt` replaced by a host array dt_host[n_ticks]: tick s of the call runs with dt_host[s].
+ *   ..._step_sequence_dt      follows target_batch_step_sequence_reacquire
+ *   ..._step_fused_dt         follows target_batch_step_fused_gated
+ *   ..._step_sequence_all_dt  follows target_manager_step_sequence_all_reacquire
+ * poses, innov and reacq NULL with nis_max == 0 give the plain calls.  dt_host is read before the call returns.  Entries are taken
+ * as target_batch_step takes its dt: no validation of values (0.0 is a tick that only updates).
+ * CONTRACT.  For every slot the call equals n_ticks calls of its scalar-dt counterpart with n_ticks = 1 and dt = dt_host[s], the
+ * measurement, mask and stream pointers moved to tick s -- bit for bit: state, covariance and unwrap memory; measurement counter
+ * and rejection runs; every NIS row, innovation block, event row and pose block; the query outputs; and the target's time.  The
+ * clock is therefore advanced by one compensated addition per tick, in order, as target_batch_step does -- never by dt * n.
+ * A schedule whose entries are all equal gives the scalar call's bits everywhere EXCEPT the clock: the time read back may differ
+ * from the scalar call's by at most 1 ulp (both are roundings of sums exact to about 2^-106: dt added n times there, dt * n here).
+ * REFUSED (negative return, target_manager_last_error, nothing launched or changed): dt_host == NULL with n_ticks > 0, and
+ * everything the scalar counterpart refuses.
+ * RECORDED GRAPHS (use_graph = 1).  A recording bakes every tick's dt into its launch, so it is filed under the schedule's VALUES,
+ * compared as bits (0.0 and -0.0 differ).  A replay with the same schedule reuses the recording -- a ring replayed in blocks
+ * with a repeating schedule is such a case; a different schedule records anew.  A caller with a fresh schedule every call gains
+ * nothing over use_graph = 0 (it records every time): the fused call is the form for that case.
+ * WHO SERVES THE FUSED CALL.  One-class batches in the axis-separable layouts (lanes 201 and 301), fp64 and fp32, every model: one
+ * launch for the whole call -- the fused loop (kf_step_sep_fused_dt_kernel) or, with an innovation stream, a gate or a policy, the
+ * gated fused loop (kf_step_sep_fused_gate_dt_kernel) -- whose tick s reads entry s of a device table of doubles with one scalar
+ * load.  The batch owns the table and fills it on its stream ahead of the launch; every call takes a fresh run of it, so calls
+ * enqueued back to back without a synchronisation do not see each other's values.  Every instantiation has zero scratch
+ * (profiles/dt_schedule_kernel_resources.txt); none had to be routed tick by tick.  ..._step_fused_dt_served says 1 for these.
+ * Served TICK BY TICK INSIDE THE CALL, same results, reported as 0: a call with `poses`; the dense layouts and the
+ * symmetric-packed EKF; several (Q, R) classes; batches that keep measured poses; a call of more than 2^28 ticks.  A shared-axes
+ * batch is expanded to the plain form first, as for every fused call; it reports 0 until then (its first call is the expansion,
+ * a synchronisation and then the plain form's launch) and what the plain form reports afterwards.
+ * ..._step_fused_dt_served(b, gated): gated = the call would carry innov, nis_max > 0 or reacq.  1 = one launch for the whole call
+ * (without `poses`); 0 = tick by tick inside the call; -1 on error.
+ * OUT OF SCOPE.  Resident sessions keep the one dt of target_batch_live_start (a schedule there needs a hand-off of its own
+ * through the ring and the clock kept on the device); a dt per target inside a dense tick (the by-id calls have one); the fused
+ * kernel of the dense layouts stays as it is (such a batch's schedule call runs its single ticks). */
+int target_batch_step_sequence_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride,
+                                  long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                  const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                  const target_reacquire_c* reacq, int use_graph);
+int target_batch_step_fused_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride, long ld,
+                               const unsigned char* has_meas_dev, long has_stride,
+                               const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                               const target_reacquire_c* reacq);
+int target_batch_step_fused_dt_served(target_batch_c* b, int gated);   /* 1: one launch for the whole call; 0: tick by tick inside the call; -1 error */
+int target_manager_step_sequence_all_dt(target_manager_c* m, long n_ticks, const double* dt_host,
+                                        const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                        const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                                        const target_reacquire_c* per_batch_reacq, long n_batches,
+                                        int query, const double* origin, double radius, int use_graph);
+/* recordings made so far by the batch's step_sequence* calls with use_graph != 0 (a counter for tests of the graph cache); -1 on error */
+long target_batch_graph_recordings(target_batch_c* b);
 /* the rejection run of every slot, slot order, into runs_host [size]; synchronises */
 int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host);
 /* the rejection run of one target: >= 0, or negative: unknown id */

@@ -180,6 +180,17 @@ SIGNATURES = {
     "target_batch_step_fused_gated": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
                                                 C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.POINTER(Reacquire)]),
     "target_batch_step_fused_gate_served": (C.c_int, [C.c_void_p]),
+    # a time step per tick (dt_host [n_ticks] in place of dt)
+    "target_batch_step_sequence_dt": (C.c_int, [C.c_void_p, C.c_long, c_double_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                                C.c_long, C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.POINTER(Reacquire),
+                                                C.c_int]),
+    "target_batch_step_fused_dt": (C.c_int, [C.c_void_p, C.c_long, c_double_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_long,
+                                             C.POINTER(PoseStream), C.POINTER(InnovStream), C.c_double, C.POINTER(Reacquire)]),
+    "target_batch_step_fused_dt_served": (C.c_int, [C.c_void_p, C.c_int]),
+    "target_manager_step_sequence_all_dt": (C.c_int, [C.c_void_p, C.c_long, c_double_p, C.c_void_p, C.POINTER(PoseStream),
+                                                      C.POINTER(InnovStream), c_double_p, C.POINTER(Reacquire), C.c_long, C.c_int,
+                                                      c_double_p, C.c_double, C.c_int]),
+    "target_batch_graph_recordings": (C.c_long, [C.c_void_p]),
     "target_batch_rejection_runs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "target_manager_get_rejection_run": (C.c_int, [C.c_void_p, C.c_uint]),
     "target_manager_set_update_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),

@@ -431,6 +431,9 @@ Batch::~Batch() {
   device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
   device_free(d_dtper_); device_free(d_lastmeas_);
+  device_free(d_dttab_);
+  if (h_dttab_) (void)hipHostFree(h_dttab_);
+  for (double* h : h_dttab_retired_) (void)hipHostFree(h);
   if (h_pin_) (void)hipHostFree(h_pin_);
   if (h_pol_) (void)hipHostFree(h_pol_);
   device_free(bar_pin_);
@@ -796,9 +799,10 @@ void Batch::check_innov_stream(const InnovStream& q, bool count_only_needs_no_p0
 
 void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                           const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks, const PoseStream& poses,
-                          const InnovStream& innov) {
+                          const InnovStream& innov, const DtSchedule& sched) {
   check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
   check_innov_stream(innov);
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
   prepare_reacquire(innov);   // (before anything is enqueued or recorded)
@@ -809,7 +813,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     p.meas = meas_base ? static_cast<const char*>(meas_base) + (size_t)(s * tick_stride) * es : nullptr;
     p.meas_ld = ld;
     p.has_meas = has_base ? has_base + s * has_stride : nullptr;
-    p.dt = dt;
+    p.dt = sched.at(s0, dt);   // (tick s0 of the call, whatever entry of a measurement ring it reads)
     p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
     p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
     p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld; p.gate = innov.gate;
@@ -830,7 +834,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     GraphEntry* hit = nullptr;
     for (auto& g : graphs_)
       if (g.n_ticks == n_ticks && g.tick_stride == tick_stride && g.ld == ld && g.has_stride == has_stride && g.n == n_ &&
-          g.dt == dt && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks &&
+          dt_key_matches(g.dt_key, g.dt_is_schedule, g.dt, sched, dt) && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks &&
           g.poses.dev == poses.dev && g.poses.ld == poses.ld && g.poses.tick_stride == poses.tick_stride && g.poses.ring == poses.ring &&
           g.innov.same(innov)) hit = &g;
     if (!hit) {
@@ -847,6 +851,8 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
       GraphEntry e{n_ticks, tick_stride, ld, has_stride, n_, dt, meas_base, has_base, d_rec_, nullptr, nullptr, ring_ticks};
       e.poses = poses;
       e.innov = innov;
+      e.dt_is_schedule = sched.on();
+      e.dt_key = sched.key();   // (a recording bakes every tick's dt into its launch: filed under the values, compared as bits)
       TE_HIP_CHECK(hipStreamBeginCapture(cap_stream_, hipStreamCaptureModeThreadLocal));
       recording_ = true;   // (a recording is a dense streak: its ticks promote)
       try {
@@ -872,6 +878,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
         throw std::runtime_error("target_estimation_amd: hipGraphInstantiate failed for a step sequence");
       }
       graphs_.push_back(e);
+      ++graph_recordings_;
       hit = &graphs_.back();
     }
     hit->last_use = ++graph_clock_;
@@ -880,7 +887,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     note_replay(n_ticks);
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
-  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
+  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
 }
 
@@ -980,8 +987,43 @@ void Batch::account_sequence(long n_ticks, double dt, bool all_measured) {
   if (all_measured) nm_acc_ += n_ticks;
 }
 
+void Batch::account_sequence(const DtSchedule& sched, bool all_measured) {
+  t_acc_ = sched.advance(t_acc_);
+  if (all_measured) nm_acc_ += sched.n;
+}
+
+const double* Batch::dt_table_push(const double* dt_host, long n) {
+  if (n > dttab_cap_) {   // grow: nothing in flight may still read the old blocks
+    const long want = (std::max<long>(std::max<long>(n, 256), dttab_cap_ * 2) + 15) / 16 * 16;
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+    double* h = nullptr;
+    double* d = nullptr;
+    TE_HIP_CHECK(hipHostMalloc((void**)&h, (size_t)want * sizeof(double), hipHostMallocDefault));
+    if (hipMalloc((void**)&d, (size_t)want * sizeof(double)) != hipSuccess) {
+      (void)hipHostFree(h);
+      throw std::runtime_error("target_estimation_amd: no device memory for the time-step table");
+    }
+    device_free(d_dttab_);   // (deferred while a resident session of the process is alive)
+    if (h_dttab_) h_dttab_retired_.push_back(h_dttab_);
+    d_dttab_ = d; h_dttab_ = h; dttab_cap_ = want; dttab_off_ = 0;
+  } else if (dttab_off_ + n > dttab_cap_) {   // wrap: the runs at the head of the ring may still be in flight
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+    dttab_off_ = 0;
+  }
+  double* h = h_dttab_ + dttab_off_;
+  double* d = d_dttab_ + dttab_off_;
+  std::memcpy(h, dt_host, (size_t)n * sizeof(double));   // (the caller's array is read here, before the call returns)
+  TE_HIP_CHECK(hipMemcpyAsync(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream_));
+  dttab_off_ += n;
+  return d;
+}
+
 void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                       const unsigned char* has_base, long has_stride, const PoseStream& poses) {
+                       const unsigned char* has_base, long has_stride, const PoseStream& poses, const DtSchedule& sched) {
+  if (sched.on()) {   // the schedule form: step_fused_gated's refusals and its table
+    step_fused_gated(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses, InnovStream{}, sched);
+    return;
+  }
   check_pose_stream(poses);
   touch();
   demote_shared();   // (the temporally fused kernels exist for the plain form only)
@@ -997,12 +1039,14 @@ void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick
 }
 
 void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
-                             long has_stride, const PoseStream& poses, const InnovStream& innov) {
-  if (!innov.on() && !innov.gated() && !innov.reacq.on) {   // no stream, no gate: the plain fused call, the same kernels
+                             long has_stride, const PoseStream& poses, const InnovStream& innov, const DtSchedule& sched) {
+  const bool plain = !innov.on() && !innov.gated() && !innov.reacq.on;   // no stream, no gate: the plain fused loop
+  if (plain && !sched.on()) {   // ... of the plain fused call, the same kernels
     step_fused(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses);
     return;
   }
-  const bool one_launch = fused_gate_served() && !poses.dev;
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
+  const bool one_launch = (sched.on() ? fused_dt_served(!plain) : fused_gate_served()) && !poses.dev;
   check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
   check_innov_stream(innov, one_launch);   // (the kernel's K = 0 reads no initial covariance; the single ticks' launch is given the table)
   if (n_ticks > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: step_fused_gated: n_ticks does not fit an int");
@@ -1011,8 +1055,10 @@ void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, lon
   touch();
   demote_shared();   // (the temporally fused kernels exist for the plain form only)
   if (n_ == 0 || n_ticks <= 0) return;
-  if (keep_meas_) {   // measured-pose rows keep ACCEPTED measurements, tick by tick: the sequence's launches
-    step_sequence(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, 0, 0, poses, innov);
+  // measured-pose rows keep ACCEPTED measurements, tick by tick: the sequence's launches.  So does a schedule beyond what one
+  // table's 32-bit byte offsets reach (kDtTabMaxTicks).
+  if (keep_meas_ || (sched.on() && n_ticks > kDtTabMaxTicks)) {
+    step_sequence(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, 0, 0, poses, innov, sched);
     return;
   }
   if (innov.reacq.on && (innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
@@ -1021,16 +1067,22 @@ void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, lon
   p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
   p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
   p.pose = poses.dev; p.pose_ld = poses.ld; p.pose_tick_stride = poses.tick_stride; p.pose_ring = poses.ring;
-  p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
-  p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
-  p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
-  if (innov.reacq.on) {
-    p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
-    p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
+  if (!plain) {
+    p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
+    p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
+    p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
+    if (innov.reacq.on) {
+      p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+      p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
+    }
+  }
+  if (sched.on()) {   // the table: a run of the batch's ring that no other call shares, filled on the stream ahead of the launch
+    p.dt_sched = 1; p.dt_host = sched.dt; p.dt = 0.0;
+    p.dt_tab = dt_table_push(sched.dt, n_ticks);
   }
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
-  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
+  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
 }
 

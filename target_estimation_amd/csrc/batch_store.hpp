@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "dt_schedule.hpp"
 #include "kf_ops.hpp"
 #include "reacquire_plan.hpp"
 
@@ -144,14 +145,17 @@ class Batch {
   // innov: the per-tick innovation stream of the call (InnovStream; by default none), written by the step kernel where the layout
   // has an INNOV variant, by an innovation-writer launch ahead of every tick otherwise (OpsImpl::step).  Its ticks run in place
   // (no A -> B variant) -- same bits.
+  // sched: the call's time-step schedule (DtSchedule; by default none).  With one, tick s is launched with dt = sched.dt[s] and `dt`
+  // is not read; the clock advances by one te_clock_add per tick, and a recording is filed under the schedule's bits.
   void step_sequence(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                      const unsigned char* has_base, long has_stride, int use_graph, long ring_ticks = 0,
-                     const PoseStream& poses = PoseStream{}, const InnovStream& innov = InnovStream{});
+                     const PoseStream& poses = PoseStream{}, const InnovStream& innov = InnovStream{}, const DtSchedule& sched = DtSchedule{});
   // n_ticks ticks in ONE launch: every target's state stays in registers across the ticks and only
   // the measurements are read per tick.  Same results as n_ticks single ticks; a different
   // ("effective", temporally fused) cost model -- for replaying recorded streams.
+  // sched: the call's time-step schedule, or none (step_fused_gated below says who serves it).
   void step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
-                  const unsigned char* has_base, long has_stride, const PoseStream& poses = PoseStream{});
+                  const unsigned char* has_base, long has_stride, const PoseStream& poses = PoseStream{}, const DtSchedule& sched = DtSchedule{});
   // step_fused with the innovation stream, the validation gate and the re-acquisition policy of step_sequence INSIDE the fused call
   // (target_batch_step_fused_gated): per slot and tick, bit for bit, what step_sequence(..., use_graph 0, ring_ticks 0, poses, innov)
   // leaves -- state, covariance, unwrap memory, counter, clock, rejection runs, every NIS row, innovation block, event row and pose
@@ -159,8 +163,20 @@ class Batch {
   // re-initialised in registers) where fused_gate_served(); every other batch, and a call with a pose stream, runs the sequence's
   // ticks -- same results, its launch counts.  !innov.on(): exactly step_fused.  Refusals (invalid_argument, nothing launched): those
   // of step_sequence's streams, n_ticks beyond an int, negative strides, ld < size.  A shared-axes batch is expanded first.
+  // sched: the call's time-step schedule (target_batch_step_fused_dt), or none.  With one, tick s of the call runs with sched.dt[s]: per
+  // slot and tick, bit for bit, what the single ticks step_dense(sched.dt[s], ...) / step_sequence(1, sched.dt[s], ...) leave, the
+  // clock included.  ONE launch where fused_dt_served(): the kFused loop, plain or gated, reading a device table the batch owns and
+  // fills on its stream ahead of the launch (dt_table_push); everywhere else the single ticks -- same results.
   void step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
-                        long has_stride, const PoseStream& poses, const InnovStream& innov);
+                        long has_stride, const PoseStream& poses, const InnovStream& innov, const DtSchedule& sched = DtSchedule{});
+  // one launch per fused call with a schedule (without a pose stream): gated = the call carries an innovation stream, a gate or a
+  // policy (the gated loop), else the plain loop
+  // (a shared-axes batch says no: its call is the expansion to the plain form, a synchronisation, and then that form's launch)
+  bool fused_dt_served(bool gated) const {
+    if (shared_axes()) return false;
+    if (gated) return fused_gate_served() && ops_->fused_gate_dt != 0;
+    return ops_->fused_dt != 0 && n_classes_ == 1 && !keep_meas_;
+  }
   // one launch per fused gated call (without a pose stream): the plain form of this batch has the kernel, one (Q, R) class, no
   // measured-pose rows
   bool fused_gate_served() const {
@@ -313,6 +329,7 @@ class Batch {
   // query of every slot runs inside the step kernel (one launch).
   // ab: 1 = an A -> B tick (records read from the current buffer, written to the alternate one, buffers swapped; never
   // inside a stream capture: a recorded graph bakes its pointers), 0 = in place.
+  // (a call with a time-step schedule hands every tick its own dt here and in tick_params)
   void enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& spec, bool query, const double* origin, double radius,
                     bool reverse = false, bool ab = false);
   // The same tick as launch parameters only, for the manager's one-launch population tick (kf_population.hpp): possible when
@@ -326,12 +343,14 @@ class Batch {
   void swap_records() { std::swap(d_rec_, d_rec_alt_); }
   // (all_measured: measurements without a mask and without a gate -- a gated tick counts its accepted ones on the device)
   void account_sequence(long n_ticks, double dt, bool all_measured);
+  void account_sequence(const DtSchedule& sched, bool all_measured);   // the schedule form: one te_clock_add per tick, in order
   // identity of everything a recorded launch sequence refers to
   // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
   struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; const void* p0tab; };
   // (the tile arrays, the rejection runs and the slot -> row index are allocated and freed with the records: rec identifies them too)
   DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_, d_p0tab_}; }
   void prepare() { touch(); }
+  long graph_recordings() const { return graph_recordings_; }
 
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121), optional: see measured_pose.hpp
   void set_keep_measurement(bool on);
@@ -473,11 +492,24 @@ class Batch {
     unsigned long last_use = 0;
     PoseStream poses{};   // (recorded graphs write into the pose buffers they were recorded with)
     InnovStream innov{};  // (... and into the innovation buffers)
+    bool dt_is_schedule = false;   // recorded from a call with a time-step schedule: filed under its values as bits, not under dt
+    std::vector<double> dt_key;
   };
   std::vector<GraphEntry> graphs_;
   unsigned long graph_clock_ = 0;   // recorded sequences are evicted least-recently-used first (64 kept)
   hipStream_t cap_stream_ = nullptr;
   void drop_graphs();
+  long graph_recordings_ = 0;      // recordings made so far (graph_recordings(): what a test of the cache observes)
+  // The device table of a fused call with a time-step schedule.  Every call takes a fresh run of a ring -- pinned host words the
+  // schedule is copied into before the call returns, and the device words behind them, filled by a copy on the batch's stream
+  // ahead of the launch -- so two calls enqueued back to back never share a word; the ring wraps, or grows, behind a
+  // synchronisation of the stream.  The device block goes through device_free (deferred while a resident session of the process is
+  // alive); retired host blocks are kept until the batch goes.
+  double* d_dttab_ = nullptr;
+  double* h_dttab_ = nullptr;
+  long dttab_cap_ = 0, dttab_off_ = 0;
+  std::vector<double*> h_dttab_retired_;
+  const double* dt_table_push(const double* dt_host, long n);   // the device address of the call's n entries
   // queue of one-target creations (append with count == 1): consecutive ones with the same (t0, P0, class) become one init launch
   struct InitQueue { std::vector<unsigned> ids; std::vector<double> p0, v0, a0, P0; double t0 = 0.0; int cls = 0; long first = 0; } initq_;
   void flush_inits();

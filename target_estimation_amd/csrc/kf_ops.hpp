@@ -126,6 +126,14 @@ struct StepParams {
   int fused_gate_k = -1;
   unsigned char* fused_gate_event = nullptr;
   long fused_gate_event_stride = 0, fused_gate_event_ring = 0;
+  // The time-step schedule of a launched fused call (target_batch_step_fused_dt; kf_step_sep.hpp, DTTAB): dt_sched = 1 on a dense
+  // request in place of n_ticks >= 1 ticks, plain or with fused_gate.  Tick s of the call runs with dt_host[s]; dt_tab holds the same
+  // n_ticks doubles in device memory, written on the launch's stream ahead of it, and `dt` is not read.  One launch where the layout
+  // has the kernel (Ops::fused_dt / fused_gate_dt, one (Q, R) class, no pose stream in the call); otherwise OpsImpl::step runs the
+  // ticks as single requests with dt = dt_host[s] -- same results.
+  int dt_sched = 0;
+  const double* dt_host = nullptr;
+  const double* dt_tab = nullptr;
 };
 
 // The launch behind a gated tick that keeps the rejection runs and re-initialises lost targets (kf_reacquire_impl.hpp).
@@ -185,6 +193,10 @@ struct Ops {
   // 1: this (model, precision, layout) has a launched fused gated kernel (kf_step_sep_fused_gate_kernel); 0: a fused gated request
   // is served tick by tick
   int fused_gate = 0;
+  // 1: ... has the launched fused kernel with a time-step table, plain (kf_step_sep_fused_dt_kernel) / gated
+  // (kf_step_sep_fused_gate_dt_kernel); 0: a fused request with a schedule is served tick by tick
+  int fused_dt = 0;
+  int fused_gate_dt = 0;
 };
 
 // g == 0 selects the default lanes-per-target of the (model, precision); nullptr if unsupported

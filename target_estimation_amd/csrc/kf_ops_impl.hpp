@@ -60,6 +60,13 @@ int live_gate_blocks_per_cu();
 template <class M, typename T, int LAYOUT>
 void launch_sep_fused_gate_step(const StepArgs<T>& a, const FusedGate& g, unsigned blocks, unsigned threads, hipStream_t s);
 
+// The launched fused kernels with a time-step table (kf_step_sep.hpp, kf_step_sep_fused_dt_kernel / kf_step_sep_fused_gate_dt_kernel), in
+// kf_fused_dt_{uv,ua,ar,av}.hip (kf_fused_dt_impl.hpp) likewise.
+template <class M, typename T, int LAYOUT>
+void launch_sep_fused_dt_step(const StepArgs<T>& a, const double* dt_tab, unsigned blocks, unsigned threads, hipStream_t s);
+template <class M, typename T, int LAYOUT>
+void launch_sep_fused_gate_dt_step(const StepArgs<T>& a, const FusedGate& g, const double* dt_tab, unsigned blocks, unsigned threads, hipStream_t s);
+
 // reacquire_kernel (kf_reacquire_impl.hpp), in kf_reacquire_{uv,ua,ar,av}.hip likewise: one instance per OpsImpl.
 template <class M, typename T, int G, int LAYOUT>
 void launch_reacquire(const ReacquireArgs& a, hipStream_t s);
@@ -113,7 +120,14 @@ struct OpsImpl {
   // by tick (profiles/fused_gate_kernel_resources.txt).  None does.
   static constexpr bool kFusedGateTickByTick = false;
   static constexpr bool kHasFusedGate = C::SEP && !C::SHARED && !kGateByWriter && !kFusedGateTickByTick;
-  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW, kGateByWriter, kFusedGateTickByTick};
+  // Launched fused instantiations with a time-step table that would need scratch are not shipped: such a batch's schedule call is
+  // served tick by tick (profiles/dt_schedule_kernel_resources.txt).  None does.
+  static constexpr bool kFusedDtTickByTick = false;
+  static constexpr bool kFusedGateDtTickByTick = false;
+  static constexpr bool kHasFusedDt = C::SEP && !C::SHARED && !kFusedDtTickByTick;
+  static constexpr bool kHasFusedGateDt = kHasFusedGate && !kFusedGateDtTickByTick;
+  static constexpr StepTraits kTraits{C::SEP, C::SHARED, C::UT, kHasLive, kFusedPoseTickByTick, kFusedSpills, C::TPW, kGateByWriter, kFusedGateTickByTick,
+                                      kFusedDtTickByTick, kFusedGateDtTickByTick};
   // the pose-writer launch behind a tick whose kernel has no pose output: outputs_kernel into the tick's block
   static void write_pose_block(const StepParams& p, double* pose, hipStream_t s) {
     OutArgs o;
@@ -169,7 +183,11 @@ struct OpsImpl {
       throw std::runtime_error("target_estimation_amd: the resident gate: no resident kernel for this batch");
     }
   }
-  static void launch_fused_gate(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s) {
+  static void launch_fused_dt(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s) {
+    if constexpr (kHasFusedDt) launch_sep_fused_dt_step<M, T, LAYOUT>(a, p.dt_tab, blocks, threads, s);
+    else throw std::runtime_error("target_estimation_amd: the time-step schedule: no fused kernel with a table for this batch");
+  }
+  static void launch_fused_gate(const StepArgs<T>& a, const StepParams& p, unsigned blocks, unsigned threads, hipStream_t s, bool dt_table = false) {
     if constexpr (kHasFusedGate) {
       FusedGate g;
       g.gate = p.fused_gate_nis_max; g.nis = p.fused_gate_nis; g.nis_stride = p.fused_gate_nis_stride; g.nis_ring = p.fused_gate_nis_ring;
@@ -177,7 +195,12 @@ struct OpsImpl {
       g.k = p.fused_gate_k; g.run = p.reacq_run; g.p0_tab = p.reacq_p0; g.p0_idx = p.reacq_p0_idx;
       // (a predict-only call changes no run and, like the single ticks, writes no event row)
       g.event = p.meas ? p.fused_gate_event : nullptr; g.event_stride = p.fused_gate_event_stride; g.event_ring = p.fused_gate_event_ring;
-      launch_sep_fused_gate_step<M, T, LAYOUT>(a, g, blocks, threads, s);
+      if (dt_table) {
+        if constexpr (kHasFusedGateDt) launch_sep_fused_gate_dt_step<M, T, LAYOUT>(a, g, p.dt_tab, blocks, threads, s);
+        else throw std::runtime_error("target_estimation_amd: the time-step schedule: no fused gated kernel with a table for this batch");
+      } else {
+        launch_sep_fused_gate_step<M, T, LAYOUT>(a, g, blocks, threads, s);
+      }
     } else {
       throw std::runtime_error("target_estimation_amd: the fused gate: no fused gated kernel for this batch");
     }
@@ -188,6 +211,7 @@ struct OpsImpl {
     for (long t = 0; t < (long)p.n_ticks; ++t) {
       StepParams q = p;
       q.fused_gate = 0; q.n_ticks = 1; q.tick_stride = 0; q.has_stride = 0;
+      if (p.dt_sched) { q.dt = p.dt_host[t]; q.dt_sched = 0; q.dt_host = nullptr; q.dt_tab = nullptr; }   // (a single tick takes its dt by value)
       q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
       q.has_meas = p.has_meas ? p.has_meas + t * p.has_stride : nullptr;
       const long b = p.fused_gate_nis_ring > 0 ? t % p.fused_gate_nis_ring : t;
@@ -240,16 +264,19 @@ struct OpsImpl {
       q.n_ticks = 1;
       if (p.pose) { q.pose_tick_stride = 0; q.pose_ring = 0; }
     }
+    if (p.dt_sched && !plan.dt_table) { q.dt_sched = 0; q.dt_host = nullptr; q.dt_tab = nullptr; }   // (single ticks take their dt by value)
     for (int t = 0, launches = plan.tick_by_tick ? p.n_ticks : 1; t < launches; ++t) {
       double* pose = p.pose;
       if (plan.tick_by_tick) {   // tick t's measurement block, mask row and pose block
         q.meas = p.meas ? static_cast<const char*>(p.meas) + (size_t)t * (size_t)p.tick_stride * sizeof(T) : nullptr;
         q.has_meas = p.has_meas ? p.has_meas + (long)t * p.has_stride : nullptr;
+        if (p.dt_sched) q.dt = p.dt_host[t];
         if (p.pose) pose = p.pose + (p.pose_ring > 0 ? (long)t % p.pose_ring : (long)t) * p.pose_tick_stride;
       }
       q.pose = plan.pose_writer_after_each_tick ? nullptr : pose;
       if (plan.gate_by_id) launch_gate_by_id(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
-      else if (plan.fused_gated) launch_fused_gate(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
+      else if (plan.fused_gated) launch_fused_gate(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s, plan.dt_table);
+      else if (plan.dt_table) launch_fused_dt(make_step_args<T>(q), p, blocks, 64u * (unsigned)wpb, s);
       else if (gate_kernel) launch_gate(make_step_args<T>(q), p.gate, blocks, 64u * (unsigned)wpb, s);
       else launch_variant(plan.variant, make_step_args<T>(q), blocks, 64u * (unsigned)wpb, s);
       if (plan.reacquire_after_step) reacquire(make_reacquire_args(p), s);   // (p: the caller's mask and NIS row; gated ticks are single)
@@ -330,7 +357,7 @@ struct OpsImpl {
         LayoutInfo{C::N, C::K, G, C::SHARED ? (int)LAYOUT_SEPARABLE_PACKED : LAYOUT, C::TPW, C::LPT, C::RW, C::TILE_BYTES, C::TILE_PAYLOAD, C::SHARED ? 1 : 0,
                    C::UT ? C::LW : 0, C::UT ? C::LIN_CHUNKS : 0},
         C::WPB, &step, &live_capacity, &init, &get_state, &set_state, &move_record, &move_records, &outputs, &pack_meas, &intersect, &outputs_rows, &innov, &innov_gate,
-        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr, &reacquire, kHasFusedGate ? 1 : 0};
+        C::SHARED ? &expand : nullptr, C::UT ? &settle : nullptr, &reacquire, kHasFusedGate ? 1 : 0, kHasFusedDt ? 1 : 0, kHasFusedGateDt ? 1 : 0};
     return &ops;
   }
 };

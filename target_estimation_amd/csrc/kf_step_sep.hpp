@@ -431,6 +431,9 @@ struct FusedGate {
 // Both kernel arguments as they lie in the segment (explicit arguments in order, each at its natural alignment): every read is then
 // a scalar load at a constant offset from the segment pointer, which a kernel holds anyway -- no second pointer to keep.
 template <typename T> struct FusedGateSegment { StepArgs<T> a; FusedGate g; };
+// ... and of the gated kernel with a time-step schedule (kf_step_sep_fused_gate_dt_kernel): the table's pointer is a third
+// argument, read per tick from the segment like the rest
+template <typename T> struct FusedGateDtSegment { StepArgs<T> a; FusedGate g; const double* dt_tab; };
 
 // The form of the re-initialisation per instantiation.  In registers (above) where that costs no wavefront per SIMD against the
 // same kernel without it; elsewhere the record is written once more BEHIND store_record, word by word through state_set /
@@ -448,9 +451,12 @@ constexpr bool gate_id_tail_in_registers() {
 #endif
 }
 
-template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false>
+// DTTAB: the launched fused call with a time-step schedule (target_batch_step_fused_dt): tick s of the loop runs with dt_tab[s], a
+// device table of doubles read through the constant address space like Qm -- uniform across the wavefront, one scalar load and
+// one conversion per tick.  A template argument next to the variant word, as GATE is; the kernels without it compile to what they were.
+template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false, bool DTTAB = false>
 __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0, const GateById* gid = nullptr,
-                                              const LiveGateArg* lg = nullptr) {
+                                              const LiveGateArg* lg = nullptr, const double* dt_tab = nullptr) {
   constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
                  AB = sv_has(VAR, kAB), POSE = sv_has(VAR, kPose), INNOV = sv_has(VAR, kInnov);
   constexpr int LIVE = sv_live(VAR);
@@ -465,6 +471,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   static_assert(BYID == (INNOV && INDEXED) && (!BYID || GATE), "kInnov | kIndexed is the gated by-id step and nothing else");
   if constexpr (!BYID) (void)gid;
   if constexpr (!LGATE) (void)lg;
+  static_assert(!DTTAB || (FUSED && LIVE == 0 && !INDEXED), "the time-step table belongs to the launched fused loops");
+  if constexpr (!DTTAB || FGATE) (void)dt_tab;   // (FGATE: read per tick where it arrived -- FusedGateDtSegment)
   // FGATE: the kernel's two arguments where they arrived (FusedGateSegment)
   typedef const FusedGateSegment<T> __attribute__((address_space(4))) FusedSeg;
 #define FG0_ (((FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr())->g)
@@ -592,7 +600,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   if constexpr (INDEXED) {
     if (a.dt_per && valid) dtd = a.dt_per[entry];
   }
-  const T dt = (T)dtd;
+  const T dt_call = (T)dtd;   // (DTTAB: unread -- every tick takes its own from the table)
   // The one (Q, R) row of a one-class batch, through the CONSTANT address space: uniform and never written while a step kernel
   // runs, so every read is a scalar load wherever it sits.  As a plain global pointer it stops being one behind the resident
   // loop's atomics (the compiler can no longer prove that nothing clobbers it): the fp64 angular kernels, whose 60 words do not
@@ -723,6 +731,21 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   const auto* const fgt = &kt->g;
   const auto* const at = &kt->a;
   (void)fgt; (void)at;
+  // the tick's dt: the launch's, or (DTTAB) entry `tick` of the schedule -- a scalar load at a uniform address, converted once
+  T dt_tick = dt_call;
+  if constexpr (DTTAB) {
+    // base + a 32-bit byte offset: the scalar load's own addressing form, no 64-bit address arithmetic in scalar registers (with it
+    // the gated angular-velocities fp64 kernel on packed groups had 36 B of scalar spill slots accounted as scratch).  The host
+    // launches at most kDtTabMaxTicks ticks (dt_schedule.hpp) with a table -- Batch::step_fused_gated runs a longer call as single
+    // ticks -- so the offset cannot wrap.
+    typedef const double __attribute__((address_space(4))) ConstD;
+    typedef const char __attribute__((address_space(4))) ConstB;
+    typedef const FusedGateDtSegment<T> __attribute__((address_space(4))) FusedDtSeg;
+    const unsigned dt_off = (unsigned)tick << 3;
+    if constexpr (FGATE) dt_tick = (T) * (ConstD*)((ConstB*)((FusedDtSeg*)kt)->dt_tab + dt_off);
+    else dt_tick = (T) * (ConstD*)((ConstB*)dt_tab + dt_off);
+  }
+  const T dt = dt_tick;
 #define GATE_T_ (LGATE ? lgt->gate : FGATE ? fgt->gate : gate)
   // the policy's arguments of a gate that lives inside a tick loop (constant condition: only the live arm is compiled)
 #define PG_(f_) (LGATE ? lgt->f_ : fgt->f_)
@@ -1678,6 +1701,25 @@ __global__ void __launch_bounds__(256) kf_step_sep_fused_gate_kernel(const StepA
   static_assert(offsetof(FusedGateSegment<T>, g) == (sizeof(StepArgs<T>) + alignof(FusedGate) - 1) / alignof(FusedGate) * alignof(FusedGate),
                 "explicit kernel arguments lie in the segment in order, each at its natural alignment");
   sep_step_wave<M, T, LAYOUT, kFused, true, false>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate);
+}
+
+// The launched fused calls with a time-step schedule (sep_step_wave, DTTAB): target_batch_step_fused_dt.  dt_tab [a.n_ticks] doubles in
+// device memory, written on the stream ahead of the launch and never while it runs; StepArgs::dt is not read.  The plain loop and
+// the gated one, each the kernel above it with the table as one more argument -- StepArgs and FusedGate keep their sizes.  Instantiated
+// in kf_fused_dt_{uv,ua,ar,av}.hip (kf_fused_dt_impl.hpp) for the two separable layouts in both precisions; the grids are the plain
+// fused launch's.
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256, (sep_min_waves<M, T, LAYOUT, false, 0>())) kf_step_sep_fused_dt_kernel(const StepArgs<T> a, const double* dt_tab) {
+  sep_step_wave<M, T, LAYOUT, kFused, false, false, true>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), 0.0, nullptr,
+                                                          nullptr, dt_tab);
+}
+template <class M, typename T, int LAYOUT>
+__global__ void __launch_bounds__(256) kf_step_sep_fused_gate_dt_kernel(const StepArgs<T> a, const FusedGate g, const double* dt_tab) {
+  static_assert(offsetof(FusedGateDtSegment<T>, g) == offsetof(FusedGateSegment<T>, g) &&
+                    offsetof(FusedGateDtSegment<T>, dt_tab) == (offsetof(FusedGateSegment<T>, g) + sizeof(FusedGate) + 7) / 8 * 8,
+                "explicit kernel arguments lie in the segment in order, each at its natural alignment");
+  (void)dt_tab;   // (sep_step_wave reads it where the launch put it, tick by tick)
+  sep_step_wave<M, T, LAYOUT, kFused, true, false, true>(a, (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (int)(threadIdx.x & 63), g.gate);
 }
 
 // ---- one launch for the whole population of a manager ------------------------------------------------------------------------

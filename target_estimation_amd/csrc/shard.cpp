@@ -854,9 +854,10 @@ void Shard::enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch
 }
 
 void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
-                                    const double* origin, double radius, int use_graph) {
+                                    const double* origin, double radius, int use_graph, const DtSchedule& sched) {
   const size_t nb = batches_.size();
   if ((size_t)n_specs != nb) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
   for (size_t b = 0; b < nb; ++b) {   // (before anything is enqueued)
     batches_[b]->check_pose_stream(specs[b].poses);
     batches_[b]->check_innov_stream(specs[b].innov);
@@ -886,11 +887,11 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     for (long s = 0; s < n_ticks; ++s) {
       const bool rev = zz && seq_flip_;
       if (pop) {
-        enqueuePopulationTick(stream_, s, dt, specs, query, org, radius, rev, ab && !query);
+        enqueuePopulationTick(stream_, s, sched.at(s, dt), specs, query, org, radius, rev, ab && !query);
       } else {
         for (size_t k = 0; k < nb; ++k) {
           const size_t b = rev ? nb - 1 - k : k;
-          batches_[b]->enqueue_tick(stream_, s, dt, specs[b], query, org, radius, rev, ab);
+          batches_[b]->enqueue_tick(stream_, s, sched.at(s, dt), specs[b], query, org, radius, rev, ab);
         }
       }
       seq_flip_ = !seq_flip_;
@@ -908,7 +909,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     };
     SeqGraph* hit = nullptr;
     for (auto& g : seq_graphs_) {
-      if (g.n_ticks != n_ticks || g.dt != dt || g.query != query || g.specs.size() != nb) continue;
+      if (g.n_ticks != n_ticks || !dt_key_matches(g.dt_key, g.dt_is_schedule, g.dt, sched, dt) || g.query != query || g.specs.size() != nb) continue;
       if (query && (g.origin[0] != org[0] || g.origin[1] != org[1] || g.origin[2] != org[2] || g.radius != radius)) continue;
       bool ok = true;
       for (size_t b = 0; b < nb && ok; ++b) ok = same_spec(g.specs[b], specs[b]) && same_id(g.ident[b], batches_[b]->dev_identity());
@@ -927,6 +928,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
       }
       SeqGraph g;
       g.n_ticks = n_ticks; g.dt = dt; g.query = query; g.radius = radius;
+      g.dt_is_schedule = sched.on(); g.dt_key = sched.key();   // (every tick's dt is baked into its launch)
       g.origin[0] = org[0]; g.origin[1] = org[1]; g.origin[2] = org[2];
       g.specs.assign(specs, specs + nb);
       for (size_t b = 0; b < nb; ++b) g.ident.push_back(batches_[b]->dev_identity());
@@ -954,13 +956,13 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
           long state = 0;
           for (size_t b = 0; b < nb; ++b) state += batches_[b]->state_bytes();
           const bool zz = state >= Batch::zigzag_min_bytes();
-          for (long s = 0; s < n_ticks; ++s) enqueuePopulationTick(cap, s, dt, specs, query, org, radius, zz && (s & 1) != 0, false);
+          for (long s = 0; s < n_ticks; ++s) enqueuePopulationTick(cap, s, sched.at(s, dt), specs, query, org, radius, zz && (s & 1) != 0, false);
         } else
         for (size_t b = 0; b < nb; ++b) {
           if (batches_[b]->size() == 0) continue;
           set_deps(none);                                  // a new chain: no predecessor
           const bool zz = batches_[b]->state_bytes() >= Batch::zigzag_min_bytes();
-          for (long s = 0; s < n_ticks; ++s) batches_[b]->enqueue_tick(cap, s, dt, specs[b], query, org, radius, zz && (s & 1) != 0);
+          for (long s = 0; s < n_ticks; ++s) batches_[b]->enqueue_tick(cap, s, sched.at(s, dt), specs[b], query, org, radius, zz && (s & 1) != 0);
 #ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library
           if (std::getenv("TE_TEST_FAIL_IN_CAPTURE")) throw std::runtime_error("target_estimation_amd: injected failure inside stream capture");
 #endif
@@ -980,14 +982,19 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
       TE_HIP_CHECK(hipStreamEndCapture(cap, &g.graph));
       TE_HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
       seq_graphs_.push_back(std::move(g));
+      ++seq_recordings_;
       hit = &seq_graphs_.back();
     }
     if (use_graph == 2) return;
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
     for (size_t b = 0; b < nb; ++b) batches_[b]->note_replay(n_ticks);
   }
-  for (size_t b = 0; b < nb; ++b)
-    if (batches_[b]->size() > 0) batches_[b]->account_sequence(n_ticks, dt, specs[b].meas_base && !specs[b].has_base && !specs[b].innov.gated());
+  for (size_t b = 0; b < nb; ++b) {
+    if (batches_[b]->size() == 0) continue;
+    const bool all_measured = specs[b].meas_base && !specs[b].has_base && !specs[b].innov.gated();
+    if (sched.on()) batches_[b]->account_sequence(sched, all_measured);
+    else batches_[b]->account_sequence(n_ticks, dt, all_measured);
+  }
 }
 
 void Shard::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s,

@@ -133,8 +133,10 @@ class Shard {
 
   // ---- every batch at once (TargetManager::stepSequenceAll, live*All, posesToDevice, getEstAllById, log)
   bool populationTick() const;   // the tick of all batches as one launch (kf_population.hpp)
+  // sched: the call's time-step schedule (dt_schedule.hpp; by default none): tick s of every batch runs with sched.dt[s]
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query, const double* origin, double radius,
-                       int use_graph);
+                       int use_graph, const DtSchedule& sched = DtSchedule{});
+  long seqRecordings() const { return seq_recordings_; }   // all-batches recordings made so far
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -180,8 +182,11 @@ class Shard {
     std::vector<Batch::SeqSpec> specs;
     std::vector<Batch::DevIdentity> ident;
     hipGraph_t graph; hipGraphExec_t exec;
+    bool dt_is_schedule = false;   // recorded from a call with a time-step schedule: filed under its values as bits, not under dt
+    std::vector<double> dt_key;
   };
   std::vector<SeqGraph> seq_graphs_;
+  long seq_recordings_ = 0;
   std::vector<hipStream_t> branch_streams_;   // [0]: the capture stream
   std::vector<hipEvent_t> branch_events_;
   void dropSeqGraphs();

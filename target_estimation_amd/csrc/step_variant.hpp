@@ -79,6 +79,10 @@ struct StepTraits {
   int tpw;                       // targets per wavefront
   bool gate_by_writer = false;   // no gated kernel (it would spill or need scratch): the gate's mask comes from the innovation writer
   bool fused_gate_tick_by_tick = false;   // no launched fused gated kernel (it would need scratch): a fused gated request is served tick by tick
+  // no launched fused kernel with a time-step table (it would need scratch): a fused request with a schedule is served tick by
+  // tick -- the plain loop / the gated loop, each on its own
+  bool fused_dt_tick_by_tick = false;
+  bool fused_gate_dt_tick_by_tick = false;
 };
 
 template <unsigned N>
@@ -121,6 +125,10 @@ struct StepPlan {
   // stream in the same call, StepTraits::fused_gate_tick_by_tick): the caller runs the call's ticks as single gated requests, each
   // planned on its own -- `variant` is then 0 and says nothing.
   bool fused_gated = false;
+  // the request carries a time-step schedule (P::dt_sched) and ONE launch serves it: the kFused loop -- plain, or with fused_gated
+  // the gated one -- whose tick s reads entry s of the device table P::dt_tab (kf_step_sep.hpp, DTTAB: a template argument next to
+  // the variant word, not a bit of it).  A schedule request without it is tick_by_tick: the caller gives tick s the dt P::dt_host[s].
+  bool dt_table = false;
 };
 
 // The gate of a request: P::gate (a double, 0 = none) and P::gate_by_writer (the caller asks for the writer's mask row) where the
@@ -172,6 +180,24 @@ template <class P>
 constexpr bool requested_fused_gate(const P& p) {
   if constexpr (has_fused_gate_member<P>::value) return p.fused_gate != 0;
   else return false;
+}
+// The time-step schedule of a launched fused call: P::dt_sched (non-zero = the request is target_batch_step_fused_dt's: a dense request in
+// place of n_ticks >= 1 ticks, plain or with P::fused_gate, whose tick s runs with dt[s]; it then has P::dt_host, the schedule on
+// the host [n_ticks], and P::dt_tab, the same values in device memory, written on the stream ahead of the launch).  A request type
+// without the member plans as it always did.
+template <class P, class = void> struct has_dt_sched_member : std::false_type {};
+template <class P> struct has_dt_sched_member<P, std::void_t<decltype(std::declval<const P&>().dt_sched)>> : std::true_type {};
+template <class P>
+constexpr bool requested_dt_sched(const P& p) {
+  if constexpr (has_dt_sched_member<P>::value) return p.dt_sched != 0;
+  else return false;
+}
+template <class P>
+void check_dt_sched(const P& p, bool one_launch) {
+  if constexpr (has_dt_sched_member<P>::value) {
+    if (!p.dt_host) throw std::runtime_error("target_estimation_amd: the time-step schedule: a request carries it on the host");
+    if (one_launch && !p.dt_tab) throw std::runtime_error("target_estimation_amd: the time-step schedule: one launch reads it from a device table");
+  }
 }
 template <class P>
 constexpr bool requested_gate_by_writer(const P& p) {
@@ -231,6 +257,11 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
         throw std::runtime_error(std::string(pre) + "not together with the single ticks' gate, streams or policies");
       plan.fused_gated = true;
       plan.tick_by_tick = !t.sep || p.cls || p.pose || t.fused_gate_tick_by_tick || t.gate_by_writer;
+      if (requested_dt_sched(p)) {   // the gated loop with the table, where it exists
+        plan.tick_by_tick = plan.tick_by_tick || t.fused_gate_dt_tick_by_tick;
+        plan.dt_table = !plan.tick_by_tick;
+        check_dt_sched(p, plan.dt_table);
+      }
       plan.variant = plan.tick_by_tick ? 0u : (unsigned)kFused;
       return plan;
     }
@@ -252,6 +283,11 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
     throw std::runtime_error("target_estimation_amd: the shared-axes storage form has single-tick kernels of one-class batches only");
   if (p.tile_uni && (!t.uniform_tiles || p.idx || !p.tile_blk))
     throw std::runtime_error("target_estimation_amd: uniform tiles are a property of dense ticks of the shared-axes storage form");
+  if (requested_dt_sched(p)) {
+    if (p.n_ticks < 1 || p.idx || p.live_posted || p.rec_out || p.q_delta || p.o_pose || p.nis || p.tile_uni || t.shared || plan.gated ||
+        requested_reacquire(p) || requested_gate_by_id(p) || requested_live_gate(p))
+      throw std::runtime_error("target_estimation_amd: the time-step schedule: a dense fused launch in place of a batch in the plain form");
+  }
   if (requested_live_gate(p) && !p.live_posted)
     throw std::runtime_error("target_estimation_amd: the resident gate belongs to a live launch (live_posted)");
   if (p.live_posted) {   // a resident launch serves its ticks, query and poses by itself
@@ -298,7 +334,14 @@ StepPlan plan_step(const StepTraits& t, const P& p) {
   // A fused request is served tick by tick -- same results, one launch per tick -- where its kernel does not exist: several
   // (Q, R) classes, poses without a kFused | kPose kernel, the dense kernels that would spill.
   plan.tick_by_tick = p.n_ticks > 1 && (p.cls || t.fused_spills || (p.pose && (!streams_in_kernel || t.fused_pose_tick_by_tick)));
-  plan.variant = requested_variant(p) & ~((plan.tick_by_tick ? kFused : 0u) | (plan.pose_writer_after_each_tick ? kPose : 0u) |
+  // A schedule: the kFused loop with the table (one tick included), or tick by tick where that kernel does not exist -- the dense
+  // layouts, several (Q, R) classes, a pose stream in the same call, StepTraits::fused_dt_tick_by_tick.
+  if (requested_dt_sched(p)) {
+    plan.tick_by_tick = !t.sep || p.cls || p.pose || t.fused_dt_tick_by_tick;
+    plan.dt_table = !plan.tick_by_tick;
+    check_dt_sched(p, plan.dt_table);
+  }
+  plan.variant = (requested_variant(p) | (plan.dt_table ? (unsigned)kFused : 0u)) & ~((plan.tick_by_tick ? kFused : 0u) | (plan.pose_writer_after_each_tick ? kPose : 0u) |
                                           (plan.innov_writer_first ? kInnov : 0u));
   if (!variant_shipped(plan.variant, t)) throw std::runtime_error("target_estimation_amd: no step kernel for this request");
   return plan;

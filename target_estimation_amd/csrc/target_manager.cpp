@@ -660,7 +660,7 @@ bool TargetManager::populationTickNow() {
 }
 
 void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
-                                    const double* origin, double radius, int use_graph, const InnovStream* innov) {
+                                    const double* origin, double radius, int use_graph, const InnovStream* innov, const DtSchedule& sched) {
   if (n_specs < 0) throw std::invalid_argument("target_estimation_amd: stepSequenceAll: negative number of batches");
   std::vector<Batch::SeqSpec> with((size_t)n_specs);
   for (long b = 0; b < n_specs; ++b) {
@@ -668,12 +668,13 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
     with[(size_t)b].poses = poses ? poses[b] : PoseStream{};
     with[(size_t)b].innov = innov ? innov[b] : InnovStream{};
   }
-  stepSequenceAll(n_ticks, dt, with.data(), n_specs, query, origin, radius, use_graph);
+  stepSequenceAll(n_ticks, dt, with.data(), n_specs, query, origin, radius, use_graph, sched);
 }
 
 void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
-                                    const double* origin, double radius, int use_graph) {
+                                    const double* origin, double radius, int use_graph, const DtSchedule& sched) {
   lock_guard<mutex> lg(target_lock_);
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
   if (several()) {   // specs shard-major (numBatches order); a shard checks its own slice, so here every check before any shard launches
     if (n_specs != (long)numBatches()) throw std::runtime_error("target_estimation_amd: stepSequenceAll needs one spec per batch");
     long off = 0;
@@ -690,7 +691,7 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
   for (size_t k = 0; k < shards_.size(); ++k) {
     const long nk = several() ? (long)shards_[k]->batches().size() : n_specs;
     DeviceGuard g(guardDev(k));
-    shards_[k]->stepSequenceAll(n_ticks, dt, specs + off, nk, query, origin, radius, use_graph);
+    shards_[k]->stepSequenceAll(n_ticks, dt, specs + off, nk, query, origin, radius, use_graph, sched);
     off += nk;
   }
 }

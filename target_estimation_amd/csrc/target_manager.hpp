@@ -172,8 +172,10 @@ class TargetManager {
   // and the branches run concurrently; the query runs inside the step kernel (QUERY variants).
   // use_graph == 2 records without launching.  use_graph == 0 issues the same launches eagerly, batch after batch per tick.
   bool populationTickNow();
+  // sched: the call's time-step schedule (dt_schedule.hpp; by default none): tick s of every batch of every shard runs with
+  // sched.dt[s], `dt` is not read, every batch's clock advances tick by tick.
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query,
-                       const double* origin, double radius, int use_graph);
+                       const double* origin, double radius, int use_graph, const DtSchedule& sched = DtSchedule{});
   // The same with a per-tick pose stream per batch (poses[b], PoseStream; one with a null dev writes nothing for that batch):
   // written by the step kernels -- the population kernel's POSE variant where the tick is one launch -- or by a pose-writer
   // launch behind each tick of a batch whose layout has no POSE kernel.  Every stream is checked before anything is enqueued.
@@ -181,7 +183,8 @@ class TargetManager {
   // that batch), routed like the pose streams: the step kernels' INNOV variants -- the population kernel's where the tick is one
   // launch -- or an innovation-writer launch ahead of each tick of a batch whose layout has none.
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, const PoseStream* poses, long n_specs, bool query,
-                       const double* origin, double radius, int use_graph, const InnovStream* innov = nullptr);
+                       const double* origin, double radius, int use_graph, const InnovStream* innov = nullptr,
+                       const DtSchedule& sched = DtSchedule{});
 
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and

@@ -615,6 +615,68 @@ int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks
   });
 }
 
+// ---- step sequences and fused replays with a time step per tick
+static te::DtSchedule dt_schedule(long n_ticks, const double* dt_host) {
+  if (n_ticks > 0 && !dt_host) throw std::invalid_argument("dt_host must not be NULL");
+  return n_ticks > 0 ? te::DtSchedule(dt_host, n_ticks) : te::DtSchedule();
+}
+
+int target_batch_step_sequence_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride,
+                                  long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
+                                  const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                                  const target_reacquire_c* reacq, int use_graph) {
+  return guarded("target_batch_step_sequence_dt", [&] {
+    const te::DtSchedule sched = dt_schedule(n_ticks, dt_host);
+    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
+    BatchLock lk(B(b));
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, 0.0, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream, sched);
+  });
+}
+
+int target_batch_step_fused_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride, long ld,
+                               const unsigned char* has_meas_dev, long has_stride,
+                               const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
+                               const target_reacquire_c* reacq) {
+  return guarded("target_batch_step_fused_dt", [&] {
+    const te::DtSchedule sched = dt_schedule(n_ticks, dt_host);
+    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
+    BatchLock lk(B(b));
+    B(b)->step_fused_gated(n_ticks, 0.0, meas_dev, tick_stride, ld, has_meas_dev, has_stride, pose_stream(poses), stream, sched);
+  });
+}
+
+int target_batch_step_fused_dt_served(target_batch_c* b, int gated) {
+  return guarded_value<int>("target_batch_step_fused_dt_served", -1, [&] { BatchLock lk(B(b)); return B(b)->fused_dt_served(gated != 0) ? 1 : 0; });
+}
+
+long target_batch_graph_recordings(target_batch_c* b) {
+  return guarded_value<long>("target_batch_graph_recordings", -1, [&]() -> long { BatchLock lk(B(b)); return B(b)->graph_recordings(); });
+}
+
+int target_manager_step_sequence_all_dt(target_manager_c* m, long n_ticks, const double* dt_host,
+                                        const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                                        const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                                        const target_reacquire_c* per_batch_reacq, long n_batches,
+                                        int query, const double* origin, double radius, int use_graph) {
+  return guarded("target_manager_step_sequence_all_dt", [&] {
+    const te::DtSchedule sched = dt_schedule(n_ticks, dt_host);
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    std::vector<te::InnovStream> innov(nb);
+    for (size_t i = 0; i < nb; ++i)   // (every gate and policy is looked at before anything else is)
+      innov[i] = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
+                                  per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+    }
+    M(m)->stepSequenceAll(n_ticks, 0.0, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data(), sched);
+  });
+}
+
 int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host) {
   return guarded("target_batch_rejection_runs", [&] {
     BatchLock lk(B(b));

@@ -87,6 +87,17 @@ def _innov_stream(innov, size, m, n_ticks):
     return s
 
 
+def _dt_schedule(dt, n_ticks):
+    """dt of a multi-tick call: a number -> None (the scalar calls, exactly as ever); a sequence or array -> its float64 copy, one
+    entry per tick of the call (the ..._dt calls).  A wrong length raises ValueError before any library call."""
+    if np.ndim(dt) == 0:
+        return None
+    sched = np.ascontiguousarray(dt, dtype=np.float64)
+    if sched.ndim != 1 or sched.shape[0] != int(n_ticks):
+        raise ValueError("dt: a time-step schedule has one entry per tick: expected %d, got shape %s" % (int(n_ticks), sched.shape))
+    return sched
+
+
 def _reacquire(policy, size, n_ticks):
     """(K, events_or_None) -> capi.Reacquire.  events: uint8 CUDA tensor [blocks, ld] (or [ld]): one block, every tick overwrites
     it; fewer blocks than ticks make a ring, as for the innovation stream.  None: no policy (max_rejects = -1)."""
@@ -191,13 +202,27 @@ class Batch:
         inside the gated ticks (target_batch_step_sequence_reacquire): every slot's run of consecutive rejections is kept on the
         device (rejection_runs()), and on its K-th consecutive rejection a target is re-initialised from that tick's
         measurement with its own initial covariance (K = 0: count only); events: uint8 CUDA tensor [ticks_or_ring, ld] (or
-        [ld]) that receives every tick's event bytes (0, the run c', or 0x80 | c' for a re-initialisation).  Needs gate."""
+        [ld]) that receives every tick's event bytes (0, the run c', or 0x80 | c' for a re-initialisation).  Needs gate.
+        dt: a number, or a sequence / array with one time step per tick of the call (target_batch_step_sequence_dt): tick s
+        runs with dt[s], per slot the results of step(dt[s], ...) tick after tick, bit for bit, the target's time included.  A
+        recorded graph (use_graph) is reused by a call with the same schedule, value for value."""
+        sched = _dt_schedule(dt, meas.shape[0] if n_ticks is None else n_ticks)
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if sched is not None:
+            ticks = sched.shape[0]
+            ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
+            ins = _innov_stream(innov, self.size, self.meas_dim, ticks) if innov is not None else None
+            rq = _reacquire(reacquire, self.size, ticks) if reacquire is not None else None
+            _check(self._lib.target_batch_step_sequence_dt(
+                self._h, ticks, sched.ctypes.data_as(capi.c_double_p), meas.data_ptr(), meas.stride(0), meas.stride(1), hp, hs,
+                meas.shape[0] if ticks != meas.shape[0] else 0, None if ps is None else C.byref(ps), None if ins is None else C.byref(ins),
+                0.0 if gate is None else float(gate), None if rq is None else C.byref(rq), int(use_graph)), "target_batch_step_sequence_dt")
+            return
         if innov is not None or gate is not None or reacquire is not None:   # (a gate without a stream, a policy without a gate: the library's to refuse)
             ticks = meas.shape[0] if n_ticks is None else int(n_ticks)
             ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
@@ -234,13 +259,27 @@ class Batch:
         step_sequence (target_batch_step_fused_poses).  innov, gate, reacquire: the keywords of step_sequence with their
         meanings there, served inside the fused call (target_batch_step_fused_gated): per slot and tick the results of
         step_sequence(dt, meas, has_meas, poses=, innov=, gate=, reacquire=) bit for bit -- one launch for the whole call where
-        fused_gate_served is 1 and no poses are asked for, tick by tick inside the call otherwise."""
+        fused_gate_served is 1 and no poses are asked for, tick by tick inside the call otherwise.
+        dt: a number, or a sequence / array with one time step per tick (target_batch_step_fused_dt): tick s runs with dt[s], the
+        results of step(dt[s], ...) tick after tick, bit for bit -- one launch where fused_dt_served(gated) is 1 and no poses are
+        asked for."""
+        sched = _dt_schedule(dt, meas.shape[0])
         assert meas.is_cuda and meas.dim() == 3 and meas.shape[1] == 7 and (meas.shape[2] == 1 or meas.stride(2) == 1)
         assert meas.dtype == self.torch_dtype() and meas.shape[2] >= self.size
         hp, hs = None, 0
         if has_meas is not None:
             assert has_meas.is_cuda and has_meas.dim() == 2 and has_meas.element_size() == 1
             hp, hs = has_meas.data_ptr(), has_meas.stride(0)
+        if sched is not None:
+            ticks = sched.shape[0]
+            ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
+            ins = _innov_stream(innov, self.size, self.meas_dim, ticks) if innov is not None else None
+            rq = _reacquire(reacquire, self.size, ticks) if reacquire is not None else None
+            _check(self._lib.target_batch_step_fused_dt(
+                self._h, ticks, sched.ctypes.data_as(capi.c_double_p), meas.data_ptr(), meas.stride(0), meas.stride(1), hp, hs,
+                None if ps is None else C.byref(ps), None if ins is None else C.byref(ins),
+                0.0 if gate is None else float(gate), None if rq is None else C.byref(rq)), "target_batch_step_fused_dt")
+            return
         if innov is not None or gate is not None or reacquire is not None:   # (a gate without a stream, a policy without a gate: the library's to refuse)
             ticks = meas.shape[0]
             ps = _pose_stream(poses, self.size, ticks) if poses is not None else None
@@ -261,6 +300,14 @@ class Batch:
 
     # 1: a fused call with innov= / gate= / reacquire= (and without poses=) is one launch; 0: served tick by tick inside the call
     fused_gate_served = property(lambda s: s._lib.target_batch_step_fused_gate_served(s._h))
+
+    def fused_dt_served(self, gated=False):
+        """1: a fused call with a time-step schedule (and without poses=) is one launch -- gated: a call with innov= / gate= /
+        reacquire= --; 0: served tick by tick inside the call (target_batch_step_fused_dt_served)."""
+        return _check(self._lib.target_batch_step_fused_dt_served(self._h, 1 if gated else 0), "target_batch_step_fused_dt_served")
+
+    # recordings made so far by step_sequence(..., use_graph=True) on this batch (target_batch_graph_recordings)
+    graph_recordings = property(lambda s: s._lib.target_batch_graph_recordings(s._h))
 
     # ---- resident ("live") mode: one launch serves tick after tick as the host posts them (target_batch_c.h)
     def live_start(self, dt, meas_ring, has_ring=None, first_entry=0, max_ticks=1 << 30, idle_limit_s=10.0):
@@ -765,10 +812,13 @@ class TargetManager:
         gate: the NIS validation gate of every batch (a number) or one per batch (a list; 0 or None: that batch has none), as for
         Batch.step_sequence (target_manager_step_sequence_all_gated).
         reacquire: the re-acquisition policy (K, events_or_None) of every batch (one tuple) or one per batch (a list; None: that
-        batch has none), as for Batch.step_sequence (target_manager_step_sequence_all_reacquire)."""
+        batch has none), as for Batch.step_sequence (target_manager_step_sequence_all_reacquire).
+        dt: a number, or a sequence / array with one time step per tick (target_manager_step_sequence_all_dt): tick s of every
+        batch runs with dt[s]."""
         nb = len(meas)          # the library checks it against the number of batches
         ring = meas[0].shape[0] if nb else 0
         ticks = ring if n_ticks is None else int(n_ticks)      # n_ticks > ring: the tensors are rings (tick s reads s % ring)
+        sched = _dt_schedule(dt, ticks)
         specs = (capi.BatchSequence * max(nb, 1))()
         for i, t in enumerate(meas):
             assert t.is_cuda and t.dim() == 3 and t.shape[0] == ring and t.shape[1] == 7 and (t.shape[2] == 1 or t.stride(2) == 1)
@@ -785,6 +835,37 @@ class TargetManager:
             for i in range(nb):
                 specs[i].delta_dev = deltas[i].data_ptr()
                 specs[i].pose_dev = None if qposes is None or qposes[i] is None else qposes[i].data_ptr()
+        if sched is not None:   # the most general form: streams, gates and policies as given, or NULL
+            bs = self.batches()
+            sizes = [bs[i].size if i < len(bs) else 0 for i in range(nb)]
+            pss = iss = gs = rqs = None
+            if poses is not None:
+                assert len(poses) == nb, "one pose stream (or None) per batch"
+                pss = (capi.PoseStream * max(nb, 1))()
+                for i in range(nb):
+                    if poses[i] is not None:
+                        pss[i] = _pose_stream(poses[i], sizes[i], ticks)
+            if innov is not None:
+                assert len(innov) == nb, "one stream (or None) per batch"
+                iss = (capi.InnovStream * max(nb, 1))()
+                for i in range(nb):
+                    if innov[i] is not None:
+                        iss[i] = _innov_stream(innov[i], sizes[i], bs[i].meas_dim if i < len(bs) else 3, ticks)
+            if gate is not None:
+                per = list(gate) if isinstance(gate, (list, tuple)) else [gate] * nb
+                assert len(per) == nb, "one gate (or None) per batch"
+                gs = (C.c_double * max(nb, 1))(*[0.0 if g is None else float(g) for g in per])
+            if reacquire is not None:
+                per = list(reacquire) if isinstance(reacquire, list) else [reacquire] * nb
+                assert len(per) == nb, "one re-acquisition policy (or None) per batch"
+                rqs = (capi.Reacquire * max(nb, 1))()
+                for i in range(nb):
+                    rqs[i] = _reacquire(per[i], sizes[i], ticks)
+            _check(self._lib.target_manager_step_sequence_all_dt(
+                self._h, ticks, sched.ctypes.data_as(capi.c_double_p), C.cast(specs, C.c_void_p), pss, iss, gs, rqs, nb,
+                0 if query is None else 1, None if origin is None else _dp(origin), float(radius), int(use_graph)),
+                "target_manager_step_sequence_all_dt")
+            return
         gates = None
         if reacquire is not None and gate is None:
             gate = 0.0   # (a policy without a gate is the library's to refuse)

@@ -24,5 +24,6 @@ def variant_word(*names):
 def name_variants(kernel):
     """'kf_step_sep_kernel<te::ModelUV, double, 3, 258u>' -> '...<te::ModelUV, double, 3, FUSED|LIVE2>' (other names pass).
     c++filt and rocprofv3 print an unsigned template argument as `258u`; a bare `258` is taken too.  The gated kernels
-    (kf_step_sep_gate_kernel<model, T, layout>, kf_step_population_gate_kernel<T, shared>) carry no variant word and pass."""
-    return re.sub(r"(kf_step(?!\w*_gate_)\w*kernel<[^>]*?,\s*)(\d+)u?>", lambda m: m.group(1) + variant_name(int(m.group(2))) + ">", kernel)
+    (kf_step_sep_gate_kernel<model, T, layout>, kf_step_population_gate_kernel<T, shared>) and the fused kernels with a time-step
+    table (kf_step_sep_fused_dt_kernel<model, T, layout>) carry no variant word and pass."""
+    return re.sub(r"(kf_step(?!\w*_gate_)(?!\w*_fused_dt_)\w*kernel<[^>]*?,\s*)(\d+)u?>", lambda m: m.group(1) + variant_name(int(m.group(2))) + ">", kernel)
