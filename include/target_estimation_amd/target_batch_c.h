@@ -590,7 +590,8 @@ int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks
  * the fused gated kernels carry no pose block (chosen over a second set of instantiations; the bits are the same either way).
  * target_batch_step_fused and target_batch_step_fused_poses stay exactly as they are.
  * ..._step_fused_gate_served: 1 = one launch for the whole call (without `poses`); 0 = served tick by tick inside the call; -1 on error.
- * Not served: a manager-level fused call; per-axis gates; M-of-N logic. */
+ * The same call for every batch of a manager at once: target_manager_step_fused_all below.
+ * Not served: per-axis gates; M-of-N logic. */
 int target_batch_step_fused_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
                                   const unsigned char* has_meas_dev, long has_stride,
                                   const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
@@ -645,6 +646,39 @@ int target_manager_step_sequence_all_dt(target_manager_c* m, long n_ticks, const
                                         const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
                                         const target_reacquire_c* per_batch_reacq, long n_batches,
                                         int query, const double* origin, double radius, int use_graph);
+/* ---- ONE LAUNCH for a temporally fused replay of a WHOLE MANAGER.
+ * The manager-level form of target_batch_step_fused_gated (..._all) and target_batch_step_fused_dt (..._all_dt): a manager with one
+ * batch per motion model replays a recording of n_ticks ticks as one launch per device instead of one per batch.
+ * per_batch [n_batches] in batch order (shard-major on several devices, as for ..._step_sequence_all); per_batch_poses,
+ * per_batch_innov, per_batch_nis_max and per_batch_reacq [n_batches] may each be NULL (none for any batch), and an entry with
+ * max_rejects < 0 in per_batch_reacq is no policy for that batch.  per_batch[i].ring_ticks must be 0 (fused calls read linearly);
+ * delta_dev and pose_dev are ignored (fused calls have no query).
+ * CONTRACT.  For every batch i the call equals target_batch_step_fused_gated (..._all_dt: target_batch_step_fused_dt) on batch i with
+ * the same arguments, bit for bit: state, covariance and unwrap memory; measurement counters, clock and rejection runs; every NIS
+ * row, innovation block, event row and pose block.
+ * WHO SERVES IT.  ONE LAUNCH PER DEVICE (kf_step_population_fused_kernel: the grid of the population tick, each part the per-batch
+ * fused loop of its model on its own arguments, every part reading the call's one time-step table) when all of these hold: at
+ * least two non-empty batches, each a one-class batch of its own model in the axis-separable layout with packed groups (lanes 301,
+ * fp64 or fp32; a shared-axes batch is expanded to the plain form first, as for every fused call); no batch has `poses` in the
+ * call or keeps measured-pose rows; with a schedule, n_ticks <= 2^28; and either no batch carries a stream, a gate or a policy (the
+ * plain loop) or every non-empty batch carries at least its NIS rows (the gated loop; nis_max per batch, 0 = that batch's plain
+ * stream).  Every instantiation has zero scratch (profiles/fused_all_kernel_resources.txt).  EVERYTHING ELSE is served inside the
+ * same call by the per-batch calls in batch order -- same bits, their launch counts: a single non-empty batch, the coupled or dense
+ * layouts, several (Q, R) classes, a call in which only some batches carry streams, a call with `poses`, batches that keep
+ * measured poses.
+ * REFUSED (negative return, target_manager_last_error, NO batch launched or changed, its storage form included): a NULL manager;
+ * n_batches other than the manager's number of batches; ring_ticks != 0; ..._all_dt with dt_host == NULL and n_ticks > 0; and, for
+ * every batch, everything target_batch_step_fused_gated refuses -- ld < size with measurements also where that batch carries no
+ * stream.
+ * ..._served(m, gated, scheduled): gated = every batch would carry NIS rows; scheduled = the ..._all_dt form.  1 = one launch per
+ * device for such a call without `poses`, as the batches are now; 0 = per batch inside the call; -1 on error. */
+int target_manager_step_fused_all(target_manager_c* m, long n_ticks, double dt, const target_batch_sequence_c* per_batch,
+                                  const target_pose_stream_c* per_batch_poses, const target_innov_stream_c* per_batch_innov,
+                                  const double* per_batch_nis_max, const target_reacquire_c* per_batch_reacq, long n_batches);
+int target_manager_step_fused_all_dt(target_manager_c* m, long n_ticks, const double* dt_host, const target_batch_sequence_c* per_batch,
+                                     const target_pose_stream_c* per_batch_poses, const target_innov_stream_c* per_batch_innov,
+                                     const double* per_batch_nis_max, const target_reacquire_c* per_batch_reacq, long n_batches);
+int target_manager_step_fused_all_served(target_manager_c* m, int gated, int scheduled);   /* 1: one launch per device; 0: per batch inside the call; -1 error */
 /* recordings made so far by the batch's step_sequence* calls with use_graph != 0 (a counter for tests of the graph cache); -1 on error */
 long target_batch_graph_recordings(target_batch_c* b);
 /* the rejection run of every slot, slot order, into runs_host [size]; synchronises */

@@ -190,6 +190,12 @@ SIGNATURES = {
     "target_manager_step_sequence_all_dt": (C.c_int, [C.c_void_p, C.c_long, c_double_p, C.c_void_p, C.POINTER(PoseStream),
                                                       C.POINTER(InnovStream), c_double_p, C.POINTER(Reacquire), C.c_long, C.c_int,
                                                       c_double_p, C.c_double, C.c_int]),
+    # one launch for a temporally fused replay of a whole manager
+    "target_manager_step_fused_all": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.POINTER(PoseStream), C.POINTER(InnovStream),
+                                                c_double_p, C.POINTER(Reacquire), C.c_long]),
+    "target_manager_step_fused_all_dt": (C.c_int, [C.c_void_p, C.c_long, c_double_p, C.c_void_p, C.POINTER(PoseStream), C.POINTER(InnovStream),
+                                                   c_double_p, C.POINTER(Reacquire), C.c_long]),
+    "target_manager_step_fused_all_served": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "target_batch_graph_recordings": (C.c_long, [C.c_void_p]),
     "target_batch_rejection_runs": (C.c_int, [C.c_void_p, C.c_void_p]),
     "target_manager_get_rejection_run": (C.c_int, [C.c_void_p, C.c_uint]),

@@ -431,9 +431,6 @@ Batch::~Batch() {
   device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
   device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
   device_free(d_dtper_); device_free(d_lastmeas_);
-  device_free(d_dttab_);
-  if (h_dttab_) (void)hipHostFree(h_dttab_);
-  for (double* h : h_dttab_retired_) (void)hipHostFree(h);
   if (h_pin_) (void)hipHostFree(h_pin_);
   if (h_pol_) (void)hipHostFree(h_pol_);
   device_free(bar_pin_);
@@ -992,31 +989,7 @@ void Batch::account_sequence(const DtSchedule& sched, bool all_measured) {
   if (all_measured) nm_acc_ += sched.n;
 }
 
-const double* Batch::dt_table_push(const double* dt_host, long n) {
-  if (n > dttab_cap_) {   // grow: nothing in flight may still read the old blocks
-    const long want = (std::max<long>(std::max<long>(n, 256), dttab_cap_ * 2) + 15) / 16 * 16;
-    TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    double* h = nullptr;
-    double* d = nullptr;
-    TE_HIP_CHECK(hipHostMalloc((void**)&h, (size_t)want * sizeof(double), hipHostMallocDefault));
-    if (hipMalloc((void**)&d, (size_t)want * sizeof(double)) != hipSuccess) {
-      (void)hipHostFree(h);
-      throw std::runtime_error("target_estimation_amd: no device memory for the time-step table");
-    }
-    device_free(d_dttab_);   // (deferred while a resident session of the process is alive)
-    if (h_dttab_) h_dttab_retired_.push_back(h_dttab_);
-    d_dttab_ = d; h_dttab_ = h; dttab_cap_ = want; dttab_off_ = 0;
-  } else if (dttab_off_ + n > dttab_cap_) {   // wrap: the runs at the head of the ring may still be in flight
-    TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    dttab_off_ = 0;
-  }
-  double* h = h_dttab_ + dttab_off_;
-  double* d = d_dttab_ + dttab_off_;
-  std::memcpy(h, dt_host, (size_t)n * sizeof(double));   // (the caller's array is read here, before the call returns)
-  TE_HIP_CHECK(hipMemcpyAsync(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream_));
-  dttab_off_ += n;
-  return d;
-}
+const double* Batch::dt_table_push(const double* dt_host, long n) { return dttab_.push(dt_host, n, stream_); }
 
 void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                        const unsigned char* has_base, long has_stride, const PoseStream& poses, const DtSchedule& sched) {
@@ -1038,6 +1011,53 @@ void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick
   if (meas_base && !has_base) nm_acc_ += n_ticks;
 }
 
+void Batch::check_fused_call(long n_ticks, const SeqSpec& q, const DtSchedule& sched, bool one_launch) const {
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
+  check_pose_stream(q.poses);   // (before touch(): a refused call launches nothing)
+  check_innov_stream(q.innov, one_launch);   // (the kernel's K = 0 reads no initial covariance; the single ticks' launch is given the table)
+  if (n_ticks > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: step_fused_gated: n_ticks does not fit an int");
+  if (q.tick_stride < 0 || q.has_stride < 0) throw std::invalid_argument("target_estimation_amd: step_fused_gated: negative stride");
+  if (q.meas_base && q.ld < n_) throw std::invalid_argument("target_estimation_amd: step_fused_gated: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
+}
+
+bool Batch::fused_call_one_launch(const SeqSpec& q, const DtSchedule& sched) const {
+  const bool plain = !q.innov.on() && !q.innov.gated() && !q.innov.reacq.on;
+  return (sched.on() ? fused_dt_served(!plain) : fused_gate_served()) && !q.poses.dev;
+}
+
+void Batch::fused_call_begin(const SeqSpec& q) {
+  touch();
+  demote_shared();   // (the temporally fused kernels exist for the plain form only)
+  if (n_ == 0) return;
+  if (q.innov.reacq.on && (q.innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
+}
+
+StepParams Batch::fused_call_params(long n_ticks, double dt, const SeqSpec& q, const DtSchedule& sched, const double* dt_tab) {
+  const InnovStream& innov = q.innov;
+  const bool plain = !innov.on() && !innov.gated() && !innov.reacq.on;   // no stream, no gate: the plain fused loop
+  StepParams p = base_params();
+  p.gate_row = d_has_eff_;   // (the dense layouts' single gated ticks take their mask from the writer's row)
+  p.meas = q.meas_base; p.meas_ld = q.ld; p.has_meas = q.has_base; p.dt = dt;
+  p.n_ticks = (int)n_ticks; p.tick_stride = q.tick_stride; p.has_stride = q.has_stride;
+  p.pose = q.poses.dev; p.pose_ld = q.poses.ld; p.pose_tick_stride = q.poses.tick_stride; p.pose_ring = q.poses.ring;
+  if (!plain) {
+    p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
+    p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
+    p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
+    if (innov.reacq.on) {
+      p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+      p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
+    }
+  }
+  if (sched.on()) { p.dt_sched = 1; p.dt_host = sched.dt; p.dt = 0.0; p.dt_tab = dt_tab; }
+  return p;
+}
+
+void Batch::fused_call_account(long n_ticks, double dt, const SeqSpec& q, const DtSchedule& sched) {
+  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
+  if (q.meas_base && !q.has_base && !q.innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
+}
+
 void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
                              long has_stride, const PoseStream& poses, const InnovStream& innov, const DtSchedule& sched) {
   const bool plain = !innov.on() && !innov.gated() && !innov.reacq.on;   // no stream, no gate: the plain fused loop
@@ -1045,13 +1065,8 @@ void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, lon
     step_fused(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses);
     return;
   }
-  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
-  const bool one_launch = (sched.on() ? fused_dt_served(!plain) : fused_gate_served()) && !poses.dev;
-  check_pose_stream(poses);   // (before touch(): a refused call launches nothing)
-  check_innov_stream(innov, one_launch);   // (the kernel's K = 0 reads no initial covariance; the single ticks' launch is given the table)
-  if (n_ticks > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: step_fused_gated: n_ticks does not fit an int");
-  if (tick_stride < 0 || has_stride < 0) throw std::invalid_argument("target_estimation_amd: step_fused_gated: negative stride");
-  if (meas_base && ld < n_) throw std::invalid_argument("target_estimation_amd: step_fused_gated: ld " + std::to_string(ld) + " < batch size " + std::to_string(n_));
+  const SeqSpec q{meas_base, tick_stride, ld, has_base, has_stride, nullptr, nullptr, 0, poses, innov};
+  check_fused_call(n_ticks, q, sched, fused_call_one_launch(q, sched));
   touch();
   demote_shared();   // (the temporally fused kernels exist for the plain form only)
   if (n_ == 0 || n_ticks <= 0) return;
@@ -1062,28 +1077,10 @@ void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, lon
     return;
   }
   if (innov.reacq.on && (innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
-  StepParams p = base_params();
-  p.gate_row = d_has_eff_;   // (the dense layouts' single gated ticks take their mask from the writer's row)
-  p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
-  p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
-  p.pose = poses.dev; p.pose_ld = poses.ld; p.pose_tick_stride = poses.tick_stride; p.pose_ring = poses.ring;
-  if (!plain) {
-    p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
-    p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
-    p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
-    if (innov.reacq.on) {
-      p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
-      p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
-    }
-  }
-  if (sched.on()) {   // the table: a run of the batch's ring that no other call shares, filled on the stream ahead of the launch
-    p.dt_sched = 1; p.dt_host = sched.dt; p.dt = 0.0;
-    p.dt_tab = dt_table_push(sched.dt, n_ticks);
-  }
-  launch_step(p, stream_);
+  // the table: a run of the batch's ring that no other call shares, filled on the stream ahead of the launch
+  launch_step(fused_call_params(n_ticks, dt, q, sched, sched.on() ? dt_table_push(sched.dt, n_ticks) : nullptr), stream_);
   TE_HIP_CHECK(hipGetLastError());
-  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
-  if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
+  fused_call_account(n_ticks, dt, q, sched);
 }
 
 // device block of a live session: [one mirror word per kLiveGroup wavefronts, 128 bytes apart][progress words]

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dt_schedule.hpp"
+#include "dt_table_ring.hpp"
 #include "kf_ops.hpp"
 #include "reacquire_plan.hpp"
 
@@ -341,6 +342,19 @@ class Batch {
   // output) for this batch: the pose-writer launch into tick s's pose block and / or the own-time sphere query, as launches.
   void enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& spec, bool query, const double* origin, double radius);
   void swap_records() { std::swap(d_rec_, d_rec_alt_); }
+  // Building blocks of the manager's fused replay of all batches (Shard::stepFusedAll), and of step_fused_gated itself.  spec: the
+  // call's measurements, masks, pose stream and innovation stream (ring_ticks, delta_dev and pose_dev unread: fused calls read
+  // linearly and have no query).
+  //   check_fused_call       every refusal of step_fused_gated, nothing changed (one_launch: see check_innov_stream)
+  //   fused_call_one_launch  would step_fused_gated serve the call by one launch of its own
+  //   fused_call_begin       touch(), demote_shared(), then the device tables of a re-acquisition policy
+  //   fused_call_params      the launch parameters of the whole call (dt_tab: the schedule in device memory, or null without one)
+  //   fused_call_account     the clock and the measurement counter behind the call
+  void check_fused_call(long n_ticks, const SeqSpec& spec, const DtSchedule& sched, bool one_launch) const;
+  bool fused_call_one_launch(const SeqSpec& spec, const DtSchedule& sched) const;
+  void fused_call_begin(const SeqSpec& spec);
+  StepParams fused_call_params(long n_ticks, double dt, const SeqSpec& spec, const DtSchedule& sched, const double* dt_tab);
+  void fused_call_account(long n_ticks, double dt, const SeqSpec& spec, const DtSchedule& sched);
   // (all_measured: measurements without a mask and without a gate -- a gated tick counts its accepted ones on the device)
   void account_sequence(long n_ticks, double dt, bool all_measured);
   void account_sequence(const DtSchedule& sched, bool all_measured);   // the schedule form: one te_clock_add per tick, in order
@@ -500,15 +514,8 @@ class Batch {
   hipStream_t cap_stream_ = nullptr;
   void drop_graphs();
   long graph_recordings_ = 0;      // recordings made so far (graph_recordings(): what a test of the cache observes)
-  // The device table of a fused call with a time-step schedule.  Every call takes a fresh run of a ring -- pinned host words the
-  // schedule is copied into before the call returns, and the device words behind them, filled by a copy on the batch's stream
-  // ahead of the launch -- so two calls enqueued back to back never share a word; the ring wraps, or grows, behind a
-  // synchronisation of the stream.  The device block goes through device_free (deferred while a resident session of the process is
-  // alive); retired host blocks are kept until the batch goes.
-  double* d_dttab_ = nullptr;
-  double* h_dttab_ = nullptr;
-  long dttab_cap_ = 0, dttab_off_ = 0;
-  std::vector<double*> h_dttab_retired_;
+  // The device table of a fused call with a time-step schedule: a fresh run of a ring per call (dt_table_ring.hpp)
+  DtTableRing dttab_;
   const double* dt_table_push(const double* dt_host, long n);   // the device address of the call's n entries
   // queue of one-target creations (append with count == 1): consecutive ones with the same (t0, P0, class) become one init launch
   struct InitQueue { std::vector<unsigned> ids; std::vector<double> p0, v0, a0, P0; double t0 = 0.0; int cls = 0; long first = 0; } initq_;

@@ -19,4 +19,13 @@ namespace te {
 // shared: every present batch is in the shared-axes storage form (te_layout.hpp; fp64 only) instead of the plain one.
 void launch_population_step(int dtype, const StepParams parts[4], bool query, bool ab, bool reverse, hipStream_t s, bool shared = false);
 
+// A temporally fused replay of the whole population as ONE launch (kf_step_sep.hpp, kf_step_population_fused_kernel).  parts[k] = the
+// dense fused launch parameters of the batch of model type k, as Batch::step_fused_gated hands them to its own launch: n_ticks >= 1
+// (the same in every present part), in place, the plain form, no pose stream.  gated: the gated loop -- every present part has
+// StepParams::fused_gate set with its NIS rows (fused_gate_nis_max 0: that part's plain stream; fused_gate_k -1: no policy) -- else
+// the plain loop, no part with fused_gate.  dt_tab: the call's time-step table in device memory [n_ticks] (every present part has
+// StepParams::dt_sched set), or null.  The grid is split as launch_population_step's and never reversed.  Throws for anything else,
+// and for an instantiation that is not shipped (step_variant.hpp, population_fused_ok).
+void launch_population_fused(int dtype, const StepParams parts[4], bool gated, const double* dt_tab, hipStream_t s);
+
 }  // namespace te

@@ -454,7 +454,10 @@ constexpr bool gate_id_tail_in_registers() {
 // DTTAB: the launched fused call with a time-step schedule (target_batch_step_fused_dt): tick s of the loop runs with dt_tab[s], a
 // device table of doubles read through the constant address space like Qm -- uniform across the wavefront, one scalar load and
 // one conversion per tick.  A template argument next to the variant word, as GATE is; the kernels without it compile to what they were.
-template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false, bool DTTAB = false>
+// SEG: the byte offset in the kernel-argument segment at which the launched fused gated loop finds its FusedGateSegment /
+// FusedGateDtSegment -- 0 for the per-batch kernels (their arguments ARE the segment), part k's element of PopulationFusedArgs::part in
+// kf_step_population_fused_kernel.  A compile-time constant: every read stays a scalar load at a constant offset from the segment pointer.
+template <class M, typename T, int LAYOUT, unsigned VAR, bool GATE = false, bool BYID = false, bool DTTAB = false, unsigned SEG = 0>
 __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, const int lane, const double gate = 0.0, const GateById* gid = nullptr,
                                               const LiveGateArg* lg = nullptr, const double* dt_tab = nullptr) {
   constexpr bool INDEXED = sv_has(VAR, kIndexed), FUSED = sv_has(VAR, kFused), QUERY = sv_has(VAR, kQuery), PERQR = sv_has(VAR, kPerQR),
@@ -475,7 +478,9 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   if constexpr (!DTTAB || FGATE) (void)dt_tab;   // (FGATE: read per tick where it arrived -- FusedGateDtSegment)
   // FGATE: the kernel's two arguments where they arrived (FusedGateSegment)
   typedef const FusedGateSegment<T> __attribute__((address_space(4))) FusedSeg;
-#define FG0_ (((FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr())->g)
+  typedef const char __attribute__((address_space(4))) SegByte;
+#define FSEG_ ((FusedSeg*)((SegByte*)__builtin_amdgcn_kernarg_segment_ptr() + SEG))
+#define FG0_ (FSEG_->g)
   constexpr int N = C::N, K = C::K, NB = C::NB, TPW = C::TPW;
   using F = Mth<T>;
 
@@ -708,7 +713,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   const int n_ticks = FUSED ? a.n_ticks : 1;
   long long live_seen = 0;
   // (FGATE: the bound read per tick as well -- FusedGateSegment)
-  for (int tick = 0; tick < (FGATE ? ((FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr())->a.n_ticks : n_ticks); ++tick) {
+  for (int tick = 0; tick < (FGATE ? FSEG_->a.n_ticks : n_ticks); ++tick) {
   long slot_tick = tick;
   if constexpr (LIVE) {
     // (the worker's own limit is a backstop far behind the relay's: a relay round is a PCIe read + a scan, a worker poll an L2 hit)
@@ -721,13 +726,14 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   else (void)lgt;
   // FGATE: likewise, and the tick's view of StepArgs as well (FusedGateSegment): the fp64 angular kernels spilled scalar
   // registers otherwise, which the compiler accounts as scratch
-  FusedSeg* kt = FGATE ? (FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+  // (SEG is added behind the barrier: it then folds into every load's constant offset instead of costing scalar address arithmetic per tick)
+  SegByte* kt0 = FGATE ? (SegByte*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
   if constexpr (FGATE) {
-    asm volatile("" : "+s"(kt));
+    asm volatile("" : "+s"(kt0));
     nis = T(0);   // (one sum per tick)
-  } else {
-    (void)kt;
   }
+  FusedSeg* kt = (FusedSeg*)(kt0 + (FGATE ? SEG : 0u));
+  (void)kt;
   const auto* const fgt = &kt->g;
   const auto* const at = &kt->a;
   (void)fgt; (void)at;
@@ -1497,9 +1503,10 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   }
   }  // tick loop
   // FGATE: what follows the loop reads its arguments afresh as well (behind the loop: nothing of it is held across)
-  FusedSeg* ke = FGATE ? (FusedSeg*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
-  if constexpr (FGATE) asm volatile("" : "+s"(ke));
-  else (void)ke;
+  SegByte* ke0 = FGATE ? (SegByte*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+  if constexpr (FGATE) asm volatile("" : "+s"(ke0));
+  FusedSeg* ke = (FusedSeg*)(ke0 + (FGATE ? SEG : 0u));
+  (void)ke;
   if constexpr (UT) {
     // Does the tile leave this tick uniform?  Its lanes must have taken the same has-bit (dt is the launch's).  A uniform tile
     // then stays one -- every lane has computed the same block from the same block -- and a tile that is not becomes one, in a
@@ -1640,6 +1647,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #undef PG_
 #undef A_
 #undef FG0_
+#undef FSEG_
 #undef GW_
 #undef UWW_
 #undef XR_
@@ -1774,6 +1782,44 @@ __global__ void __launch_bounds__(256) kf_step_population_gate_kernel(const Popu
   else if (b < p.end[1]) sep_step_wave<ModelAV, T, L, kInnov, true>(p.part[1], (long)(b - p.end[0]) * wpb + wave, lane, g.gate[1]);
   else if (b < p.end[2]) sep_step_wave<ModelUA, T, L, kInnov, true>(p.part[2], (long)(b - p.end[1]) * wpb + wave, lane, g.gate[2]);
   else sep_step_wave<ModelUV, T, L, kInnov, true>(p.part[3], (long)(b - p.end[2]) * wpb + wave, lane, g.gate[3]);
+}
+
+// ---- one launch for a temporally fused replay of the whole population ------------------------------------------------------------
+// The launched fused loops (sep_step_wave, kFused; with GATE the loop of kf_step_sep_fused_gate_kernel, with DTTAB the schedule's
+// table) on the population grid: the first end[0] workgroups run the angular-rates batch's whole call, the next ones the
+// angular-velocities batch's, and so on -- the split of kf_step_population_kernel, never reversed (a fused call walks its tiles
+// once).  Each part is exactly its per-batch kernel's arithmetic on its own arguments; the plain form of the separable layout with
+// packed groups only (the host expands a shared-axes batch first, as for every fused call).
+// The ONE kernel argument is, for every instantiation, four FusedGateDtSegment -- what the per-batch gated kernel with a table finds
+// at offset 0 of its segment -- followed by the grid split: the gated loop of part k reads its arguments per tick at the
+// compile-time offset k * sizeof(FusedGateDtSegment<T>) (sep_step_wave, SEG), the plain loops take part[k].a by reference and (DTTAB)
+// part[k].dt_tab by value.  Every part carries the call's one table.  A part without a gate has gate 0 (acc = has), one without a
+// policy k = -1; in a gated launch every non-empty part has NIS rows (the host's rule: Shard::stepFusedAll).
+// (the struct itself and the offset of part k are stated in step_variant.hpp, where a host test holds them to offsetof)
+template <typename T>
+using PopulationFusedArgs = PopulationFusedLayout<FusedGateDtSegment<T>>;
+static_assert(population_fused_args_fit<FusedGateDtSegment<double>>() && population_fused_args_fit<FusedGateDtSegment<float>>(),
+              "the arguments of a kernel are at most 4 KB");
+template <typename T>
+constexpr unsigned population_fused_seg(int k) { return population_fused_seg_offset<FusedGateDtSegment<T>>(k); }
+static_assert(offsetof(PopulationFusedArgs<double>, part[3].g) == population_fused_seg<double>(3) + offsetof(FusedGateSegment<double>, g) &&
+                  offsetof(PopulationFusedArgs<float>, part[1].dt_tab) == population_fused_seg<float>(1) + offsetof(FusedGateDtSegment<float>, dt_tab),
+              "part k of the argument struct lies where sep_step_wave's SEG says");
+
+template <typename T, bool GATE, bool DTTAB>
+__global__ void __launch_bounds__(256) kf_step_population_fused_kernel(const PopulationFusedArgs<T> p) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned wpb = blockDim.x >> 6, wave = threadIdx.x >> 6;
+  const unsigned b = blockIdx.x;
+  constexpr int L = LAYOUT_SEPARABLE_PACKED;
+#define TE_POP_FUSED_PART_(k_, Model_, first_)                                                                                       \
+  sep_step_wave<Model_, T, L, kFused, GATE, false, DTTAB, population_fused_seg<T>(k_)>(p.part[k_].a, (long)(b - (first_)) * wpb + wave, lane, \
+                                                                                      p.part[k_].g.gate, nullptr, nullptr, p.part[k_].dt_tab)
+  if (b < p.end[0]) TE_POP_FUSED_PART_(0, ModelAR, 0u);
+  else if (b < p.end[1]) TE_POP_FUSED_PART_(1, ModelAV, p.end[0]);
+  else if (b < p.end[2]) TE_POP_FUSED_PART_(2, ModelUA, p.end[1]);
+  else TE_POP_FUSED_PART_(3, ModelUV, p.end[2]);
+#undef TE_POP_FUSED_PART_
 }
 
 }  // namespace te

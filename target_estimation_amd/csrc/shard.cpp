@@ -997,6 +997,57 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
   }
 }
 
+// The route of a fused replay of all batches (step_variant.hpp, plan_fused_all), from the batches as they are and the call's streams
+FusedAllRoute Shard::fusedAllRoute(const Batch::SeqSpec* specs, bool scheduled, long n_ticks) const {
+  std::vector<FusedAllBatch> fb(batches_.size());
+  for (size_t b = 0; b < batches_.size(); ++b) {
+    const Batch& q = *batches_[b];
+    FusedAllBatch& f = fb[b];
+    f.n = q.size(); f.type = q.type(); f.ready = q.population_ready(); f.keep_meas = q.keep_measurement();
+    if (!specs) continue;   // (a question about the batches alone: fusedAllServed)
+    f.pose = specs[b].poses.dev != nullptr;
+    f.nis = specs[b].innov.on();
+    f.gate_or_policy = specs[b].innov.gated() || specs[b].innov.reacq.on;
+  }
+  return plan_fused_all(set_.population_tick, set_.dtype == F64, fb.data(), (long)fb.size(), scheduled, n_ticks, kDtTabMaxTicks);
+}
+
+int Shard::fusedAllServed(bool gated, bool scheduled) const {
+  std::vector<Batch::SeqSpec> specs(batches_.size(), Batch::SeqSpec{nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0});
+  static double some_row;   // (never dereferenced: the route asks whether a batch carries rows, not where)
+  if (gated) for (auto& q : specs) { q.innov.nis = &some_row; q.innov.gate = 1.0; }
+  return fusedAllRoute(specs.data(), scheduled, 1) != FusedAllRoute::kPerBatch ? 1 : 0;
+}
+
+void Shard::stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched) {
+  const size_t nb = batches_.size();
+  if ((size_t)n_specs != nb) throw std::runtime_error("target_estimation_amd: stepFusedAll needs one spec per batch");
+  const FusedAllRoute route = fusedAllRoute(specs, sched.on(), n_ticks);
+  for (size_t b = 0; b < nb; ++b) {   // every refusal of every batch's own call, before anything is enqueued or changed
+    if (specs[b].ring_ticks != 0) throw std::invalid_argument("target_estimation_amd: stepFusedAll: a fused call reads its measurements linearly (ring_ticks must be 0)");
+    batches_[b]->check_fused_call(n_ticks, specs[b], sched, route != FusedAllRoute::kPerBatch || batches_[b]->fused_call_one_launch(specs[b], sched));
+  }
+  if (nb == 0) return;
+  if (route == FusedAllRoute::kPerBatch) {   // the per-batch calls in batch order: same bits, their launch counts
+    for (size_t b = 0; b < nb; ++b)
+      batches_[b]->step_fused_gated(n_ticks, dt, specs[b].meas_base, specs[b].tick_stride, specs[b].ld, specs[b].has_base, specs[b].has_stride,
+                                    specs[b].poses, specs[b].innov, sched);
+    return;
+  }
+  for (size_t b = 0; b < nb; ++b) batches_[b]->fused_call_begin(specs[b]);
+  if (n_ticks <= 0) return;
+  // one table for all parts: a run of the shard's ring that no other call shares, filled on the stream ahead of the launch
+  const double* dt_tab = sched.on() ? dttab_.push(sched.dt, n_ticks, stream_) : nullptr;
+  StepParams parts[4];
+  for (auto& q : parts) { q = StepParams{}; q.n = 0; }
+  for (size_t b = 0; b < nb; ++b)
+    if (batches_[b]->size() > 0) parts[batches_[b]->type()] = batches_[b]->fused_call_params(n_ticks, dt, specs[b], sched, dt_tab);
+  launch_population_fused(set_.dtype, parts, route == FusedAllRoute::kGatedLoop, dt_tab, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+  for (size_t b = 0; b < nb; ++b)
+    if (batches_[b]->size() > 0) batches_[b]->fused_call_account(n_ticks, dt, specs[b], sched);
+}
+
 void Shard::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s,
                          bool query, const double* origin, double radius) {
   const size_t nb = batches_.size();

@@ -17,6 +17,7 @@
 #include "batch_store.hpp"
 #include "id_table.hpp"
 #include "row_split.hpp"
+#include "step_variant.hpp"
 
 namespace te {
 
@@ -137,6 +138,16 @@ class Shard {
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query, const double* origin, double radius,
                        int use_graph, const DtSchedule& sched = DtSchedule{});
   long seqRecordings() const { return seq_recordings_; }   // all-batches recordings made so far
+  // A temporally fused replay of every batch (target_manager_step_fused_all): for every batch, bit for bit, what
+  // Batch::step_fused_gated(n_ticks, dt, spec..., sched) leaves.  ONE launch of kf_step_population_fused_kernel where plan_fused_all
+  // (step_variant.hpp) says so: the population rule holds once every batch is expanded from the shared-axes form, no batch has a
+  // pose stream in the call or keeps measured-pose rows, a schedule fits one table, and either no batch carries a stream, gate or
+  // policy (the plain loop) or every non-empty batch carries at least its NIS rows (the gated loop).  Everything else is served
+  // inside the call by the per-batch calls in batch order.  Every refusal of every batch's call is made before anything is
+  // enqueued or changed (the storage form included); specs[b].ring_ticks must be 0, delta_dev and pose_dev are not read.
+  void stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched = DtSchedule{});
+  // 1: such a call -- gated: every batch with NIS rows; scheduled: with a time-step schedule -- would be one launch now; 0: per batch
+  int fusedAllServed(bool gated, bool scheduled) const;
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -192,6 +203,8 @@ class Shard {
   void dropSeqGraphs();
   void enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin, double radius,
                              bool reverse, bool ab);
+  FusedAllRoute fusedAllRoute(const Batch::SeqSpec* specs, bool scheduled, long n_ticks) const;
+  DtTableRing dttab_;   // the time-step table of stepFusedAll's one launch: one table serves all parts (dt_table_ring.hpp)
   bool seq_flip_ = false;   // zig-zag across the whole tick: the next eager all-batches tick runs last batch first, tiles backwards
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call

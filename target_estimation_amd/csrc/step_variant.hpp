@@ -63,6 +63,69 @@ constexpr bool population_variant_ok(unsigned v, bool shared_layout) {
   return (v & ~(kQuery | kAB | kPose | kInnov)) == 0 && sep_variant_ok(v, shared_layout);
 }
 
+// kf_step_population_fused_kernel<T, GATE, DTTAB>: the launched fused loops (variant word kFused; the gate and the table are template
+// arguments next to it, as for the per-batch kernels) on the population grid, plain form of the separable layout with packed
+// groups.  An instantiation that would need scratch is not shipped -- its requests are served per batch -- and is listed here
+// (profiles/fused_all_kernel_resources.txt).  None is.
+constexpr bool population_fused_ok(bool f64, bool gated, bool dt_table) {
+  (void)f64; (void)gated; (void)dt_table;
+  return sep_variant_ok(kFused, false);
+}
+
+// The ONE argument of kf_step_population_fused_kernel: per part what the per-batch gated kernel with a time-step table finds at
+// offset 0 of its kernel-argument segment (Seg = FusedGateDtSegment<T>, kf_step_sep.hpp), then the grid split.  The gated loop of
+// part k reads its arguments at the compile-time offset population_fused_seg_offset<Seg>(k) of the segment; the whole struct must
+// stay within the 4 KB a kernel's arguments may take.
+template <class Seg>
+struct PopulationFusedLayout {
+  Seg part[4];       // indexed by ModelType
+  unsigned end[4];   // first workgroup BEHIND part k (cumulative; an absent model has end[k] == end[k - 1])
+};
+template <class Seg>
+constexpr unsigned population_fused_seg_offset(int k) {
+  return (unsigned)(sizeof(Seg) * (unsigned)k);   // (part is the first member: offset 0, asserted where the kernel is)
+}
+template <class Seg>
+constexpr bool population_fused_args_fit() {
+  return sizeof(PopulationFusedLayout<Seg>) <= 4096;
+}
+
+// Who serves a fused replay of a whole manager's shard (Shard::stepFusedAll): ONE launch of kf_step_population_fused_kernel -- the
+// plain loop or the gated one -- or the per-batch calls in batch order inside the same call (same bits, their launch counts).
+struct FusedAllBatch {
+  long n = 0;                // targets (0: the batch takes no part)
+  int type = 0;              // ModelType
+  bool ready = false;        // separable layout with packed groups, one (Q, R) class (Batch::population_ready; the storage form does
+                             // not matter: a shared-axes batch is expanded ahead of every fused call)
+  bool keep_meas = false;    // keeps measured-pose rows
+  bool pose = false;         // a pose stream in the call
+  bool nis = false;          // NIS rows in the call
+  bool gate_or_policy = false;   // nis_max > 0 or a re-acquisition policy in the call
+};
+enum class FusedAllRoute { kPerBatch, kPlainLoop, kGatedLoop };
+// population_tick: ShardSettings::population_tick; max_table_ticks: kDtTabMaxTicks (dt_schedule.hpp)
+constexpr FusedAllRoute plan_fused_all(bool population_tick, bool f64, const FusedAllBatch* b, long nb, bool scheduled, long n_ticks, long max_table_ticks) {
+  if (!population_tick) return FusedAllRoute::kPerBatch;
+  bool seen[4] = {false, false, false, false};
+  int present = 0, with_nis = 0;
+  bool anything = false;
+  for (long i = 0; i < nb; ++i) {
+    if (b[i].n <= 0) continue;
+    if (!b[i].ready || b[i].keep_meas || b[i].pose || b[i].type < 0 || b[i].type > 3 || seen[b[i].type]) return FusedAllRoute::kPerBatch;
+    seen[b[i].type] = true;
+    ++present;
+    with_nis += b[i].nis ? 1 : 0;
+    anything = anything || b[i].nis || b[i].gate_or_policy;
+  }
+  if (present < 2) return FusedAllRoute::kPerBatch;
+  if (scheduled && n_ticks > max_table_ticks) return FusedAllRoute::kPerBatch;
+  // the plain loop: nothing to report or decide anywhere; the gated loop: every part has at least its NIS rows (a part's nis_max may
+  // be 0: the plain stream).  A call in which only some batches carry streams is served per batch.
+  if (!anything) return population_fused_ok(f64, false, scheduled) ? FusedAllRoute::kPlainLoop : FusedAllRoute::kPerBatch;
+  if (with_nis != present) return FusedAllRoute::kPerBatch;
+  return population_fused_ok(f64, true, scheduled) ? FusedAllRoute::kGatedLoop : FusedAllRoute::kPerBatch;
+}
+
 // The variants the library instantiates, before the per-layout exclusions of variant_shipped.
 constexpr unsigned kSepVariants[] = {0, kIndexed, kFused, kQuery, kAB, kPose, kAB | kPose, kFused | kPose, kQuery | kPose, kInnov,
                                      kFused | kLive1, kFused | kLive2, kPerQR, kIndexed | kPerQR, kPerQR | kAB};

@@ -696,6 +696,40 @@ void TargetManager::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpe
   }
 }
 
+void TargetManager::stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched) {
+  lock_guard<mutex> lg(target_lock_);
+  if (n_specs < 0) throw std::invalid_argument("target_estimation_amd: stepFusedAll: negative number of batches");
+  if (sched.on() && sched.n != n_ticks) throw std::invalid_argument("target_estimation_amd: the time-step schedule has one entry per tick of the call");
+  if (several()) {   // specs shard-major (numBatches order): every shard's refusals before any shard changes anything
+    if (n_specs != (long)numBatches()) throw std::runtime_error("target_estimation_amd: stepFusedAll needs one spec per batch");
+    long off = 0;
+    for (auto& s : shards_)
+      for (auto& b : s->batches()) {
+        if (specs[off].ring_ticks != 0) throw std::invalid_argument("target_estimation_amd: stepFusedAll: a fused call reads its measurements linearly (ring_ticks must be 0)");
+        b->check_fused_call(n_ticks, specs[off], sched, false);
+        ++off;
+      }
+  }
+  long off = 0;
+  for (size_t k = 0; k < shards_.size(); ++k) {
+    const long nk = several() ? (long)shards_[k]->batches().size() : n_specs;
+    DeviceGuard g(guardDev(k));
+    shards_[k]->stepFusedAll(n_ticks, dt, specs + off, nk, sched);
+    off += nk;
+  }
+}
+
+int TargetManager::fusedAllServed(bool gated, bool scheduled) {
+  lock_guard<mutex> lg(target_lock_);
+  bool any = false;   // every shard that holds targets replays them in one launch
+  for (const auto& s : shards_) {
+    if (s->size() == 0) continue;
+    if (!s->fusedAllServed(gated, scheduled)) return 0;
+    any = true;
+  }
+  return any ? 1 : 0;
+}
+
 void TargetManager::synchronize() {
   lock_guard<mutex> lg(target_lock_);
   for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(guardDev(k)); shards_[k]->synchronize(); }

@@ -186,6 +186,12 @@ class TargetManager {
                        const double* origin, double radius, int use_graph, const InnovStream* innov = nullptr,
                        const DtSchedule& sched = DtSchedule{});
 
+  // A temporally fused replay of EVERY batch (specs in batch order, shard-major; poses and innov inside the specs): for every batch
+  // what Batch::step_fused_gated leaves, bit for bit, with one launch per shard where Shard::stepFusedAll says so.  Every refusal is
+  // made before any batch of any shard is changed.
+  void stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched = DtSchedule{});
+  int fusedAllServed(bool gated, bool scheduled);   // 1: one launch per shard that holds targets; 0: per batch
+
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and
   // their per-GPU share (62 500 + 62 500 targets) is launch-bound.  specs as for stepSequenceAll (ring_ticks > 0 required).

@@ -677,6 +677,47 @@ int target_manager_step_sequence_all_dt(target_manager_c* m, long n_ticks, const
   });
 }
 
+// ---- one launch for a temporally fused replay of a whole manager
+static int step_fused_all(const char* what, target_manager_c* m, long n_ticks, double dt, const double* dt_host, bool scheduled,
+                          const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                          const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                          const target_reacquire_c* per_batch_reacq, long n_batches) {
+  return guarded(what, [&] {
+    TargetManager* mgr = M(m);
+    const te::DtSchedule sched = scheduled ? dt_schedule(n_ticks, dt_host) : te::DtSchedule();
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    if (nb > 0 && !per_batch) throw std::invalid_argument("per_batch must not be NULL");
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    for (size_t i = 0; i < nb; ++i) {   // (every gate and policy is looked at before anything else is)
+      const target_batch_sequence_c& s = per_batch[i];
+      if (s.ring_ticks != 0) throw std::invalid_argument("a fused call reads its measurements linearly: ring_ticks must be 0");
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, nullptr, nullptr, 0};
+      specs[i].poses = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+      specs[i].innov = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
+                                        per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
+    }
+    mgr->stepFusedAll(n_ticks, dt, specs.data(), n_batches, sched);
+  });
+}
+
+int target_manager_step_fused_all(target_manager_c* m, long n_ticks, double dt, const target_batch_sequence_c* per_batch,
+                                  const target_pose_stream_c* per_batch_poses, const target_innov_stream_c* per_batch_innov,
+                                  const double* per_batch_nis_max, const target_reacquire_c* per_batch_reacq, long n_batches) {
+  return step_fused_all("target_manager_step_fused_all", m, n_ticks, dt, nullptr, false, per_batch, per_batch_poses, per_batch_innov, per_batch_nis_max,
+                        per_batch_reacq, n_batches);
+}
+
+int target_manager_step_fused_all_dt(target_manager_c* m, long n_ticks, const double* dt_host, const target_batch_sequence_c* per_batch,
+                                     const target_pose_stream_c* per_batch_poses, const target_innov_stream_c* per_batch_innov,
+                                     const double* per_batch_nis_max, const target_reacquire_c* per_batch_reacq, long n_batches) {
+  return step_fused_all("target_manager_step_fused_all_dt", m, n_ticks, 0.0, dt_host, true, per_batch, per_batch_poses, per_batch_innov, per_batch_nis_max,
+                        per_batch_reacq, n_batches);
+}
+
+int target_manager_step_fused_all_served(target_manager_c* m, int gated, int scheduled) {
+  return guarded_value<int>("target_manager_step_fused_all_served", -1, [&] { return M(m)->fusedAllServed(gated != 0, scheduled != 0); });
+}
+
 int target_batch_rejection_runs(target_batch_c* b, unsigned char* runs_host) {
   return guarded("target_batch_rejection_runs", [&] {
     BatchLock lk(B(b));

@@ -798,6 +798,67 @@ class TargetManager:
             "target_manager_intersect_sphere_converged_batch")
         return conv.astype(bool), pose, delta, filt
 
+    def step_fused_all(self, dt, meas, has_meas=None, n_ticks=None, poses=None, innov=None, gate=None, reacquire=None):
+        """A temporally fused replay of every batch (target_manager_step_fused_all): for every batch, bit for bit, what
+        Batch.step_fused(dt, meas[i], ..., innov=, gate=, reacquire=) leaves -- as ONE launch per device where
+        fused_all_served() is 1, otherwise batch by batch inside the call.
+        meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order), or None for a batch that only predicts; has_meas, poses,
+        innov, gate and reacquire per batch with step_sequence_all's conventions.  n_ticks: the ticks of the call (by default those
+        of the first tensor); the tensors are read linearly, never as rings.
+        dt: a number, or a sequence / array with one time step per tick (target_manager_step_fused_all_dt)."""
+        nb = len(meas)          # the library checks it against the number of batches
+        first = next((t for t in meas if t is not None), None)
+        ticks = int(n_ticks) if n_ticks is not None else (first.shape[0] if first is not None else 0)
+        sched = _dt_schedule(dt, ticks)
+        specs = (capi.BatchSequence * max(nb, 1))()
+        for i, t in enumerate(meas):
+            if t is not None:
+                assert t.is_cuda and t.dim() == 3 and t.shape[0] >= ticks and t.shape[1] == 7 and (t.shape[2] == 1 or t.stride(2) == 1)
+                specs[i].meas_dev, specs[i].tick_stride, specs[i].ld = t.data_ptr(), t.stride(0), t.stride(1)
+            if has_meas is not None and has_meas[i] is not None:
+                h = has_meas[i]
+                assert h.is_cuda and h.dim() == 2 and h.element_size() == 1 and h.shape[0] >= ticks
+                specs[i].has_meas_dev, specs[i].has_stride = h.data_ptr(), h.stride(0)
+        bs = self.batches()
+        sizes = [bs[i].size if i < len(bs) else 0 for i in range(nb)]
+        pss = iss = gs = rqs = None
+        if poses is not None:
+            assert len(poses) == nb, "one pose stream (or None) per batch"
+            pss = (capi.PoseStream * max(nb, 1))()
+            for i in range(nb):
+                if poses[i] is not None:
+                    pss[i] = _pose_stream(poses[i], sizes[i], ticks)
+        if innov is not None:
+            assert len(innov) == nb, "one stream (or None) per batch"
+            iss = (capi.InnovStream * max(nb, 1))()
+            for i in range(nb):
+                if innov[i] is not None:
+                    iss[i] = _innov_stream(innov[i], sizes[i], bs[i].meas_dim if i < len(bs) else 3, ticks)
+        if gate is not None:
+            per = list(gate) if isinstance(gate, (list, tuple)) else [gate] * nb
+            assert len(per) == nb, "one gate (or None) per batch"
+            gs = (C.c_double * max(nb, 1))(*[0.0 if g is None else float(g) for g in per])
+        if reacquire is not None:
+            per = list(reacquire) if isinstance(reacquire, list) else [reacquire] * nb
+            assert len(per) == nb, "one re-acquisition policy (or None) per batch"
+            rqs = (capi.Reacquire * max(nb, 1))()
+            for i in range(nb):
+                rqs[i] = _reacquire(per[i], sizes[i], ticks)
+        if sched is not None:
+            _check(self._lib.target_manager_step_fused_all_dt(
+                self._h, ticks, sched.ctypes.data_as(capi.c_double_p), C.cast(specs, C.c_void_p), pss, iss, gs, rqs, nb),
+                "target_manager_step_fused_all_dt")
+        else:
+            _check(self._lib.target_manager_step_fused_all(self._h, ticks, float(dt), C.cast(specs, C.c_void_p), pss, iss, gs, rqs, nb),
+                   "target_manager_step_fused_all")
+
+    def fused_all_served(self, gated=False, scheduled=False):
+        """1: step_fused_all would be one launch per device as the batches are now -- gated: with a stream (innov=, gate=) on every
+        batch; scheduled: with a time step per tick --; 0: served batch by batch inside the call
+        (target_manager_step_fused_all_served)."""
+        return _check(self._lib.target_manager_step_fused_all_served(self._h, 1 if gated else 0, 1 if scheduled else 0),
+                      "target_manager_step_fused_all_served")
+
     def step_sequence_all(self, dt, meas, has_meas=None, query=None, use_graph=True, n_ticks=None, poses=None, innov=None, gate=None,
                           reacquire=None):
         """meas: one CUDA tensor [ticks, 7, ld] per batch (batches() order): `ticks` ticks of every batch -- ONE launch per
