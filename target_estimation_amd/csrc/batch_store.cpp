@@ -766,11 +766,6 @@ void Batch::step_dense(double dt, const void* meas_dev, long ld, const unsigned 
   if (meas_dev && !has_dev) nm_acc_ += 1;
 }
 
-void Batch::drop_graphs() {
-  for (auto& g : graphs_) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-  graphs_.clear();
-}
-
 void Batch::check_pose_stream(const PoseStream& q) const {
   if (!q.dev) return;
   if (q.ld < n_) throw std::invalid_argument("target_estimation_amd: pose stream: ld " + std::to_string(q.ld) + " < batch size " + std::to_string(n_));
@@ -803,126 +798,77 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
   touch();
   if (n_ == 0 || n_ticks <= 0) return;
   prepare_reacquire(innov);   // (before anything is enqueued or recorded)
-  const size_t es = elem_size();
-  auto params = [&](long s0) {
-    const long s = ring_ticks > 0 ? s0 % ring_ticks : s0;   // the measurements form a ring of ring_ticks ticks
-    StepParams p = dense_params();
-    p.meas = meas_base ? static_cast<const char*>(meas_base) + (size_t)(s * tick_stride) * es : nullptr;
-    p.meas_ld = ld;
-    p.has_meas = has_base ? has_base + s * has_stride : nullptr;
-    p.dt = sched.at(s0, dt);   // (tick s0 of the call, whatever entry of a measurement ring it reads)
-    p.reverse = zigzag() ? (int)((s0 + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) : 0;   // zig-zag; a recorded graph starts forwards
-    p.pose = poses.block(s0); p.pose_ld = poses.ld;   // (the pose stream's own ring: tick s0 of the call)
-    p.nis = innov.nis_row(s0); p.innov = innov.innov_block(s0); p.innov_ld = innov.ld; p.gate = innov.gate;
-    fill_reacquire(p, innov, s0);
-    return p;
+  const SeqSpec q{meas_base, tick_stride, ld, has_base, has_stride, nullptr, nullptr, ring_ticks, poses, innov};
+  auto tick = [&](hipStream_t st, long s, bool ab) {
+    const bool reverse = zigzag() && ((s + (use_graph ? 0 : (flip_ ? 1 : 0))) & 1) != 0;   // zig-zag; a recorded graph starts forwards
+    enqueue_tick(st, s, sched.at(s, dt), q, false, nullptr, 0.0, reverse, ab);
   };
   if (!use_graph) {
     const bool ab = pingpong() && !innov.on();   // (a tick with an innovation stream runs in place: same bits)
-    for (long s = 0; s < n_ticks; ++s) {
-      StepParams p = params(s);
-      if (ab) p.rec_out = alt_records();
-      launch_step(p, stream_);
-      if (p.rec_out) std::swap(d_rec_, d_rec_alt_);
-    }
+    for (long s = 0; s < n_ticks; ++s) tick(stream_, s, ab);
     TE_HIP_CHECK(hipGetLastError());
     if (n_ticks & 1) flip_ = !flip_;
   } else {
-    GraphEntry* hit = nullptr;
-    for (auto& g : graphs_)
-      if (g.n_ticks == n_ticks && g.tick_stride == tick_stride && g.ld == ld && g.has_stride == has_stride && g.n == n_ &&
-          dt_key_matches(g.dt_key, g.dt_is_schedule, g.dt, sched, dt) && g.meas_base == meas_base && g.has_base == has_base && g.rec == d_rec_ && g.ring_ticks == ring_ticks &&
-          g.poses.dev == poses.dev && g.poses.ld == poses.ld && g.poses.tick_stride == poses.tick_stride && g.poses.ring == poses.ring &&
-          g.innov.same(innov)) hit = &g;
-    if (!hit) {
-      if (graphs_.size() >= 64) {   // e.g. a ring of 4096 ticks replayed in 64-tick blocks: evict the least recently used one
-        size_t victim = 0;
-        for (size_t k = 1; k < graphs_.size(); ++k)
-          if (graphs_[k].last_use < graphs_[victim].last_use) victim = k;
-        TE_HIP_CHECK(hipStreamSynchronize(stream_));   // it may still be running
-        (void)hipGraphExecDestroy(graphs_[victim].exec);
-        (void)hipGraphDestroy(graphs_[victim].graph);
-        graphs_.erase(graphs_.begin() + (long)victim);
-      }
+    auto* hit = graphs_.find([&](const SeqKey& k) { return k.n_ticks == n_ticks && k.n == n_ && k.rec == d_rec_ && k.dt.matches(sched, dt) && k.spec.same(q); });
+    if (!hit) {   // (full, e.g. a ring of 4096 ticks replayed in 64-tick blocks: the least recently used recording goes)
       if (!cap_stream_) TE_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
-      GraphEntry e{n_ticks, tick_stride, ld, has_stride, n_, dt, meas_base, has_base, d_rec_, nullptr, nullptr, ring_ticks};
-      e.poses = poses;
-      e.innov = innov;
-      e.dt_is_schedule = sched.on();
-      e.dt_key = sched.key();   // (a recording bakes every tick's dt into its launch: filed under the values, compared as bits)
-      TE_HIP_CHECK(hipStreamBeginCapture(cap_stream_, hipStreamCaptureModeThreadLocal));
-      recording_ = true;   // (a recording is a dense streak: its ticks promote)
-      try {
+      hit = &graphs_.record(SeqKey{n_ticks, n_, d_rec_, q, DtKey(sched, dt)}, stream_, cap_stream_, [&] {
+        const RecordingScope recording(*this);
         for (long s = 0; s < n_ticks; ++s) {
-          launch_step(params(s), cap_stream_);
+          tick(cap_stream_, s, false);
 #ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`)
           if (s == 0 && std::getenv("TE_TEST_FAIL_IN_CAPTURE"))   // test hook: a launch that throws between Begin and EndCapture
             throw std::runtime_error("target_estimation_amd: injected failure inside stream capture");
 #endif
         }
         TE_HIP_CHECK(hipGetLastError());
-      } catch (...) {
-        recording_ = false;
-        hipGraph_t broken = nullptr;
-        (void)hipStreamEndCapture(cap_stream_, &broken);   // never leave the stream in capture mode
-        if (broken) (void)hipGraphDestroy(broken);
-        throw;
-      }
-      recording_ = false;
-      TE_HIP_CHECK(hipStreamEndCapture(cap_stream_, &e.graph));
-      if (hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGraphDestroy(e.graph);
-        throw std::runtime_error("target_estimation_amd: hipGraphInstantiate failed for a step sequence");
-      }
-      graphs_.push_back(e);
-      ++graph_recordings_;
-      hit = &graphs_.back();
+      });
     }
-    hit->last_use = ++graph_clock_;
+    graphs_.stamp(*hit);
     if (use_graph == 2) return;  // record only
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
     note_replay(n_ticks);
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
-  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
-  if (meas_base && !has_base && !innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
+  account(n_ticks, dt, sched, q.all_measured());
+}
+
+StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius, bool ab) {
+  const long sm = q.ring_ticks > 0 ? s % q.ring_ticks : s;   // the measurements' ring; the streams have their own: tick s of the call
+  StepParams p = dense_params();
+  p.pose = q.poses.block(s); p.pose_ld = q.poses.ld;
+  p.nis = q.innov.nis_row(s); p.innov = q.innov.innov_block(s); p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
+  p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(sm * q.tick_stride) * elem_size() : nullptr;
+  p.meas_ld = q.ld;
+  p.has_meas = q.has_base ? q.has_base + sm * q.has_stride : nullptr;
+  p.dt = dt;
+  if (query) {
+    p.q_origin[0] = origin[0]; p.q_origin[1] = origin[1]; p.q_origin[2] = origin[2];
+    p.q_radius = radius; p.q_delta = q.delta_dev; p.q_pose = q.pose_dev;
+  }
+  if (ab && !p.q_delta) p.rec_out = alt_records();   // (the fused query's kernels have no A -> B form: in place)
+  return p;
 }
 
 void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius,
                          bool reverse, bool ab) {
   if (n_ == 0) return;
-  double* pose_block = q.poses.block(s);   // (tick s of the call: the pose stream's own ring)
-  double* nis_row = q.innov.nis_row(s);    // (... and the innovation stream's)
-  double* innov_block = q.innov.innov_block(s);
-  const long s_call = s;
-  if (q.ring_ticks > 0) s %= q.ring_ticks;
-  const size_t es = elem_size();
   // (a tick with an innovation stream runs in place and without the fused query: the query follows as intersect_kernel)
-  const bool fused_q = n_classes_ == 1 && !q.innov.on();
-  if (q.innov.on()) ab = false;
-  StepParams p = dense_params();
-  p.pose = pose_block; p.pose_ld = q.poses.ld;
-  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
-  fill_reacquire(p, q.innov, s_call);
-  p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
-  p.meas_ld = q.ld;
-  p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
-  p.dt = dt;
+  const bool fused_q = query && n_classes_ == 1 && !q.innov.on();
+  StepParams p = tick_params(s, dt, q, fused_q, origin, radius, ab && !q.innov.on());
+  fill_reacquire(p, q.innov, s);
   p.reverse = reverse ? 1 : 0;
-  if (query && fused_q) {
-    p.q_origin[0] = origin[0]; p.q_origin[1] = origin[1]; p.q_origin[2] = origin[2];
-    p.q_radius = radius; p.q_delta = q.delta_dev; p.q_pose = q.pose_dev;
-  }
-  if (ab && !p.q_delta) p.rec_out = alt_records();   // (the fused query's kernels have no A -> B form: in place)
   launch_step(p, st);
   if (p.rec_out) std::swap(d_rec_, d_rec_alt_);
-  if (query && !fused_q) {
-    IntersectArgs a;
-    a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
-    a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-    a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
-    ops_->intersect(a, st);
-  }
+  if (query && !fused_q) enqueue_own_time_query(st, q, origin, radius);
+}
+
+void Batch::enqueue_own_time_query(hipStream_t st, const SeqSpec& q, const double* origin, double radius) {
+  IntersectArgs a;
+  a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
+  a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
+  a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
+  ops_->intersect(a, st);
 }
 
 bool Batch::population_ready() const {
@@ -949,66 +895,19 @@ void Batch::enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& q, b
     o.pose_soa = q.poses.block(s); o.pose_ld = q.poses.ld;
     ops_->outputs(o, st);
   }
-  if (query) {
-    IntersectArgs a;
-    a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
-    a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-    a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
-    ops_->intersect(a, st);
-  }
+  if (query) enqueue_own_time_query(st, q, origin, radius);
 }
 
-StepParams Batch::tick_params(long s, double dt, const SeqSpec& q, bool query, const double* origin, double radius, bool ab) {
-  double* pose_block = q.poses.block(s);
-  double* nis_row = q.innov.nis_row(s);
-  double* innov_block = q.innov.innov_block(s);
-  if (q.ring_ticks > 0) s %= q.ring_ticks;
-  const size_t es = elem_size();
-  StepParams p = dense_params();
-  p.pose = pose_block; p.pose_ld = q.poses.ld;
-  p.nis = nis_row; p.innov = innov_block; p.innov_ld = q.innov.ld; p.gate = q.innov.gate;
-  p.meas = q.meas_base ? static_cast<const char*>(q.meas_base) + (size_t)(s * q.tick_stride) * es : nullptr;
-  p.meas_ld = q.ld;
-  p.has_meas = q.has_base ? q.has_base + s * q.has_stride : nullptr;
-  p.dt = dt;
-  if (query) {
-    p.q_origin[0] = origin[0]; p.q_origin[1] = origin[1]; p.q_origin[2] = origin[2];
-    p.q_radius = radius; p.q_delta = q.delta_dev; p.q_pose = q.pose_dev;
-  }
-  if (ab && !query) p.rec_out = alt_records();
-  return p;
-}
-
-void Batch::account_sequence(long n_ticks, double dt, bool all_measured) {
-  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
+void Batch::account(long n_ticks, double dt, const DtSchedule& sched, bool all_measured) {
+  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
   if (all_measured) nm_acc_ += n_ticks;
-}
-
-void Batch::account_sequence(const DtSchedule& sched, bool all_measured) {
-  t_acc_ = sched.advance(t_acc_);
-  if (all_measured) nm_acc_ += sched.n;
 }
 
 const double* Batch::dt_table_push(const double* dt_host, long n) { return dttab_.push(dt_host, n, stream_); }
 
 void Batch::step_fused(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld,
                        const unsigned char* has_base, long has_stride, const PoseStream& poses, const DtSchedule& sched) {
-  if (sched.on()) {   // the schedule form: step_fused_gated's refusals and its table
-    step_fused_gated(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses, InnovStream{}, sched);
-    return;
-  }
-  check_pose_stream(poses);
-  touch();
-  demote_shared();   // (the temporally fused kernels exist for the plain form only)
-  if (n_ == 0 || n_ticks <= 0) return;
-  StepParams p = base_params();
-  p.meas = meas_base; p.meas_ld = ld; p.has_meas = has_base; p.dt = dt;
-  p.n_ticks = (int)n_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
-  p.pose = poses.dev; p.pose_ld = poses.ld; p.pose_tick_stride = poses.tick_stride; p.pose_ring = poses.ring;
-  launch_step(p, stream_);
-  TE_HIP_CHECK(hipGetLastError());
-  t_acc_ = te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
-  if (meas_base && !has_base) nm_acc_ += n_ticks;
+  step_fused_gated(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses, InnovStream{}, sched);
 }
 
 void Batch::check_fused_call(long n_ticks, const SeqSpec& q, const DtSchedule& sched, bool one_launch) const {
@@ -1021,26 +920,27 @@ void Batch::check_fused_call(long n_ticks, const SeqSpec& q, const DtSchedule& s
 }
 
 bool Batch::fused_call_one_launch(const SeqSpec& q, const DtSchedule& sched) const {
-  const bool plain = !q.innov.on() && !q.innov.gated() && !q.innov.reacq.on;
-  return (sched.on() ? fused_dt_served(!plain) : fused_gate_served()) && !q.poses.dev;
+  return (sched.on() ? fused_dt_served(!q.innov.plain()) : fused_gate_served()) && !q.poses.dev;
 }
 
 void Batch::fused_call_begin(const SeqSpec& q) {
   touch();
   demote_shared();   // (the temporally fused kernels exist for the plain form only)
-  if (n_ == 0) return;
-  if (q.innov.reacq.on && (q.innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
+  if (n_ > 0) prepare_fused_reacquire(q.innov);
+}
+
+void Batch::prepare_fused_reacquire(const InnovStream& innov) {
+  if (innov.reacq.on && (innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
 }
 
 StepParams Batch::fused_call_params(long n_ticks, double dt, const SeqSpec& q, const DtSchedule& sched, const double* dt_tab) {
   const InnovStream& innov = q.innov;
-  const bool plain = !innov.on() && !innov.gated() && !innov.reacq.on;   // no stream, no gate: the plain fused loop
   StepParams p = base_params();
   p.gate_row = d_has_eff_;   // (the dense layouts' single gated ticks take their mask from the writer's row)
   p.meas = q.meas_base; p.meas_ld = q.ld; p.has_meas = q.has_base; p.dt = dt;
   p.n_ticks = (int)n_ticks; p.tick_stride = q.tick_stride; p.has_stride = q.has_stride;
   p.pose = q.poses.dev; p.pose_ld = q.poses.ld; p.pose_tick_stride = q.poses.tick_stride; p.pose_ring = q.poses.ring;
-  if (!plain) {
+  if (!innov.plain()) {   // (plain: no stream, no gate -- the plain fused loop)
     p.fused_gate = 1; p.fused_gate_nis_max = innov.gate;
     p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
     p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
@@ -1053,34 +953,26 @@ StepParams Batch::fused_call_params(long n_ticks, double dt, const SeqSpec& q, c
   return p;
 }
 
-void Batch::fused_call_account(long n_ticks, double dt, const SeqSpec& q, const DtSchedule& sched) {
-  t_acc_ = sched.on() ? sched.advance(t_acc_) : te_clock_add_ticks(t_acc_, dt, (double)n_ticks);
-  if (q.meas_base && !q.has_base && !q.innov.gated()) nm_acc_ += n_ticks;   // (a gated tick counts its accepted measurements per slot)
-}
-
 void Batch::step_fused_gated(long n_ticks, double dt, const void* meas_base, long tick_stride, long ld, const unsigned char* has_base,
                              long has_stride, const PoseStream& poses, const InnovStream& innov, const DtSchedule& sched) {
-  const bool plain = !innov.on() && !innov.gated() && !innov.reacq.on;   // no stream, no gate: the plain fused loop
-  if (plain && !sched.on()) {   // ... of the plain fused call, the same kernels
-    step_fused(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, poses);
-    return;
-  }
   const SeqSpec q{meas_base, tick_stride, ld, has_base, has_stride, nullptr, nullptr, 0, poses, innov};
-  check_fused_call(n_ticks, q, sched, fused_call_one_launch(q, sched));
+  const bool fused_only = innov.plain() && !sched.on();   // step_fused as it always was: its refusals are the pose stream's
+  if (fused_only) check_pose_stream(poses);
+  else check_fused_call(n_ticks, q, sched, fused_call_one_launch(q, sched));
   touch();
   demote_shared();   // (the temporally fused kernels exist for the plain form only)
   if (n_ == 0 || n_ticks <= 0) return;
   // measured-pose rows keep ACCEPTED measurements, tick by tick: the sequence's launches.  So does a schedule beyond what one
   // table's 32-bit byte offsets reach (kDtTabMaxTicks).
-  if (keep_meas_ || (sched.on() && n_ticks > kDtTabMaxTicks)) {
+  if (!fused_only && (keep_meas_ || (sched.on() && n_ticks > kDtTabMaxTicks))) {
     step_sequence(n_ticks, dt, meas_base, tick_stride, ld, has_base, has_stride, 0, 0, poses, innov, sched);
     return;
   }
-  if (innov.reacq.on && (innov.reacq.k > 0 || p0_kept_)) prepare_p0_tables();   // (before anything is enqueued)
+  prepare_fused_reacquire(innov);
   // the table: a run of the batch's ring that no other call shares, filled on the stream ahead of the launch
   launch_step(fused_call_params(n_ticks, dt, q, sched, sched.on() ? dt_table_push(sched.dt, n_ticks) : nullptr), stream_);
   TE_HIP_CHECK(hipGetLastError());
-  fused_call_account(n_ticks, dt, q, sched);
+  account(n_ticks, dt, sched, q.all_measured());
 }
 
 // device block of a live session: [one mirror word per kLiveGroup wavefronts, 128 bytes apart][progress words]
@@ -1331,8 +1223,7 @@ long Batch::live_stop() {
   // the relay's last word: the ticks EVERY wavefront served.  The host's stop, or the relay's own after a silent host, reaches
   // all workers through one device word, so they all stop at the same tick.
   const long mn = std::max(0L, (long)__atomic_load_n(live_.h_done, __ATOMIC_ACQUIRE));
-  t_acc_ = te_clock_add_ticks(t_acc_, live_.dt, (double)mn);
-  if (live_.all_measured) nm_acc_ += mn;
+  account(mn, live_.dt, DtSchedule{}, live_.all_measured);
   if (mn != live_.posted)
     throw std::runtime_error("target_estimation_amd: live session ended after " + std::to_string(mn) + " of " + std::to_string(live_.posted) +
                              " posted ticks (the idle limit stopped it before the last post?)");

@@ -17,6 +17,7 @@
 #include "dt_table_ring.hpp"
 #include "kf_ops.hpp"
 #include "reacquire_plan.hpp"
+#include "seq_graph_cache.hpp"
 
 namespace te {
 
@@ -29,6 +30,7 @@ struct PoseStream {
   long tick_stride = 0;
   long ring = 0;
   double* block(long s) const { return dev ? dev + (ring > 0 ? s % ring : s) * tick_stride : nullptr; }
+  bool same(const PoseStream& o) const { return dev == o.dev && ld == o.ld && tick_stride == o.tick_stride && ring == o.ring; }
 };
 
 // A per-tick innovation stream (target_innov_stream_c): after tick s of a call, for every slot (column), the tick's normalised
@@ -51,6 +53,7 @@ struct InnovStream {
   // re-initialisation on the K-th consecutive rejection.  Off by default.
   Reacquire reacq{};
   bool on() const { return nis != nullptr; }
+  bool plain() const { return !on() && !gated() && !reacq.on; }   // no stream, no gate, no policy
   double* nis_row(long s) const { return nis ? nis + (ring > 0 ? s % ring : s) * nis_tick_stride : nullptr; }
   double* innov_block(long s) const { return (nis && innov) ? innov + (ring > 0 ? s % ring : s) * innov_tick_stride : nullptr; }
   bool same(const InnovStream& o) const {
@@ -103,7 +106,12 @@ class Batch {
   void settle_tiles();
   long uniform_tiles();        // tiles flagged now: reads the flags back on the batch's stream (SYNCHRONISES)
   static long promote_after();
-  void set_recording(bool on) { recording_ = on; }   // the dense ticks enqueued meanwhile go into a recorded graph
+  struct RecordingScope {   // while one lives, the dense ticks enqueued go into a recorded graph (they promote: a dense streak)
+    Batch& b;
+    explicit RecordingScope(Batch& x) : b(x) { b.recording_ = true; }
+    ~RecordingScope() { b.recording_ = false; }
+    RecordingScope(const RecordingScope&) = delete;
+  };
   void note_replay(long n_ticks) { if (uniform_tiles_enabled()) { ut_flagged_ = true; dense_streak_ += n_ticks; } }   // a recorded sequence was launched
   long size() const { return n_; }
   bool getter_table_is_cheap() const { return n_ <= kCacheMax; }   // (its one-target getters read a host-resident table from the first call after a change)
@@ -325,19 +333,31 @@ class Batch {
     long ring_ticks;                                    // > 0: the measurements are a ring, tick s reads entry s % ring_ticks
     PoseStream poses{};                                 // the per-tick pose stream of the batch (tick s: poses.block(s)), or none
     InnovStream innov{};                                // the per-tick innovation stream of the batch, or none
+    // (a gated tick counts its accepted measurements per slot, a masked one its measured slots: on the device)
+    bool all_measured() const { return meas_base && !has_base && !innov.gated(); }
+    // everything a recording made from the spec refers to (recorded graphs are keyed by it)
+    bool same(const SeqSpec& o) const {
+      return meas_base == o.meas_base && tick_stride == o.tick_stride && ld == o.ld && has_base == o.has_base && has_stride == o.has_stride &&
+             delta_dev == o.delta_dev && pose_dev == o.pose_dev && ring_ticks == o.ring_ticks && poses.same(o.poses) && innov.same(o.innov);
+    }
   };
-  // tick s of the spec on `st`, without touching the batch clock.  With query: the own-time sphere
-  // query of every slot runs inside the step kernel (one launch).
-  // ab: 1 = an A -> B tick (records read from the current buffer, written to the alternate one, buffers swapped; never
-  // inside a stream capture: a recorded graph bakes its pointers), 0 = in place.
-  // (a call with a time-step schedule hands every tick its own dt here and in tick_params)
-  void enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& spec, bool query, const double* origin, double radius,
-                    bool reverse = false, bool ab = false);
-  // The same tick as launch parameters only, for the manager's one-launch population tick (kf_population.hpp): possible when
-  // population_ready() -- separable layout with packed groups, one (Q, R) class, no measured-pose rows to keep.  With ab the
-  // caller calls swap_records() once the launch is queued (and only if the returned parameters carry rec_out).
+  // THE launch parameters of dense tick s of the spec (every launched dense tick is built here, once): the ring-reduced
+  // measurement block and mask row, dt (a call with a time-step schedule hands every tick its own), the pose block, NIS row and
+  // innovation block of tick s of the call, the gate, with query the fused own-time sphere query, with ab (and no fused query,
+  // whose kernels have no A -> B form) rec_out.  No re-acquisition policy: that is enqueue_tick's, or a launch behind the
+  // population tick (enqueue_after_innov_tick).  Used as it is by the manager's one-launch population tick (kf_population.hpp),
+  // possible when population_ready() -- separable layout with packed groups, one (Q, R) class, no measured-pose rows to keep;
+  // with ab that caller calls swap_records() once the launch is queued (and only if the returned parameters carry rec_out).
   bool population_ready() const;
   StepParams tick_params(long s, double dt, const SeqSpec& spec, bool query, const double* origin, double radius, bool ab);
+  // tick s of the spec on `st`, without touching the batch clock: tick_params, the policy, the launch, the buffer swap.  With
+  // query: the own-time sphere query of every slot runs inside the step kernel (one launch) where the batch has one (Q, R) class
+  // and the tick no innovation stream, behind it as intersect_kernel otherwise.
+  // ab: 1 = an A -> B tick (records read from the current buffer, written to the alternate one, buffers swapped; never
+  // inside a stream capture: a recorded graph bakes its pointers), 0 = in place (as is every tick with an innovation stream).
+  // step_sequence enqueues its ticks, eager and recorded, through here as well.
+  void enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& spec, bool query, const double* origin, double radius,
+                    bool reverse = false, bool ab = false);
   // What follows a population tick that carried an innovation stream (whose kernel has neither the fused query nor the pose
   // output) for this batch: the pose-writer launch into tick s's pose block and / or the own-time sphere query, as launches.
   void enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& spec, bool query, const double* origin, double radius);
@@ -349,22 +369,26 @@ class Batch {
   //   fused_call_one_launch  would step_fused_gated serve the call by one launch of its own
   //   fused_call_begin       touch(), demote_shared(), then the device tables of a re-acquisition policy
   //   fused_call_params      the launch parameters of the whole call (dt_tab: the schedule in device memory, or null without one)
-  //   fused_call_account     the clock and the measurement counter behind the call
+  //   account                the clock and the measurement counter behind the call
   void check_fused_call(long n_ticks, const SeqSpec& spec, const DtSchedule& sched, bool one_launch) const;
   bool fused_call_one_launch(const SeqSpec& spec, const DtSchedule& sched) const;
   void fused_call_begin(const SeqSpec& spec);
   StepParams fused_call_params(long n_ticks, double dt, const SeqSpec& spec, const DtSchedule& sched, const double* dt_tab);
-  void fused_call_account(long n_ticks, double dt, const SeqSpec& spec, const DtSchedule& sched);
-  // (all_measured: measurements without a mask and without a gate -- a gated tick counts its accepted ones on the device)
-  void account_sequence(long n_ticks, double dt, bool all_measured);
-  void account_sequence(const DtSchedule& sched, bool all_measured);   // the schedule form: one te_clock_add per tick, in order
+  // Behind every multi-tick call: the batch clock advances by dt x n_ticks or, with a schedule, by one te_clock_add per tick in
+  // order; the measurement counter by n_ticks where all_measured (SeqSpec::all_measured).
+  void account(long n_ticks, double dt, const DtSchedule& sched, bool all_measured);
   // identity of everything a recorded launch sequence refers to
   // (ops: the launch table, i.e. which kernels a recording holds -- it changes when a shared-axes batch is expanded)
-  struct DevIdentity { const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; const void* p0tab; };
+  struct DevIdentity {
+    const void* rec; const void* qr; const void* tbase; const void* nmbase; long n; const void* ops; const void* p0tab;
+    bool same(const DevIdentity& o) const {
+      return rec == o.rec && qr == o.qr && tbase == o.tbase && nmbase == o.nmbase && n == o.n && ops == o.ops && p0tab == o.p0tab;
+    }
+  };
   // (the tile arrays, the rejection runs and the slot -> row index are allocated and freed with the records: rec identifies them too)
   DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_, d_p0tab_}; }
   void prepare() { touch(); }
-  long graph_recordings() const { return graph_recordings_; }
+  long graph_recordings() const { return graphs_.recordings(); }   // recordings made so far (what a test of the cache observes)
 
   // TargetInterface::getMeasuredPose (target_interface.cpp:117-121), optional: see measured_pose.hpp
   void set_keep_measurement(bool on);
@@ -456,6 +480,8 @@ class Batch {
   void run_move(long src, long dst);
   void fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const;   // the policy's launch parameters of tick s_call of a call
   void prepare_p0_tables();              // the body of prepare_reacquire
+  void prepare_fused_reacquire(const InnovStream& innov);   // ... of a fused call (whose kernel reads no table for K = 0)
+  void enqueue_own_time_query(hipStream_t st, const SeqSpec& spec, const double* origin, double radius);   // intersect_kernel, every slot
   // the by-id update policy: its by-entry NIS row and event row (host-mapped, sized with the staging and queue blocks; the host
   // reads them as cached host memory, never through the write-combined BAR block)
   UpdateGate pol_{};
@@ -494,26 +520,12 @@ class Batch {
   void gate_reserve(int window);
   void gate_move(long src, long dst);
   void gate_reset(long first, long count);
-  struct GraphEntry {
-    long n_ticks, tick_stride, ld, has_stride, n;
-    double dt;
-    const void* meas_base;
-    const unsigned char* has_base;
-    char* rec;
-    hipGraphExec_t exec;
-    hipGraph_t graph;
-    long ring_ticks;
-    unsigned long last_use = 0;
-    PoseStream poses{};   // (recorded graphs write into the pose buffers they were recorded with)
-    InnovStream innov{};  // (... and into the innovation buffers)
-    bool dt_is_schedule = false;   // recorded from a call with a time-step schedule: filed under its values as bits, not under dt
-    std::vector<double> dt_key;
-  };
-  std::vector<GraphEntry> graphs_;
-  unsigned long graph_clock_ = 0;   // recorded sequences are evicted least-recently-used first (64 kept)
+  // Recorded sequences (step_sequence with use_graph): 64 kept, stamped on every use, so the least recently used one goes.
+  // (a recording writes into the pose and innovation buffers it was recorded with, and bakes every tick's dt into its launch)
+  struct SeqKey { long n_ticks; long n; char* rec; SeqSpec spec; DtKey dt; };
+  SeqGraphCache<SeqKey> graphs_{64};
   hipStream_t cap_stream_ = nullptr;
-  void drop_graphs();
-  long graph_recordings_ = 0;      // recordings made so far (graph_recordings(): what a test of the cache observes)
+  void drop_graphs() { graphs_.drop(); }
   // The device table of a fused call with a time-step schedule: a fresh run of a ring per call (dt_table_ring.hpp)
   DtTableRing dttab_;
   const double* dt_table_push(const double* dt_host, long n);   // the device address of the call's n entries

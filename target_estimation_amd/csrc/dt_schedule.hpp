@@ -62,4 +62,14 @@ inline bool dt_key_matches(const std::vector<double>& key, bool key_is_schedule,
   return key_is_schedule ? sched.same_bits(key) : key_scalar == dt;
 }
 
+// What a recording is filed under: the call's scalar dt, or its schedule's bits.
+struct DtKey {
+  double dt = 0.0;
+  bool is_schedule = false;
+  std::vector<double> bits;
+  DtKey() = default;
+  DtKey(const DtSchedule& sched, double scalar) : dt(scalar), is_schedule(sched.on()), bits(sched.key()) {}
+  bool matches(const DtSchedule& sched, double scalar) const { return dt_key_matches(bits, is_schedule, dt, sched, scalar); }
+};
+
 }  // namespace te

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <iostream>
 
 #include "hip_check.hpp"
@@ -792,11 +793,6 @@ void Shard::setStream(hipStream_t s) {
   stream_ = s;
 }
 
-void Shard::dropSeqGraphs() {
-  for (auto& g : seq_graphs_) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-  seq_graphs_.clear();
-}
-
 // Can the tick of all batches be ONE launch?  At least two non-empty batches, every one of them a one-class batch in the
 // separable layout with packed groups (the automatic choice for the shipped models) -- then there is at most one batch per motion
 // model.  ShardSettings::population_tick off (TE_POPULATION_TICK=0) keeps the launch per batch (experiments, and the comparison in profiles/).
@@ -898,41 +894,20 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     }
     TE_HIP_CHECK(hipGetLastError());
   } else {
-    auto same_spec = [](const Batch::SeqSpec& x, const Batch::SeqSpec& y) {
-      return x.meas_base == y.meas_base && x.tick_stride == y.tick_stride && x.ld == y.ld && x.has_base == y.has_base &&
-             x.has_stride == y.has_stride && x.delta_dev == y.delta_dev && x.pose_dev == y.pose_dev && x.ring_ticks == y.ring_ticks &&
-             x.poses.dev == y.poses.dev && x.poses.ld == y.poses.ld && x.poses.tick_stride == y.poses.tick_stride && x.poses.ring == y.poses.ring &&
-             x.innov.same(y.innov);
-    };
-    auto same_id = [](const Batch::DevIdentity& x, const Batch::DevIdentity& y) {
-      return x.rec == y.rec && x.qr == y.qr && x.tbase == y.tbase && x.nmbase == y.nmbase && x.n == y.n && x.ops == y.ops && x.p0tab == y.p0tab;
-    };
-    SeqGraph* hit = nullptr;
-    for (auto& g : seq_graphs_) {
-      if (g.n_ticks != n_ticks || !dt_key_matches(g.dt_key, g.dt_is_schedule, g.dt, sched, dt) || g.query != query || g.specs.size() != nb) continue;
-      if (query && (g.origin[0] != org[0] || g.origin[1] != org[1] || g.origin[2] != org[2] || g.radius != radius)) continue;
-      bool ok = true;
-      for (size_t b = 0; b < nb && ok; ++b) ok = same_spec(g.specs[b], specs[b]) && same_id(g.ident[b], batches_[b]->dev_identity());
-      if (ok) { hit = &g; break; }
-    }
+    auto* hit = seq_graphs_.find([&](const SeqKey& g) {
+      if (g.n_ticks != n_ticks || !g.dt.matches(sched, dt) || g.query != query || g.specs.size() != nb) return false;
+      if (query && (g.origin[0] != org[0] || g.origin[1] != org[1] || g.origin[2] != org[2] || g.radius != radius)) return false;
+      for (size_t b = 0; b < nb; ++b)
+        if (!g.specs[b].same(specs[b]) || !g.ident[b].same(batches_[b]->dev_identity())) return false;
+      return true;
+    });
     if (!hit) {
-      if (seq_graphs_.size() >= 8) {   // evict the oldest recording (they are appended in order of creation)
-        TE_HIP_CHECK(hipStreamSynchronize(stream_));
-        (void)hipGraphExecDestroy(seq_graphs_.front().exec);
-        (void)hipGraphDestroy(seq_graphs_.front().graph);
-        seq_graphs_.erase(seq_graphs_.begin());
-      }
       if (branch_streams_.empty()) {
         hipStream_t st; TE_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         branch_streams_.push_back(st);
       }
-      SeqGraph g;
-      g.n_ticks = n_ticks; g.dt = dt; g.query = query; g.radius = radius;
-      g.dt_is_schedule = sched.on(); g.dt_key = sched.key();   // (every tick's dt is baked into its launch)
-      g.origin[0] = org[0]; g.origin[1] = org[1]; g.origin[2] = org[2];
-      g.specs.assign(specs, specs + nb);
-      for (size_t b = 0; b < nb; ++b) g.ident.push_back(batches_[b]->dev_identity());
-      g.graph = nullptr; g.exec = nullptr;
+      SeqKey key{n_ticks, DtKey(sched, dt), query, {org[0], org[1], org[2]}, radius, std::vector<Batch::SeqSpec>(specs, specs + nb), {}};
+      for (size_t b = 0; b < nb; ++b) key.ident.push_back(batches_[b]->dev_identity());
       // The launches are captured on ONE stream whose dependency set is replaced at the head of every
       // batch's chain (hipStreamUpdateCaptureDependencies): the chains become the branches of the graph.
       hipStream_t cap = branch_streams_[0];
@@ -946,9 +921,9 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
         TE_HIP_CHECK(hipStreamGetCaptureInfo_v2(cap, &status, &id, &gr, &deps, &n));
         return Nodes(deps, deps + n);
       };
-      TE_HIP_CHECK(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-      for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(true);   // (uniform tiles: a recording's ticks promote)
-      try {
+      hit = &seq_graphs_.record(std::move(key), stream_, cap, [&] {
+        std::deque<Batch::RecordingScope> recording;   // (uniform tiles: a recording's ticks promote)
+        for (size_t b = 0; b < nb; ++b) recording.emplace_back(*batches_[b]);
         Nodes leaves, none;
         if (populationTick()) {
           // one launch per tick for the whole population: a single chain, nothing left to the placement of branches on
@@ -971,19 +946,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
         }
         TE_HIP_CHECK(hipGetLastError());
         if (!leaves.empty()) set_deps(leaves);
-      } catch (...) {
-        for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(false);
-        hipGraph_t broken = nullptr;
-        (void)hipStreamEndCapture(cap, &broken);   // leave capture mode before reporting
-        if (broken) (void)hipGraphDestroy(broken);
-        throw;
-      }
-      for (size_t b = 0; b < nb; ++b) batches_[b]->set_recording(false);
-      TE_HIP_CHECK(hipStreamEndCapture(cap, &g.graph));
-      TE_HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
-      seq_graphs_.push_back(std::move(g));
-      ++seq_recordings_;
-      hit = &seq_graphs_.back();
+      });
     }
     if (use_graph == 2) return;
     TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
@@ -991,9 +954,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
   }
   for (size_t b = 0; b < nb; ++b) {
     if (batches_[b]->size() == 0) continue;
-    const bool all_measured = specs[b].meas_base && !specs[b].has_base && !specs[b].innov.gated();
-    if (sched.on()) batches_[b]->account_sequence(sched, all_measured);
-    else batches_[b]->account_sequence(n_ticks, dt, all_measured);
+    batches_[b]->account(n_ticks, dt, sched, specs[b].all_measured());
   }
 }
 
@@ -1045,7 +1006,7 @@ void Shard::stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, l
   launch_population_fused(set_.dtype, parts, route == FusedAllRoute::kGatedLoop, dt_tab, stream_);
   TE_HIP_CHECK(hipGetLastError());
   for (size_t b = 0; b < nb; ++b)
-    if (batches_[b]->size() > 0) batches_[b]->fused_call_account(n_ticks, dt, specs[b], sched);
+    if (batches_[b]->size() > 0) batches_[b]->account(n_ticks, dt, sched, specs[b].all_measured());
 }
 
 void Shard::liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s,

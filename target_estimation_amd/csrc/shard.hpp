@@ -137,7 +137,7 @@ class Shard {
   // sched: the call's time-step schedule (dt_schedule.hpp; by default none): tick s of every batch runs with sched.dt[s]
   void stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, bool query, const double* origin, double radius,
                        int use_graph, const DtSchedule& sched = DtSchedule{});
-  long seqRecordings() const { return seq_recordings_; }   // all-batches recordings made so far
+  long seqRecordings() const { return seq_graphs_.recordings(); }   // all-batches recordings made so far
   // A temporally fused replay of every batch (target_manager_step_fused_all): for every batch, bit for bit, what
   // Batch::step_fused_gated(n_ticks, dt, spec..., sched) leaves.  ONE launch of kf_step_population_fused_kernel where plan_fused_all
   // (step_variant.hpp) says so: the population rule holds once every batch is expanded from the shared-axes form, no batch has a
@@ -187,20 +187,16 @@ class Shard {
   std::vector<std::unique_ptr<Batch>> batches_;
   hipStream_t stream_ = nullptr;
 
-  // recorded all-batches sequences (stepSequenceAll)
-  struct SeqGraph {
-    long n_ticks; double dt; bool query; double origin[3]; double radius;
+  // recorded all-batches sequences (stepSequenceAll): 8 kept, stamped when they are made only, so the oldest one goes
+  struct SeqKey {
+    long n_ticks; DtKey dt; bool query; double origin[3]; double radius;
     std::vector<Batch::SeqSpec> specs;
     std::vector<Batch::DevIdentity> ident;
-    hipGraph_t graph; hipGraphExec_t exec;
-    bool dt_is_schedule = false;   // recorded from a call with a time-step schedule: filed under its values as bits, not under dt
-    std::vector<double> dt_key;
   };
-  std::vector<SeqGraph> seq_graphs_;
-  long seq_recordings_ = 0;
+  SeqGraphCache<SeqKey> seq_graphs_{8};
   std::vector<hipStream_t> branch_streams_;   // [0]: the capture stream
   std::vector<hipEvent_t> branch_events_;
-  void dropSeqGraphs();
+  void dropSeqGraphs() { seq_graphs_.drop(); }
   void enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin, double radius,
                              bool reverse, bool ab);
   FusedAllRoute fusedAllRoute(const Batch::SeqSpec* specs, bool scheduled, long n_ticks) const;

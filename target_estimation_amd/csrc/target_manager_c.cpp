@@ -429,31 +429,69 @@ int target_batch_step_host(target_batch_c* b, double dt, const void* meas_soa_ho
   return guarded("target_batch_step_host", [&] { BatchLock lk(B(b)); B(b)->step_dense_host_soa(dt, meas_soa_host, ld_host, has_meas_host); });
 }
 
+static te::DtSchedule dt_schedule(long n_ticks, const double* dt_host) {
+  if (n_ticks > 0 && !dt_host) throw std::invalid_argument("dt_host must not be NULL");
+  return n_ticks > 0 ? te::DtSchedule(dt_host, n_ticks) : te::DtSchedule();
+}
+
+// The target_batch_step_sequence* family: every older symbol is the newest one with nulls.  The schedule, the gate and the policy
+// are looked at before the handle, the ring after the lock is taken (ring_needed: target_batch_step_sequence_ring's rule).
+static int step_sequence(const char* what, target_batch_c* b, long n_ticks, double dt, const double* dt_host, bool scheduled,
+                         const void* meas_dev, long tick_stride, long ld, const unsigned char* has_meas_dev, long has_stride,
+                         long ring_ticks, bool ring_needed, const target_pose_stream_c* poses, const target_innov_stream_c* innov,
+                         double nis_max, const target_reacquire_c* reacq, int use_graph) {
+  return guarded(what, [&] {
+    const te::DtSchedule sched = scheduled ? dt_schedule(n_ticks, dt_host) : te::DtSchedule();
+    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
+    BatchLock lk(B(b));
+    if (ring_needed && ring_ticks <= 0) throw std::invalid_argument("ring_ticks must be positive");
+    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
+    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream, sched);
+  });
+}
+
+// The target_manager_step_sequence_all* family, in the same way.  Every gate and policy is looked at before anything else is.
+// streams: every symbol but the first goes through the manager's entry that refuses a negative number of batches by name.
+static int step_sequence_all(const char* what, target_manager_c* m, long n_ticks, double dt, const double* dt_host, bool scheduled,
+                             bool streams, const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
+                             const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
+                             const target_reacquire_c* per_batch_reacq, long n_batches, int query, const double* origin, double radius,
+                             int use_graph) {
+  return guarded(what, [&] {
+    const te::DtSchedule sched = scheduled ? dt_schedule(n_ticks, dt_host) : te::DtSchedule();
+    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
+    std::vector<te::Batch::SeqSpec> specs(nb);
+    std::vector<te::PoseStream> poses(nb);
+    std::vector<te::InnovStream> innov(nb);
+    for (size_t i = 0; i < nb; ++i)
+      innov[i] = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
+                                  per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
+    for (size_t i = 0; i < nb; ++i) {
+      const target_batch_sequence_c& s = per_batch[i];
+      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
+      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
+    }
+    if (streams) M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data(), sched);
+    else M(m)->stepSequenceAll(n_ticks, dt, specs.data(), n_batches, query != 0, origin, radius, use_graph);
+  });
+}
+
 int target_batch_step_sequence(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
                                const unsigned char* has_meas_dev, long has_stride, int use_graph) {
-  return guarded("target_batch_step_sequence", [&] { BatchLock lk(B(b));
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph);
-  });
+  return step_sequence("target_batch_step_sequence", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride, 0, false,
+                       nullptr, nullptr, 0.0, nullptr, use_graph);
 }
 
 int target_batch_step_sequence_ring(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
                                     const unsigned char* has_meas_dev, long has_stride, long ring_ticks, int use_graph) {
-  return guarded("target_batch_step_sequence_ring", [&] { BatchLock lk(B(b));
-    if (ring_ticks <= 0) throw std::invalid_argument("ring_ticks must be positive");
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks);
-  });
+  return step_sequence("target_batch_step_sequence_ring", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, true, nullptr, nullptr, 0.0, nullptr, use_graph);
 }
 
 int target_manager_step_sequence_all(target_manager_c* m, long n_ticks, double dt, const target_batch_sequence_c* per_batch,
                                      long n_batches, int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all", [&] {
-    std::vector<te::Batch::SeqSpec> specs((size_t)(n_batches > 0 ? n_batches : 0));
-    for (long i = 0; i < n_batches; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[(size_t)i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-    }
-    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), n_batches, query != 0, origin, radius, use_graph);
-  });
+  return step_sequence_all("target_manager_step_sequence_all", m, n_ticks, dt, nullptr, false, false, per_batch, nullptr, nullptr, nullptr, nullptr,
+                           n_batches, query, origin, radius, use_graph);
 }
 
 int target_manager_population_tick(target_manager_c* m) {
@@ -473,10 +511,8 @@ int target_batch_step_fused(target_batch_c* b, long n_ticks, double dt, const vo
 int target_batch_step_sequence_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                      const target_pose_stream_c* poses, int use_graph) {
-  return guarded("target_batch_step_sequence_poses", [&] { BatchLock lk(B(b));
-    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses));
-  });
+  return step_sequence("target_batch_step_sequence_poses", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, false, poses, nullptr, 0.0, nullptr, use_graph);
 }
 
 int target_batch_step_fused_poses(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride, long ld,
@@ -489,79 +525,40 @@ int target_batch_step_fused_poses(target_batch_c* b, long n_ticks, double dt, co
 int target_manager_step_sequence_all_poses(target_manager_c* m, long n_ticks, double dt,
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            long n_batches, int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all_poses", [&] {
-    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
-    std::vector<te::Batch::SeqSpec> specs(nb);
-    std::vector<te::PoseStream> poses(nb);
-    for (size_t i = 0; i < nb; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
-    }
-    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph);
-  });
+  return step_sequence_all("target_manager_step_sequence_all_poses", m, n_ticks, dt, nullptr, false, true, per_batch, per_batch_poses, nullptr, nullptr,
+                           nullptr, n_batches, query, origin, radius, use_graph);
 }
 
 // ---- per-tick innovation streams of launched ticks
 int target_batch_step_sequence_innov(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                      const target_pose_stream_c* poses, const target_innov_stream_c* innov, int use_graph) {
-  return guarded("target_batch_step_sequence_innov", [&] { BatchLock lk(B(b));
-    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses),
-                        innov_stream(innov));
-  });
+  return step_sequence("target_batch_step_sequence_innov", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, false, poses, innov, 0.0, nullptr, use_graph);
 }
 
 int target_manager_step_sequence_all_innov(target_manager_c* m, long n_ticks, double dt,
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            const target_innov_stream_c* per_batch_innov, long n_batches,
                                            int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all_innov", [&] {
-    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
-    std::vector<te::Batch::SeqSpec> specs(nb);
-    std::vector<te::PoseStream> poses(nb);
-    std::vector<te::InnovStream> innov(nb);
-    for (size_t i = 0; i < nb; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
-      innov[i] = innov_stream(per_batch_innov ? &per_batch_innov[i] : nullptr);
-    }
-    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
-  });
+  return step_sequence_all("target_manager_step_sequence_all_innov", m, n_ticks, dt, nullptr, false, true, per_batch, per_batch_poses, per_batch_innov,
+                           nullptr, nullptr, n_batches, query, origin, radius, use_graph);
 }
 
 // ---- the NIS validation gate inside launched ticks
 int target_batch_step_sequence_gated(target_batch_c* b, long n_ticks, double dt, const void* meas_dev, long tick_stride,
                                      long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                      const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max, int use_graph) {
-  return guarded("target_batch_step_sequence_gated", [&] {
-    const te::InnovStream stream = gated_stream(innov, nis_max);
-    BatchLock lk(B(b));
-    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream);
-  });
+  return step_sequence("target_batch_step_sequence_gated", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, false, poses, innov, nis_max, nullptr, use_graph);
 }
 
 int target_manager_step_sequence_all_gated(target_manager_c* m, long n_ticks, double dt,
                                            const target_batch_sequence_c* per_batch, const target_pose_stream_c* per_batch_poses,
                                            const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max, long n_batches,
                                            int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all_gated", [&] {
-    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
-    std::vector<te::Batch::SeqSpec> specs(nb);
-    std::vector<te::PoseStream> poses(nb);
-    std::vector<te::InnovStream> innov(nb);
-    for (size_t i = 0; i < nb; ++i)   // (every gate is looked at before anything else is)
-      innov[i] = gated_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0);
-    for (size_t i = 0; i < nb; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
-    }
-    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
-  });
+  return step_sequence_all("target_manager_step_sequence_all_gated", m, n_ticks, dt, nullptr, false, true, per_batch, per_batch_poses, per_batch_innov,
+                           per_batch_nis_max, nullptr, n_batches, query, origin, radius, use_graph);
 }
 
 // ---- re-acquisition of lost tracks inside the gated ticks
@@ -569,12 +566,8 @@ int target_batch_step_sequence_reacquire(target_batch_c* b, long n_ticks, double
                                          long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                          const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
                                          const target_reacquire_c* reacq, int use_graph) {
-  return guarded("target_batch_step_sequence_reacquire", [&] {
-    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
-    BatchLock lk(B(b));
-    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
-    B(b)->step_sequence(n_ticks, dt, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream);
-  });
+  return step_sequence("target_batch_step_sequence_reacquire", b, n_ticks, dt, nullptr, false, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, false, poses, innov, nis_max, reacq, use_graph);
 }
 
 // ---- the gate, the innovation stream and the re-acquisition inside a launched fused call
@@ -598,40 +591,17 @@ int target_manager_step_sequence_all_reacquire(target_manager_c* m, long n_ticks
                                                const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
                                                const target_reacquire_c* per_batch_reacq, long n_batches,
                                                int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all_reacquire", [&] {
-    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
-    std::vector<te::Batch::SeqSpec> specs(nb);
-    std::vector<te::PoseStream> poses(nb);
-    std::vector<te::InnovStream> innov(nb);
-    for (size_t i = 0; i < nb; ++i)   // (every gate and policy is looked at before anything else is)
-      innov[i] = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
-                                  per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
-    for (size_t i = 0; i < nb; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
-    }
-    M(m)->stepSequenceAll(n_ticks, dt, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data());
-  });
+  return step_sequence_all("target_manager_step_sequence_all_reacquire", m, n_ticks, dt, nullptr, false, true, per_batch, per_batch_poses,
+                           per_batch_innov, per_batch_nis_max, per_batch_reacq, n_batches, query, origin, radius, use_graph);
 }
 
 // ---- step sequences and fused replays with a time step per tick
-static te::DtSchedule dt_schedule(long n_ticks, const double* dt_host) {
-  if (n_ticks > 0 && !dt_host) throw std::invalid_argument("dt_host must not be NULL");
-  return n_ticks > 0 ? te::DtSchedule(dt_host, n_ticks) : te::DtSchedule();
-}
-
 int target_batch_step_sequence_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride,
                                   long ld, const unsigned char* has_meas_dev, long has_stride, long ring_ticks,
                                   const target_pose_stream_c* poses, const target_innov_stream_c* innov, double nis_max,
                                   const target_reacquire_c* reacq, int use_graph) {
-  return guarded("target_batch_step_sequence_dt", [&] {
-    const te::DtSchedule sched = dt_schedule(n_ticks, dt_host);
-    const te::InnovStream stream = reacquire_stream(innov, nis_max, reacq, false);
-    BatchLock lk(B(b));
-    if (ring_ticks < 0) throw std::invalid_argument("ring_ticks must not be negative");
-    B(b)->step_sequence(n_ticks, 0.0, meas_dev, tick_stride, ld, has_meas_dev, has_stride, use_graph, ring_ticks, pose_stream(poses), stream, sched);
-  });
+  return step_sequence("target_batch_step_sequence_dt", b, n_ticks, 0.0, dt_host, true, meas_dev, tick_stride, ld, has_meas_dev, has_stride,
+                       ring_ticks, false, poses, innov, nis_max, reacq, use_graph);
 }
 
 int target_batch_step_fused_dt(target_batch_c* b, long n_ticks, const double* dt_host, const void* meas_dev, long tick_stride, long ld,
@@ -659,22 +629,8 @@ int target_manager_step_sequence_all_dt(target_manager_c* m, long n_ticks, const
                                         const target_innov_stream_c* per_batch_innov, const double* per_batch_nis_max,
                                         const target_reacquire_c* per_batch_reacq, long n_batches,
                                         int query, const double* origin, double radius, int use_graph) {
-  return guarded("target_manager_step_sequence_all_dt", [&] {
-    const te::DtSchedule sched = dt_schedule(n_ticks, dt_host);
-    const size_t nb = (size_t)(n_batches > 0 ? n_batches : 0);
-    std::vector<te::Batch::SeqSpec> specs(nb);
-    std::vector<te::PoseStream> poses(nb);
-    std::vector<te::InnovStream> innov(nb);
-    for (size_t i = 0; i < nb; ++i)   // (every gate and policy is looked at before anything else is)
-      innov[i] = reacquire_stream(per_batch_innov ? &per_batch_innov[i] : nullptr, per_batch_nis_max ? per_batch_nis_max[i] : 0.0,
-                                  per_batch_reacq ? &per_batch_reacq[i] : nullptr, true);
-    for (size_t i = 0; i < nb; ++i) {
-      const target_batch_sequence_c& s = per_batch[i];
-      specs[i] = te::Batch::SeqSpec{s.meas_dev, s.tick_stride, s.ld, s.has_meas_dev, s.has_stride, s.delta_dev, s.pose_dev, s.ring_ticks};
-      poses[i] = pose_stream(per_batch_poses ? &per_batch_poses[i] : nullptr);
-    }
-    M(m)->stepSequenceAll(n_ticks, 0.0, specs.data(), poses.data(), n_batches, query != 0, origin, radius, use_graph, innov.data(), sched);
-  });
+  return step_sequence_all("target_manager_step_sequence_all_dt", m, n_ticks, 0.0, dt_host, true, true, per_batch, per_batch_poses, per_batch_innov,
+                           per_batch_nis_max, per_batch_reacq, n_batches, query, origin, radius, use_graph);
 }
 
 // ---- one launch for a temporally fused replay of a whole manager
