@@ -315,20 +315,30 @@ __device__ __forceinline__ void wave_lds_fence() {
 __device__ __forceinline__ float opaque_copy(float v) { float o; asm("v_mov_b32 %0, %1" : "=v"(o) : "v"(v)); return o; }
 __device__ __forceinline__ double opaque_copy(double v) { double o; asm("v_mov_b64 %0, %1" : "=v"(o) : "v"(v)); return o; }
 
-template <class C, typename T>
+// PART: which chunks a call requests, for the callers that order a wavefront's loads by when their words are consumed
+// (kf_step_sep.hpp, sep_meas_first): kRecAll = every chunk in record order; kRecState = the chunks and tail pieces that hold a word
+// of x or of the unwrap memory (the record ends with them; a chunk that mixes P and x words goes with x); kRecCov = the others.
+enum RecPart : int { kRecAll = 0, kRecState = 1, kRecCov = 2 };
+template <class C> constexpr bool rec_state_chunk(int c) { return (c + 1) * C::VW > C::X_OFF; }
+template <class C> constexpr bool rec_part_has(int part, int c) { return part == kRecAll || (part == kRecState) == rec_state_chunk<C>(c); }
+template <class C, typename T, int PART = kRecAll>
 __device__ __forceinline__ void load_record(const char* tb, int lane, T* rec) {
   using V = typename Vec16<T>::type;
+  static_assert(C::NC * C::VW >= C::X_OFF, "the tail pieces hold x / unwrap words only");
 #pragma unroll
   for (int c = 0; c < C::NC; ++c) {
+    if (!rec_part_has<C>(PART, c)) continue;
     V v = *reinterpret_cast<const V*>(tb + (long)c * C::LPT * 16 + (long)lane * 16);
     if constexpr (sizeof(T) == 8) { rec[c * 2] = v.x; rec[c * 2 + 1] = v.y; }
     else { rec[c * 4] = v.x; rec[c * 4 + 1] = v.y; rec[c * 4 + 2] = v.z; rec[c * 4 + 3] = v.w; }
   }
-  if constexpr (C::REM2) {
-    float2 v = *reinterpret_cast<const float2*>(tb + C::TAIL2_OFF + (long)lane * 8);
-    rec[C::NC * C::VW] = v.x; rec[C::NC * C::VW + 1] = v.y;
+  if constexpr (PART != kRecCov) {
+    if constexpr (C::REM2) {
+      float2 v = *reinterpret_cast<const float2*>(tb + C::TAIL2_OFF + (long)lane * 8);
+      rec[C::NC * C::VW] = v.x; rec[C::NC * C::VW + 1] = v.y;
+    }
+    if constexpr (C::REM1) rec[C::RW - 1] = *reinterpret_cast<const T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T));
   }
-  if constexpr (C::REM1) rec[C::RW - 1] = *reinterpret_cast<const T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T));
 }
 
 template <class C, typename T, bool OPAQUE = false, bool NT = false>

@@ -241,16 +241,35 @@ __device__ __forceinline__ void sep_gate_update_P(T (&P)[NB][NB], const T (&Kg)[
 
 // Uniform tiles (te_layout.hpp Cfg::UT): a record in two parts -- its linear-covariance chunks (LIN), which a uniform tile neither
 // loads nor stores, and everything else (the other chunks and the tail row).
-template <class C, typename T, bool LIN>
+// PART (kf_step.hpp RecPart): of that part, the chunks that hold x / unwrap words, or the others.
+template <class C, typename T, bool LIN, int PART = kRecAll>
 __device__ __forceinline__ void load_record_part(const char* tb, int lane, T* rec) {
   static_assert(sizeof(T) == 8 && C::REM2 == 0, "the shared-axes form is fp64");
 #pragma unroll
   for (int c = 0; c < C::NC; ++c) {
-    if (C::lin_chunk(c) != LIN) continue;
+    if (C::lin_chunk(c) != LIN || !rec_part_has<C>(PART, c)) continue;
     const double2 v = *reinterpret_cast<const double2*>(tb + (long)c * C::LPT * 16 + (long)lane * 16);
     rec[c * 2] = v.x; rec[c * 2 + 1] = v.y;
   }
-  if constexpr (C::REM1 && !LIN) rec[C::RW - 1] = *reinterpret_cast<const T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T));
+  if constexpr (C::REM1 && !LIN && PART != kRecCov) rec[C::RW - 1] = *reinterpret_cast<const T*>(tb + C::TAIL1_OFF + (long)lane * (long)sizeof(T));
+}
+
+// The order of a wavefront's loads in a launched dense single tick (sep_step_wave, MF): the tile flag, then the measurement words
+// and the has-byte, then the record's x / unwrap chunks, then its P chunks -- the order in which the tick consumes them.  The
+// measurement is the only operand that comes from HBM rather than a cache, and its conversion (quat_normalize, quat_to_rpy) touches
+// no record word: requested first, it is waited for alone and converted while the record is still on its way; the EKF group's
+// trigonometry, which reads x alone, follows while the P chunks are.  Off for the by-id kernels, the temporally fused loops, the
+// resident sessions and the per-class (kPerQR) ticks, which compile to what they were.  -DTE_MEAS_FIRST=0 builds the former order into every kernel, for A/B
+// records only (the library is built without it).
+// Angular-velocities fp32 on packed groups keeps the former order as well: with the new one every dense kernel of it, and the fp32
+// population kernels through their part of it, got 48 B of scratch (profiles/load_order_kernel_resources.txt).
+template <class M, typename T, int LAYOUT, unsigned VAR>
+constexpr bool sep_meas_first() {
+#ifdef TE_MEAS_FIRST
+  if (TE_MEAS_FIRST == 0) return false;
+#endif
+  if (M::TYPE == ANGULAR_VELOCITIES && sizeof(T) == 4 && LAYOUT == LAYOUT_SEPARABLE_PACKED) return false;
+  return !sv_has(VAR, kIndexed) && !sv_has(VAR, kFused) && !sv_has(VAR, kPerQR) && sv_live(VAR) == 0;
 }
 template <class C, typename T, bool NT>
 __device__ __forceinline__ void store_record_nonlin(char* tb, int lane, const T* rec) {
@@ -522,6 +541,17 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   T blk[BLK_EARLY ? C::LW : 1];
   if constexpr (!UT) { (void)uni_flag; (void)uni; (void)uni_out; }
   if constexpr (!BLK_EARLY) (void)blk;
+  // the launched dense single tick requests its measurement ahead of its record (sep_meas_first)
+  constexpr bool MF = sep_meas_first<M, T, LAYOUT, VAR>();
+  constexpr int MW = M::ANGULAR ? 7 : 3;
+  T ymeas0[MF ? MW : 1];
+  unsigned char hmask0 = 1;
+  if constexpr (MF) {
+#pragma unroll
+    for (int c = 0; c < MW; ++c) ymeas0[c] = 0;
+  } else {
+    (void)ymeas0; (void)hmask0;
+  }
   // LIVE: the parked part of the record (LivePark) lives in the wavefront's LDS for the whole session
   using Park = LivePark<C, M, T>;
   constexpr int NPARK = (LIVE != 0 && C::SEPPK) ? Park::SLOT.count : 0;
@@ -551,6 +581,59 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       if (Park::SLOT.v[C::RW - 1] >= 0) park_lds[Park::SLOT.v[C::RW - 1] * 64 + lane] = v;
       else mem[C::RW - 1] = v;
     }
+  } else if constexpr (MF) {
+    // (sep_meas_first) The flag first: loads return in order, so waiting for it waits for nothing else.  The block of a model that
+    // asks for it up front rides with the flag.
+    if constexpr (UT) {
+      if (a.tile_uni != nullptr) {
+        uni_flag = a.tile_uni[tile];
+        if constexpr (BLK_EARLY) {
+#pragma unroll
+          for (int k = 0; k < C::LW; ++k) blk[k] = a.tile_blk[tile * C::LW + k];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (UT) {
+#pragma unroll
+      for (int w = 0; w < C::RW; ++w) mem[w] = 0;
+    }
+    // One region for the measurement and the record: the compiler counts the loads behind the measurement words only along paths it
+    // can see, and two conditions side by side would make it wait for all of them.  Every measurement word of the tick, regardless of
+    // the mask, and the has-byte -- without a condition of its own, which would get a branch and a full wait: a batch without a mask
+    // reads a byte of its measurement instead (the line is on its way anyhow) and ignores it.
+    if (valid) {
+      if (a.meas != nullptr) {   // (wave-uniform)
+#pragma unroll
+        for (int c = 0; c < MW; ++c) ymeas0[c] = load_meas(&a.meas[(long)c * a.meas_ld + entry], a.nt_meas);
+        const unsigned char* hp = a.has_meas != nullptr ? &a.has_meas[entry] : reinterpret_cast<const unsigned char*>(&a.meas[entry]);
+        hmask0 = *hp;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // x and the unwrap memory, then the covariance chunks that move whatever the flag says
+      if constexpr (UT) load_record_part<C, T, false, kRecState>(tb, lt, mem);
+      else load_record<C, T, kRecState>(tb, lt, mem);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (UT) load_record_part<C, T, false, kRecCov>(tb, lt, mem);
+      else load_record<C, T, kRecCov>(tb, lt, mem);
+    } else if constexpr (!UT) {
+#pragma unroll
+      for (int w = 0; w < C::RW; ++w) mem[w] = 0;
+    }
+    // behind the flag, what depends on it: the tile's block in a uniform tile, the lanes' linear-covariance chunks in another
+    if constexpr (UT) {
+      uni = __builtin_amdgcn_readfirstlane(uni_flag) != 0;
+      if (uni) {   // (wave-uniform) every lane takes the tile's block
+#pragma unroll
+        for (int k = 0; k < C::LW; ++k) {
+          if constexpr (BLK_EARLY) mem[C::LIN.w[k]] = blk[k];
+          else mem[C::LIN.w[k]] = a.tile_blk[tile * C::LW + k];
+        }
+      } else if (valid) {
+        load_record_part<C, T, true>(tb, lt, mem);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);   // every request is out: what follows waits for the words it reads, in the order they arrive
   } else if constexpr (UT) {
     // The flag first (loads return in order: waiting for it waits for nothing else), then every part of the record that moves
     // whatever the flag says.  What depends on the flag follows behind the measurement loads: the lanes' linear-covariance chunks
@@ -761,12 +844,20 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   // Every measurement word of the tick is requested up front, right behind the record loads and regardless
   // of the mask: with a cache-resident state they are the only operands that come from HBM itself, and one
   // round trip for all of them replaces one per axis.
-  constexpr int MW = M::ANGULAR ? 7 : 3;
+  // (MF: they were, ahead of the record -- the one tick of the launch)
   T ymeas[MW];
 #pragma unroll
   for (int c = 0; c < MW; ++c) ymeas[c] = 0;
   unsigned char hmask = 1;
-  if (valid && meas_t != nullptr) {
+  if constexpr (MF) {
+#pragma unroll
+    for (int c = 0; c < MW; ++c) ymeas[c] = ymeas0[c];
+    // the byte is looked at here, behind every request, and not where it was asked for: left to itself the compiler forms
+    // `byte != 0` next to the load and waits for the measurement there, ahead of the record's requests
+    unsigned hraw = hmask0;
+    asm volatile("" : "+v"(hraw));
+    hmask = has_t != nullptr ? (unsigned char)hraw : (unsigned char)1;   // (without a mask the byte read was a stand-in)
+  } else if (valid && meas_t != nullptr) {
 #pragma unroll
     for (int c = 0; c < MW; ++c) {
       if constexpr (LIVE) ymeas[c] = load_meas_live(&meas_t[(long)c * a.meas_ld + entry]);   // (no per-load run-time choice here: it would get a branch and a wait per word)
@@ -779,7 +870,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
   }
   const bool has = valid && meas_t != nullptr && hmask != 0;
   if constexpr (!GATE) n_has += has ? 1 : 0;
-  if constexpr (UT) {
+  if constexpr (UT && !MF) {
     uni = __builtin_amdgcn_readfirstlane(uni_flag) != 0;
     if (uni) {   // (wave-uniform) every lane takes the tile's block
 #pragma unroll
@@ -828,6 +919,8 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
       quat_normalize(q);
       quat_to_rpy<T, (LIVE != 0 && sizeof(T) == 8)>(q, mrpy);
     }
+    // MF: the conversion has waited for the measurement alone; nothing that reads the record moves up into it
+    if constexpr (MF) __builtin_amdgcn_sched_barrier(0);
   }
 #define XW_(r) mem[C::X_OFF + (r)]
   // the GATE body's words: a register, or in a resident session (NPARK > 0) possibly a parked word.  Macros with the constant test
@@ -837,6 +930,41 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #define UWW_(s) mem[C::UW_OFF + (s)]
 #define XR_(r) RD(C::X_OFF + (r))
 #define XS_(r, v) WR(C::X_OFF + (r), (v))
+
+  // EKF group: the Jacobians of the transition at the previous posterior read the group's x words alone (roll, pitch and the body
+  // rates wy, wz, which no [p v] chain writes).  MF: formed here, behind the measurement's conversion and ahead of the first use of a
+  // P word, i.e. while the covariance chunks are still on their way; otherwise where the group's turn comes.  One text for both places.
+  // geometry.hpp:394-426 (Jacobians at the previous posterior), :359-374 (EarBaseInv)
+#define TE_EKF_JACOBIAN_(Jr, Jw, Ei, roll_, pitch_, wy_, wz_)                                      \
+  do {                                                                                              \
+    T s_r, c_r, s_p, c_p;                                                                           \
+    F::sincos(roll_, &s_r, &c_r);                                                                   \
+    F::sincos(pitch_, &s_p, &c_p);                                                                  \
+    const T wy = wy_, wz = wz_;                                                                     \
+    Jr[0][0] = (dt * (wy * c_r * s_p - wz * s_p * s_r)) / c_p + 1;                                  \
+    Jr[0][1] = (dt * (wz * c_r + wy * s_r)) / (c_p * c_p);                                          \
+    Jr[0][2] = 0;                                                                                   \
+    Jr[1][0] = -dt * (wz * c_r + wy * s_r);                                                         \
+    Jr[1][1] = 1;                                                                                   \
+    Jr[1][2] = 0;                                                                                   \
+    Jr[2][0] = (dt * (wy * c_r - wz * s_r)) / c_p;                                                  \
+    Jr[2][1] = (dt * s_p * (wz * c_r + wy * s_r)) / (c_p * c_p);                                    \
+    Jr[2][2] = 1;                                                                                   \
+    Jw[0][0] = dt; Jw[0][1] = (dt * s_p * s_r) / c_p; Jw[0][2] = (dt * c_r * s_p) / c_p;            \
+    Jw[1][0] = 0;  Jw[1][1] = dt * c_r;               Jw[1][2] = -dt * s_r;                         \
+    Jw[2][0] = 0;  Jw[2][1] = (dt * s_r) / c_p;       Jw[2][2] = (dt * c_r) / c_p;                  \
+    Ei[0][0] = 1; Ei[0][1] = (s_p * s_r) / c_p; Ei[0][2] = (c_r * s_p) / c_p;                       \
+    Ei[1][0] = 0; Ei[1][1] = c_r;               Ei[1][2] = -s_r;                                    \
+    Ei[2][0] = 0; Ei[2][1] = s_r / c_p;         Ei[2][2] = c_r / c_p;                               \
+  } while (0)
+  constexpr bool JAC_EARLY = MF && M::EKF;
+  T Jr0[JAC_EARLY ? 3 : 1][3], Jw0[JAC_EARLY ? 3 : 1][3], Ei0[JAC_EARLY ? 3 : 1][3];
+  if constexpr (JAC_EARLY) {
+    TE_EKF_JACOBIAN_(Jr0, Jw0, Ei0, XW_(3), XW_(4), XW_(10), XW_(11));
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    (void)Jr0; (void)Jw0; (void)Ei0;
+  }
 
   // ---- the [p v (a)] chains
   if constexpr (GATE) {
@@ -1022,27 +1150,15 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
 #pragma unroll
       for (int c = 0; c < 6; ++c) Pr[r][c] = mem[C::PWORD.v[GR[r]][GR[c]]];
     }
-    T s_r, c_r, s_p, c_p;
-    F::sincos(xr[0], &s_r, &c_r);
-    F::sincos(xr[1], &s_p, &c_p);
-    const T wy = xr[4], wz = xr[5];
-    // geometry.hpp:394-426 (Jacobians at the previous posterior), :359-374 (EarBaseInv)
     T Jr[3][3], Jw[3][3], Ei[3][3];
-    Jr[0][0] = (dt * (wy * c_r * s_p - wz * s_p * s_r)) / c_p + 1;
-    Jr[0][1] = (dt * (wz * c_r + wy * s_r)) / (c_p * c_p);
-    Jr[0][2] = 0;
-    Jr[1][0] = -dt * (wz * c_r + wy * s_r);
-    Jr[1][1] = 1;
-    Jr[1][2] = 0;
-    Jr[2][0] = (dt * (wy * c_r - wz * s_r)) / c_p;
-    Jr[2][1] = (dt * s_p * (wz * c_r + wy * s_r)) / (c_p * c_p);
-    Jr[2][2] = 1;
-    Jw[0][0] = dt; Jw[0][1] = (dt * s_p * s_r) / c_p; Jw[0][2] = (dt * c_r * s_p) / c_p;
-    Jw[1][0] = 0;  Jw[1][1] = dt * c_r;               Jw[1][2] = -dt * s_r;
-    Jw[2][0] = 0;  Jw[2][1] = (dt * s_r) / c_p;       Jw[2][2] = (dt * c_r) / c_p;
-    Ei[0][0] = 1; Ei[0][1] = (s_p * s_r) / c_p; Ei[0][2] = (c_r * s_p) / c_p;
-    Ei[1][0] = 0; Ei[1][1] = c_r;               Ei[1][2] = -s_r;
-    Ei[2][0] = 0; Ei[2][1] = s_r / c_p;         Ei[2][2] = c_r / c_p;
+    if constexpr (JAC_EARLY) {   // formed ahead of the chains, under the P loads
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { Jr[r][c] = Jr0[r][c]; Jw[r][c] = Jw0[r][c]; Ei[r][c] = Ei0[r][c]; }
+    } else {
+      TE_EKF_JACOBIAN_(Jr, Jw, Ei, xr[0], xr[1], xr[4], xr[5]);
+    }
     // x^- = f(x): rpy += dt * EarBaseInv(rpy) * omega  (angular_velocities.cpp:137)
     {
       T nr[3];
@@ -1642,6 +1758,7 @@ __device__ __forceinline__ void sep_step_wave(const StepArgs<T>& a, long wg, con
     }
   }
 #undef XW_
+#undef TE_EKF_JACOBIAN_
 #undef GR_
 #undef GATE_T_
 #undef PG_
