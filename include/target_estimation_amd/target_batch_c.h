@@ -762,6 +762,57 @@ int target_batch_intersect_sphere_converged_dev(target_batch_c* b, double t1, do
  * (MovingAvgFilter::getVariance, utils.hpp:241-251; O(filters_length) per target, NULL skips it) are optional. */
 int target_batch_gate_update_dev(target_batch_c* b, const double* delta_dev, const double* pose_dev, double pos_th, double ang_th,
                                  int filters_length, unsigned char* converged_dev, double* filtered_dev, double* variance_dev);
+/* ---- THE k SOONEST CROSSINGS: a stream-ordered selection over query results already on the device.
+ * What an interceptor asks of the delta [size] / pose [size][7] arrays a tick with the query leaves behind: which few targets
+ * cross the sphere soonest, when, and where.  Inputs: delta_dev [size] and, or not, pose_dev [size][7] (device doubles, whatever
+ * the batch precision) and ok_dev [size] (device bytes, e.g. the `converged` of target_batch_gate_update_dev; NULL: every slot).
+ * CANDIDATES.  Slot i is a candidate iff (ok_dev == NULL || ok_dev[i] != 0) && delta[i] >= delta_lo && delta[i] <= delta_hi.  A NaN
+ * delta is never one; the library's "no intersection" -1 is never one (delta_lo >= 0 is required); delta_hi may be +inf.
+ * ORDER.  Ascending by delta compared as doubles (-0.0 == 0.0), ties by ascending slot; across a manager by (delta, batch index
+ * in target_manager_get_batch order, slot).  Deterministic: the result is a function of the inputs alone.
+ * RESULT.  count = min(k, number of candidates) rows in that order: the slot (and the batch index at manager level), delta as the
+ * input's own bits and, with the pose pair, that slot's 7 pose words bit for bit.  Rows count .. k-1 are slot -1, batch -1,
+ * delta -1, pose [0 0 0 0 0 0 1] (id 0xffffffff in the host forms).  1 <= k <= TARGET_SOONEST_MAX_K.
+ * REFUSED (-1, target_manager_last_error, nothing enqueued, nothing written): k out of range; delta_lo < 0 or NaN; delta_hi <
+ * delta_lo or NaN; a NULL delta_dev; a NULL output other than the pose pair; pose_out without pose_dev, or the reverse.  An empty
+ * batch gives count 0 and k filler rows.  uniform_velocity and angular_velocities batches never intersect (all -1): nothing selected.
+ * SLOTS are positions in the dense order (target_batch_slot_ids) and stay valid until the next erase or init of that batch; so
+ * does a device result.  The host forms translate them to ids before they return.
+ * The selection reads NO filter record: it settles no uniform tiles, expands no shared-axes batch, drops no recorded sequence and
+ * does not run the queued one-target steps.  Three launches whatever size and k (a top-k per workgroup, then two merges;
+ * DESIGN.md 3.16), no atomics, plain stores; TE_SELECT_SOONEST_MAX_WGS (default 1024, read when the manager is created) caps the
+ * first launch's workgroups.
+ *   ..._select_soonest_dev   enqueued on the batch's stream behind whatever produced the inputs there; no host synchronisation
+ *                            and, after the device's first selection, no allocation: it may be captured in the caller's own
+ *                            hipGraph behind target_manager_step_sequence_all(..., n_ticks = 1, query = 1, ...).  Outputs in
+ *                            device memory: slot_out_dev int[k], delta_out_dev double[k], pose_out_dev double[k][7] or NULL,
+ *                            count_out_dev int[1].
+ *   ..._select_soonest       the same plus one small copy and a synchronisation; ids_out unsigned[k], slots_out int[k],
+ *                            delta_out double[k], pose_out double[k][7] or NULL are host arrays.  Returns count (or -1).
+ *   target_manager_select_soonest       every batch of the manager: per_batch [n_batches] is the array handed to
+ *                            target_manager_step_sequence_all, of which only delta_dev and pose_dev are read (a NULL delta_dev
+ *                            skips the batch); ok_dev_per_batch [n_batches] device pointers or NULL (an entry may be NULL).  Here
+ *                            pose_out decides about the gather: with it every selected batch needs its pose_dev, without it the
+ *                            pose_dev entries are not read.  All batches of a device are selected together by one set of
+ *                            launches (at most 16 per device), the devices' rows merged on the host.  Everything is checked
+ *                            before anything is enqueued on any device.  batch_out int[k].  Returns count (or -1).
+ *   target_manager_select_soonest_dev   the device form for a manager on ONE device, on the manager's stream; refused on a manager
+ *                            with several shards: there is no single device to leave the result on.
+ * Not served: the selection as a per-tick stream inside recorded sequences, fused calls and resident sessions; ids on the device. */
+#define TARGET_SOONEST_MAX_K 256
+int target_batch_select_soonest_dev(target_batch_c* b, const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev,
+                                    double delta_lo, double delta_hi, long k, int* slot_out_dev, double* delta_out_dev,
+                                    double* pose_out_dev, int* count_out_dev);
+long target_batch_select_soonest(target_batch_c* b, const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev,
+                                 double delta_lo, double delta_hi, long k, unsigned int* ids_out, int* slots_out, double* delta_out,
+                                 double* pose_out);
+long target_manager_select_soonest(target_manager_c* m, const target_batch_sequence_c* per_batch, long n_batches,
+                                   const unsigned char* const* ok_dev_per_batch, double delta_lo, double delta_hi, long k,
+                                   unsigned int* ids_out, int* batch_out, int* slots_out, double* delta_out, double* pose_out);
+int target_manager_select_soonest_dev(target_manager_c* m, const target_batch_sequence_c* per_batch, long n_batches,
+                                      const unsigned char* const* ok_dev_per_batch, double delta_lo, double delta_hi, long k,
+                                      int* batch_out_dev, int* slot_out_dev, double* delta_out_dev, double* pose_out_dev,
+                                      int* count_out_dev);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

@@ -108,6 +108,15 @@ SIGNATURES = {
     "target_batch_intersect_sphere_converged_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, c_double_p, C.c_double,
                                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "target_batch_gate_update_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the k soonest crossings: device pointers as void*, host arrays typed
+    "target_batch_select_soonest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_long,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_batch_select_soonest": (C.c_long, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_long,
+                                               c_uint_p, C.POINTER(C.c_int), c_double_p, c_double_p]),
+    "target_manager_select_soonest": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_long,
+                                                 c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]),
+    "target_manager_select_soonest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_void_p), C.c_double, C.c_double,
+                                                    C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),
     "target_comm_unique_id": (C.c_int, [C.c_char_p]),
     "target_comm_new": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int]),

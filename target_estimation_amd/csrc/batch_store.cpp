@@ -1781,6 +1781,26 @@ double Batch::time(long slot) {
   return te_clock_time(v, t_acc_);
 }
 
+// ---------------------------------------------------------------- the k soonest crossings (select_soonest.hpp)
+void Batch::select_soonest_dev(const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev, double lo, double hi, long k,
+                               int* slot_out_dev, double* delta_out_dev, double* pose_out_dev, int* count_out_dev) {
+  check_soonest_args(k, lo, hi, delta_dev != nullptr, pose_dev != nullptr, pose_out_dev != nullptr,
+                     slot_out_dev != nullptr && delta_out_dev != nullptr && count_out_dev != nullptr);
+  if (!soonest_) throw std::logic_error("target_estimation_amd: select_soonest: the batch belongs to no shard");
+  soonest_->ensure(soonest_max_wgs_);
+  const SoonestPart part{delta_dev, ok_dev, pose_dev, n_, 0};
+  launch_select_soonest(&part, 1, lo, hi, (int)k, SoonestOut{nullptr, slot_out_dev, delta_out_dev, pose_out_dev, count_out_dev}, *soonest_, stream_);
+}
+
+long Batch::select_soonest(const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev, double lo, double hi, long k,
+                           bool with_pose, SoonestRow* rows) {
+  check_soonest_args(k, lo, hi, delta_dev != nullptr, pose_dev != nullptr, with_pose, rows != nullptr);
+  if (!soonest_) throw std::logic_error("target_estimation_amd: select_soonest: the batch belongs to no shard");
+  soonest_->ensure(soonest_max_wgs_);
+  const SoonestPart part{delta_dev, ok_dev, pose_dev, n_, 0};
+  return select_soonest_to_host(&part, 1, lo, hi, (int)k, with_pose, *soonest_, stream_, rows);
+}
+
 }  // namespace te
 
 #ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library

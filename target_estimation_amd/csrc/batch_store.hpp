@@ -18,6 +18,7 @@
 #include "kf_ops.hpp"
 #include "reacquire_plan.hpp"
 #include "seq_graph_cache.hpp"
+#include "select_soonest.hpp"
 
 namespace te {
 
@@ -323,6 +324,18 @@ class Batch {
   void gate_update_dev(const double* delta_dev, const double* pose_dev, double pos_th, double ang_th, int window,
                        unsigned char* converged_dev, double* filt_dev, double* var_dev);
 
+  // THE k SOONEST CROSSINGS (select_soonest.hpp; target_batch_select_soonest[_dev]) among this batch's size() entries of a query's
+  // outputs already on the device: candidates are the slots with (ok == null || ok[i]) && lo <= delta[i] <= hi, ordered by
+  // (delta, slot); rows count .. k-1 get the filler.  Three launches on the batch's stream, no allocation once the shard's scratch
+  // is there, no host wait in the _dev form.  It reads NO record and does not go through records(): it settles no tiles, demotes
+  // nothing, drops no recording and does not flush the one-target queue.  Refusals (check_soonest_args) throw before anything is
+  // enqueued.  select_soonest: the same into the scratch's device result, one copy, a synchronisation; rows [k]; returns count.
+  void set_soonest_scratch(SoonestScratch* s, int max_wgs) { soonest_ = s; soonest_max_wgs_ = max_wgs; }
+  void select_soonest_dev(const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev, double lo, double hi, long k,
+                          int* slot_out_dev, double* delta_out_dev, double* pose_out_dev, int* count_out_dev);
+  long select_soonest(const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev, double lo, double hi, long k,
+                      bool with_pose, SoonestRow* rows);
+
   // Building blocks of the manager's all-batches sequence (TargetManager::stepSequenceAll): enqueue
   // n_ticks ticks -- each optionally followed by the own-time sphere query of every slot -- on `st`
   // without touching the batch clock, then account for them.
@@ -425,6 +438,8 @@ class Batch {
   void upload_slots(const int* slots, long n);
 
   int type_, dtype_, lanes_code_;
+  SoonestScratch* soonest_ = nullptr;   // the owning shard's (set_soonest_scratch)
+  int soonest_max_wgs_ = kSoonestDefaultMaxWgs;
   std::mutex* owner_lock_ = nullptr;
   const Ops* ops_;
   hipStream_t stream_;

@@ -188,6 +188,7 @@ int Shard::findOrCreateBatch(int type, const double* Q, const double* R, int lan
     }
   // (the batch itself decides from Q and R whether it starts in the shared-axes form, and from every P0 whether it stays in it)
   batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes, set_.uniform_tiles));
+  batches_.back()->set_soonest_scratch(&soonest_, set_.soonest_max_wgs);
   if (set_.keep_meas) batches_.back()->set_keep_measurement(true);
   if (type >= 0 && type < 4 && set_.gate[type].on()) batches_.back()->set_update_gate(set_.gate[type]);
   cls = 0;
@@ -1117,6 +1118,44 @@ void Shard::uploadRanks(const std::vector<unsigned>& sorted_all) {
     TE_HIP_CHECK(hipEventRecord(r.copied, st));
   }
 }
+
+// ---------------------------------------------------------------- the k soonest crossings (select_soonest.hpp)
+void Shard::checkSelectSoonest(const SoonestSpec* specs, long n_specs, bool with_pose) const {
+  const std::string pre = "target_estimation_amd: select_soonest: ";
+  if (n_specs != (long)batches_.size()) throw std::invalid_argument(pre + "one description per batch is needed");
+  long selected = 0;
+  for (long b = 0; b < n_specs; ++b) {
+    if (!specs[b].delta) continue;
+    ++selected;
+    if (with_pose && !specs[b].pose) throw std::invalid_argument(pre + "pose_out without pose_dev in batch " + std::to_string(b) + ": there is nothing to gather from");
+  }
+  check_soonest_parts(selected);
+}
+
+int Shard::soonestParts(const SoonestSpec* specs, long n_specs, int first_batch, SoonestPart* parts) const {
+  int n = 0;
+  for (long b = 0; b < n_specs; ++b)
+    if (specs[b].delta) parts[n++] = SoonestPart{specs[b].delta, specs[b].ok, specs[b].pose, batches_[(size_t)b]->size(), first_batch + (int)b};
+  return n;
+}
+
+void Shard::selectSoonestDev(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, const SoonestOut& out) {
+  checkSelectSoonest(specs, n_specs, out.pose != nullptr);
+  SoonestPart parts[kSoonestMaxParts];
+  const int n = soonestParts(specs, n_specs, first_batch, parts);
+  soonest_.ensure(set_.soonest_max_wgs);
+  launch_select_soonest(parts, n, lo, hi, k, out, soonest_, stream_);
+}
+
+void Shard::selectSoonestBegin(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, bool with_pose) {
+  checkSelectSoonest(specs, n_specs, with_pose);
+  SoonestPart parts[kSoonestMaxParts];
+  const int n = soonestParts(specs, n_specs, first_batch, parts);
+  soonest_.ensure(set_.soonest_max_wgs);
+  select_soonest_begin(parts, n, lo, hi, k, with_pose, soonest_, stream_);
+}
+
+long Shard::selectSoonestEnd(int k, bool with_pose, SoonestRow* rows) { return select_soonest_end(k, with_pose, soonest_, stream_, rows); }
 
 void Shard::launchRows(double* pose_out) {
   for (size_t b = 0; b < batches_.size(); ++b)

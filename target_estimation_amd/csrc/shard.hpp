@@ -51,6 +51,15 @@ struct ShardSettings {
   bool uniform_tiles = true;     // TE_UNIFORM_TILES / TargetManager::setUniformTiles: new shared-axes batches keep uniform tiles (Batch)
   bool shared_axes = true;       // TE_SHARED_AXES / TargetManager::setSharedAxes: new fp64 batches may use the shared-axes storage form (Batch)
   UpdateGate gate[4];            // TargetManager::setUpdateGate: the by-id update policy per model type; batches created later inherit it
+  int soonest_max_wgs = kSoonestDefaultMaxWgs;   // TE_SELECT_SOONEST_MAX_WGS: the cap on the selection's first-stage workgroups (select_soonest.hpp)
+};
+
+// one batch of a manager-level selection (TargetManager::selectSoonest): the query outputs of target_batch_sequence_c and the
+// batch's mask.  delta == null: the batch is skipped.
+struct SoonestSpec {
+  const double* delta = nullptr;
+  const double* pose = nullptr;
+  const unsigned char* ok = nullptr;
 };
 
 // one target's log rows, formatted per channel (TargetManager::log); batch: the shard's batch index as logCollect leaves it
@@ -148,6 +157,18 @@ class Shard {
   void stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched = DtSchedule{});
   // 1: such a call -- gated: every batch with NIS rows; scheduled: with a time-step schedule -- would be one launch now; 0: per batch
   int fusedAllServed(bool gated, bool scheduled) const;
+  // THE k SOONEST CROSSINGS of all this shard's batches together (select_soonest.hpp): specs [batches().size()], batch i's rows
+  // carry the index first_batch + i.  One set of three launches on the shard's stream, the first stage's grid split over the
+  // batches by cumulative workgroup counts.  It reads no record of any batch (Batch::select_soonest_dev says what follows).
+  //   checkSelectSoonest   what is refused about the specs (more batches than a launch takes, a pose gather from a batch without
+  //                        pose rows); throws, nothing enqueued.  The window and k are the manager's to check.
+  //   selectSoonestDev     into device memory, no host wait
+  //   selectSoonestBegin   into the scratch's device result and, by one copy, its pinned mirror; no host wait
+  //   selectSoonestEnd     waits for that copy: rows [k] on the host; returns count
+  void checkSelectSoonest(const SoonestSpec* specs, long n_specs, bool with_pose) const;
+  void selectSoonestDev(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, const SoonestOut& out);
+  void selectSoonestBegin(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, bool with_pose);
+  long selectSoonestEnd(int k, bool with_pose, SoonestRow* rows);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -202,6 +223,10 @@ class Shard {
   FusedAllRoute fusedAllRoute(const Batch::SeqSpec* specs, bool scheduled, long n_ticks) const;
   DtTableRing dttab_;   // the time-step table of stepFusedAll's one launch: one table serves all parts (dt_table_ring.hpp)
   bool seq_flip_ = false;   // zig-zag across the whole tick: the next eager all-batches tick runs last batch first, tiles backwards
+  // the scratch of the selections of this shard and of its batches (Batch::set_soonest_scratch): allocated at the first selection,
+  // released through device_free
+  SoonestScratch soonest_;
+  int soonestParts(const SoonestSpec* specs, long n_specs, int first_batch, SoonestPart* parts) const;
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call
   struct DevIds {

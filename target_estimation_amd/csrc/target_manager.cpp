@@ -32,6 +32,9 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) {
   settings_.shared_axes = shared;
   static const bool uniform = [] { const char* e = std::getenv("TE_UNIFORM_TILES"); return !(e && e[0] == '0'); }();
   settings_.uniform_tiles = uniform;
+  // TE_SELECT_SOONEST_MAX_WGS=<n>: the cap on the first-stage workgroups of select_soonest (read per manager, so that one process
+  // can hold managers with different grids: tests reach the several-rounds paths at a few thousand entries)
+  settings_.soonest_max_wgs = soonest_max_wgs_from(std::getenv("TE_SELECT_SOONEST_MAX_WGS"));
   const char* ld = std::getenv("TARGET_ESTIMATION_LOG_DIR");
   if (ld && ld[0]) { log_dir_ = ld; settings_.keep_meas = true; }   // batches created later inherit the measured-pose rows
   int count = 0;
@@ -728,6 +731,47 @@ int TargetManager::fusedAllServed(bool gated, bool scheduled) {
     any = true;
   }
   return any ? 1 : 0;
+}
+
+long TargetManager::selectSoonest(const SoonestSpec* specs, long n_specs, double lo, double hi, long k, bool with_pose, SoonestRow* rows,
+                                  unsigned* ids) {
+  lock_guard<mutex> lg(target_lock_);
+  check_soonest_args(k, lo, hi, true, with_pose, with_pose, rows != nullptr && ids != nullptr);
+  if (n_specs != (long)numBatches() || (n_specs > 0 && !specs)) throw std::invalid_argument("target_estimation_amd: select_soonest: one description per batch is needed");
+  long off = 0;
+  for (auto& s : shards_) {   // every shard's refusals before any shard enqueues
+    const long nk = (long)s->batches().size();
+    s->checkSelectSoonest(specs + off, nk, with_pose);
+    off += nk;
+  }
+  off = 0;
+  for (size_t s = 0; s < shards_.size(); ++s) {
+    const long nk = (long)shards_[s]->batches().size();
+    DeviceGuard g(guardDev(s));
+    shards_[s]->selectSoonestBegin(specs + off, nk, (int)off, lo, hi, (int)k, with_pose);
+    off += nk;
+  }
+  std::vector<std::vector<SoonestRow>> per(shards_.size());
+  for (size_t s = 0; s < shards_.size(); ++s) {
+    DeviceGuard g(guardDev(s));
+    per[s].resize((size_t)k);
+    per[s].resize((size_t)shards_[s]->selectSoonestEnd((int)k, with_pose, per[s].data()));
+  }
+  const long count = merge_soonest(per, k, rows);
+  for (long i = 0; i < k; ++i) ids[i] = i < count ? batch(rows[i].batch)->slot_id(rows[i].slot) : ~0u;
+  return count;
+}
+
+void TargetManager::selectSoonestDev(const SoonestSpec* specs, long n_specs, double lo, double hi, long k, const SoonestOut& out) {
+  lock_guard<mutex> lg(target_lock_);
+  if (several())
+    throw std::runtime_error("target_estimation_amd: select_soonest_dev: the manager spans " + std::to_string(shards_.size()) +
+                             " shards, so there is no single device to leave the result on (use select_soonest, which merges on the host)");
+  check_soonest_args(k, lo, hi, true, out.pose != nullptr, out.pose != nullptr,
+                     out.batch != nullptr && out.slot != nullptr && out.delta != nullptr && out.count != nullptr);
+  if (n_specs != (long)numBatches() || (n_specs > 0 && !specs)) throw std::invalid_argument("target_estimation_amd: select_soonest: one description per batch is needed");
+  DeviceGuard g(guardDev(0));
+  shards_[0]->selectSoonestDev(specs, n_specs, 0, lo, hi, (int)k, out);
 }
 
 void TargetManager::synchronize() {

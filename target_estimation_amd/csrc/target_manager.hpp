@@ -192,6 +192,16 @@ class TargetManager {
   void stepFusedAll(long n_ticks, double dt, const Batch::SeqSpec* specs, long n_specs, const DtSchedule& sched = DtSchedule{});
   int fusedAllServed(bool gated, bool scheduled);   // 1: one launch per shard that holds targets; 0: per batch
 
+  // THE k SOONEST CROSSINGS of the whole manager (select_soonest.hpp; target_manager_select_soonest[_dev]): specs [numBatches()]
+  // in batch order, shard-major (a spec without delta skips its batch).  Candidates: (ok == null || ok[i]) && lo <= delta[i] <= hi;
+  // order: (delta, batch index, slot).  Per shard all its batches are selected together by one set of launches on the shard's
+  // stream; the shards' <= k rows each are merged on the host (merge_soonest).  Everything is checked before anything is enqueued
+  // on any shard.  No record is read: no tile is settled, no batch demoted, no recording dropped.  rows [k]; ids [k] from the
+  // batches' slot -> id tables ((unsigned)-1 in a filler row).  Returns count.
+  long selectSoonest(const SoonestSpec* specs, long n_specs, double lo, double hi, long k, bool with_pose, SoonestRow* rows, unsigned* ids);
+  // the same into device memory, without a host wait: a manager on one device only (several have no single device to write to)
+  void selectSoonestDev(const SoonestSpec* specs, long n_specs, double lo, double hi, long k, const SoonestOut& out);
+
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and
   // their per-GPU share (62 500 + 62 500 targets) is launch-bound.  specs as for stepSequenceAll (ring_ticks > 0 required).

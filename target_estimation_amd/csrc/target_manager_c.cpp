@@ -349,6 +349,73 @@ int target_batch_gate_update_dev(target_batch_c* b, const double* delta_dev, con
   });
 }
 
+// ---- the k soonest crossings (select_soonest.hpp).  The host forms write their arrays only after the call has succeeded.
+int target_batch_select_soonest_dev(target_batch_c* b, const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev,
+                                    double delta_lo, double delta_hi, long k, int* slot_out_dev, double* delta_out_dev,
+                                    double* pose_out_dev, int* count_out_dev) {
+  return guarded_value<int>("target_batch_select_soonest_dev", -1, [&]() -> int { BatchLock lk(B(b));
+    B(b)->select_soonest_dev(delta_dev, pose_dev, ok_dev, delta_lo, delta_hi, k, slot_out_dev, delta_out_dev, pose_out_dev, count_out_dev);
+    return 0;
+  });
+}
+
+long target_batch_select_soonest(target_batch_c* b, const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev,
+                                 double delta_lo, double delta_hi, long k, unsigned int* ids_out, int* slots_out, double* delta_out,
+                                 double* pose_out) {
+  return guarded_value<long>("target_batch_select_soonest", -1L, [&]() -> long { BatchLock lk(B(b));
+    te::check_soonest_args(k, delta_lo, delta_hi, delta_dev != nullptr, pose_dev != nullptr, pose_out != nullptr,
+                           ids_out != nullptr && slots_out != nullptr && delta_out != nullptr);
+    std::vector<te::SoonestRow> rows((size_t)k);
+    const long count = B(b)->select_soonest(delta_dev, pose_dev, ok_dev, delta_lo, delta_hi, k, pose_out != nullptr, rows.data());
+    for (long i = 0; i < k; ++i) {
+      const te::SoonestRow& r = rows[(size_t)i];
+      ids_out[i] = i < count ? B(b)->slot_id(r.slot) : ~0u;
+      slots_out[i] = r.slot; delta_out[i] = r.delta;
+      if (pose_out) for (int c = 0; c < 7; ++c) pose_out[i * 7 + c] = r.pose[c];
+    }
+    return count;
+  });
+}
+
+static std::vector<te::SoonestSpec> soonest_specs(const target_batch_sequence_c* per_batch, long n_batches, const unsigned char* const* ok) {
+  if (n_batches < 0 || (n_batches > 0 && !per_batch)) throw std::invalid_argument("target_estimation_amd: select_soonest: one description per batch is needed");
+  std::vector<te::SoonestSpec> specs((size_t)n_batches);
+  for (long i = 0; i < n_batches; ++i) specs[(size_t)i] = te::SoonestSpec{per_batch[i].delta_dev, per_batch[i].pose_dev, ok ? ok[i] : nullptr};
+  return specs;
+}
+
+long target_manager_select_soonest(target_manager_c* m, const target_batch_sequence_c* per_batch, long n_batches,
+                                   const unsigned char* const* ok_dev_per_batch, double delta_lo, double delta_hi, long k,
+                                   unsigned int* ids_out, int* batch_out, int* slots_out, double* delta_out, double* pose_out) {
+  return guarded_value<long>("target_manager_select_soonest", -1L, [&]() -> long {
+    TargetManager* mgr = M(m);
+    te::check_soonest_args(k, delta_lo, delta_hi, true, pose_out != nullptr, pose_out != nullptr,
+                           ids_out != nullptr && batch_out != nullptr && slots_out != nullptr && delta_out != nullptr);
+    const std::vector<te::SoonestSpec> specs = soonest_specs(per_batch, n_batches, ok_dev_per_batch);
+    std::vector<te::SoonestRow> rows((size_t)k);
+    std::vector<unsigned> ids((size_t)k);
+    const long count = mgr->selectSoonest(specs.data(), n_batches, delta_lo, delta_hi, k, pose_out != nullptr, rows.data(), ids.data());
+    for (long i = 0; i < k; ++i) {
+      const te::SoonestRow& r = rows[(size_t)i];
+      ids_out[i] = ids[(size_t)i]; batch_out[i] = r.batch; slots_out[i] = r.slot; delta_out[i] = r.delta;
+      if (pose_out) for (int c = 0; c < 7; ++c) pose_out[i * 7 + c] = r.pose[c];
+    }
+    return count;
+  });
+}
+
+int target_manager_select_soonest_dev(target_manager_c* m, const target_batch_sequence_c* per_batch, long n_batches,
+                                      const unsigned char* const* ok_dev_per_batch, double delta_lo, double delta_hi, long k,
+                                      int* batch_out_dev, int* slot_out_dev, double* delta_out_dev, double* pose_out_dev,
+                                      int* count_out_dev) {
+  return guarded_value<int>("target_manager_select_soonest_dev", -1, [&]() -> int {
+    TargetManager* mgr = M(m);
+    const std::vector<te::SoonestSpec> specs = soonest_specs(per_batch, n_batches, ok_dev_per_batch);
+    mgr->selectSoonestDev(specs.data(), n_batches, delta_lo, delta_hi, k, te::SoonestOut{batch_out_dev, slot_out_dev, delta_out_dev, pose_out_dev, count_out_dev});
+    return 0;
+  });
+}
+
 int target_batch_intersect_sphere_dev(target_batch_c* b, double t1, const double* origin, double radius,
                                       double* delta_dev, double* pose_dev) {
   return guarded("target_batch_intersect_sphere_dev", [&] { BatchLock lk(B(b)); B(b)->intersect_dev(t1, origin, radius, delta_dev, pose_dev); });

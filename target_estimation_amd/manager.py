@@ -420,6 +420,38 @@ class Batch:
                                                        None if var is None else var.data_ptr()), "target_batch_gate_update_dev")
         return conv, filt, var
 
+    def select_soonest(self, delta, pose=None, ok=None, k=8, window=(0.0, float("inf")), device=False, out=None):
+        """The k soonest sphere crossings among this batch's query results on the device (target_batch_select_soonest[_dev]):
+        delta [size] and pose [size, 7] (or None: no gather) CUDA doubles, ok [size] a CUDA uint8 / bool mask or None.
+        Candidates are the slots with ok != 0 and window[0] <= delta <= window[1], ordered by (delta, slot).
+        device=False -> (count, ids [k] uint32, slots [k] int32, delta [k], pose [k, 7] or None) as NumPy arrays, after one small
+        copy and a synchronisation; rows count .. k-1 are id 0xffffffff, slot -1, delta -1, pose [0 0 0 0 0 0 1].
+        device=True -> (count [1] int32, slots [k] int32, delta [k], pose [k, 7] or None) CUDA tensors, enqueued on the batch's
+        stream without a host wait.  Slots (and so a device result) are valid until the next erase or init of the batch.
+        out: the output arrays to use, in the order returned (without count for device=False; None entries are passed as NULL)."""
+        import torch
+        k = int(k)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if device:
+            if out is None:
+                kk = max(k, 1)
+                out = (torch.empty(1, dtype=torch.int32, device="cuda"), torch.empty(kk, dtype=torch.int32, device="cuda"),
+                       torch.empty(kk, dtype=torch.float64, device="cuda"),
+                       None if pose is None else torch.empty((kk, 7), dtype=torch.float64, device="cuda"))
+            cnt, so, do, po = out
+            _check(self._lib.target_batch_select_soonest_dev(self._h, ptr(delta), ptr(pose), ptr(ok), float(window[0]), float(window[1]), k,
+                                                             ptr(so), ptr(do), ptr(po), ptr(cnt)), "target_batch_select_soonest_dev")
+            return cnt, so, do, po
+        if out is None:
+            kk = max(k, 1)
+            out = (np.empty(kk, dtype=np.uint32), np.empty(kk, dtype=np.int32), np.empty(kk), None if pose is None else np.empty((kk, 7)))
+        ids, so, do, po = out
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        count = _check(self._lib.target_batch_select_soonest(self._h, ptr(delta), ptr(pose), ptr(ok), float(window[0]), float(window[1]), k,
+                                                             None if ids is None else ids.ctypes.data_as(capi.c_uint_p), ip(so), _dp(do), _dp(po)),
+                       "target_batch_select_soonest")
+        return count, ids, so, do, po
+
     def pack_meas(self, meas_aos, out=None):
         """CUDA double [n,7] (the reference's row layout) -> SoA [7,n] in the batch precision."""
         import torch
@@ -980,6 +1012,49 @@ class TargetManager:
         _check(self._lib.target_manager_step_sequence_all(
             self._h, ticks, float(dt), C.cast(specs, C.c_void_p), nb, 0 if query is None else 1,
             None if origin is None else _dp(origin), float(radius), int(use_graph)), "target_manager_step_sequence_all")
+
+    def select_soonest(self, per_batch, ok=None, k=8, window=(0.0, float("inf")), want_pose=True, device=False, out=None):
+        """The k soonest sphere crossings of the whole manager (target_manager_select_soonest[_dev]).  per_batch: the per-batch
+        description step_sequence_all's query= uses -- (origin, radius, deltas, poses), of which only the last two are read -- or
+        (deltas, poses): deltas[i] [size_i] and poses[i] [size_i, 7] (poses or an entry None) CUDA doubles per batch in batches()
+        order; a None delta skips the batch.  ok: one CUDA uint8 / bool mask (or None) per batch, or None.  Order: (delta, batch
+        index, slot).  want_pose=False leaves the poses alone.
+        device=False -> (count, ids [k], batch [k], slots [k], delta [k], pose [k, 7] or None) NumPy arrays, the shards' rows merged
+        on the host.  device=True (a manager on one device only) -> (count [1], batch [k], slots [k], delta [k], pose or None) CUDA
+        tensors, no host wait.  out: the output arrays to use, in the order returned (without count for device=False)."""
+        import torch
+        deltas, poses = per_batch[-2], per_batch[-1]
+        nb = len(deltas)
+        k = int(k)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        specs = (capi.BatchSequence * max(nb, 1))()
+        for i in range(nb):
+            specs[i].delta_dev = ptr(deltas[i])
+            specs[i].pose_dev = None if poses is None else ptr(poses[i])
+        oks = None
+        if ok is not None:
+            assert len(ok) == nb, "one mask (or None) per batch"
+            oks = (C.c_void_p * max(nb, 1))(*[ptr(o) for o in ok])
+        with_pose = want_pose and poses is not None and any(p is not None for p in poses)
+        kk = max(k, 1)
+        if device:
+            if out is None:
+                out = (torch.empty(1, dtype=torch.int32, device="cuda"), torch.empty(kk, dtype=torch.int32, device="cuda"),
+                       torch.empty(kk, dtype=torch.int32, device="cuda"), torch.empty(kk, dtype=torch.float64, device="cuda"),
+                       torch.empty((kk, 7), dtype=torch.float64, device="cuda") if with_pose else None)
+            cnt, bo, so, do, po = out
+            _check(self._lib.target_manager_select_soonest_dev(self._h, C.cast(specs, C.c_void_p), nb, oks, float(window[0]), float(window[1]), k,
+                                                               ptr(bo), ptr(so), ptr(do), ptr(po), ptr(cnt)), "target_manager_select_soonest_dev")
+            return cnt, bo, so, do, po
+        if out is None:
+            out = (np.empty(kk, dtype=np.uint32), np.empty(kk, dtype=np.int32), np.empty(kk, dtype=np.int32), np.empty(kk),
+                   np.empty((kk, 7)) if with_pose else None)
+        ids, bo, so, do, po = out
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        count = _check(self._lib.target_manager_select_soonest(self._h, C.cast(specs, C.c_void_p), nb, oks, float(window[0]), float(window[1]), k,
+                                                               None if ids is None else ids.ctypes.data_as(capi.c_uint_p), ip(bo), ip(so),
+                                                               _dp(do), _dp(po)), "target_manager_select_soonest")
+        return count, ids, bo, so, do, po
 
     def population_tick(self):
         """True if step_sequence_all steps every batch with ONE launch per tick (target_manager_population_tick)."""
