@@ -813,6 +813,48 @@ int target_manager_select_soonest_dev(target_manager_c* m, const target_batch_se
                                       const unsigned char* const* ok_dev_per_batch, double delta_lo, double delta_hi, long k,
                                       int* batch_out_dev, int* slot_out_dev, double* delta_out_dev, double* pose_out_dev,
                                       int* count_out_dev);
+/* ---- POSITION COVARIANCE AND TIME SPREAD AT A SPHERE CROSSING: how well a crossing is known, from the filter's own covariance.
+ * For row i with delta[i] >= 0 (a query's time to the crossing) and its slot's state x, covariance P and class matrix Q:
+ *   tau   = delta[i] + dq, dq the query's own offset: 0 for t1 = NaN (each target's own time), else t1 - the target's time
+ *   Sigma = (A(tau) P A(tau)^T + Q)[0:3, 0:3], the position block a predict-only update(dt = tau) of the reference would leave (Q
+ *           added once, as every predict does), in the batch's precision and in the predict's statement order of the step kernels.
+ *           Only the position chains {r, r + K, (r + 2K)}, r = 0..2, enter; in the axis-separable layouts the off-diagonal entries
+ *           are exact zeros, and a shared-axes batch has three equal diagonal entries.
+ *   cov_out [n][6] = the upper triangle of Sigma: xx xy xz yy yz zz.
+ * With origin (host double[3]; radius > 0 is checked, the query that made delta used it), in double: p_c, v_c = position and linear
+ * velocity at tau as the query extrapolates them, n = (p_c - o) / |p_c - o|,
+ *   sigma_out [n][2] = { sigma_r = sqrt(n^T Sigma n), sigma_t = sigma_r / |n . v_c| } -- the spread of the position along the
+ *           sphere's normal, and to first order of the crossing time; sigma_t = +inf when n . v_c == 0.  Nothing is clamped: a
+ *           negative form or |p_c - o| == 0 gives NaN.
+ *   ok_out [n]       = delta >= 0 && sigma_r <= sigma_r_max && sigma_t <= sigma_t_max (<=: a NaN rejects; a bound may be +inf) --
+ *           a mask for target_batch_select_soonest_dev.
+ * NON-CANDIDATES.  A row whose delta is negative or NaN, or whose slot is -1 (or outside the batch), gets cov 0, sigma {-1, -1},
+ * ok 0, and costs no record word: its delta is all that is read.
+ * ROWS.  slots_dev == NULL: dense, row i is slot i, n <= size.  Else slots_dev int[n] (device), n <= TARGET_CROSSING_COV_MAX_ROWS,
+ * delta_dev [n] by row -- the slot_out_dev / delta_out_dev of a selection.  At manager level batch_dev int[n] runs alongside (the
+ * batch_out_dev of target_manager_select_soonest_dev): every batch's launch serves its rows, every row is written exactly once.
+ * REFUSED (-1, target_manager_last_error, nothing enqueued, nothing written): a NULL delta or cov_out; sigma_out or ok_out without
+ * origin; radius <= 0 or NaN with origin; a NaN threshold; n < 0 or beyond the form's limit; the manager's device form on a
+ * manager with several shards.
+ * The call reads the records as they are stored (a uniform tile's words from the tile's block): it settles no tile, expands no
+ * shared-axes batch, drops no recorded sequence and leaves rejection runs and clocks alone; the queued one-target steps run first.
+ *   ..._crossing_cov_dev     one launch per batch on its stream, no allocation, no host synchronisation: it may be captured in
+ *                            the caller's hipGraph behind target_manager_step_sequence_all(..., n_ticks = 1, query = 1, ...) and a
+ *                            selection.  All arrays but origin in device memory.
+ *   target_manager_crossing_cov_batch   by id with host arrays (delta_host [n], e.g. of target_manager_get_intersection_batch), any
+ *                            number of ids over any number of shards; an unknown id gets the non-candidate row.  Returns the
+ *                            number of ids found (or -1).
+ * Not served: the Eigen facade; a per-tick stream of these rows inside recorded sequences, fused calls and resident sessions. */
+#define TARGET_CROSSING_COV_MAX_ROWS 8192
+int target_batch_crossing_cov_dev(target_batch_c* b, double t1, const double* origin, double radius, const double* delta_dev,
+                                  const int* slots_dev, long n, double sigma_r_max, double sigma_t_max, double* cov_out_dev,
+                                  double* sigma_out_dev, unsigned char* ok_out_dev);
+int target_manager_crossing_cov_dev(target_manager_c* m, double t1, const double* origin, double radius, const int* batch_dev,
+                                    const int* slots_dev, const double* delta_dev, long n, double sigma_r_max, double sigma_t_max,
+                                    double* cov_out_dev, double* sigma_out_dev, unsigned char* ok_out_dev);
+long target_manager_crossing_cov_batch(target_manager_c* m, const unsigned int* ids, long n, double t1, const double* origin, double radius,
+                                       const double* delta_host, double sigma_r_max, double sigma_t_max, double* cov_out,
+                                       double* sigma_out, unsigned char* ok_out);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

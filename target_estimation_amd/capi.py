@@ -117,6 +117,13 @@ SIGNATURES = {
                                                  c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]),
     "target_manager_select_soonest_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_void_p), C.c_double, C.c_double,
                                                     C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # covariance and time spread at a crossing: origin a host double[3], device pointers as void*, host arrays typed
+    "target_batch_crossing_cov_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p, C.c_long, C.c_double,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_manager_crossing_cov_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
+                                                  C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_manager_crossing_cov_batch": (C.c_long, [C.c_void_p, c_uint_p, C.c_long, C.c_double, c_double_p, C.c_double, c_double_p, C.c_double,
+                                                     C.c_double, c_double_p, c_double_p, c_ubyte_p]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),
     "target_comm_unique_id": (C.c_int, [C.c_char_p]),
     "target_comm_new": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int]),

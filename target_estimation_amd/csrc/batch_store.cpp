@@ -1801,6 +1801,53 @@ long Batch::select_soonest(const double* delta_dev, const double* pose_dev, cons
   return select_soonest_to_host(&part, 1, lo, hi, (int)k, with_pose, *soonest_, stream_, rows);
 }
 
+// ---------------------------------------------------------------- covariance and time spread at a crossing (crossing_cov.hpp)
+void Batch::crossing_cov_dev(double t1, const double* origin, double radius, const double* delta_dev, const int* slots_dev, long n,
+                             double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev, unsigned char* ok_dev,
+                             const int* batch_dev, int batch_index) {
+  check_crossing_cov_args(delta_dev != nullptr, origin != nullptr, radius, cov_dev != nullptr, sigma_dev != nullptr, ok_dev != nullptr,
+                          sigma_r_max, sigma_t_max, slots_dev != nullptr, n, n_);
+  const CrossingCovLaunch launch = crossing_cov_launcher(type_, dtype_, ops_->L.g, ops_->L.layout, shared_axes());
+  if (!launch) throw std::logic_error("target_estimation_amd: crossing_cov: no kernel for this (model, precision, layout)");   // (never a fall-back)
+  flush();
+  if (n == 0) return;
+  CrossingCovArgs a;
+  a.rec = records_as_stored(); a.qr = d_qr_; a.cls = n_classes_ > 1 ? d_cls_ : nullptr;
+  // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
+  a.tile_blk = d_tile_uni_ ? d_tile_blk_ : nullptr; a.tile_uni = d_tile_uni_;
+  a.size = n_; a.n = n; a.slots = slots_dev; a.batch = batch_dev; a.batch_index = batch_index; a.delta = delta_dev;
+  a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
+  a.have_origin = origin ? 1 : 0;
+  for (int c = 0; c < 3; ++c) a.origin[c] = origin ? origin[c] : 0.0;
+  a.sigma_r_max = sigma_r_max; a.sigma_t_max = sigma_t_max;
+  a.cov = cov_dev; a.sigma = sigma_dev; a.ok = ok_dev;
+  launch(a, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+}
+
+void Batch::crossing_cov(const int* slots, long n, double t1, const double* origin, double radius, const double* delta, double sigma_r_max,
+                         double sigma_t_max, double* cov, double* sigma, unsigned char* ok) {
+  check_crossing_cov_args(delta != nullptr, origin != nullptr, radius, cov != nullptr, sigma != nullptr, ok != nullptr, sigma_r_max,
+                          sigma_t_max, false, 0, 0);
+  if (n <= 0) return;
+  if (!slots) throw std::invalid_argument("target_estimation_amd: crossing_cov: a slot list is required");
+  for (long done = 0; done < n; done += kCrossingCovMaxRows) {   // a list of any length, kCrossingCovMaxRows rows per launch
+    const long k = std::min<long>(kCrossingCovMaxRows, n - done);
+    flush();
+    stage_reserve(k);
+    upload_slots(slots + done, k);
+    double* d_delta = d_aos_;            // [k] | cov [k][6] | sigma [k][2] of the staging's 19 doubles per entry
+    double* d_cov = d_aos_ + k;
+    double* d_sigma = d_aos_ + 7 * k;
+    TE_HIP_CHECK(hipMemcpyAsync(d_delta, delta + done, sizeof(double) * k, hipMemcpyHostToDevice, stream_));
+    crossing_cov_dev(t1, origin, radius, d_delta, d_idx_, k, sigma_r_max, sigma_t_max, d_cov, sigma ? d_sigma : nullptr, ok ? d_mask_ : nullptr);
+    TE_HIP_CHECK(hipMemcpyAsync(cov + done * 6, d_cov, sizeof(double) * 6 * k, hipMemcpyDeviceToHost, stream_));
+    if (sigma) TE_HIP_CHECK(hipMemcpyAsync(sigma + done * 2, d_sigma, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, stream_));
+    if (ok) TE_HIP_CHECK(hipMemcpyAsync(ok + done, d_mask_, (size_t)k, hipMemcpyDeviceToHost, stream_));
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+}
+
 }  // namespace te
 
 #ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library

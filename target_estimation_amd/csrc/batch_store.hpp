@@ -19,6 +19,7 @@
 #include "reacquire_plan.hpp"
 #include "seq_graph_cache.hpp"
 #include "select_soonest.hpp"
+#include "crossing_cov.hpp"
 
 namespace te {
 
@@ -335,6 +336,23 @@ class Batch {
                           int* slot_out_dev, double* delta_out_dev, double* pose_out_dev, int* count_out_dev);
   long select_soonest(const double* delta_dev, const double* pose_dev, const unsigned char* ok_dev, double lo, double hi, long k,
                       bool with_pose, SoonestRow* rows);
+
+  // POSITION COVARIANCE AND TIME SPREAD AT A SPHERE CROSSING (crossing_cov.hpp; target_batch_crossing_cov_dev): for row i with a
+  // candidate delta[i] (>= 0), Sigma = (A(tau) P A(tau)^T + Q)[0:3, 0:3] of its slot at tau = delta[i] + (t1 - its time; 0 for
+  // t1 = NaN), as cov [n][6] (xx xy xz yy yz zz); with origin also sigma [n][2] = {sigma_r, sigma_t} and ok [n] =
+  // sigma_r <= sigma_r_max && sigma_t <= sigma_t_max.  slots_dev == null: dense, row i is slot i, n <= size(); else a device list
+  // of n <= kCrossingCovMaxRows slots (-1: none).  batch_dev (manager level): the launch serves only the rows whose entry is
+  // batch_index.  Every other row of the call gets the filler (crossing_cov_fill) and costs no record word.  One launch on the
+  // batch's stream, no allocation, no host wait: it may be captured.  The records are read as stored, a flagged uniform tile's
+  // words from its block: no tile is settled, no shared-axes batch demoted, no recording dropped; rejection runs and the clock
+  // are not touched.  The queued one-target steps run first (flush), as ahead of every reader.  Refusals
+  // (check_crossing_cov_args) throw before anything is enqueued.
+  void crossing_cov_dev(double t1, const double* origin, double radius, const double* delta_dev, const int* slots_dev, long n,
+                        double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev, unsigned char* ok_dev,
+                        const int* batch_dev = nullptr, int batch_index = 0);
+  // the same for a host list of slots with host arrays (staged, one synchronisation): the by-id form's building block
+  void crossing_cov(const int* slots, long n, double t1, const double* origin, double radius, const double* delta, double sigma_r_max,
+                    double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
 
   // Building blocks of the manager's all-batches sequence (TargetManager::stepSequenceAll): enqueue
   // n_ticks ticks -- each optionally followed by the own-time sphere query of every slot -- on `st`

@@ -1157,6 +1157,42 @@ void Shard::selectSoonestBegin(const SoonestSpec* specs, long n_specs, int first
 
 long Shard::selectSoonestEnd(int k, bool with_pose, SoonestRow* rows) { return select_soonest_end(k, with_pose, soonest_, stream_, rows); }
 
+// ---------------------------------------------------------------- covariance and time spread at a crossing (crossing_cov.hpp)
+void Shard::crossingCovDev(double t1, const double* origin, double radius, const int* batch_dev, const int* slots_dev, const double* delta_dev,
+                           long n, double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev,
+                           unsigned char* ok_dev) {
+  check_crossing_cov_args(delta_dev != nullptr, origin != nullptr, radius, cov_dev != nullptr, sigma_dev != nullptr, ok_dev != nullptr,
+                          sigma_r_max, sigma_t_max, true, n, 0);
+  if (!batch_dev || !slots_dev) throw std::invalid_argument("target_estimation_amd: crossing_cov: the batch and slot lists are required");
+  if (n == 0) return;
+  launch_crossing_cov_orphans(batch_dev, n, (int)batches_.size(), cov_dev, sigma_dev, ok_dev, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+  for (size_t b = 0; b < batches_.size(); ++b)
+    batches_[b]->crossing_cov_dev(t1, origin, radius, delta_dev, slots_dev, n, sigma_r_max, sigma_t_max, cov_dev, sigma_dev, ok_dev, batch_dev, (int)b);
+}
+
+long Shard::crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
+                             double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok) {
+  check_crossing_cov_args(delta != nullptr, origin != nullptr, radius, cov != nullptr, sigma != nullptr, ok != nullptr, sigma_r_max,
+                          sigma_t_max, false, 0, 0);
+  for (long i = 0; i < n; ++i) crossing_cov_fill(i, cov, sigma, ok);
+  BySlot by;
+  splitBySlot(ids, n, by, [](size_t, const Loc&) {});
+  for (size_t b = 0; b < batches_.size(); ++b) {
+    const long k = (long)by.slots[b].size();
+    if (!k) continue;
+    const std::vector<double> d2 = gatherRows(delta, by.sp.src[b], 1);
+    std::vector<double> c2((size_t)k * 6), s2(sigma ? (size_t)k * 2 : 0);
+    std::vector<unsigned char> o2(ok ? (size_t)k : 0);
+    batches_[b]->crossing_cov(by.slots[b].data(), k, t1, origin, radius, d2.data(), sigma_r_max, sigma_t_max, c2.data(),
+                              sigma ? s2.data() : nullptr, ok ? o2.data() : nullptr);
+    scatterRows(cov, c2, by.sp.src[b], 6);
+    scatterRows(sigma, s2, by.sp.src[b], 2);
+    scatterRows(ok, o2, by.sp.src[b], 1);
+  }
+  return by.known;
+}
+
 void Shard::launchRows(double* pose_out) {
   for (size_t b = 0; b < batches_.size(); ++b)
     if (batches_[b]->size() > 0) batches_[b]->outputs_rows_dev(pose_out, rank_maps_[b].dev);

@@ -169,6 +169,19 @@ class Shard {
   void selectSoonestDev(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, const SoonestOut& out);
   void selectSoonestBegin(const SoonestSpec* specs, long n_specs, int first_batch, double lo, double hi, int k, bool with_pose);
   long selectSoonestEnd(int k, bool with_pose, SoonestRow* rows);
+  // POSITION COVARIANCE AND TIME SPREAD AT THE CROSSINGS (crossing_cov.hpp; Batch::crossing_cov_dev says what is computed and
+  // what is left alone).
+  //   crossingCovDev    the rows a manager-level selection left on the device: batch_dev / slots_dev / delta_dev [n], batch entries
+  //                     are the shard's batch indices.  One launch per batch of the shard, each serving the rows that carry its index,
+  //                     and one that writes the filler into the rows that carry no batch of the shard: every row is written once.
+  //                     No allocation, no host wait.  Everything is checked before anything is enqueued.
+  //   crossingCovBatch  by id, host arrays: delta [n] is the caller's (e.g. of intersectBatch); unknown ids get the filler.
+  //                     Runs the queued one-target steps first.  Returns the number of ids found.
+  void crossingCovDev(double t1, const double* origin, double radius, const int* batch_dev, const int* slots_dev, const double* delta_dev,
+                      long n, double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev,
+                      unsigned char* ok_dev);
+  long crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
+                        double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);

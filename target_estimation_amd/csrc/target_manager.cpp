@@ -774,6 +774,35 @@ void TargetManager::selectSoonestDev(const SoonestSpec* specs, long n_specs, dou
   shards_[0]->selectSoonestDev(specs, n_specs, 0, lo, hi, (int)k, out);
 }
 
+void TargetManager::crossingCovDev(double t1, const double* origin, double radius, const int* batch_dev, const int* slots_dev,
+                                   const double* delta_dev, long n, double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev,
+                                   unsigned char* ok_dev) {
+  lock_guard<mutex> lg(target_lock_);
+  check_crossing_cov_one_shard((long)shards_.size());
+  DeviceGuard g(guardDev(0));
+  shards_[0]->crossingCovDev(t1, origin, radius, batch_dev, slots_dev, delta_dev, n, sigma_r_max, sigma_t_max, cov_dev, sigma_dev, ok_dev);
+}
+
+long TargetManager::crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
+                                     double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok) {
+  lock_guard<mutex> lg(target_lock_);
+  check_crossing_cov_args(delta != nullptr, origin != nullptr, radius, cov != nullptr, sigma != nullptr, ok != nullptr, sigma_r_max,
+                          sigma_t_max, false, 0, 0);
+  if (n <= 0) return 0;
+  if (!ids) throw std::invalid_argument("target_estimation_amd: crossing_cov: ids are required");
+  const Split sp = splitIds(ids, n);
+  for (long i : sp.unknown) crossing_cov_fill(i, cov, sigma, ok);
+  long done = 0;
+  forShards(sp, ids, n, [&](Shard& sh, size_t, const unsigned* ids2, long m, const std::vector<long>* pos) {
+    RowsIn<double> d2(delta, pos, 1);
+    RowsOut<double> c2(cov, pos, 6), s2(sigma, pos, 2);
+    RowsOut<unsigned char> o2(ok, pos, 1);
+    done += sh.crossingCovBatch(ids2, m, t1, origin, radius, d2.get(), sigma_r_max, sigma_t_max, c2.get(), s2.get(), o2.get());
+    scatterAll(c2, s2, o2);
+  });
+  return done;
+}
+
 void TargetManager::synchronize() {
   lock_guard<mutex> lg(target_lock_);
   for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(guardDev(k)); shards_[k]->synchronize(); }

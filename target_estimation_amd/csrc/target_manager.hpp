@@ -202,6 +202,15 @@ class TargetManager {
   // the same into device memory, without a host wait: a manager on one device only (several have no single device to write to)
   void selectSoonestDev(const SoonestSpec* specs, long n_specs, double lo, double hi, long k, const SoonestOut& out);
 
+  // POSITION COVARIANCE AND TIME SPREAD AT THE CROSSINGS (crossing_cov.hpp; target_manager_crossing_cov_dev / _batch).
+  // crossingCovDev: for the rows selectSoonestDev left on the device (batch / slots / delta [n <= kCrossingCovMaxRows]); a manager
+  // on one device only.  crossingCovBatch: by id with host arrays, over every shard; the queued one-target steps run first; unknown
+  // ids get the filler; returns the ids found.  Neither settles a tile, demotes a batch, drops a recording or touches a clock.
+  void crossingCovDev(double t1, const double* origin, double radius, const int* batch_dev, const int* slots_dev, const double* delta_dev,
+                      long n, double sigma_r_max, double sigma_t_max, double* cov_dev, double* sigma_dev, unsigned char* ok_dev);
+  long crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
+                        double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
+
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and
   // their per-GPU share (62 500 + 62 500 targets) is launch-bound.  specs as for stepSequenceAll (ring_ticks > 0 required).

@@ -416,6 +416,40 @@ int target_manager_select_soonest_dev(target_manager_c* m, const target_batch_se
   });
 }
 
+// ---- position covariance and time spread at a crossing (crossing_cov.hpp).  What does not depend on the handle is refused before
+// the handle is looked at.
+int target_batch_crossing_cov_dev(target_batch_c* b, double t1, const double* origin, double radius, const double* delta_dev,
+                                  const int* slots_dev, long n, double sigma_r_max, double sigma_t_max, double* cov_out_dev,
+                                  double* sigma_out_dev, unsigned char* ok_out_dev) {
+  return guarded("target_batch_crossing_cov_dev", [&] {
+    te::check_crossing_cov_args(delta_dev != nullptr, origin != nullptr, radius, cov_out_dev != nullptr, sigma_out_dev != nullptr,
+                                ok_out_dev != nullptr, sigma_r_max, sigma_t_max, slots_dev != nullptr, n, n);
+    BatchLock lk(B(b));
+    B(b)->crossing_cov_dev(t1, origin, radius, delta_dev, slots_dev, n, sigma_r_max, sigma_t_max, cov_out_dev, sigma_out_dev, ok_out_dev);
+  });
+}
+
+int target_manager_crossing_cov_dev(target_manager_c* m, double t1, const double* origin, double radius, const int* batch_dev,
+                                    const int* slots_dev, const double* delta_dev, long n, double sigma_r_max, double sigma_t_max,
+                                    double* cov_out_dev, double* sigma_out_dev, unsigned char* ok_out_dev) {
+  return guarded("target_manager_crossing_cov_dev", [&] {
+    te::check_crossing_cov_args(delta_dev != nullptr, origin != nullptr, radius, cov_out_dev != nullptr, sigma_out_dev != nullptr,
+                                ok_out_dev != nullptr, sigma_r_max, sigma_t_max, true, n, 0);
+    if (!batch_dev || !slots_dev) throw std::invalid_argument("target_estimation_amd: crossing_cov: the batch and slot lists are required");
+    M(m)->crossingCovDev(t1, origin, radius, batch_dev, slots_dev, delta_dev, n, sigma_r_max, sigma_t_max, cov_out_dev, sigma_out_dev, ok_out_dev);
+  });
+}
+
+long target_manager_crossing_cov_batch(target_manager_c* m, const unsigned int* ids, long n, double t1, const double* origin, double radius,
+                                       const double* delta_host, double sigma_r_max, double sigma_t_max, double* cov_out,
+                                       double* sigma_out, unsigned char* ok_out) {
+  return guarded_value<long>("target_manager_crossing_cov_batch", -1L, [&]() -> long {
+    te::check_crossing_cov_args(delta_host != nullptr, origin != nullptr, radius, cov_out != nullptr, sigma_out != nullptr, ok_out != nullptr,
+                                sigma_r_max, sigma_t_max, false, n, n);
+    return M(m)->crossingCovBatch(ids, n, t1, origin, radius, delta_host, sigma_r_max, sigma_t_max, cov_out, sigma_out, ok_out);
+  });
+}
+
 int target_batch_intersect_sphere_dev(target_batch_c* b, double t1, const double* origin, double radius,
                                       double* delta_dev, double* pose_dev) {
   return guarded("target_batch_intersect_sphere_dev", [&] { BatchLock lk(B(b)); B(b)->intersect_dev(t1, origin, radius, delta_dev, pose_dev); });

@@ -452,6 +452,30 @@ class Batch:
                        "target_batch_select_soonest")
         return count, ids, so, do, po
 
+    def crossing_cov(self, delta, slots=None, origin=None, radius=0.0, t1=float("nan"), sigma_r_max=float("inf"), sigma_t_max=float("inf"),
+                     want_ok=None, out=None):
+        """Position covariance and time spread at the sphere crossings (target_batch_crossing_cov_dev), on the batch's stream, no
+        host wait.  delta: CUDA doubles, [size] of a query (slots=None: row i is slot i) or [n] alongside slots, a CUDA int32
+        list of n <= 8192 slots (-1: none) -- the slots / delta a select_soonest(device=True) returned.  t1: the query's time (NaN:
+        each target's own).  Returns (cov [n, 6] = Sigma's upper triangle xx xy xz yy yz zz, sigma [n, 2] = (sigma_r, sigma_t) or
+        None without origin, ok [n] uint8 = sigma_r <= sigma_r_max and sigma_t <= sigma_t_max or None) as CUDA tensors; ok is made
+        when origin is given unless want_ok=False.  Rows whose delta is negative or NaN (or whose slot is -1) are cov 0, sigma
+        (-1, -1), ok 0.  out: (cov, sigma, ok) to use; None entries are passed as NULL."""
+        import torch
+        n = int(delta.shape[0])
+        origin = _d(origin, (3,))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if out is None:
+            with_ok = (origin is not None) if want_ok is None else bool(want_ok)
+            out = (torch.empty((n, 6), dtype=torch.float64, device="cuda"),
+                   None if origin is None else torch.empty((n, 2), dtype=torch.float64, device="cuda"),
+                   torch.empty(n, dtype=torch.uint8, device="cuda") if with_ok else None)
+        cov, sigma, ok = out
+        _check(self._lib.target_batch_crossing_cov_dev(self._h, float(t1), _dp(origin), float(radius), ptr(delta), ptr(slots), n,
+                                                       float(sigma_r_max), float(sigma_t_max), ptr(cov), ptr(sigma), ptr(ok)),
+               "target_batch_crossing_cov_dev")
+        return cov, sigma, ok
+
     def pack_meas(self, meas_aos, out=None):
         """CUDA double [n,7] (the reference's row layout) -> SoA [7,n] in the batch precision."""
         import torch
@@ -1055,6 +1079,44 @@ class TargetManager:
                                                                None if ids is None else ids.ctypes.data_as(capi.c_uint_p), ip(bo), ip(so),
                                                                _dp(do), _dp(po)), "target_manager_select_soonest")
         return count, ids, bo, so, do, po
+
+    def crossing_cov(self, batch, slots, delta, origin=None, radius=0.0, t1=float("nan"), sigma_r_max=float("inf"),
+                     sigma_t_max=float("inf"), want_ok=None, out=None):
+        """Position covariance and time spread (target_manager_crossing_cov_dev) of the rows select_soonest(device=True) left on
+        the device: batch / slots CUDA int32 [n], delta CUDA doubles [n], n <= 8192; a manager on one device only, no host wait.
+        Returns (cov [n, 6], sigma [n, 2] or None, ok [n] uint8 or None) CUDA tensors as Batch.crossing_cov; rows of batch -1 or
+        slot -1 are cov 0, sigma (-1, -1), ok 0."""
+        import torch
+        n = int(delta.shape[0])
+        origin = _d(origin, (3,))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        if out is None:
+            with_ok = (origin is not None) if want_ok is None else bool(want_ok)
+            out = (torch.empty((n, 6), dtype=torch.float64, device="cuda"),
+                   None if origin is None else torch.empty((n, 2), dtype=torch.float64, device="cuda"),
+                   torch.empty(n, dtype=torch.uint8, device="cuda") if with_ok else None)
+        cov, sigma, ok = out
+        _check(self._lib.target_manager_crossing_cov_dev(self._h, float(t1), _dp(origin), float(radius), ptr(batch), ptr(slots), ptr(delta), n,
+                                                         float(sigma_r_max), float(sigma_t_max), ptr(cov), ptr(sigma), ptr(ok)),
+               "target_manager_crossing_cov_dev")
+        return cov, sigma, ok
+
+    def crossing_cov_batch(self, ids, delta, origin=None, radius=0.0, t1=float("nan"), sigma_r_max=float("inf"), sigma_t_max=float("inf")):
+        """The same by id with host arrays (target_manager_crossing_cov_batch): delta [n] as intersect_batch returned it for the
+        same t1, origin and radius.  Any number of ids over any number of devices; the queued one-target steps run first.
+        Returns (found count, cov [n, 6], sigma [n, 2] or None, ok [n] bool or None); unknown ids are cov 0, sigma (-1, -1), ok 0."""
+        ids, idp = _ids(ids)
+        n = len(ids)
+        origin = _d(origin, (3,))
+        delta = _d(delta, (n,))
+        cov = np.empty((n, 6))
+        sigma = None if origin is None else np.empty((n, 2))
+        ok = None if origin is None else np.zeros(n, dtype=np.uint8)
+        found = _check(self._lib.target_manager_crossing_cov_batch(self._h, idp, n, float(t1), _dp(origin), float(radius), _dp(delta),
+                                                                   float(sigma_r_max), float(sigma_t_max), _dp(cov), _dp(sigma),
+                                                                   None if ok is None else ok.ctypes.data_as(capi.c_ubyte_p)),
+                       "target_manager_crossing_cov_batch")
+        return found, cov, sigma, None if ok is None else ok.astype(bool)
 
     def population_tick(self):
         """True if step_sequence_all steps every batch with ONE launch per tick (target_manager_population_tick)."""
