@@ -855,6 +855,67 @@ int target_manager_crossing_cov_dev(target_manager_c* m, double t1, const double
 long target_manager_crossing_cov_batch(target_manager_c* m, const unsigned int* ids, long n, double t1, const double* origin, double radius,
                                        const double* delta_host, double sigma_r_max, double sigma_t_max, double* cov_out,
                                        double* sigma_out, unsigned char* ok_out);
+/* ---- ASSOCIATION OF UNLABELLED DETECTIONS: a frame of M detections without target labels is paired with the targets of a batch (or
+ * of a whole manager on ONE device) on the device, from the filter's own predicted positions and innovation covariances, and
+ * scattered into the form the tick reads.  
+ * INPUTS.  dt: the time step of the tick that will consume the result.  det [M][7] doubles in the reference's pose layout
+ * [x y z qx qy qz qw].  gate > 0 (may be +inf).  rounds: 1 .. TARGET_ASSOC_MAX_ROUNDS.
+ * PER TARGET (slot), whatever its model:
+ *   zhat  = the position a predict-only update(dt) would give, as the getters extrapolate it to the offset dt, in the batch's precision
+ *   Sigma = (A(dt) P A(dt)^T + Q)[0:3, 0:3] exactly as target_batch_crossing_cov_dev forms it at tau = dt: the batch's precision, the
+ *           stored words (a uniform tile's from the tile's block), exact zeros between the axes of the separable layouts
+ *   S     = Sigma + R[0:3, 0:3], R of the slot's own (Q, R) class, summed in double
+ *   W     = S^-1 in double, by cofactors: symmetric, 6 words.  A slot whose S is not finite, has a non-positive diagonal entry or a
+ *           non-positive determinant is never a candidate.
+ * PAIR COST.  d2(i, j) = nu^T W_i nu, nu = det_j[0:3] - zhat_i, in double; (i, j) is a candidate iff d2 <= gate, so a NaN in either
+ * operand rejects the pair.  POSITION ONLY, for all four models: a detection's orientation is not used for pairing.  The angular
+ * models' full 6-dof NIS is still applied afterwards by the tick's own gate, if one is set.
+ * MATCHING, in rounds of mutual best: every unmatched target picks its best unmatched candidate detection by (d2, detection index),
+ * every unmatched detection its best unmatched candidate target by (d2, batch index, slot); a pair that picked each other is
+ * matched; the next round repeats on what is left.  At its fixed point this is greedy global-nearest-neighbour: take the smallest
+ * remaining pair by (d2, batch, slot, detection), remove its row and column, repeat.  The result is a function of the inputs alone.
+ * ROUNDS.  A round is settled if every unmatched detection that had a candidate at its start was matched in it (also: none had
+ * one).  After a settled round no pair remains; the launches of later rounds return at once.  info[2] = 1 guarantees the greedy
+ * result, 0 means that more rounds might add matches.
+ * OUTPUTS.  meas_out SoA [7][ld] in the batch precision and has_meas_out [size] bytes, as target_batch_step reads them: a matched
+ * slot gets its detection's 7 words rounded once and 1, an unmatched slot [0 0 0 0 0 0 1] and 0.  det_of_slot int[size] (-1: none),
+ * d2_of_slot double[size] (-1: none); slot_of_det int[M] (and batch_of_det int[M] at manager level), d2_of_det double[M] (-1: none).
+ * d2_of_slot comes from the target-major scan, d2_of_det from the detection-major one: the same bits for a matched pair.
+ * info int[4] = {matched, rounds_run, settled, 0}.  Required: meas_out, has_meas_out, info (device forms); the others may be NULL.
+ * REFUSED (-1, target_manager_last_error, nothing enqueued, nothing written): a NULL handle; a NULL required output; M < 0 or
+ * M > TARGET_ASSOC_MAX_DETECTIONS; det NULL with M > 0; ld < size; rounds out of range; gate <= 0 or NaN; dt negative or NaN; a
+ * manager form on a manager with several shards.  M == 0 or an empty batch is no error: nothing matched, info = {0, 0, 1, 0}.
+ * The call reads the records as they are stored: it settles no uniform tile, expands no shared-axes batch, drops no recorded
+ * sequence and leaves rejection runs and clocks alone; the queued one-target steps run first.
+ *   ..._associate_dev   everything in device memory, on the batch's (manager's) stream.  After the first call of at least that size
+ *                       on a device it allocates nothing, and it never waits on the host: associate -> target_batch_step, or
+ *                       associate -> target_manager_step_sequence_all(n_ticks = 1), may be captured in the caller's hipGraph.
+ *   ..._associate       detections from host memory; the per-detection rows come back with slots translated to ids (~0u: none);
+ *                       unmatched_out [M] receives the unmatched detection indices in ascending order, *n_unmatched_out their
+ *                       number.  The device outputs (meas_out_dev ...) are optional here.  Returns the matched count (or -1).
+ * Not built: a spatial index (the scans are brute force over all pairs), orientation in the cost, a likelihood cost, several shards. */
+#define TARGET_ASSOC_MAX_DETECTIONS 65536
+#define TARGET_ASSOC_MAX_ROUNDS 16
+/* what one batch's slots get from a manager-level call: one per batch, in target_manager_get_batch order */
+typedef struct target_assoc_out_c {
+  void* meas_out_dev;               /* SoA [7][ld] in the batch precision */
+  long ld;
+  unsigned char* has_meas_out_dev;  /* [size] */
+  int* det_of_slot_dev;             /* [size] or NULL */
+  double* d2_of_slot_dev;           /* [size] or NULL */
+} target_assoc_out_c;
+int target_batch_associate_dev(target_batch_c* b, double dt, const double* det_dev, long M, double gate, int rounds, void* meas_out_dev,
+                               long ld, unsigned char* has_meas_out_dev, int* det_of_slot_dev, double* d2_of_slot_dev,
+                               int* slot_of_det_dev, double* d2_of_det_dev, int* info_dev);
+long target_batch_associate(target_batch_c* b, double dt, const double* det_host, long M, double gate, int rounds, void* meas_out_dev,
+                            long ld, unsigned char* has_meas_out_dev, unsigned int* ids_of_det_out, int* slot_of_det_out,
+                            double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out);
+int target_manager_associate_dev(target_manager_c* m, double dt, const double* det_dev, long M, double gate, int rounds,
+                                 const target_assoc_out_c* per_batch, long n_batches, int* slot_of_det_dev, int* batch_of_det_dev,
+                                 double* d2_of_det_dev, int* info_dev);
+long target_manager_associate(target_manager_c* m, double dt, const double* det_host, long M, double gate, int rounds,
+                              const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out, int* batch_of_det_out,
+                              int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

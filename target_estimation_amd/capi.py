@@ -44,6 +44,12 @@ class StreamSpec(C.Structure):
                 ("availability", C.c_double), ("rpy_noise", C.c_double)]
 
 
+class AssocOut(C.Structure):
+    """target_assoc_out_c of target_batch_c.h: what one batch's slots get from a manager-level association"""
+    _fields_ = [("meas_out_dev", C.c_void_p), ("ld", C.c_long), ("has_meas_out_dev", C.c_void_p), ("det_of_slot_dev", C.c_void_p),
+                ("d2_of_slot_dev", C.c_void_p)]
+
+
 SIGNATURES = {
     # target_manager_c.h (the reference's ten symbols)
     "target_manager_new": (C.c_void_p, [C.c_char_p]),
@@ -124,6 +130,17 @@ SIGNATURES = {
                                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "target_manager_crossing_cov_batch": (C.c_long, [C.c_void_p, c_uint_p, C.c_long, C.c_double, c_double_p, C.c_double, c_double_p, C.c_double,
                                                      C.c_double, c_double_p, c_double_p, c_ubyte_p]),
+    # association of unlabelled detections: device pointers as void*, host arrays typed
+    "target_batch_associate_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_batch_associate": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                          c_uint_p, C.POINTER(C.c_int), c_double_p, C.POINTER(C.c_long), C.POINTER(C.c_long),
+                                          C.POINTER(C.c_int)]),
+    "target_manager_associate_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_int, C.POINTER(AssocOut), C.c_long,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_manager_associate": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.POINTER(AssocOut), C.c_long,
+                                            c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, C.POINTER(C.c_long),
+                                            C.POINTER(C.c_long), C.POINTER(C.c_int)]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),
     "target_comm_unique_id": (C.c_int, [C.c_char_p]),
     "target_comm_new": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int]),

@@ -1848,9 +1848,98 @@ void Batch::crossing_cov(const int* slots, long n, double t1, const double* orig
   }
 }
 
+// ---------------------------------------------------------------- association of unlabelled detections (associate.hpp)
+void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index) {
+  const AssocTableLaunch launch = assoc_table_launcher(type_, dtype_, ops_->L.g, ops_->L.layout, shared_axes());
+  if (!launch) throw std::logic_error("target_estimation_amd: associate: no kernel for this (model, precision, layout)");   // (never a fall-back)
+  flush();
+  if (n_ == 0) return;
+  AssocTableArgs a;
+  a.rec = records_as_stored(); a.qr = d_qr_; a.cls = n_classes_ > 1 ? d_cls_ : nullptr;
+  // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
+  a.tile_blk = d_tile_uni_ ? d_tile_blk_ : nullptr; a.tile_uni = d_tile_uni_;
+  a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index;
+  launch(a, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+}
+
+void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det_dev, long M,
+                       double gate, long rounds, const AssocSlotOut* out, int* slot_of_det, int* batch_of_det, double* d2_of_det, int* info,
+                       hipStream_t st) {
+  long rows = 0;
+  for (int b = 0; b < n_batches; ++b) {
+    const LayoutInfo L = batches[b]->layout();
+    if (!assoc_table_launcher(batches[b]->type(), batches[b]->dtype(), L.g, L.layout, L.shared_axes != 0))
+      throw std::logic_error("target_estimation_amd: associate: no kernel for this (model, precision, layout)");
+    rows += batches[b]->size();
+  }
+  if (rows > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: associate: more than 2^31 - 1 targets on one device");
+  const AssocGrid gr = plan_assoc_grid(rows, M, forced_chunks), gd = plan_assoc_grid(M, rows, forced_chunks);
+  scratch.ensure(rows, M, rows * gr.chunks, M * gd.chunks);
+  long off = 0;
+  for (int b = 0; b < n_batches; ++b) {
+    batches[b]->assoc_table_dev(dt, scratch.table + off, b);
+    off += batches[b]->size();
+  }
+  launch_assoc_match(scratch, rows, det_dev, M, gate, (int)rounds, forced_chunks, st);
+  off = 0;
+  for (int b = 0; b < n_batches; ++b) {
+    launch_assoc_scatter(batches[b]->dtype(), scratch, off, batches[b]->size(), det_dev, out[b], st);
+    off += batches[b]->size();
+  }
+  launch_assoc_dets(scratch, M, slot_of_det, batch_of_det, d2_of_det, info, st);
+  TE_HIP_CHECK(hipGetLastError());
+}
+
+void Batch::associate_dev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut& out, int* slot_of_det_dev,
+                          double* d2_of_det_dev, int* info_dev) {
+  check_assoc_args(dt, det_dev != nullptr, M, gate, rounds, out.meas != nullptr && out.has_meas != nullptr && info_dev != nullptr, out.ld, n_);
+  if (!assoc_) throw std::logic_error("target_estimation_amd: associate: the batch belongs to no shard");
+  Batch* self = this;
+  associate_batches(&self, 1, *assoc_, assoc_forced_chunks_, dt, det_dev, M, gate, rounds, &out, slot_of_det_dev, nullptr, d2_of_det_dev, info_dev, stream_);
+}
+
+long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& s, int forced_chunks, double dt, const double* det, long M, double gate,
+                            long rounds, const AssocSlotOut* out, unsigned* ids_of_det, int* batch_of_det, int* slot_of_det, double* d2_of_det,
+                            long* unmatched, long* n_unmatched, int* info, hipStream_t st) {
+  s.ensure_host(M);
+  if (M > 0) TE_HIP_CHECK(hipMemcpyAsync(s.det_stage, det, sizeof(double) * 7 * (size_t)M, hipMemcpyHostToDevice, st));
+  char* d = s.result_dev;
+  associate_batches(batches, n_batches, s, forced_chunks, dt, s.det_stage, M, gate, rounds, out, (int*)(d + AssocScratch::off_slot(M)),
+                    (int*)(d + AssocScratch::off_batch(M)), (double*)(d + AssocScratch::off_d2(M)), (int*)(d + AssocScratch::off_info(M)), st);
+  TE_HIP_CHECK(hipMemcpyAsync(s.result_host, d, AssocScratch::result_bytes(M), hipMemcpyDeviceToHost, st));
+  TE_HIP_CHECK(hipStreamSynchronize(st));
+  const char* h = s.result_host;
+  const int* hs = (const int*)(h + AssocScratch::off_slot(M));
+  const int* hb = (const int*)(h + AssocScratch::off_batch(M));
+  const double* hd = (const double*)(h + AssocScratch::off_d2(M));
+  const int* hi = (const int*)(h + AssocScratch::off_info(M));
+  long nu = 0;
+  for (long j = 0; j < M; ++j) {
+    if (slot_of_det) slot_of_det[j] = hs[j];
+    if (batch_of_det) batch_of_det[j] = hb[j];
+    if (ids_of_det) ids_of_det[j] = hs[j] >= 0 ? batches[hb[j]]->slot_id(hs[j]) : ~0u;
+    if (d2_of_det) d2_of_det[j] = hd[j];
+    if (hs[j] < 0) { if (unmatched) unmatched[nu] = j; ++nu; }
+  }
+  if (n_unmatched) *n_unmatched = nu;
+  if (info) for (int c = 0; c < 4; ++c) info[c] = hi[c];
+  return hi[0];
+}
+
+long Batch::associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut& out, unsigned* ids_of_det,
+                      int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info) {
+  // (the host form's device outputs are optional: without them the call only reports the pairing)
+  check_assoc_args(dt, det != nullptr, M, gate, rounds, true, out.meas ? out.ld : n_, n_);
+  if (!assoc_) throw std::logic_error("target_estimation_amd: associate: the batch belongs to no shard");
+  Batch* self = this;
+  return associate_batches_host(&self, 1, *assoc_, assoc_forced_chunks_, dt, det, M, gate, rounds, &out, ids_of_det, nullptr, slot_of_det, d2_of_det,
+                                unmatched, n_unmatched, info, stream_);
+}
+
 }  // namespace te
 
-#ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library
+#ifdef TE_TEST_HOOKS  // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`), never in the product library
 // Batch::set_state has no entry in the public headers; tests/test_gpu_uniform_tiles.py reaches it through this one (slots = null:
 // slots 0 .. n - 1; x [n][N], P [n][N][N], host arrays).  0, or -1 and the message on stderr.
 extern "C" int te_test_batch_set_state(void* batch, long n, const double* x, const double* P) {

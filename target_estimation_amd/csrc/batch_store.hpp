@@ -20,6 +20,7 @@
 #include "seq_graph_cache.hpp"
 #include "select_soonest.hpp"
 #include "crossing_cov.hpp"
+#include "associate.hpp"
 
 namespace te {
 
@@ -354,6 +355,22 @@ class Batch {
   void crossing_cov(const int* slots, long n, double t1, const double* origin, double radius, const double* delta, double sigma_r_max,
                     double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
 
+  // ASSOCIATION OF UNLABELLED DETECTIONS (associate.hpp; target_batch_associate[_dev]).
+  //   assoc_table_dev    this batch's rows of a call's table: for every slot zhat = the position a predict-only update(dt) would
+  //                      give and W = (Sigma + R[0:3, 0:3])^-1, Sigma as crossing_cov_dev forms it at tau = dt.  One launch on the
+  //                      batch's stream.  The records are read as stored: no tile is settled, no shared-axes batch demoted, no
+  //                      recording dropped, rejection runs and the clock are not touched; the queued one-target steps run first.
+  //   associate_dev      the whole call for this batch alone (associate_batches below).
+  //   associate          the host form: detections from host memory, the per-detection rows back (ids translated), one wait.
+  void set_assoc_scratch(AssocScratch* s, int forced_chunks) { assoc_ = s; assoc_forced_chunks_ = forced_chunks; }
+  AssocScratch* assoc_scratch() const { return assoc_; }
+  int assoc_forced_chunks() const { return assoc_forced_chunks_; }
+  void assoc_table_dev(double dt, AssocRow* rows, int batch_index);
+  void associate_dev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut& out, int* slot_of_det_dev,
+                     double* d2_of_det_dev, int* info_dev);
+  long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut& out, unsigned* ids_of_det,
+                 int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
+
   // Building blocks of the manager's all-batches sequence (TargetManager::stepSequenceAll): enqueue
   // n_ticks ticks -- each optionally followed by the own-time sphere query of every slot -- on `st`
   // without touching the batch clock, then account for them.
@@ -457,6 +474,8 @@ class Batch {
 
   int type_, dtype_, lanes_code_;
   SoonestScratch* soonest_ = nullptr;   // the owning shard's (set_soonest_scratch)
+  AssocScratch* assoc_ = nullptr;       // the owning shard's (set_assoc_scratch)
+  int assoc_forced_chunks_ = 0;
   int soonest_max_wgs_ = kSoonestDefaultMaxWgs;
   std::mutex* owner_lock_ = nullptr;
   const Ops* ops_;
@@ -641,5 +660,20 @@ class Batch {
   } live_;
   void live_release();
 };
+
+// ONE ASSOCIATION CALL over the batches of one device (associate.hpp lists the launches): the batches' table rows concatenated in
+// the order given, det_dev [M][7] in device memory, out [n_batches] what each batch's slots get.  slot_of_det / batch_of_det /
+// d2_of_det [M] may be null; info [4] = {matched, rounds_run, settled, 0}.  Everything on `st` (the shard's one stream), no host
+// wait, no allocation unless the call is larger than every call before it on this scratch.  The arguments are the caller's to
+// check (check_assoc_args); nothing is enqueued before every batch has been found to have a table kernel.
+void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det_dev, long M,
+                       double gate, long rounds, const AssocSlotOut* out, int* slot_of_det, int* batch_of_det, double* d2_of_det, int* info,
+                       hipStream_t st);
+// ... and its host form: det [M][7] in host memory is staged, the per-detection rows come back through the scratch's pinned mirror
+// (one wait), slots are translated to ids (~0u: none), unmatched [M] receives the unmatched detections in ascending order.  Any
+// output may be null.  Returns the matched count.
+long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det, long M,
+                            double gate, long rounds, const AssocSlotOut* out, unsigned* ids_of_det, int* batch_of_det, int* slot_of_det,
+                            double* d2_of_det, long* unmatched, long* n_unmatched, int* info, hipStream_t st);
 
 }  // namespace te

@@ -52,6 +52,7 @@ struct ShardSettings {
   bool shared_axes = true;       // TE_SHARED_AXES / TargetManager::setSharedAxes: new fp64 batches may use the shared-axes storage form (Batch)
   UpdateGate gate[4];            // TargetManager::setUpdateGate: the by-id update policy per model type; batches created later inherit it
   int soonest_max_wgs = kSoonestDefaultMaxWgs;   // TE_SELECT_SOONEST_MAX_WGS: the cap on the selection's first-stage workgroups (select_soonest.hpp)
+  int assoc_col_chunks = 0;      // TE_ASSOC_COL_CHUNKS: the column chunks of the association scans, 0 = planned (associate_plan.hpp)
 };
 
 // one batch of a manager-level selection (TargetManager::selectSoonest): the query outputs of target_batch_sequence_c and the
@@ -182,6 +183,14 @@ class Shard {
                       unsigned char* ok_dev);
   long crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
                         double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
+  // ASSOCIATION OF UNLABELLED DETECTIONS with the targets of every batch of this shard together (associate.hpp; associate_batches
+  // says what is launched, Batch::assoc_table_dev what is left alone): out [batches().size()], batch entries of batch_of_det are the
+  // shard's batch indices.  associateDev: everything in device memory, no host wait.  associate: detections from host memory, the
+  // per-detection rows back with ids; returns the matched count.
+  void associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
+                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev);
+  long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
+                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -239,6 +248,7 @@ class Shard {
   // the scratch of the selections of this shard and of its batches (Batch::set_soonest_scratch): allocated at the first selection,
   // released through device_free
   SoonestScratch soonest_;
+  AssocScratch assoc_;   // ... and of its associations (Batch::set_assoc_scratch): grow-only
   int soonestParts(const SoonestSpec* specs, long n_specs, int first_batch, SoonestPart* parts) const;
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call

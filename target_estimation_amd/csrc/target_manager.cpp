@@ -35,6 +35,8 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) {
   // TE_SELECT_SOONEST_MAX_WGS=<n>: the cap on the first-stage workgroups of select_soonest (read per manager, so that one process
   // can hold managers with different grids: tests reach the several-rounds paths at a few thousand entries)
   settings_.soonest_max_wgs = soonest_max_wgs_from(std::getenv("TE_SELECT_SOONEST_MAX_WGS"));
+  // TE_ASSOC_COL_CHUNKS=<n>: the column chunks of the association scans, so that small calls exercise the merge of the partials
+  settings_.assoc_col_chunks = assoc_forced_chunks_from(std::getenv("TE_ASSOC_COL_CHUNKS"));
   const char* ld = std::getenv("TARGET_ESTIMATION_LOG_DIR");
   if (ld && ld[0]) { log_dir_ = ld; settings_.keep_meas = true; }   // batches created later inherit the measured-pose rows
   int count = 0;
@@ -801,6 +803,23 @@ long TargetManager::crossingCovBatch(const unsigned* ids, long n, double t1, con
     scatterAll(c2, s2, o2);
   });
   return done;
+}
+
+void TargetManager::associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
+                                 int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev) {
+  lock_guard<mutex> lg(target_lock_);
+  check_assoc_one_shard((long)shards_.size());
+  DeviceGuard g(guardDev(0));
+  shards_[0]->associateDev(dt, det_dev, M, gate, rounds, out, n_out, slot_of_det_dev, batch_of_det_dev, d2_of_det_dev, info_dev);
+}
+
+long TargetManager::associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
+                              unsigned* ids_of_det, int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched,
+                              int* info) {
+  lock_guard<mutex> lg(target_lock_);
+  check_assoc_one_shard((long)shards_.size());
+  DeviceGuard g(guardDev(0));
+  return shards_[0]->associate(dt, det, M, gate, rounds, out, n_out, ids_of_det, batch_of_det, slot_of_det, d2_of_det, unmatched, n_unmatched, info);
 }
 
 void TargetManager::synchronize() {

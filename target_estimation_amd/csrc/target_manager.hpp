@@ -211,6 +211,15 @@ class TargetManager {
   long crossingCovBatch(const unsigned* ids, long n, double t1, const double* origin, double radius, const double* delta,
                         double sigma_r_max, double sigma_t_max, double* cov, double* sigma, unsigned char* ok);
 
+  // ASSOCIATION OF UNLABELLED DETECTIONS with every target of the manager (associate.hpp; target_manager_associate[_dev]): out
+  // [numBatches()] in target_manager_get_batch order; a manager on one device only.  associateDev: no host wait; associate: host
+  // detections in, per-detection rows with ids back, returns the matched count.  Neither settles a tile, demotes a batch, drops a
+  // recording or touches a clock; the queued one-target steps run first.
+  void associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
+                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev);
+  long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
+                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
+
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and
   // their per-GPU share (62 500 + 62 500 targets) is launch-bound.  specs as for stepSequenceAll (ring_ticks > 0 required).

@@ -450,6 +450,67 @@ long target_manager_crossing_cov_batch(target_manager_c* m, const unsigned int* 
   });
 }
 
+// ---- association of unlabelled detections (associate.hpp).  What does not depend on the handle is refused before the handle is
+// looked at; the host forms write their arrays only after the call has succeeded.
+static TargetManager* assoc_manager(const target_manager_c* m) { return M(m); }   // (the ABI names the detection count M)
+static std::vector<te::AssocSlotOut> assoc_outs(const target_assoc_out_c* per_batch, long n_batches) {
+  if (n_batches < 0 || (n_batches > 0 && !per_batch)) throw std::invalid_argument("target_estimation_amd: associate: one output description per batch is needed");
+  std::vector<te::AssocSlotOut> outs((size_t)n_batches);
+  for (long i = 0; i < n_batches; ++i) {
+    te::AssocSlotOut& o = outs[(size_t)i];
+    o.meas = per_batch[i].meas_out_dev; o.ld = per_batch[i].ld; o.has_meas = per_batch[i].has_meas_out_dev;
+    o.det_of_slot = per_batch[i].det_of_slot_dev; o.d2_of_slot = per_batch[i].d2_of_slot_dev;
+  }
+  return outs;
+}
+
+int target_batch_associate_dev(target_batch_c* b, double dt, const double* det_dev, long M, double gate, int rounds, void* meas_out_dev,
+                               long ld, unsigned char* has_meas_out_dev, int* det_of_slot_dev, double* d2_of_slot_dev,
+                               int* slot_of_det_dev, double* d2_of_det_dev, int* info_dev) {
+  return guarded("target_batch_associate_dev", [&] {
+    te::check_assoc_args(dt, det_dev != nullptr, M, gate, rounds, meas_out_dev != nullptr && has_meas_out_dev != nullptr && info_dev != nullptr, 0, 0);
+    BatchLock lk(B(b));
+    te::AssocSlotOut out;
+    out.meas = meas_out_dev; out.ld = ld; out.has_meas = has_meas_out_dev; out.det_of_slot = det_of_slot_dev; out.d2_of_slot = d2_of_slot_dev;
+    B(b)->associate_dev(dt, det_dev, M, gate, rounds, out, slot_of_det_dev, d2_of_det_dev, info_dev);
+  });
+}
+
+long target_batch_associate(target_batch_c* b, double dt, const double* det_host, long M, double gate, int rounds, void* meas_out_dev,
+                            long ld, unsigned char* has_meas_out_dev, unsigned int* ids_of_det_out, int* slot_of_det_out,
+                            double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out) {
+  return guarded_value<long>("target_batch_associate", -1L, [&]() -> long {
+    te::check_assoc_args(dt, det_host != nullptr, M, gate, rounds, true, 0, 0);
+    BatchLock lk(B(b));
+    te::AssocSlotOut out;
+    out.meas = meas_out_dev; out.ld = ld; out.has_meas = has_meas_out_dev;
+    return B(b)->associate(dt, det_host, M, gate, rounds, out, ids_of_det_out, slot_of_det_out, d2_of_det_out, unmatched_out, n_unmatched_out, info_out);
+  });
+}
+
+int target_manager_associate_dev(target_manager_c* m, double dt, const double* det_dev, long M, double gate, int rounds,
+                                 const target_assoc_out_c* per_batch, long n_batches, int* slot_of_det_dev, int* batch_of_det_dev,
+                                 double* d2_of_det_dev, int* info_dev) {
+  return guarded("target_manager_associate_dev", [&] {
+    te::check_assoc_args(dt, det_dev != nullptr, M, gate, rounds, info_dev != nullptr, 0, 0);
+    TargetManager* mgr = assoc_manager(m);
+    const std::vector<te::AssocSlotOut> outs = assoc_outs(per_batch, n_batches);
+    mgr->associateDev(dt, det_dev, M, gate, rounds, outs.data(), n_batches, slot_of_det_dev, batch_of_det_dev, d2_of_det_dev, info_dev);
+  });
+}
+
+long target_manager_associate(target_manager_c* m, double dt, const double* det_host, long M, double gate, int rounds,
+                              const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out, int* batch_of_det_out,
+                              int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out) {
+  return guarded_value<long>("target_manager_associate", -1L, [&]() -> long {
+    te::check_assoc_args(dt, det_host != nullptr, M, gate, rounds, true, 0, 0);
+    TargetManager* mgr = assoc_manager(m);
+    const std::vector<te::AssocSlotOut> outs = assoc_outs(per_batch, n_batches);
+    return mgr->associate(dt, det_host, M, gate, rounds, per_batch ? outs.data() : nullptr, n_batches, ids_of_det_out, batch_of_det_out,
+                          slot_of_det_out, d2_of_det_out, unmatched_out, n_unmatched_out, info_out);
+  });
+}
+
 int target_batch_intersect_sphere_dev(target_batch_c* b, double t1, const double* origin, double radius,
                                       double* delta_dev, double* pose_dev) {
   return guarded("target_batch_intersect_sphere_dev", [&] { BatchLock lk(B(b)); B(b)->intersect_dev(t1, origin, radius, delta_dev, pose_dev); });

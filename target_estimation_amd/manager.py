@@ -476,6 +476,54 @@ class Batch:
                "target_batch_crossing_cov_dev")
         return cov, sigma, ok
 
+    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None):
+        """Pair a frame of unlabelled detections with this batch's targets on the device (target_batch_associate[_dev]): the cost
+        is the position-only Mahalanobis distance d2 against the filter's own predicted position and innovation covariance at
+        dt, pairs with d2 <= gate are candidates, matching runs `rounds` rounds of mutual best (info[2] = 1: the greedy
+        global-nearest-neighbour result).  det: [M, 7] rows [x y z qx qy qz qw].
+        A CUDA double tensor: the device form, on the batch's stream, no host wait.  Returns a SimpleNamespace of CUDA tensors:
+        meas [7, size] (batch precision) and has_meas [size] uint8 -- feed them to step(dt, r.meas, r.has_meas) --, det_of_slot
+        [size] int32, d2_of_slot [size], slot_of_det [M] int32, d2_of_det [M], info [4] int32 = (matched, rounds_run, settled, 0).
+        out: such a namespace to write into (a call with the same tensors allocates nothing and may be captured in a graph).
+        A host array: the host form.  Returns a SimpleNamespace of meas / has_meas (CUDA, as above) and NumPy arrays ids_of_det
+        [M] uint32 (0xffffffff: none), slot_of_det, d2_of_det, unmatched (ascending detection indices), info, and matched."""
+        import torch
+        from types import SimpleNamespace
+        n = self.size
+        if out is None:
+            out = SimpleNamespace(meas=torch.empty((7, max(n, 1)), dtype=self.torch_dtype(), device="cuda"),
+                                  has_meas=torch.empty(max(n, 1), dtype=torch.uint8, device="cuda"))
+        ld = out.meas.stride(0)
+        if isinstance(det, torch.Tensor) and det.is_cuda:
+            assert det.dtype == torch.float64 and det.dim() == 2 and det.shape[1] == 7 and det.is_contiguous()
+            M = int(det.shape[0])
+            if not hasattr(out, "info"):
+                out.det_of_slot = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+                out.d2_of_slot = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
+                out.slot_of_det = torch.empty(M, dtype=torch.int32, device="cuda")
+                out.d2_of_det = torch.empty(M, dtype=torch.float64, device="cuda")
+                out.info = torch.empty(4, dtype=torch.int32, device="cuda")
+            _check(self._lib.target_batch_associate_dev(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), out.meas.data_ptr(), ld,
+                                                        out.has_meas.data_ptr(), out.det_of_slot.data_ptr(), out.d2_of_slot.data_ptr(),
+                                                        out.slot_of_det.data_ptr(), out.d2_of_det.data_ptr(), out.info.data_ptr()),
+                   "target_batch_associate_dev")
+            return out
+        det = np.ascontiguousarray(np.asarray(det, dtype=np.float64).reshape(-1, 7))
+        M = det.shape[0]
+        out.ids_of_det = np.empty(M, dtype=np.uint32)
+        out.slot_of_det = np.empty(M, dtype=np.int32)
+        out.d2_of_det = np.empty(M)
+        unmatched = np.empty(max(M, 1), dtype=np.int64)
+        nu = C.c_long(0)
+        out.info = np.zeros(4, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        out.matched = _check(self._lib.target_batch_associate(
+            self._h, float(dt), _dp(det), M, float(gate), int(rounds), out.meas.data_ptr(), ld, out.has_meas.data_ptr(),
+            out.ids_of_det.ctypes.data_as(capi.c_uint_p), ip(out.slot_of_det), _dp(out.d2_of_det),
+            unmatched.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nu), ip(out.info)), "target_batch_associate")
+        out.unmatched = unmatched[:nu.value].copy()
+        return out
+
     def pack_meas(self, meas_aos, out=None):
         """CUDA double [n,7] (the reference's row layout) -> SoA [7,n] in the batch precision."""
         import torch
@@ -1117,6 +1165,58 @@ class TargetManager:
                                                                    None if ok is None else ok.ctypes.data_as(capi.c_ubyte_p)),
                        "target_manager_crossing_cov_batch")
         return found, cov, sigma, None if ok is None else ok.astype(bool)
+
+    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None):
+        """Pair a frame of unlabelled detections with every target of the manager on the device (target_manager_associate[_dev];
+        a manager on one device only): as Batch.associate, a detection picking among the targets of all batches by (d2, batch,
+        slot).  det: [M, 7].  A CUDA double tensor: the device form, no host wait.  Returns a SimpleNamespace: meas / has_meas /
+        det_of_slot / d2_of_slot are LISTS with one CUDA tensor per batch (batches() order; meas[i] is [1, 7, size_i], the
+        one-tick form step_sequence_all(dt, r.meas, r.has_meas, n_ticks=1) reads, has_meas[i] [1, size_i]), slot_of_det /
+        batch_of_det / d2_of_det [M] and info [4] CUDA tensors.  out: such a namespace to write into.
+        A host array: the host form; the per-detection results come back as NumPy arrays ids_of_det, batch_of_det, slot_of_det,
+        d2_of_det, unmatched, info, and matched."""
+        import torch
+        from types import SimpleNamespace
+        bs = self.batches()
+        nb = len(bs)
+        if out is None:
+            out = SimpleNamespace(meas=[torch.empty((1, 7, max(b.size, 1)), dtype=b.torch_dtype(), device="cuda") for b in bs],
+                                  has_meas=[torch.empty((1, max(b.size, 1)), dtype=torch.uint8, device="cuda") for b in bs],
+                                  det_of_slot=[torch.empty(max(b.size, 1), dtype=torch.int32, device="cuda") for b in bs],
+                                  d2_of_slot=[torch.empty(max(b.size, 1), dtype=torch.float64, device="cuda") for b in bs])
+        per = (capi.AssocOut * max(nb, 1))()
+        for i in range(nb):
+            per[i].meas_out_dev, per[i].ld = out.meas[i].data_ptr(), out.meas[i].stride(1)
+            per[i].has_meas_out_dev = out.has_meas[i].data_ptr()
+            per[i].det_of_slot_dev, per[i].d2_of_slot_dev = out.det_of_slot[i].data_ptr(), out.d2_of_slot[i].data_ptr()
+        if isinstance(det, torch.Tensor) and det.is_cuda:
+            assert det.dtype == torch.float64 and det.dim() == 2 and det.shape[1] == 7 and det.is_contiguous()
+            M = int(det.shape[0])
+            if not hasattr(out, "info"):
+                out.slot_of_det = torch.empty(M, dtype=torch.int32, device="cuda")
+                out.batch_of_det = torch.empty(M, dtype=torch.int32, device="cuda")
+                out.d2_of_det = torch.empty(M, dtype=torch.float64, device="cuda")
+                out.info = torch.empty(4, dtype=torch.int32, device="cuda")
+            _check(self._lib.target_manager_associate_dev(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), per, nb,
+                                                          out.slot_of_det.data_ptr(), out.batch_of_det.data_ptr(), out.d2_of_det.data_ptr(),
+                                                          out.info.data_ptr()), "target_manager_associate_dev")
+            return out
+        det = np.ascontiguousarray(np.asarray(det, dtype=np.float64).reshape(-1, 7))
+        M = det.shape[0]
+        out.ids_of_det = np.empty(M, dtype=np.uint32)
+        out.batch_of_det = np.empty(M, dtype=np.int32)
+        out.slot_of_det = np.empty(M, dtype=np.int32)
+        out.d2_of_det = np.empty(M)
+        unmatched = np.empty(max(M, 1), dtype=np.int64)
+        nu = C.c_long(0)
+        out.info = np.zeros(4, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        out.matched = _check(self._lib.target_manager_associate(
+            self._h, float(dt), _dp(det), M, float(gate), int(rounds), per, nb, out.ids_of_det.ctypes.data_as(capi.c_uint_p),
+            ip(out.batch_of_det), ip(out.slot_of_det), _dp(out.d2_of_det), unmatched.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nu),
+            ip(out.info)), "target_manager_associate")
+        out.unmatched = unmatched[:nu.value].copy()
+        return out
 
     def population_tick(self):
         """True if step_sequence_all steps every batch with ONE launch per tick (target_manager_population_tick)."""
