@@ -263,73 +263,59 @@ __global__ void assoc_dets_kernel(long M, const AssocRow* table, const int* row_
 }
 
 // ---------------------------------------------------------------- the scratch
-namespace {
-template <class P>
-void regrow(P*& p, size_t bytes) {
-  device_free(p);
-  p = nullptr;
-  void* q = nullptr;
-  TE_HIP_CHECK(hipMalloc(&q, bytes ? bytes : 16));
-  p = (P*)q;
-}
-}  // namespace
-
-AssocScratch::~AssocScratch() {
-  device_free(table); device_free(det_of_row); device_free(d2_of_row); device_free(row_of_det); device_free(d2_of_det);
-  device_free(part_rows_d2); device_free(part_rows_idx); device_free(part_dets_d2); device_free(part_dets_idx); device_free(state);
-  device_free(det_stage); device_free(result_dev);
-  if (result_host) (void)hipHostFree(result_host);
-}
-
+// (a scratch carries nothing over: every block is released before its replacement exists, with its capacity at 0 meanwhile, so a
+// throw leaves a scratch that the next call grows again.  A first call allocates every block, a call with a zero count included --
+// the presence test is on the block of each group that is allocated last --, so no launch or copy is ever handed a null array)
 void AssocScratch::ensure(long rows, long dets, long part_rows, long part_dets) {
-  if (!state) regrow(state, 16);
-  if (rows > cap_rows_ || !table) {
-    const long want = rows > 64 ? rows : 64;
-    regrow(table, (size_t)want * sizeof(AssocRow)); regrow(det_of_row, (size_t)want * 4); regrow(d2_of_row, (size_t)want * 8);
-    cap_rows_ = want;
+  if (!state) state.alloc(4);
+  if (rows > cap_rows_ || !d2_of_row) {
+    const size_t want = rows > 64 ? rows : 64;
+    cap_rows_ = 0;
+    table.alloc(want); det_of_row.alloc(want); d2_of_row.alloc(want);
+    cap_rows_ = (long)want;
   }
-  if (dets > cap_dets_ || !row_of_det) {
-    const long want = dets > 64 ? dets : 64;
-    regrow(row_of_det, (size_t)want * 4); regrow(d2_of_det, (size_t)want * 8);
-    cap_dets_ = want;
+  if (dets > cap_dets_ || !d2_of_det) {
+    const size_t want = dets > 64 ? dets : 64;
+    cap_dets_ = 0;
+    row_of_det.alloc(want); d2_of_det.alloc(want);
+    cap_dets_ = (long)want;
   }
-  if (part_rows > cap_part_rows_ || !part_rows_d2) {
-    const long want = part_rows > 64 ? part_rows : 64;
-    regrow(part_rows_d2, (size_t)want * 8); regrow(part_rows_idx, (size_t)want * 4);
-    cap_part_rows_ = want;
+  if (part_rows > cap_part_rows_ || !part_rows_idx) {
+    const size_t want = part_rows > 64 ? part_rows : 64;
+    cap_part_rows_ = 0;
+    part_rows_d2.alloc(want); part_rows_idx.alloc(want);
+    cap_part_rows_ = (long)want;
   }
-  if (part_dets > cap_part_dets_ || !part_dets_d2) {
-    const long want = part_dets > 64 ? part_dets : 64;
-    regrow(part_dets_d2, (size_t)want * 8); regrow(part_dets_idx, (size_t)want * 4);
-    cap_part_dets_ = want;
+  if (part_dets > cap_part_dets_ || !part_dets_idx) {
+    const size_t want = part_dets > 64 ? part_dets : 64;
+    cap_part_dets_ = 0;
+    part_dets_d2.alloc(want); part_dets_idx.alloc(want);
+    cap_part_dets_ = (long)want;
   }
 }
 
 void AssocScratch::ensure_host(long dets) {
-  if (dets <= cap_host_ && det_stage) return;
-  const long want = dets > 64 ? dets : 64;
-  regrow(det_stage, (size_t)want * 7 * 8);
-  regrow(result_dev, result_bytes(want));
-  if (result_host) (void)hipHostFree(result_host);
-  result_host = nullptr;
-  void* q = nullptr;
-  TE_HIP_CHECK(hipHostMalloc(&q, result_bytes(want), hipHostMallocDefault));
-  result_host = (char*)q;
-  cap_host_ = want;
+  if (dets <= cap_host_ && result_host) return;
+  const size_t want = dets > 64 ? dets : 64;
+  cap_host_ = 0;
+  det_stage.alloc(want * 7);
+  result_dev.alloc(result_bytes((long)want));
+  result_host.alloc(result_bytes((long)want));
+  cap_host_ = (long)want;
 }
 
 // ---------------------------------------------------------------- the launches
 void launch_assoc_match(const AssocScratch& s, long rows, const double* det, long M, double gate, int rounds, int forced_chunks, hipStream_t st) {
   const long most = rows > M ? rows : M;
   hipLaunchKernelGGL(assoc_init_kernel, dim3((unsigned)((most + 255) / 256 > 0 ? (most + 255) / 256 : 1)), dim3(256), 0, st, rows, M,
-                     s.det_of_row, s.d2_of_row, s.row_of_det, s.d2_of_det, s.state);
+                     s.det_of_row.get(), s.d2_of_row.get(), s.row_of_det.get(), s.d2_of_det.get(), s.state.get());
   if (rows <= 0 || M <= 0) return;   // (the state says settled, no round run)
   const AssocGrid gr = plan_assoc_grid(rows, M, forced_chunks);   // target-major: rows own, detections walked
   const AssocGrid gd = plan_assoc_grid(M, rows, forced_chunks);   // detection-major
-  AssocScanArgs ar{s.table, det, s.det_of_row, s.row_of_det, s.state, rows, M, gate, gr, s.part_rows_d2, s.part_rows_idx};
-  AssocScanArgs ad{s.table, det, s.det_of_row, s.row_of_det, s.state, rows, M, gate, gd, s.part_dets_d2, s.part_dets_idx};
-  AssocResolveArgs rs{rows, M, gr.chunks, gd.chunks, s.part_rows_d2, s.part_rows_idx, s.part_dets_d2, s.part_dets_idx,
-                      s.det_of_row, s.d2_of_row, s.row_of_det, s.d2_of_det, s.state};
+  AssocScanArgs ar{s.table.get(), det, s.det_of_row.get(), s.row_of_det.get(), s.state.get(), rows, M, gate, gr, s.part_rows_d2.get(), s.part_rows_idx.get()};
+  AssocScanArgs ad{s.table.get(), det, s.det_of_row.get(), s.row_of_det.get(), s.state.get(), rows, M, gate, gd, s.part_dets_d2.get(), s.part_dets_idx.get()};
+  AssocResolveArgs rs{rows, M, gr.chunks, gd.chunks, s.part_rows_d2.get(), s.part_rows_idx.get(), s.part_dets_d2.get(), s.part_dets_idx.get(),
+                      s.det_of_row.get(), s.d2_of_row.get(), s.row_of_det.get(), s.d2_of_det.get(), s.state.get()};
   for (int r = 0; r < rounds; ++r) {
     hipLaunchKernelGGL(assoc_scan_rows_kernel, dim3((unsigned)gr.row_tiles, (unsigned)gr.chunks), dim3(kAssocTile), 0, st, ar);
     hipLaunchKernelGGL(assoc_scan_dets_kernel, dim3((unsigned)gd.row_tiles, (unsigned)gd.chunks), dim3(kAssocTile), 0, st, ad);
@@ -341,18 +327,18 @@ void launch_assoc_scatter(int dtype, const AssocScratch& s, long row_offset, lon
   if (size <= 0) return;
   const dim3 grid((unsigned)((size + 255) / 256)), block(256);
   if (dtype == F64)
-    hipLaunchKernelGGL((assoc_scatter_kernel<double>), grid, block, 0, st, row_offset, size, det, s.det_of_row, s.d2_of_row,
+    hipLaunchKernelGGL((assoc_scatter_kernel<double>), grid, block, 0, st, row_offset, size, det, s.det_of_row.get(), s.d2_of_row.get(),
                        static_cast<double*>(out.meas), out.ld, out.has_meas, out.det_of_slot, out.d2_of_slot);
   else if (dtype == F32)
-    hipLaunchKernelGGL((assoc_scatter_kernel<float>), grid, block, 0, st, row_offset, size, det, s.det_of_row, s.d2_of_row,
+    hipLaunchKernelGGL((assoc_scatter_kernel<float>), grid, block, 0, st, row_offset, size, det, s.det_of_row.get(), s.d2_of_row.get(),
                        static_cast<float*>(out.meas), out.ld, out.has_meas, out.det_of_slot, out.d2_of_slot);
   else
     throw std::logic_error("target_estimation_amd: associate: no scatter kernel for this precision");
 }
 
 void launch_assoc_dets(const AssocScratch& s, long M, int* slot_of_det, int* batch_of_det, double* d2_of_det, int* info, hipStream_t st) {
-  hipLaunchKernelGGL(assoc_dets_kernel, dim3((unsigned)((M + 255) / 256 > 0 ? (M + 255) / 256 : 1)), dim3(256), 0, st, M, s.table,
-                     s.row_of_det, s.d2_of_det, s.state, slot_of_det, batch_of_det, d2_of_det, info);
+  hipLaunchKernelGGL(assoc_dets_kernel, dim3((unsigned)((M + 255) / 256 > 0 ? (M + 255) / 256 : 1)), dim3(256), 0, st, M, s.table.get(),
+                     s.row_of_det.get(), s.d2_of_det.get(), s.state.get(), slot_of_det, batch_of_det, d2_of_det, info);
 }
 
 namespace {

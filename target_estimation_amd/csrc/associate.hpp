@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "associate_plan.hpp"
+#include "dev_mem.hpp"
 
 namespace te {
 
@@ -43,7 +44,6 @@ AssocTableLaunch assoc_table_launcher(int type, int dtype, int g, int layout, bo
 class AssocScratch {
  public:
   AssocScratch() = default;
-  ~AssocScratch();
   AssocScratch(const AssocScratch&) = delete;
   AssocScratch& operator=(const AssocScratch&) = delete;
   // room for `rows` table rows, `dets` detections and the two scans' partials (entries x chunks)
@@ -51,20 +51,20 @@ class AssocScratch {
   // ... and for the host forms: the staged detections, the device result and its pinned mirror
   void ensure_host(long dets);
 
-  AssocRow* table = nullptr;
-  int* det_of_row = nullptr;      // [rows]  -1: unmatched
-  double* d2_of_row = nullptr;    // [rows]  the target-major scan's d^2 of the match, -1: none
-  int* row_of_det = nullptr;      // [dets]
-  double* d2_of_det = nullptr;    // [dets]  the detection-major scan's
-  double* part_rows_d2 = nullptr; // [chunks][rows]
-  int* part_rows_idx = nullptr;
-  double* part_dets_d2 = nullptr; // [chunks][dets]
-  int* part_dets_idx = nullptr;
-  int* state = nullptr;           // {matched, rounds_run, settled, 0}
+  DeviceBuf<AssocRow> table;
+  DeviceBuf<int> det_of_row;       // [rows]  -1: unmatched
+  DeviceBuf<double> d2_of_row;     // [rows]  the target-major scan's d^2 of the match, -1: none
+  DeviceBuf<int> row_of_det;       // [dets]
+  DeviceBuf<double> d2_of_det;     // [dets]  the detection-major scan's
+  DeviceBuf<double> part_rows_d2;  // [chunks][rows]
+  DeviceBuf<int> part_rows_idx;
+  DeviceBuf<double> part_dets_d2;  // [chunks][dets]
+  DeviceBuf<int> part_dets_idx;
+  DeviceBuf<int> state;            // {matched, rounds_run, settled, 0}
   // host forms: det [dets][7] | the result: slot int[dets] | batch int[dets] | d2 double[dets] | info int[4]
-  double* det_stage = nullptr;
-  char* result_dev = nullptr;
-  char* result_host = nullptr;
+  DeviceBuf<double> det_stage;
+  DeviceBuf<char> result_dev;
+  PinnedBuf<char> result_host;
   static size_t off_slot(long) { return 0; }
   static size_t off_batch(long dets) { return (size_t)dets * 4; }
   static size_t off_d2(long dets) { return (size_t)dets * 8; }

@@ -98,16 +98,15 @@ void Batch::demote_shared() {
   const Ops* plain = get_ops(type_, dtype_, lanes_code_);
   if (cap_ > 0) {
     const size_t bytes = (size_t)(cap_ / plain->L.tpw) * (size_t)plain->L.tile_bytes;
-    char* rec = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&rec, bytes));
-    TE_HIP_CHECK(hipMemsetAsync(rec, 0, bytes, stream_));
-    ops_->expand(records(), rec, n_, stream_);
+    DeviceBuf<char> rec;
+    rec.alloc(bytes);
+    TE_HIP_CHECK(hipMemsetAsync(rec.get(), 0, bytes, stream_));
+    ops_->expand(records(), rec.get(), n_, stream_);
     TE_HIP_CHECK(hipGetLastError());
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    device_free(d_rec_);
-    device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;   // (the plain form has no uniform tiles)
-    device_free(d_rec_alt_); d_rec_alt_ = nullptr; alt_failed_ = false;   // re-created in the plain form by the next A -> B tick
-    d_rec_ = rec;
+    d_rec_ = std::move(rec);
+    d_tile_blk_.reset(); d_tile_uni_.reset();   // (the plain form has no uniform tiles)
+    d_rec_alt_.reset(); alt_failed_ = false;   // re-created in the plain form by the next A -> B tick
   }
   ops_ = plain;
   cache_valid_ = false;
@@ -135,14 +134,13 @@ int Batch::add_class(const double* Q, const double* R) {
   const size_t es = elem_size();
   if (n_classes_ == qr_cap_) {   // grow the device table (geometric); recorded graphs hold the old pointer
     const int want = qr_cap_ ? qr_cap_ * 2 : 1;
-    void* nt = nullptr;
-    TE_HIP_CHECK(hipMalloc(&nt, (size_t)want * words * es));
+    DeviceBuf<char> nt;
+    nt.alloc((size_t)want * words * es);
     if (n_classes_ > 0) {
       TE_HIP_CHECK(hipStreamSynchronize(stream_));
-      TE_HIP_CHECK(hipMemcpy(nt, d_qr_, (size_t)n_classes_ * words * es, hipMemcpyDeviceToDevice));
+      TE_HIP_CHECK(hipMemcpy(nt.get(), d_qr_.get(), (size_t)n_classes_ * words * es, hipMemcpyDeviceToDevice));
     }
-    device_free(d_qr_);
-    d_qr_ = nt;
+    d_qr_ = std::move(nt);
     qr_cap_ = want;
     drop_graphs();
   }
@@ -156,7 +154,7 @@ int Batch::add_class(const double* Q, const double* R) {
     for (int c = 0; c < n; ++c) put(qr_q_word(type_, sep, r, c), Q[r * n + c]);
   for (int r = 0; r < m; ++r)
     for (int c = 0; c < m; ++c) put(qr_r_word(type_, sep, r, c), R[r * m + c]);
-  TE_HIP_CHECK(hipMemcpy(static_cast<char*>(d_qr_) + (size_t)n_classes_ * words * es, host.data(), host.size(), hipMemcpyHostToDevice));
+  TE_HIP_CHECK(hipMemcpy(d_qr_.get() + (size_t)n_classes_ * words * es, host.data(), host.size(), hipMemcpyHostToDevice));
   class_index_.emplace(class_key(Q, n * n, R, m * m), n_classes_);
   class_qr_.emplace_back((size_t)(n * n + m * m));
   std::copy(Q, Q + n * n, class_qr_.back().begin());
@@ -174,7 +172,7 @@ __global__ void run_moves_kernel(unsigned char* run, const int* src, const int* 
 }  // namespace
 
 void Batch::run_move(long src, long dst) {
-  if (d_run_) TE_HIP_CHECK(hipMemcpyAsync(d_run_ + dst, d_run_ + src, 1, hipMemcpyDeviceToDevice, stream_));
+  if (d_run_) TE_HIP_CHECK(hipMemcpyAsync(d_run_.get() + dst, d_run_.get() + src, 1, hipMemcpyDeviceToDevice, stream_));
   p0idx_dirty_.mark(dst, 1);
 }
 
@@ -190,18 +188,20 @@ void Batch::prepare_p0_tables() {
   if (u.grow) {   // recorded sequences hold the old table
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
     drop_graphs();
-    device_free(d_p0tab_); d_p0tab_ = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&d_p0tab_, sizeof(double) * nn * (size_t)u.new_cap));
+    const P0TableMirror planned = p0tab_dev_;
+    p0tab_dev_.reset();   // (an allocation that throws leaves an empty table, which the next call builds whole)
+    d_p0tab_.alloc(nn * (size_t)u.new_cap);
+    p0tab_dev_ = planned;
   }
   if (u.count > 0) {
     std::vector<double> rows(nn * (size_t)u.count);
     for (long r = 0; r < u.count; ++r) std::copy(p0_tab_[(size_t)(u.first + r)].begin(), p0_tab_[(size_t)(u.first + r)].end(), rows.begin() + (size_t)r * nn);
-    TE_HIP_CHECK(hipMemcpyAsync(d_p0tab_ + (size_t)u.first * nn, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(d_p0tab_.get() + (size_t)u.first * nn, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));   // (rows goes out of scope)
   }
   p0idx_dirty_.clip(n_);
   if (!p0idx_dirty_.empty()) {
-    TE_HIP_CHECK(hipMemcpyAsync(d_p0idx_ + p0idx_dirty_.lo, slot_p0_.data() + p0idx_dirty_.lo, sizeof(int) * (size_t)(p0idx_dirty_.hi - p0idx_dirty_.lo),
+    TE_HIP_CHECK(hipMemcpyAsync(d_p0idx_.get() + p0idx_dirty_.lo, slot_p0_.data() + p0idx_dirty_.lo, sizeof(int) * (size_t)(p0idx_dirty_.hi - p0idx_dirty_.lo),
                                 hipMemcpyHostToDevice, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));   // (slot_p0_ may change before the copy has run)
     p0idx_dirty_.clear();
@@ -210,8 +210,8 @@ void Batch::prepare_p0_tables() {
 
 void Batch::fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const {
   if (!innov.reacq.on) return;
-  p.reacq = 1; p.reacq_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_event = innov.reacq.row(s_call);
-  p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+  p.reacq = 1; p.reacq_k = innov.reacq.k; p.reacq_run = d_run_.get(); p.reacq_event = innov.reacq.row(s_call);
+  p.reacq_p0 = d_p0tab_.get(); p.reacq_p0_idx = d_p0idx_.get();
 }
 
 void Batch::set_update_gate(const UpdateGate& g) {
@@ -234,10 +234,9 @@ void Batch::pol_reserve(long k) {
   if (k <= pol_cap_) return;
   const long want = (std::max<long>(std::max<long>(k, 64), pol_cap_ * 2) + 15) / 16 * 16;
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  if (h_pol_) (void)hipHostFree(h_pol_);
-  h_pol_ = nullptr; d_pol_ = nullptr; pol_cap_ = 0;
-  TE_HIP_CHECK(hipHostMalloc((void**)&h_pol_, (size_t)want * (sizeof(double) + 1) + 64, hipHostMallocMapped | hipHostMallocCoherent));
-  TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d_pol_, h_pol_, 0));
+  pol_cap_ = 0; d_pol_ = nullptr;
+  h_pol_.alloc((size_t)want * (sizeof(double) + 1) + 64, kPinnedMapped);
+  d_pol_ = h_pol_.dev();
   pol_cap_ = want;
 }
 
@@ -248,14 +247,14 @@ void Batch::fill_update_gate(StepParams& p, long k, double* nis_dev, unsigned ch
   p.nis = nis_dev; p.gate_id_event = event_dev;
   if (pol_.max_rejects >= 0) {
     prepare_p0_tables();
-    p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+    p.reacq_run = d_run_.get(); p.reacq_p0 = d_p0tab_.get(); p.reacq_p0_idx = d_p0idx_.get();
   }
 }
 
 void Batch::rejection_runs(unsigned char* out) {
   flush();
   if (n_ <= 0) return;
-  TE_HIP_CHECK(hipMemcpyAsync(out, d_run_, (size_t)n_, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(out, d_run_.get(), (size_t)n_, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -263,7 +262,7 @@ int Batch::rejection_run(long slot) {
   flush();
   if (slot < 0 || slot >= n_) throw std::runtime_error("target_estimation_amd: rejection_run: bad slot");
   unsigned char c = 0;
-  TE_HIP_CHECK(hipMemcpyAsync(&c, d_run_ + slot, 1, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(&c, d_run_.get() + slot, 1, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   return (int)c;
 }
@@ -283,10 +282,10 @@ void Batch::launch_step(const StepParams& p, hipStream_t st, int meas_rows) {
   const unsigned blocks = (unsigned)((p.n + 255) / 256);
   if (dtype_ == F64)
     keep_measurement_kernel<double><<<blocks, 256, 0, st>>>(static_cast<const double*>(p.meas), p.meas_ld, p.tick_stride, has, has_stride,
-                                                            p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_);
+                                                            p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_.get());
   else
     keep_measurement_kernel<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(p.meas), p.meas_ld, p.tick_stride, has, has_stride,
-                                                           p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_);
+                                                           p.n_ticks, p.idx, p.n, meas_rows, d_lastmeas_.get());
 }
 
 void Batch::set_keep_measurement(bool on) {
@@ -296,13 +295,12 @@ void Batch::set_keep_measurement(bool on) {
   drop_graphs();   // recorded sequences do (not) contain the row kernels
   if (on) {
     if (cap_ > 0) {
-      TE_HIP_CHECK(hipMalloc((void**)&d_lastmeas_, sizeof(double) * 7 * (size_t)cap_));
-      init_measured_rows_kernel<<<(unsigned)((cap_ * 7 + 255) / 256), 256, 0, stream_>>>(d_lastmeas_, 0, cap_);
+      d_lastmeas_.alloc(7 * (size_t)cap_);
+      init_measured_rows_kernel<<<(unsigned)((cap_ * 7 + 255) / 256), 256, 0, stream_>>>(d_lastmeas_.get(), 0, cap_);
       TE_HIP_CHECK(hipGetLastError());
     }
   } else {
-    device_free(d_lastmeas_);
-    d_lastmeas_ = nullptr;
+    d_lastmeas_.reset();
   }
   keep_meas_ = on;
 }
@@ -312,10 +310,10 @@ void Batch::measured_poses(const int* slots, long n, double* out) {
   flush();
   if (n <= 0) return;
   if (!slots) {
-    TE_HIP_CHECK(hipMemcpyAsync(out, d_lastmeas_, sizeof(double) * 7 * (size_t)n, hipMemcpyDeviceToHost, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(out, d_lastmeas_.get(), sizeof(double) * 7 * (size_t)n, hipMemcpyDeviceToHost, stream_));
   } else {
     for (long i = 0; i < n; ++i)
-      TE_HIP_CHECK(hipMemcpyAsync(out + 7 * i, d_lastmeas_ + 7 * (long)slots[i], sizeof(double) * 7, hipMemcpyDeviceToHost, stream_));
+      TE_HIP_CHECK(hipMemcpyAsync(out + 7 * i, d_lastmeas_.get() + 7 * (long)slots[i], sizeof(double) * 7, hipMemcpyDeviceToHost, stream_));
   }
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
@@ -325,7 +323,7 @@ void Batch::class_matrices(long slot, double* Q, double* R) {
   int cls = 0;
   if (n_classes_ > 1) {
     flush();
-    TE_HIP_CHECK(hipMemcpyAsync(&cls, d_cls_ + slot, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(&cls, d_cls_.get() + slot, sizeof(int), hipMemcpyDeviceToHost, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
   }
   const std::vector<double>& qr = class_qr_.at((size_t)cls);
@@ -367,11 +365,11 @@ void Batch::settle_tiles() {
   ut_flagged_ = false;
   if (!d_tile_uni_) return;
   if (n_ > 0 && ops_->settle) {
-    ops_->settle(d_rec_, n_, d_tile_blk_, d_tile_uni_, stream_);
+    ops_->settle(d_rec_.get(), n_, d_tile_blk_.get(), d_tile_uni_.get(), stream_);
     TE_HIP_CHECK(hipGetLastError());
   }
   // (also for a batch emptied by erases: its flags would otherwise outlive the targets they described)
-  TE_HIP_CHECK(hipMemsetAsync(d_tile_uni_, 0, sizeof(int) * (size_t)(cap_ / ops_->L.tpw), stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d_tile_uni_.get(), 0, sizeof(int) * (size_t)(cap_ / ops_->L.tpw), stream_));
 }
 
 long Batch::count_uniform(long* targets_in_them) {
@@ -379,7 +377,7 @@ long Batch::count_uniform(long* targets_in_them) {
   if (!ut_flagged_ || !d_tile_uni_ || n_ <= 0) return 0;
   const long tpw = ops_->L.tpw, tiles = (n_ + tpw - 1) / tpw;
   std::vector<int> h((size_t)tiles);
-  TE_HIP_CHECK(hipMemcpyAsync(h.data(), d_tile_uni_, sizeof(int) * (size_t)tiles, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(h.data(), d_tile_uni_.get(), sizeof(int) * (size_t)tiles, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   long k = 0, targets = 0;
   for (long t = 0; t < tiles; ++t)
@@ -395,12 +393,12 @@ long Batch::uniform_tiles() {
 
 StepParams Batch::dense_params() {
   StepParams p;
-  p.rec = d_rec_; p.qr = d_qr_; p.cls = n_classes_ > 1 ? d_cls_ : nullptr; p.n = n_; p.idx = nullptr;
+  p.rec = d_rec_.get(); p.qr = d_qr_.get(); p.cls = n_classes_ > 1 ? d_cls_.get() : nullptr; p.n = n_; p.idx = nullptr;
   p.meas = nullptr; p.meas_ld = 0; p.has_meas = nullptr; p.dt_per = nullptr; p.dt = 0.0;
-  p.t_base = d_tbase_; p.nm_base = d_nmbase_;
-  p.gate_row = d_has_eff_;
+  p.t_base = d_tbase_.get(); p.nm_base = d_nmbase_.get();
+  p.gate_row = d_has_eff_.get();
   if (uniform_tiles_enabled() && d_tile_uni_) {
-    p.tile_blk = d_tile_blk_; p.tile_uni = d_tile_uni_;
+    p.tile_blk = d_tile_blk_.get(); p.tile_uni = d_tile_uni_.get();
     p.promote = (recording_ || dense_streak_ >= promote_after()) ? 1 : 0;
     if (!recording_) {   // (a recording launches nothing: note_replay() when it is replayed)
       if (p.promote) ut_flagged_ = true;
@@ -412,38 +410,19 @@ StepParams Batch::dense_params() {
 
 StepParams Batch::base_params() {
   StepParams p;
-  p.rec = records(); p.qr = d_qr_; p.cls = n_classes_ > 1 ? d_cls_ : nullptr; p.n = n_; p.idx = nullptr;
+  p.rec = records(); p.qr = d_qr_.get(); p.cls = n_classes_ > 1 ? d_cls_.get() : nullptr; p.n = n_; p.idx = nullptr;
   p.meas = nullptr; p.meas_ld = 0; p.has_meas = nullptr; p.dt_per = nullptr; p.dt = 0.0;
-  p.t_base = d_tbase_; p.nm_base = d_nmbase_;
+  p.t_base = d_tbase_.get(); p.nm_base = d_nmbase_.get();
   return p;
 }
 
 Batch::~Batch() {
   if (live_.active) { try { live_stop(); } catch (...) {} }
-  if (live_.zombie && live_.stream) (void)hipStreamSynchronize(live_.stream);   // (told to stop: it ends as soon as it starts)
+  if (live_.zombie && live_.stream) (void)hipStreamSynchronize(live_.stream.get());   // (told to stop: it ends as soon as it starts)
   live_release();
   (void)hipStreamSynchronize(stream_);
   drop_graphs();
-  if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
-  device_free(d_tile_blk_); device_free(d_tile_uni_);
-  device_free(d_qr_); device_free(d_rec_); device_free(d_rec_alt_); device_free(d_tbase_); device_free(d_nmbase_); device_free(d_cls_);
-  device_free(d_has_eff_); device_free(d_run_); device_free(d_p0idx_); device_free(d_p0tab_);
-  device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_P0_);
-  device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
-  device_free(d_dtper_); device_free(d_lastmeas_);
-  if (h_pin_) (void)hipHostFree(h_pin_);
-  if (h_pol_) (void)hipHostFree(h_pol_);
-  device_free(bar_pin_);
-  if (h_cache_) (void)hipHostFree(h_cache_);
-  device_free(d_state_scratch_);
-  if (h_done_) (void)hipHostFree(h_done_);
-  if (d_done_count_) device_free(d_done_count_);
-  if (live_.h_block) (void)hipHostFree(live_.h_block);
-  device_free(live_.bar_bell);
-  device_free(live_.d_block);
-  if (live_.stream) (void)hipStreamDestroy(live_.stream);
-  if (live_.ready) (void)hipEventDestroy(live_.ready);
-}
+}   // (everything else is the members': batch_store.hpp on their order)
 
 long Batch::zigzag_min_bytes() {
   static const long v = [] { const char* e = std::getenv("TE_ZIGZAG_MIN_MB"); return (e ? std::atol(e) : 128L) << 20; }();
@@ -458,15 +437,13 @@ long Batch::pingpong_min_bytes() {
 char* Batch::alt_records() {
   if (!d_rec_alt_ && !alt_failed_) {   // same capacity as d_rec_; zero-filled so that the idle lanes of a ragged last tile hold defined words
     const size_t bytes = (size_t)(cap_ / ops_->L.tpw) * (size_t)ops_->L.tile_bytes;
-    if (hipMalloc((void**)&d_rec_alt_, bytes) != hipSuccess) {   // no room for a second copy of the state: stay in place (same results)
-      (void)hipGetLastError();
-      d_rec_alt_ = nullptr;
+    if (!d_rec_alt_.try_alloc(bytes)) {   // no room for a second copy of the state: stay in place (same results)
       alt_failed_ = true;
       return nullptr;
     }
-    TE_HIP_CHECK(hipMemsetAsync(d_rec_alt_, 0, bytes, stream_));
+    TE_HIP_CHECK(hipMemsetAsync(d_rec_alt_.get(), 0, bytes, stream_));
   }
-  return d_rec_alt_;
+  return d_rec_alt_.get();
 }
 
 void Batch::synchronize() {
@@ -512,58 +489,54 @@ void Batch::reserve(long n) {
   long want = std::max(n, cap_ * 2);
   want = (want + tpw - 1) / tpw * tpw;
   const size_t new_bytes = (size_t)(want / tpw) * (size_t)ops_->L.tile_bytes;
-  char* rec = nullptr;
-  TClock* tb = nullptr;
-  int* nm = nullptr;
-  int* cl = nullptr;
-  TE_HIP_CHECK(hipMalloc((void**)&rec, new_bytes));
-  TE_HIP_CHECK(hipMalloc((void**)&tb, sizeof(TClock) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&nm, sizeof(int) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&cl, sizeof(int) * want));
-  TE_HIP_CHECK(hipMemsetAsync(rec, 0, new_bytes, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(tb, 0, sizeof(TClock) * want, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(nm, 0, sizeof(int) * want, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(cl, 0, sizeof(int) * want, stream_));
+  const size_t tiles = uniform_tiles_enabled() ? (size_t)(want / tpw) : 0;   // about 1.5 B per target (angular_rates: 96 + 4 B per 64)
+  // Every new array first, into local owners: a throw anywhere before the commit below leaves the batch exactly as it was.
+  DeviceBuf<char> rec;
+  DeviceBuf<TClock> tb;
+  DeviceBuf<int> nm, cl, p0idx, uni;
+  DeviceBuf<double> lm, blk;
+  DeviceBuf<unsigned char> has_eff, run;
+  rec.alloc(new_bytes);
+  tb.alloc((size_t)want);
+  nm.alloc((size_t)want);
+  cl.alloc((size_t)want);
+  if (keep_meas_) lm.alloc(7 * (size_t)want);
+  has_eff.alloc((size_t)want);   // (the gate's mask row is written whole by every launch that reads it: no contents to carry over)
+  run.alloc((size_t)want);
+  p0idx.alloc((size_t)want);
+  if (tiles) { blk.alloc(tiles * (size_t)ops_->L.lin_words); uni.alloc(tiles); }
+  TE_HIP_CHECK(hipMemsetAsync(rec.get(), 0, new_bytes, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(tb.get(), 0, sizeof(TClock) * want, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(nm.get(), 0, sizeof(int) * want, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(cl.get(), 0, sizeof(int) * want, stream_));
   if (cap_ > 0) {
-    TE_HIP_CHECK(hipMemcpyAsync(rec, d_rec_, (size_t)(cap_ / tpw) * (size_t)ops_->L.tile_bytes, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(tb, d_tbase_, sizeof(TClock) * cap_, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(nm, d_nmbase_, sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(cl, d_cls_, sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(rec.get(), d_rec_.get(), (size_t)(cap_ / tpw) * (size_t)ops_->L.tile_bytes, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(tb.get(), d_tbase_.get(), sizeof(TClock) * cap_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(nm.get(), d_nmbase_.get(), sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(cl.get(), d_cls_.get(), sizeof(int) * cap_, hipMemcpyDeviceToDevice, stream_));
   }
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  device_free(d_rec_); device_free(d_tbase_); device_free(d_nmbase_); device_free(d_cls_);
-  device_free(d_rec_alt_); d_rec_alt_ = nullptr; alt_failed_ = false;   // re-created at the new capacity by the next A -> B tick
-  if (keep_meas_) {
-    double* lm = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&lm, sizeof(double) * 7 * (size_t)want));
-    if (d_lastmeas_ && cap_ > 0) TE_HIP_CHECK(hipMemcpy(lm, d_lastmeas_, sizeof(double) * 7 * (size_t)cap_, hipMemcpyDeviceToDevice));
-    device_free(d_lastmeas_);
-    d_lastmeas_ = lm;
-  }
-  d_rec_ = rec; d_tbase_ = tb; d_nmbase_ = nm; d_cls_ = cl; cap_ = want;
-  // (the gate's mask row is written whole by every launch that reads it: no contents to carry over)
-  device_free(d_has_eff_); d_has_eff_ = nullptr;
-  TE_HIP_CHECK(hipMalloc((void**)&d_has_eff_, (size_t)want));
-  {   // the rejection runs follow their targets; the slot -> row index is uploaded again from the host's (prepare_reacquire)
-    unsigned char* run = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&run, (size_t)want));
-    TE_HIP_CHECK(hipMemsetAsync(run, 0, (size_t)want, stream_));
-    if (d_run_ && n_ > 0) TE_HIP_CHECK(hipMemcpyAsync(run, d_run_, (size_t)n_, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    device_free(d_run_); d_run_ = run;
-    device_free(d_p0idx_); d_p0idx_ = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&d_p0idx_, sizeof(int) * (size_t)want));
-    p0idx_dirty_.clear(); p0idx_dirty_.mark(0, want);
-  }
-  device_free(d_tile_blk_); d_tile_blk_ = nullptr; device_free(d_tile_uni_); d_tile_uni_ = nullptr;
-  if (uniform_tiles_enabled()) {   // about 1.5 B per target (angular_rates: 96 + 4 B per 64)
-    const size_t tiles = (size_t)(want / tpw);
-    TE_HIP_CHECK(hipMalloc((void**)&d_tile_blk_, sizeof(double) * tiles * (size_t)ops_->L.lin_words));
-    TE_HIP_CHECK(hipMalloc((void**)&d_tile_uni_, sizeof(int) * tiles));
-    TE_HIP_CHECK(hipMemsetAsync(d_tile_blk_, 0, sizeof(double) * tiles * (size_t)ops_->L.lin_words, stream_));
-    TE_HIP_CHECK(hipMemsetAsync(d_tile_uni_, 0, sizeof(int) * tiles, stream_));
+  if (lm && d_lastmeas_ && cap_ > 0) TE_HIP_CHECK(hipMemcpy(lm.get(), d_lastmeas_.get(), sizeof(double) * 7 * (size_t)cap_, hipMemcpyDeviceToDevice));
+  // the rejection runs follow their targets; the slot -> row index is uploaded again from the host's (prepare_reacquire)
+  TE_HIP_CHECK(hipMemsetAsync(run.get(), 0, (size_t)want, stream_));
+  if (d_run_ && n_ > 0) TE_HIP_CHECK(hipMemcpyAsync(run.get(), d_run_.get(), (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  if (tiles) {
+    TE_HIP_CHECK(hipMemsetAsync(blk.get(), 0, sizeof(double) * tiles * (size_t)ops_->L.lin_words, stream_));
+    TE_HIP_CHECK(hipMemsetAsync(uni.get(), 0, sizeof(int) * tiles, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
   }
+  // The commit: nothing below throws.  The old arrays are released here, behind every synchronisation above, in the old order
+  // (the price of all-or-nothing: until here the old records coexist with ALL the new arrays, not only with the new records).
+  d_rec_ = std::move(rec); d_tbase_ = std::move(tb); d_nmbase_ = std::move(nm); d_cls_ = std::move(cl);
+  d_rec_alt_.reset(); alt_failed_ = false;   // re-created at the new capacity by the next A -> B tick
+  if (keep_meas_) d_lastmeas_ = std::move(lm);
+  d_has_eff_ = std::move(has_eff);
+  d_run_ = std::move(run);
+  d_p0idx_ = std::move(p0idx);
+  p0idx_dirty_.clear(); p0idx_dirty_.mark(0, want);
+  d_tile_blk_ = std::move(blk); d_tile_uni_ = std::move(uni);
+  cap_ = want;
   drop_graphs();
 }
 
@@ -571,17 +544,19 @@ void Batch::stage_reserve(long n) {
   if (n <= stage_cap_) return;
   const long want = std::max(n, stage_cap_ * 2);
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  device_free(d_idx_); device_free(d_aos_); device_free(d_meas_); device_free(d_mask_); device_free(d_dtper_);
-  TE_HIP_CHECK(hipMalloc((void**)&d_dtper_, sizeof(double) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d_idx_, sizeof(int) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d_aos_, sizeof(double) * 19 * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d_meas_, elem_size() * 7 * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d_mask_, (size_t)want));
+  // (nothing to carry over, and up to hundreds of MB: released before the new blocks exist; a throw leaves an empty staging area)
+  stage_cap_ = 0;
+  d_idx_.reset(); d_aos_.reset(); d_meas_.reset(); d_mask_.reset(); d_dtper_.reset();
+  d_dtper_.alloc((size_t)want);
+  d_idx_.alloc((size_t)want);
+  d_aos_.alloc(19 * (size_t)want);
+  d_meas_.alloc(elem_size() * 7 * (size_t)want);
+  d_mask_.alloc((size_t)want);
   stage_cap_ = want;
 }
 
 void Batch::upload_slots(const int* slots, long n) {
-  TE_HIP_CHECK(hipMemcpyAsync(d_idx_, slots, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_idx_.get(), slots, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
 }
 
 long Batch::append(long count, const unsigned* ids, double t0, const double* P0, bool per_target_P0,
@@ -634,37 +609,37 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
   std::vector<int> slots((size_t)count);
   for (long i = 0; i < count; ++i) slots[(size_t)i] = (int)(first + i);
   upload_slots(slots.data(), count);
-  double* d_p0 = d_aos_;
-  double* d_v0 = d_aos_ + 7 * count;
-  double* d_a0 = d_aos_ + 13 * count;
+  double* d_p0 = d_aos_.get();
+  double* d_v0 = d_aos_.get() + 7 * count;
+  double* d_a0 = d_aos_.get() + 13 * count;
   TE_HIP_CHECK(hipMemcpyAsync(d_p0, p0, sizeof(double) * 7 * count, hipMemcpyHostToDevice, stream_));
   if (v0) TE_HIP_CHECK(hipMemcpyAsync(d_v0, v0, sizeof(double) * 6 * count, hipMemcpyHostToDevice, stream_));
   if (a0) TE_HIP_CHECK(hipMemcpyAsync(d_a0, a0, sizeof(double) * 6 * count, hipMemcpyHostToDevice, stream_));
   const long p0_words = (P0_index ? P0_count : (per_target_P0 ? count : 1)) * (long)N * N;
   if (p0_words > P0_cap_) {
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    device_free(d_P0_);
-    TE_HIP_CHECK(hipMalloc((void**)&d_P0_, sizeof(double) * p0_words));
+    P0_cap_ = 0;
+    d_P0_.alloc((size_t)p0_words);
     P0_cap_ = p0_words;
   }
-  TE_HIP_CHECK(hipMemcpyAsync(d_P0_, P0, sizeof(double) * p0_words, hipMemcpyHostToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_P0_.get(), P0, sizeof(double) * p0_words, hipMemcpyHostToDevice, stream_));
   InitArgs a;
-  a.rec = records(); a.idx = d_idx_; a.n = count; a.p0 = d_p0; a.v0 = v0 ? d_v0 : nullptr; a.a0 = a0 ? d_a0 : nullptr;
-  a.P0 = d_P0_; a.per_target_P0 = per_target_P0 ? 1 : 0;
-  a.cls = d_cls_; a.cls_value = cls;
+  a.rec = records(); a.idx = d_idx_.get(); a.n = count; a.p0 = d_p0; a.v0 = v0 ? d_v0 : nullptr; a.a0 = a0 ? d_a0 : nullptr;
+  a.P0 = d_P0_.get(); a.per_target_P0 = per_target_P0 ? 1 : 0;
+  a.cls = d_cls_.get(); a.cls_value = cls;
   if (cls_of || P0_index) {   // per-entry class / initial-covariance indices: behind the slot list in the index staging
-    if (cls_of) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + count, cls_of, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.cls_of = d_idx_ + count; }
-    if (P0_index) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + 2 * count, P0_index, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.P0_index = d_idx_ + 2 * count; }
+    if (cls_of) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_.get() + count, cls_of, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.cls_of = d_idx_.get() + count; }
+    if (P0_index) { TE_HIP_CHECK(hipMemcpyAsync(d_idx_.get() + 2 * count, P0_index, sizeof(int) * count, hipMemcpyHostToDevice, stream_)); a.P0_index = d_idx_.get() + 2 * count; }
   }
   a.t_off = te_clock_sub(t0, t_acc_); a.nm_off = (int)(-nm_acc_);
-  a.t_base = d_tbase_; a.nm_base = d_nmbase_;
+  a.t_base = d_tbase_.get(); a.nm_base = d_nmbase_.get();
   ops_->init(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
-  TE_HIP_CHECK(hipMemsetAsync(d_run_ + first, 0, (size_t)count, stream_));   // a new target has no rejections behind it
+  TE_HIP_CHECK(hipMemsetAsync(d_run_.get() + first, 0, (size_t)count, stream_));   // a new target has no rejections behind it
   p0idx_dirty_.mark(first, count);
   if (d_gate_ring_) { if (gate_cap_ < cap_) gate_reserve(gate_window_); gate_reset(first, count); }
   if (keep_meas_) {
-    init_measured_rows_kernel<<<(unsigned)((count * 7 + 255) / 256), 256, 0, stream_>>>(d_lastmeas_, first, count);
+    init_measured_rows_kernel<<<(unsigned)((count * 7 + 255) / 256), 256, 0, stream_>>>(d_lastmeas_.get(), first, count);
     TE_HIP_CHECK(hipGetLastError());
   }
   if (p0_kept_ && bookkeeping) {   // host mirror of the initial covariances (initial_covariance)
@@ -693,11 +668,11 @@ unsigned Batch::erase_slot(long slot) {
   const long last = n_ - 1;
   unsigned moved = slot_ids_[(size_t)slot];
   if (slot != last) {
-    ops_->move_record(records(), last, slot, d_tbase_, d_nmbase_, d_cls_, stream_);
+    ops_->move_record(records(), last, slot, d_tbase_.get(), d_nmbase_.get(), d_cls_.get(), stream_);
     TE_HIP_CHECK(hipGetLastError());
     gate_move(last, slot);
     run_move(last, slot);
-    if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_ + 7 * slot, d_lastmeas_ + 7 * last, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
+    if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_.get() + 7 * slot, d_lastmeas_.get() + 7 * last, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
     if (p0_kept_) slot_p0_[(size_t)slot] = slot_p0_[(size_t)last];
     moved = slot_ids_[(size_t)last];
     slot_ids_[(size_t)slot] = moved;
@@ -730,16 +705,16 @@ void Batch::erase_slots(const int* slots, long k, std::vector<std::pair<unsigned
   const long m = (long)src.size();
   if (m > 0) {
     stage_reserve(2 * m);
-    TE_HIP_CHECK(hipMemcpyAsync(d_idx_, src.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(d_idx_ + m, dst.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
-    ops_->move_records(records(), d_idx_, d_idx_ + m, m, d_tbase_, d_nmbase_, d_cls_, stream_);
+    TE_HIP_CHECK(hipMemcpyAsync(d_idx_.get(), src.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(d_idx_.get() + m, dst.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, stream_));
+    ops_->move_records(records(), d_idx_.get(), d_idx_.get() + m, m, d_tbase_.get(), d_nmbase_.get(), d_cls_.get(), stream_);
     TE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(run_moves_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream_, d_run_, d_idx_, d_idx_ + m, m);
+    hipLaunchKernelGGL(run_moves_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream_, d_run_.get(), d_idx_.get(), d_idx_.get() + m, m);
     TE_HIP_CHECK(hipGetLastError());
     for (long j = 0; j < m; ++j) {
       p0idx_dirty_.mark(dst[(size_t)j], 1);
       gate_move(src[(size_t)j], dst[(size_t)j]);
-      if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_ + 7 * (long)dst[(size_t)j], d_lastmeas_ + 7 * (long)src[(size_t)j], sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
+      if (d_lastmeas_) TE_HIP_CHECK(hipMemcpyAsync(d_lastmeas_.get() + 7 * (long)dst[(size_t)j], d_lastmeas_.get() + 7 * (long)src[(size_t)j], sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
       if (p0_kept_) slot_p0_[(size_t)dst[(size_t)j]] = slot_p0_[(size_t)src[(size_t)j]];
       const unsigned id = slot_ids_[(size_t)src[(size_t)j]];
       slot_ids_[(size_t)dst[(size_t)j]] = id;
@@ -761,7 +736,7 @@ void Batch::step_dense(double dt, const void* meas_dev, long ld, const unsigned 
   flip_ = !flip_;
   if (pingpong()) p.rec_out = alt_records();
   launch_step(p, stream_, host_meas_rows_);
-  if (p.rec_out) std::swap(d_rec_, d_rec_alt_);   // later launches on the stream see the finished tick in the new current buffer
+  if (p.rec_out) swap_records();   // later launches on the stream see the finished tick in the new current buffer
   t_acc_ = te_clock_add(t_acc_, dt);
   if (meas_dev && !has_dev) nm_acc_ += 1;
 }
@@ -809,13 +784,13 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     TE_HIP_CHECK(hipGetLastError());
     if (n_ticks & 1) flip_ = !flip_;
   } else {
-    auto* hit = graphs_.find([&](const SeqKey& k) { return k.n_ticks == n_ticks && k.n == n_ && k.rec == d_rec_ && k.dt.matches(sched, dt) && k.spec.same(q); });
+    auto* hit = graphs_.find([&](const SeqKey& k) { return k.n_ticks == n_ticks && k.n == n_ && k.rec == d_rec_.get() && k.dt.matches(sched, dt) && k.spec.same(q); });
     if (!hit) {   // (full, e.g. a ring of 4096 ticks replayed in 64-tick blocks: the least recently used recording goes)
-      if (!cap_stream_) TE_HIP_CHECK(hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking));
-      hit = &graphs_.record(SeqKey{n_ticks, n_, d_rec_, q, DtKey(sched, dt)}, stream_, cap_stream_, [&] {
+      if (!cap_stream_) TE_HIP_CHECK(hipStreamCreateWithFlags(cap_stream_.out(), hipStreamNonBlocking));
+      hit = &graphs_.record(SeqKey{n_ticks, n_, d_rec_.get(), q, DtKey(sched, dt)}, stream_, cap_stream_.get(), [&] {
         const RecordingScope recording(*this);
         for (long s = 0; s < n_ticks; ++s) {
-          tick(cap_stream_, s, false);
+          tick(cap_stream_.get(), s, false);
 #ifdef TE_TEST_HOOKS   // only in libtarget_estimation_amd_testhooks.so (csrc/Makefile `testhooks`)
           if (s == 0 && std::getenv("TE_TEST_FAIL_IN_CAPTURE"))   // test hook: a launch that throws between Begin and EndCapture
             throw std::runtime_error("target_estimation_amd: injected failure inside stream capture");
@@ -826,7 +801,7 @@ void Batch::step_sequence(long n_ticks, double dt, const void* meas_base, long t
     }
     graphs_.stamp(*hit);
     if (use_graph == 2) return;  // record only
-    TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
+    TE_HIP_CHECK(hipGraphLaunch(hit->exec.get(), stream_));
     note_replay(n_ticks);
     flip_ = (n_ticks & 1) != 0;   // the graph's last tick ran forwards (odd count) or backwards
   }
@@ -859,7 +834,7 @@ void Batch::enqueue_tick(hipStream_t st, long s, double dt, const SeqSpec& q, bo
   fill_reacquire(p, q.innov, s);
   p.reverse = reverse ? 1 : 0;
   launch_step(p, st);
-  if (p.rec_out) std::swap(d_rec_, d_rec_alt_);
+  if (p.rec_out) swap_records();
   if (query && !fused_q) enqueue_own_time_query(st, q, origin, radius);
 }
 
@@ -867,7 +842,7 @@ void Batch::enqueue_own_time_query(hipStream_t st, const SeqSpec& q, const doubl
   IntersectArgs a;
   a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = std::numeric_limits<double>::quiet_NaN();
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-  a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_; a.delta = q.delta_dev; a.pose = q.pose_dev;
+  a.t_acc = TClock{0.0, 0.0}; a.t_base = d_tbase_.get(); a.delta = q.delta_dev; a.pose = q.pose_dev;
   ops_->intersect(a, st);
 }
 
@@ -884,14 +859,14 @@ void Batch::enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& q, b
     p.meas = static_cast<const char*>(q.meas_base) + (size_t)(sm * q.tick_stride) * elem_size(); p.meas_ld = q.ld;
     p.has_meas = q.has_base ? q.has_base + sm * q.has_stride : nullptr;
     p.nis = q.innov.nis_row(s); p.gate = q.innov.gate;
-    if (uniform_tiles_enabled() && d_tile_uni_) { p.tile_blk = d_tile_blk_; p.tile_uni = d_tile_uni_; }
+    if (uniform_tiles_enabled() && d_tile_uni_) { p.tile_blk = d_tile_blk_.get(); p.tile_uni = d_tile_uni_.get(); }
     fill_reacquire(p, q.innov, s);
     ops_->reacquire(make_reacquire_args(p), st);
   }
   if (q.poses.dev) {
     OutArgs o;
     o.rec = records_as_stored(); o.idx = nullptr; o.n = n_; o.pose = nullptr; o.twist = nullptr; o.acc = nullptr;
-    o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = d_tbase_;
+    o.at_time = 0; o.t1 = 0.0; o.t_acc = TClock{0.0, 0.0}; o.t_base = d_tbase_.get();
     o.pose_soa = q.poses.block(s); o.pose_ld = q.poses.ld;
     ops_->outputs(o, st);
   }
@@ -936,7 +911,7 @@ void Batch::prepare_fused_reacquire(const InnovStream& innov) {
 StepParams Batch::fused_call_params(long n_ticks, double dt, const SeqSpec& q, const DtSchedule& sched, const double* dt_tab) {
   const InnovStream& innov = q.innov;
   StepParams p = base_params();
-  p.gate_row = d_has_eff_;   // (the dense layouts' single gated ticks take their mask from the writer's row)
+  p.gate_row = d_has_eff_.get();   // (the dense layouts' single gated ticks take their mask from the writer's row)
   p.meas = q.meas_base; p.meas_ld = q.ld; p.has_meas = q.has_base; p.dt = dt;
   p.n_ticks = (int)n_ticks; p.tick_stride = q.tick_stride; p.has_stride = q.has_stride;
   p.pose = q.poses.dev; p.pose_ld = q.poses.ld; p.pose_tick_stride = q.poses.tick_stride; p.pose_ring = q.poses.ring;
@@ -945,7 +920,7 @@ StepParams Batch::fused_call_params(long n_ticks, double dt, const SeqSpec& q, c
     p.fused_gate_nis = innov.nis; p.fused_gate_nis_stride = innov.nis_tick_stride; p.fused_gate_nis_ring = innov.ring;
     p.fused_gate_innov = innov.innov; p.fused_gate_innov_ld = innov.ld; p.fused_gate_innov_stride = innov.innov_tick_stride;
     if (innov.reacq.on) {
-      p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+      p.fused_gate_k = innov.reacq.k; p.reacq_run = d_run_.get(); p.reacq_p0 = d_p0tab_.get(); p.reacq_p0_idx = d_p0idx_.get();
       p.fused_gate_event = innov.reacq.event; p.fused_gate_event_stride = innov.reacq.tick_stride; p.fused_gate_event_ring = innov.reacq.ring;
     }
   }
@@ -1016,11 +991,9 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
   live_.share = share;   // counted from here on; every way out of the session gives it back (live_release)
   try {
   if (!live_.h_block) {
-    char* h = nullptr;
-    TE_HIP_CHECK(hipHostMalloc((void**)&h, 128, hipHostMallocMapped | hipHostMallocCoherent));
-    char* d = nullptr;
-    TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d, h, 0));
-    live_.h_block = h;
+    live_.h_block.alloc(128, kPinnedMapped);
+    char* const h = live_.h_block.host();
+    char* const d = live_.h_block.dev();
     live_.h_posted = reinterpret_cast<long long*>(h); live_.d_posted = reinterpret_cast<long long*>(d);
     live_.h_done = reinterpret_cast<int*>(h + 64); live_.d_done = reinterpret_cast<int*>(d + 64);
     // The doorbell itself lives in DEVICE memory where the host can write it through the PCIe BAR (large-BAR systems, fine-grained
@@ -1031,20 +1004,13 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     int dev = 0, large_bar = 0;
     if (!(e && e[0] == 'h') && hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar) {
-      void* bell = nullptr;
-      if (hipExtMallocWithFlags(&bell, 128, hipDeviceMallocFinegrained) == hipSuccess) {
-        live_.bar_bell = static_cast<long long*>(bell);
-        live_.h_posted = live_.d_posted = live_.bar_bell;
-      } else {
-        (void)hipGetLastError();
-      }
+      if (live_.bar_bell.try_alloc_finegrained(128 / sizeof(long long))) live_.h_posted = live_.d_posted = live_.bar_bell.get();
     }
   }
   if (waves > live_.cap_waves) {
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    device_free(live_.d_block);
-    live_.d_block = nullptr;
-    TE_HIP_CHECK(hipMalloc((void**)&live_.d_block, live_block_bytes(waves)));
+    live_.cap_waves = 0;
+    live_.d_block.alloc(live_block_bytes(waves));
     live_.cap_waves = waves;
   }
   __atomic_store_n(live_.h_posted, 0LL, __ATOMIC_RELAXED);
@@ -1065,20 +1031,20 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     if (const char* e = std::getenv("TE_LIVE_STREAM_PRIORITY")) {   // experiments only (tools/r4_regress.sh): 0 = normal, low = least
       if (e[0] == 'l') greatest = least; else if (std::atoi(e) == 0) greatest = 0;
     }
-    TE_HIP_CHECK(hipStreamCreateWithPriority(&live_.stream, hipStreamNonBlocking, greatest));
+    TE_HIP_CHECK(hipStreamCreateWithPriority(live_.stream.out(), hipStreamNonBlocking, greatest));
   }
-  if (!live_.ready) TE_HIP_CHECK(hipEventCreateWithFlags(&live_.ready, hipEventDisableTiming));
-  TE_HIP_CHECK(hipEventRecord(live_.ready, stream_));
-  TE_HIP_CHECK(hipStreamWaitEvent(live_.stream, live_.ready, 0));
-  TE_HIP_CHECK(hipMemsetAsync(live_.d_block, 0, live_block_bytes(waves), live_.stream));   // mirrors + progress: zero before EVERY launch
+  if (!live_.ready) TE_HIP_CHECK(hipEventCreateWithFlags(live_.ready.out(), hipEventDisableTiming));
+  TE_HIP_CHECK(hipEventRecord(live_.ready.get(), stream_));
+  TE_HIP_CHECK(hipStreamWaitEvent(live_.stream.get(), live_.ready.get(), 0));
+  TE_HIP_CHECK(hipMemsetAsync(live_.d_block.get(), 0, live_block_bytes(waves), live_.stream.get()));   // mirrors + progress: zero before EVERY launch
   if (live_progress_words(waves) > waves)   // the padding of the progress words: INT_MAX, neutral in the relay's minimum
-    TE_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(live_.d_block + live_mirror_bytes(waves) + sizeof(int) * (size_t)waves), 0x7fffffff,
-                                   (size_t)(live_progress_words(waves) - waves), live_.stream));
+    TE_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(live_.d_block.get() + live_mirror_bytes(waves) + sizeof(int) * (size_t)waves), 0x7fffffff,
+                                   (size_t)(live_progress_words(waves) - waves), live_.stream.get()));
   StepParams p = base_params();
   p.meas = meas_ring; p.meas_ld = ld; p.has_meas = has_ring; p.dt = dt;
   p.n_ticks = (int)max_ticks; p.tick_stride = tick_stride; p.has_stride = has_stride;
   p.live_posted = live_.d_posted; p.live_done = live_.d_done;
-  p.live_mirror = reinterpret_cast<long long*>(live_.d_block); p.live_progress = reinterpret_cast<int*>(live_.d_block + live_mirror_bytes(waves));
+  p.live_mirror = reinterpret_cast<long long*>(live_.d_block.get()); p.live_progress = reinterpret_cast<int*>(live_.d_block.get() + live_mirror_bytes(waves));
   p.live_ring = ring_ticks; p.live_first = first_entry % ring_ticks;
   // a poll is a PCIe round trip plus s_sleep: ~1-2 us; the limit is a count of polls
   const double polls = idle_limit_s > 0 ? idle_limit_s * 5e5 : 5e6;
@@ -1102,11 +1068,11 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     p.live_gate_nis = lgate.nis; p.live_gate_nis_stride = lgate.nis_tick_stride; p.live_gate_nis_ring = lgate.ring;
     p.live_gate_k = lgate.reacq.on ? lgate.reacq.k : -1;
     if (lgate.reacq.on) {
-      p.reacq_run = d_run_; p.reacq_p0 = d_p0tab_; p.reacq_p0_idx = d_p0idx_;
+      p.reacq_run = d_run_.get(); p.reacq_p0 = d_p0tab_.get(); p.reacq_p0_idx = d_p0idx_.get();
       p.live_gate_event = lgate.reacq.event; p.live_gate_event_stride = lgate.reacq.tick_stride; p.live_gate_event_ring = lgate.reacq.ring;
     }
   }
-  ops_->step(p, live_.stream);   // (the measured-pose rows are not kept during a live session: see measured_pose.hpp)
+  ops_->step(p, live_.stream.get());   // (the measured-pose rows are not kept during a live session: see measured_pose.hpp)
   TE_HIP_CHECK(hipGetLastError());
   live_.waves = waves; live_.posted = 0; live_.max_ticks = max_ticks; live_.dt = dt;
   live_.all_measured = has_ring == nullptr && !lgate.gated();   // (a gated session counts its accepted measurements per slot)
@@ -1118,7 +1084,7 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
   for (unsigned spins = 0; __atomic_load_n(live_.h_done, __ATOMIC_ACQUIRE) < 0; ++spins) {
     __builtin_ia32_pause();
     if ((spins & 1023u) != 1023u) continue;
-    const hipError_t q = hipStreamQuery(live_.stream);
+    const hipError_t q = hipStreamQuery(live_.stream.get());
     if (q != hipErrorNotReady && q != hipSuccess) TE_HIP_CHECK(q);
     if (std::chrono::steady_clock::now() < t_end) continue;
     __atomic_store_n(live_.h_posted, kLiveStop, __ATOMIC_RELEASE);
@@ -1126,8 +1092,8 @@ void Batch::live_start(double dt, const void* meas_ring, long tick_stride, long 
     // (workers that did get a wave slot look at the host's word themselves every millisecond or two: they leave, the rest of the
     // grid gets their slots, sees the stop and leaves too; the records are back as they were)
     const auto t_gone = std::chrono::steady_clock::now() + std::chrono::duration<double>(1.0);
-    while (hipStreamQuery(live_.stream) == hipErrorNotReady && std::chrono::steady_clock::now() < t_gone) __builtin_ia32_pause();
-    live_.zombie = hipStreamQuery(live_.stream) == hipErrorNotReady;   // still queued behind somebody else's kernel: flush() waits for it before anything touches the records
+    while (hipStreamQuery(live_.stream.get()) == hipErrorNotReady && std::chrono::steady_clock::now() < t_gone) __builtin_ia32_pause();
+    live_.zombie = hipStreamQuery(live_.stream.get()) == hipErrorNotReady;   // still queued behind somebody else's kernel: flush() waits for it before anything touches the records
     if (!live_.zombie) live_release();
     throw std::runtime_error("target_estimation_amd: live mode: the resident kernel did not start within " + std::to_string(kLiveStartTimeoutS) +
                              " s (its stream shares a hardware queue with another endless kernel -- more live batches than GPU_MAX_HW_QUEUES, or a "
@@ -1216,7 +1182,7 @@ long Batch::live_stop() {
   if (live_.bar_bell) __builtin_ia32_sfence();
   live_.active = false;     // whatever happens below, the session is over (flush() must not come back here)
   {
-    const hipError_t e = hipStreamSynchronize(live_.stream);   // bounded: every wavefront drains the posted ticks, then sees the stop bit
+    const hipError_t e = hipStreamSynchronize(live_.stream.get());   // bounded: every wavefront drains the posted ticks, then sees the stop bit
     live_release();                                          // the kernel is gone: its wave slots, and the frees that waited for it
     TE_HIP_CHECK(e);
   }
@@ -1242,13 +1208,13 @@ void Batch::step_indexed(const int* slots, long n, double dt, const double* meas
   stage_reserve(n);
   upload_slots(slots, n);
   if (meas_aos) {
-    TE_HIP_CHECK(hipMemcpyAsync(d_aos_, meas_aos, sizeof(double) * 7 * n, hipMemcpyHostToDevice, stream_));
-    ops_->pack_meas(d_aos_, n, d_meas_, n, stream_);
+    TE_HIP_CHECK(hipMemcpyAsync(d_aos_.get(), meas_aos, sizeof(double) * 7 * n, hipMemcpyHostToDevice, stream_));
+    ops_->pack_meas(d_aos_.get(), n, d_meas_.get(), n, stream_);
   }
-  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_, has, (size_t)n, hipMemcpyHostToDevice, stream_));
+  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_.get(), has, (size_t)n, hipMemcpyHostToDevice, stream_));
   StepParams p = base_params();
-  p.n = n; p.idx = d_idx_; p.meas = meas_aos ? d_meas_ : nullptr; p.meas_ld = n;
-  p.has_meas = (meas_aos && has) ? d_mask_ : nullptr; p.dt = dt;
+  p.n = n; p.idx = d_idx_.get(); p.meas = meas_aos ? d_meas_.get() : nullptr; p.meas_ld = n;
+  p.has_meas = (meas_aos && has) ? d_mask_.get() : nullptr; p.dt = dt;
   if (pol) fill_update_gate(p, n);
   launch_step(p, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -1276,7 +1242,7 @@ void Batch::outputs_indexed_dev(const int* idx_dev, long n, double* pose_dev, do
   if (n <= 0) return;
   OutArgs a;
   a.rec = records_as_stored(); a.idx = idx_dev; a.n = n; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
-  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
+  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
   ops_->outputs(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
@@ -1293,10 +1259,10 @@ void Batch::step_dense_host(double dt, const double* meas_aos, const unsigned ch
   }
   stage_reserve(n_);
   if (meas_aos) {
-    TE_HIP_CHECK(hipMemcpyAsync(d_aos_, meas_aos, sizeof(double) * 7 * n_, hipMemcpyHostToDevice, stream_));
-    ops_->pack_meas(d_aos_, n_, d_meas_, n_, stream_);
+    TE_HIP_CHECK(hipMemcpyAsync(d_aos_.get(), meas_aos, sizeof(double) * 7 * n_, hipMemcpyHostToDevice, stream_));
+    ops_->pack_meas(d_aos_.get(), n_, d_meas_.get(), n_, stream_);
   }
-  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_, has, (size_t)n_, hipMemcpyHostToDevice, stream_));
+  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_.get(), has, (size_t)n_, hipMemcpyHostToDevice, stream_));
   if (pol) {
     // the whole batch in slot order under the policy: the dense gated kernel and, with runs, reacquire_kernel (one tick of
     // step_sequence with the policy as its stream), the NIS row and the event row by slot = by entry in the batch's own rows
@@ -1305,9 +1271,9 @@ void Batch::step_dense_host(double dt, const double* meas_aos, const unsigned ch
     is.nis = pol_nis_dev(); is.ld = n_; is.gate = pol_.nis_max;
     if (pol_.max_rejects >= 0) { is.reacq.on = true; is.reacq.k = pol_.max_rejects; is.reacq.event = pol_event_dev(); is.reacq.ld = n_; }
     else std::fill(pol_event_host(), pol_event_host() + n_, (unsigned char)0);
-    step_sequence(1, dt, d_meas_, 0, n_, has ? d_mask_ : nullptr, 0, 0, 0, PoseStream{}, is);
+    step_sequence(1, dt, d_meas_.get(), 0, n_, has ? d_mask_.get() : nullptr, 0, 0, 0, PoseStream{}, is);
   } else {
-    step_dense(dt, meas_aos ? d_meas_ : nullptr, n_, (meas_aos && has) ? d_mask_ : nullptr);
+    step_dense(dt, meas_aos ? d_meas_.get() : nullptr, n_, (meas_aos && has) ? d_mask_.get() : nullptr);
   }
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));  // caller's host arrays may be reused after return
@@ -1326,12 +1292,12 @@ void Batch::step_dense_host_soa(double dt, const void* meas_soa, long ld_host, c
     const bool angular = (type_ == ANGULAR_RATES || type_ == ANGULAR_VELOCITIES);
     const size_t es = elem_size();
     // rows of the device staging block are stage_cap_ elements apart
-    TE_HIP_CHECK(hipMemcpy2DAsync(d_meas_, (size_t)stage_cap_ * es, meas_soa, (size_t)ld_host * es, (size_t)n_ * es,
+    TE_HIP_CHECK(hipMemcpy2DAsync(d_meas_.get(), (size_t)stage_cap_ * es, meas_soa, (size_t)ld_host * es, (size_t)n_ * es,
                                   angular ? 7 : 3, hipMemcpyHostToDevice, stream_));
   }
-  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_, has, (size_t)n_, hipMemcpyHostToDevice, stream_));
+  if (has) TE_HIP_CHECK(hipMemcpyAsync(d_mask_.get(), has, (size_t)n_, hipMemcpyHostToDevice, stream_));
   host_meas_rows_ = (type_ == ANGULAR_RATES || type_ == ANGULAR_VELOCITIES) ? 7 : 3;   // what was transported (measured_pose.hpp)
-  step_dense(dt, meas_soa ? d_meas_ : nullptr, stage_cap_, (meas_soa && has) ? d_mask_ : nullptr);
+  step_dense(dt, meas_soa ? d_meas_.get() : nullptr, stage_cap_, (meas_soa && has) ? d_mask_.get() : nullptr);
   host_meas_rows_ = 7;
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));  // caller's host arrays may be reused after return
@@ -1351,11 +1317,9 @@ void Batch::pin_reserve(long k) {
   if (k <= pin_cap_) return;
   const long want = (std::max<long>(std::max<long>(k, 64), pin_cap_ * 2) + 15) / 16 * 16;   // keeps the sections aligned
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  if (h_pin_) (void)hipHostFree(h_pin_);
-  h_pin_ = nullptr; d_pin_ = nullptr; pin_cap_ = 0;
-  const size_t bytes = (size_t)want * (sizeof(int) + sizeof(double) + 7 * elem_size() + 1) + 64;
-  TE_HIP_CHECK(hipHostMalloc((void**)&h_pin_, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-  TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d_pin_, h_pin_, 0));
+  pin_cap_ = 0; d_pin_ = nullptr;
+  h_pin_.alloc((size_t)want * (sizeof(int) + sizeof(double) + 7 * elem_size() + 1) + 64, kPinnedMapped);
+  d_pin_ = h_pin_.dev();
   pin_cap_ = want;
 }
 
@@ -1363,10 +1327,9 @@ void Batch::cache_reserve(long n) {
   if (n <= cache_cap_) return;
   const long want = std::max<long>(std::max<long>(n, 64), std::min<long>(cache_cap_ * 2, n > kCacheMax ? kCacheBigMax : kCacheMax));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  if (h_cache_) (void)hipHostFree(h_cache_);
-  h_cache_ = nullptr; d_cache_ = nullptr; cache_cap_ = 0;
-  TE_HIP_CHECK(hipHostMalloc((void**)&h_cache_, sizeof(double) * 19 * (size_t)want, hipHostMallocMapped | hipHostMallocCoherent));
-  TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d_cache_, h_cache_, 0));
+  cache_cap_ = 0; d_cache_ = nullptr;
+  h_cache_.alloc(19 * (size_t)want, kPinnedMapped);
+  d_cache_ = h_cache_.dev();
   cache_cap_ = want;
   cache_valid_ = false;
 }
@@ -1380,7 +1343,7 @@ static bool spin_wait_enabled() {
 void Batch::flush() {
   if (live_.zombie) {              // a resident kernel that never started in time: told to stop, it leaves the records as they are
     live_.zombie = false;
-    const hipError_t e = hipStreamSynchronize(live_.stream);
+    const hipError_t e = hipStreamSynchronize(live_.stream.get());
     live_release();
     TE_HIP_CHECK(e);
   }
@@ -1401,19 +1364,16 @@ void Batch::flush() {
   const size_t es = elem_size();
   if (bar_wanted && !bar_pin_ && !bar_pin_failed_ && k <= kBarQueue) {
     int dev = 0, large_bar = 0;
-    void* q = nullptr;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar &&
-        hipExtMallocWithFlags(&q, (size_t)kBarQueue * (sizeof(int) + sizeof(double) + 7 * sizeof(double) + 1) + 64, hipDeviceMallocFinegrained) == hipSuccess) {
-      bar_pin_ = static_cast<char*>(q);
-    } else {
+    if (!(hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar &&
+          bar_pin_.try_alloc_finegrained((size_t)kBarQueue * (sizeof(int) + sizeof(double) + 7 * sizeof(double) + 1) + 64))) {
       (void)hipGetLastError();
       bar_pin_failed_ = true;
     }
   }
   const bool use_bar = bar_wanted && bar_pin_ && k <= kBarQueue;
   if (!use_bar) pin_reserve(k);
-  char* const hq = use_bar ? bar_pin_ : h_pin_;   // as the host writes it (never reads it: the BAR mapping is write-combined)
-  char* const dq = use_bar ? bar_pin_ : d_pin_;   // as the kernel reads it
+  char* const hq = use_bar ? bar_pin_.get() : h_pin_.host();   // as the host writes it (never reads it: the BAR mapping is write-combined)
+  char* const dq = use_bar ? bar_pin_.get() : d_pin_;   // as the kernel reads it
   const long qcap = use_bar ? kBarQueue : pin_cap_;
   // sections of the block (sized by its capacity, so that the offsets are 8-byte aligned)
   const size_t off_dt = (size_t)qcap * sizeof(int), off_meas = off_dt + (size_t)qcap * sizeof(double),
@@ -1459,11 +1419,12 @@ void Batch::flush() {
   int seq = 0;
   if (cache_valid_ && spin_wait_enabled() && k <= std::max<long>(std::max<long>(ops_->L.tpw, kOutputsBlock), fused_max)) {
     if (!h_done_) {
-      TE_HIP_CHECK(hipHostMalloc((void**)&h_done_, 64, hipHostMallocMapped | hipHostMallocCoherent));
-      TE_HIP_CHECK(hipHostGetDevicePointer((void**)&d_done_, h_done_, 0));
-      *h_done_ = 0;
-      TE_HIP_CHECK(hipMalloc((void**)&d_done_count_, 64));   // the wavefront counter of multi-wavefront flushes: zero between launches
-      TE_HIP_CHECK(hipMemsetAsync(d_done_count_, 0, 64, stream_));
+      PinnedBuf<int> done;
+      done.alloc(64 / sizeof(int), kPinnedMapped);
+      *done.host() = 0;
+      d_done_count_.alloc(64 / sizeof(int));   // the wavefront counter of multi-wavefront flushes: zero between launches
+      TE_HIP_CHECK(hipMemsetAsync(d_done_count_.get(), 0, 64, stream_));
+      h_done_ = std::move(done); d_done_ = h_done_.dev();   // (last: the flag's presence stands for the counter's too)
     }
     seq = (int)(++done_seq_ & 0x7fffffffu);   // never 0 (= "no flag"), wraps without overflow
     if (seq == 0) seq = (int)(++done_seq_ & 0x7fffffffu);
@@ -1471,14 +1432,14 @@ void Batch::flush() {
   const bool fused = seq != 0 && k <= std::max<long>(ops_->L.tpw, fused_max);
   if (fused) {
     p.o_pose = d_cache_; p.o_twist = d_cache_ + 7 * n_; p.o_acc = d_cache_ + 13 * n_;
-    p.done_flag = d_done_; p.done_seq = seq; p.done_count = d_done_count_;
+    p.done_flag = d_done_; p.done_seq = seq; p.done_count = d_done_count_.get();
   }
   launch_step(p, stream_);
   if (cache_valid_ && !fused) {   // keep the getter table current: only the stepped slots change
     OutArgs a;
     a.rec = records_as_stored(); a.idx = p.idx; a.n = k; a.by_slot = 1;
     a.pose = d_cache_; a.twist = d_cache_ + 7 * n_; a.acc = d_cache_ + 13 * n_;
-    a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_;
+    a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
     if (seq != 0 && k <= kOutputsBlock) { a.done_flag = d_done_; a.done_seq = seq; }
     else seq = 0;
     ops_->outputs(a, stream_);
@@ -1498,7 +1459,7 @@ void Batch::wait_done(int seq) {
   // The signalling kernel is the last launch of the flush (in-order stream): once its flag is here, the step kernel has
   // consumed the pinned inputs and the table rows are in host memory.  A round trip takes 10-20 us; after 2 ms of spinning
   // something else is going on (a busy device, a debugger) and the runtime's own wait takes over.
-  const volatile int* flag = h_done_;
+  const volatile int* flag = h_done_.host();
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned spins = 0;; ++spins) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return;
@@ -1514,9 +1475,9 @@ void Batch::outputs(const int* slots, long n, double* pose, double* twist, doubl
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   OutArgs a;
-  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n;
-  a.pose = pose ? d_aos_ : nullptr; a.twist = twist ? d_aos_ + 7 * n : nullptr; a.acc = acc ? d_aos_ + 13 * n : nullptr;
-  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_.get() : nullptr; a.n = n;
+  a.pose = pose ? d_aos_.get() : nullptr; a.twist = twist ? d_aos_.get() + 7 * n : nullptr; a.acc = acc ? d_aos_.get() + 13 * n : nullptr;
+  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
   ops_->outputs(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
   if (pose) TE_HIP_CHECK(hipMemcpyAsync(pose, a.pose, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, stream_));
@@ -1530,7 +1491,7 @@ void Batch::outputs_dev(double* pose_dev, double* twist_dev, double* acc_dev, bo
   if (n_ == 0) return;
   OutArgs a;
   a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = twist_dev; a.acc = acc_dev;
-  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
+  a.at_time = at_time ? 1 : 0; a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
   ops_->outputs(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
@@ -1540,7 +1501,7 @@ void Batch::outputs_rows_dev(double* pose_dev, const int* row_of_slot_dev) {
   if (n_ == 0) return;
   OutArgs a;
   a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.pose = pose_dev; a.twist = nullptr; a.acc = nullptr;
-  a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_; a.row_of_slot = row_of_slot_dev;
+  a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_.get(); a.row_of_slot = row_of_slot_dev;
   ops_->outputs_rows(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
@@ -1561,15 +1522,15 @@ void Batch::outputs_one(long slot, double* pose, double* twist, double* acc, boo
     OutArgs a;
     a.rec = records_as_stored(); a.idx = nullptr; a.n = n_;
     a.pose = d_cache_; a.twist = d_cache_ + 7 * n_; a.acc = d_cache_ + 13 * n_;
-    a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_;
+    a.at_time = 0; a.t1 = 0.0; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
     ops_->outputs(a, stream_);
     TE_HIP_CHECK(hipGetLastError());
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
     cache_valid_ = true;
   }
-  if (pose) std::memcpy(pose, h_cache_ + (size_t)slot * 7, sizeof(double) * 7);
-  if (twist) std::memcpy(twist, h_cache_ + (size_t)n_ * 7 + (size_t)slot * 6, sizeof(double) * 6);
-  if (acc) std::memcpy(acc, h_cache_ + (size_t)n_ * 13 + (size_t)slot * 6, sizeof(double) * 6);
+  if (pose) std::memcpy(pose, h_cache_.host() + (size_t)slot * 7, sizeof(double) * 7);
+  if (twist) std::memcpy(twist, h_cache_.host() + (size_t)n_ * 7 + (size_t)slot * 6, sizeof(double) * 6);
+  if (acc) std::memcpy(acc, h_cache_.host() + (size_t)n_ * 13 + (size_t)slot * 6, sizeof(double) * 6);
 }
 
 void Batch::intersect(const int* slots, long n, double t1, const double* origin, double radius, double* delta, double* pose) {
@@ -1578,10 +1539,10 @@ void Batch::intersect(const int* slots, long n, double t1, const double* origin,
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   IntersectArgs a;
-  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_.get() : nullptr; a.n = n; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-  a.t_acc = t_acc_; a.t_base = d_tbase_;
-  a.delta = d_aos_; a.pose = pose ? d_aos_ + n : nullptr;
+  a.t_acc = t_acc_; a.t_base = d_tbase_.get();
+  a.delta = d_aos_.get(); a.pose = pose ? d_aos_.get() + n : nullptr;
   ops_->intersect(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipMemcpyAsync(delta, a.delta, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
@@ -1595,7 +1556,7 @@ void Batch::intersect_dev(double t1, const double* origin, double radius, double
   IntersectArgs a;
   a.rec = records_as_stored(); a.idx = nullptr; a.n = n_; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-  a.t_acc = t_acc_; a.t_base = d_tbase_; a.delta = delta_dev; a.pose = pose_dev;
+  a.t_acc = t_acc_; a.t_base = d_tbase_.get(); a.delta = delta_dev; a.pose = pose_dev;
   ops_->intersect(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
@@ -1603,10 +1564,10 @@ void Batch::intersect_dev(double t1, const double* origin, double radius, double
 void Batch::gate_reset(long first, long count) {
   if (count <= 0 || !d_gate_ring_) return;
   const int W = gate_window_;
-  TE_HIP_CHECK(hipMemsetAsync(d_gate_ring_ + first * 2 * W, 0, sizeof(double) * 2 * W * count, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(d_gate_sum_ + first * 2, 0, sizeof(double) * 2 * count, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(d_gate_state_ + first * 2, 0, sizeof(int) * 2 * count, stream_));
-  hipLaunchKernelGGL(gate_reset_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream_, d_gate_prev_, first, count);
+  TE_HIP_CHECK(hipMemsetAsync(d_gate_ring_.get() + first * 2 * W, 0, sizeof(double) * 2 * W * count, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d_gate_sum_.get() + first * 2, 0, sizeof(double) * 2 * count, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d_gate_state_.get() + first * 2, 0, sizeof(int) * 2 * count, stream_));
+  hipLaunchKernelGGL(gate_reset_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream_, d_gate_prev_.get(), first, count);
   TE_HIP_CHECK(hipGetLastError());
 }
 
@@ -1615,20 +1576,20 @@ void Batch::gate_reserve(int window) {
   if (window == gate_window_ && gate_cap_ >= cap_) return;
   const bool keep = (window == gate_window_) && d_gate_ring_;
   const long old_cap = gate_cap_;
-  double* ring = nullptr; double* sum = nullptr; int* st = nullptr; double* prev = nullptr;
-  TE_HIP_CHECK(hipMalloc((void**)&ring, sizeof(double) * 2 * window * cap_));
-  TE_HIP_CHECK(hipMalloc((void**)&sum, sizeof(double) * 2 * cap_));
-  TE_HIP_CHECK(hipMalloc((void**)&st, sizeof(int) * 2 * cap_));
-  TE_HIP_CHECK(hipMalloc((void**)&prev, sizeof(double) * 7 * cap_));
+  DeviceBuf<double> ring, sum, prev;
+  DeviceBuf<int> st;
+  ring.alloc((size_t)2 * window * cap_);
+  sum.alloc((size_t)2 * cap_);
+  st.alloc((size_t)2 * cap_);
+  prev.alloc((size_t)7 * cap_);
   if (keep) {
-    TE_HIP_CHECK(hipMemcpyAsync(ring, d_gate_ring_, sizeof(double) * 2 * window * old_cap, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(sum, d_gate_sum_, sizeof(double) * 2 * old_cap, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(st, d_gate_state_, sizeof(int) * 2 * old_cap, hipMemcpyDeviceToDevice, stream_));
-    TE_HIP_CHECK(hipMemcpyAsync(prev, d_gate_prev_, sizeof(double) * 7 * old_cap, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(ring.get(), d_gate_ring_.get(), sizeof(double) * 2 * window * old_cap, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(sum.get(), d_gate_sum_.get(), sizeof(double) * 2 * old_cap, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(st.get(), d_gate_state_.get(), sizeof(int) * 2 * old_cap, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(prev.get(), d_gate_prev_.get(), sizeof(double) * 7 * old_cap, hipMemcpyDeviceToDevice, stream_));
   }
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  device_free(d_gate_ring_); device_free(d_gate_sum_); device_free(d_gate_state_); device_free(d_gate_prev_);
-  d_gate_ring_ = ring; d_gate_sum_ = sum; d_gate_state_ = st; d_gate_prev_ = prev;
+  d_gate_ring_ = std::move(ring); d_gate_sum_ = std::move(sum); d_gate_state_ = std::move(st); d_gate_prev_ = std::move(prev);
   gate_window_ = window;
   gate_cap_ = cap_;
   gate_reset(keep ? old_cap : 0, keep ? cap_ - old_cap : cap_);
@@ -1637,10 +1598,10 @@ void Batch::gate_reserve(int window) {
 void Batch::gate_move(long src, long dst) {
   if (!d_gate_ring_ || src >= gate_cap_ || dst >= gate_cap_) return;
   const int W = gate_window_;
-  TE_HIP_CHECK(hipMemcpyAsync(d_gate_ring_ + dst * 2 * W, d_gate_ring_ + src * 2 * W, sizeof(double) * 2 * W, hipMemcpyDeviceToDevice, stream_));
-  TE_HIP_CHECK(hipMemcpyAsync(d_gate_sum_ + dst * 2, d_gate_sum_ + src * 2, sizeof(double) * 2, hipMemcpyDeviceToDevice, stream_));
-  TE_HIP_CHECK(hipMemcpyAsync(d_gate_state_ + dst * 2, d_gate_state_ + src * 2, sizeof(int) * 2, hipMemcpyDeviceToDevice, stream_));
-  TE_HIP_CHECK(hipMemcpyAsync(d_gate_prev_ + dst * 7, d_gate_prev_ + src * 7, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_gate_ring_.get() + dst * 2 * W, d_gate_ring_.get() + src * 2 * W, sizeof(double) * 2 * W, hipMemcpyDeviceToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_gate_sum_.get() + dst * 2, d_gate_sum_.get() + src * 2, sizeof(double) * 2, hipMemcpyDeviceToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_gate_state_.get() + dst * 2, d_gate_state_.get() + src * 2, sizeof(int) * 2, hipMemcpyDeviceToDevice, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d_gate_prev_.get() + dst * 7, d_gate_prev_.get() + src * 7, sizeof(double) * 7, hipMemcpyDeviceToDevice, stream_));
 }
 
 void Batch::intersect_gated(const int* slots, long n, double t1, const double* origin, double radius, double pos_th,
@@ -1651,21 +1612,21 @@ void Batch::intersect_gated(const int* slots, long n, double t1, const double* o
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   IntersectArgs a;
-  a.rec = records_as_stored(); a.idx = slots ? d_idx_ : nullptr; a.n = n; a.t1 = t1;
+  a.rec = records_as_stored(); a.idx = slots ? d_idx_.get() : nullptr; a.n = n; a.t1 = t1;
   a.origin[0] = origin[0]; a.origin[1] = origin[1]; a.origin[2] = origin[2]; a.radius = radius;
-  a.t_acc = t_acc_; a.t_base = d_tbase_;
-  a.delta = d_aos_; a.pose = d_aos_ + n;                 // [n] + [n][7]
+  a.t_acc = t_acc_; a.t_base = d_tbase_.get();
+  a.delta = d_aos_.get(); a.pose = d_aos_.get() + n;                 // [n] + [n][7]
   ops_->intersect(a, stream_);
   GateArgs g;
   g.idx = a.idx; g.n = n; g.window = gate_window_; g.delta = a.delta; g.pose = a.pose; g.pos_th = pos_th; g.ang_th = ang_th;
-  g.ring = d_gate_ring_; g.sum = d_gate_sum_; g.state = d_gate_state_; g.prev = d_gate_prev_;
-  g.converged = d_mask_; g.filt = filt ? d_aos_ + 8 * n : nullptr;   // [n][2] after delta + pose
+  g.ring = d_gate_ring_.get(); g.sum = d_gate_sum_.get(); g.state = d_gate_state_.get(); g.prev = d_gate_prev_.get();
+  g.converged = d_mask_.get(); g.filt = filt ? d_aos_.get() + 8 * n : nullptr;   // [n][2] after delta + pose
   g.var = nullptr;
   hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream_, g);
   TE_HIP_CHECK(hipGetLastError());
   if (delta) TE_HIP_CHECK(hipMemcpyAsync(delta, a.delta, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
   if (pose) TE_HIP_CHECK(hipMemcpyAsync(pose, a.pose, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, stream_));
-  if (converged) TE_HIP_CHECK(hipMemcpyAsync(converged, d_mask_, (size_t)n, hipMemcpyDeviceToHost, stream_));
+  if (converged) TE_HIP_CHECK(hipMemcpyAsync(converged, d_mask_.get(), (size_t)n, hipMemcpyDeviceToHost, stream_));
   if (filt) TE_HIP_CHECK(hipMemcpyAsync(filt, g.filt, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
@@ -1684,7 +1645,7 @@ void Batch::gate_update_dev(const double* delta_dev, const double* pose_dev, dou
   gate_reserve(window);
   GateArgs g;
   g.idx = nullptr; g.n = n_; g.window = gate_window_; g.delta = delta_dev; g.pose = pose_dev; g.pos_th = pos_th; g.ang_th = ang_th;
-  g.ring = d_gate_ring_; g.sum = d_gate_sum_; g.state = d_gate_state_; g.prev = d_gate_prev_;
+  g.ring = d_gate_ring_.get(); g.sum = d_gate_sum_.get(); g.state = d_gate_state_.get(); g.prev = d_gate_prev_.get();
   g.converged = converged_dev; g.filt = filt_dev; g.var = var_dev;
   hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((n_ + 127) / 128)), dim3(128), 0, stream_, g);
   TE_HIP_CHECK(hipGetLastError());
@@ -1702,32 +1663,31 @@ void Batch::get_state(const int* slots, long n, double* x, double* P) {
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
   // scratch: up to kStateScratchKeep bytes are kept between calls (a caller reading one target's covariance at a time -- the
-  // reference test's getEstimator()->getP() -- pays no allocation, and no hipFree: that synchronises the whole device, a
+  // reference test's getEstimator()->getP() -- pays no allocation, and no free: that synchronises the whole device, a
   // resident kernel of another batch included); larger requests are freed again
   const size_t bx = x ? sizeof(double) * (size_t)N * n : 0, bP = P ? sizeof(double) * (size_t)N * N * n : 0;
-  char* big = nullptr;
+  DeviceBuf<char> big;
   char* buf = nullptr;
   if (bx + bP <= kStateScratchKeep) {
     if (bx + bP > state_scratch_bytes_) {
       TE_HIP_CHECK(hipStreamSynchronize(stream_));
-      device_free(d_state_scratch_); d_state_scratch_ = nullptr; state_scratch_bytes_ = 0;
+      state_scratch_bytes_ = 0;
       const size_t want = std::max<size_t>(bx + bP, std::min<size_t>(2 * state_scratch_bytes_ + 4096, kStateScratchKeep));
-      TE_HIP_CHECK(hipMalloc((void**)&d_state_scratch_, want));
+      d_state_scratch_.alloc(want);
       state_scratch_bytes_ = want;
     }
-    buf = d_state_scratch_;
+    buf = d_state_scratch_.get();
   } else {
-    TE_HIP_CHECK(hipMalloc((void**)&big, bx + bP));
-    buf = big;
+    big.alloc(bx + bP);
+    buf = big.get();
   }
   double* dx = x ? reinterpret_cast<double*>(buf) : nullptr;
   double* dP = P ? reinterpret_cast<double*>(buf + bx) : nullptr;
-  ops_->get_state(records_as_stored(), slots ? d_idx_ : nullptr, n, dx, dP, ut_flagged_ ? d_tile_blk_ : nullptr, ut_flagged_ ? d_tile_uni_ : nullptr, stream_);
+  ops_->get_state(records_as_stored(), slots ? d_idx_.get() : nullptr, n, dx, dP, ut_flagged_ ? d_tile_blk_.get() : nullptr, ut_flagged_ ? d_tile_uni_.get() : nullptr, stream_);
   TE_HIP_CHECK(hipGetLastError());
   if (x) TE_HIP_CHECK(hipMemcpyAsync(x, dx, bx, hipMemcpyDeviceToHost, stream_));
   if (P) TE_HIP_CHECK(hipMemcpyAsync(P, dP, bP, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  if (big) device_free(big);
 }
 
 void Batch::set_state(const int* slots, long n, const double* x, const double* P, const double* unwrap) {
@@ -1737,14 +1697,13 @@ void Batch::set_state(const int* slots, long n, const double* x, const double* P
   const int N = ops_->L.n;
   stage_reserve(n);
   if (slots) upload_slots(slots, n);
-  double *dx = nullptr, *dP = nullptr, *du = nullptr;
-  if (x) { TE_HIP_CHECK(hipMalloc((void**)&dx, sizeof(double) * N * n)); TE_HIP_CHECK(hipMemcpyAsync(dx, x, sizeof(double) * N * n, hipMemcpyHostToDevice, stream_)); }
-  if (P) { TE_HIP_CHECK(hipMalloc((void**)&dP, sizeof(double) * N * N * n)); TE_HIP_CHECK(hipMemcpyAsync(dP, P, sizeof(double) * N * N * n, hipMemcpyHostToDevice, stream_)); }
-  if (unwrap) { TE_HIP_CHECK(hipMalloc((void**)&du, sizeof(double) * 3 * n)); TE_HIP_CHECK(hipMemcpyAsync(du, unwrap, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream_)); }
-  ops_->set_state(records(), slots ? d_idx_ : nullptr, n, dx, dP, du, stream_);
+  DeviceBuf<double> dx, dP, du;
+  if (x) { dx.alloc((size_t)N * n); TE_HIP_CHECK(hipMemcpyAsync(dx.get(), x, sizeof(double) * N * n, hipMemcpyHostToDevice, stream_)); }
+  if (P) { dP.alloc((size_t)N * N * n); TE_HIP_CHECK(hipMemcpyAsync(dP.get(), P, sizeof(double) * N * N * n, hipMemcpyHostToDevice, stream_)); }
+  if (unwrap) { du.alloc((size_t)3 * n); TE_HIP_CHECK(hipMemcpyAsync(du.get(), unwrap, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream_)); }
+  ops_->set_state(records(), slots ? d_idx_.get() : nullptr, n, dx.get(), dP.get(), du.get(), stream_);
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  device_free(dx); device_free(dP); device_free(du);
 }
 
 long long Batch::n_measurements(long slot) {
@@ -1753,13 +1712,13 @@ long long Batch::n_measurements(long slot) {
   // the counters after a few single reads; any step drops it (flush() with queued steps, touch())
   if (!nm_valid_ && ++nm_reads_ > kCounterDirect) {
     h_nm_.resize((size_t)n_);
-    TE_HIP_CHECK(hipMemcpyAsync(h_nm_.data(), d_nmbase_, sizeof(int) * (size_t)n_, hipMemcpyDeviceToHost, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(h_nm_.data(), d_nmbase_.get(), sizeof(int) * (size_t)n_, hipMemcpyDeviceToHost, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
     nm_valid_ = true;
   }
   if (nm_valid_) return (long long)h_nm_[(size_t)slot] + nm_acc_;
   int v = 0;
-  TE_HIP_CHECK(hipMemcpyAsync(&v, d_nmbase_ + slot, sizeof(int), hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(&v, d_nmbase_.get() + slot, sizeof(int), hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   return (long long)v + nm_acc_;
 }
@@ -1768,7 +1727,7 @@ void Batch::times(double* out) {
   flush();
   if (n_ == 0) return;
   std::vector<TClock> tb((size_t)n_);
-  TE_HIP_CHECK(hipMemcpyAsync(tb.data(), d_tbase_, sizeof(TClock) * n_, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(tb.data(), d_tbase_.get(), sizeof(TClock) * n_, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   for (long i = 0; i < n_; ++i) out[i] = te_clock_time(tb[(size_t)i], t_acc_);
 }
@@ -1776,7 +1735,7 @@ void Batch::times(double* out) {
 double Batch::time(long slot) {
   flush();
   TClock v{0.0, 0.0};
-  TE_HIP_CHECK(hipMemcpyAsync(&v, d_tbase_ + slot, sizeof(TClock), hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(&v, d_tbase_.get() + slot, sizeof(TClock), hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   return te_clock_time(v, t_acc_);
 }
@@ -1812,11 +1771,11 @@ void Batch::crossing_cov_dev(double t1, const double* origin, double radius, con
   flush();
   if (n == 0) return;
   CrossingCovArgs a;
-  a.rec = records_as_stored(); a.qr = d_qr_; a.cls = n_classes_ > 1 ? d_cls_ : nullptr;
+  a.rec = records_as_stored(); a.qr = d_qr_.get(); a.cls = n_classes_ > 1 ? d_cls_.get() : nullptr;
   // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
-  a.tile_blk = d_tile_uni_ ? d_tile_blk_ : nullptr; a.tile_uni = d_tile_uni_;
+  a.tile_blk = d_tile_uni_.get() ? d_tile_blk_.get() : nullptr; a.tile_uni = d_tile_uni_.get();
   a.size = n_; a.n = n; a.slots = slots_dev; a.batch = batch_dev; a.batch_index = batch_index; a.delta = delta_dev;
-  a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_;
+  a.t1 = t1; a.t_acc = t_acc_; a.t_base = d_tbase_.get();
   a.have_origin = origin ? 1 : 0;
   for (int c = 0; c < 3; ++c) a.origin[c] = origin ? origin[c] : 0.0;
   a.sigma_r_max = sigma_r_max; a.sigma_t_max = sigma_t_max;
@@ -1836,14 +1795,14 @@ void Batch::crossing_cov(const int* slots, long n, double t1, const double* orig
     flush();
     stage_reserve(k);
     upload_slots(slots + done, k);
-    double* d_delta = d_aos_;            // [k] | cov [k][6] | sigma [k][2] of the staging's 19 doubles per entry
-    double* d_cov = d_aos_ + k;
-    double* d_sigma = d_aos_ + 7 * k;
+    double* d_delta = d_aos_.get();            // [k] | cov [k][6] | sigma [k][2] of the staging's 19 doubles per entry
+    double* d_cov = d_aos_.get() + k;
+    double* d_sigma = d_aos_.get() + 7 * k;
     TE_HIP_CHECK(hipMemcpyAsync(d_delta, delta + done, sizeof(double) * k, hipMemcpyHostToDevice, stream_));
-    crossing_cov_dev(t1, origin, radius, d_delta, d_idx_, k, sigma_r_max, sigma_t_max, d_cov, sigma ? d_sigma : nullptr, ok ? d_mask_ : nullptr);
+    crossing_cov_dev(t1, origin, radius, d_delta, d_idx_.get(), k, sigma_r_max, sigma_t_max, d_cov, sigma ? d_sigma : nullptr, ok ? d_mask_.get() : nullptr);
     TE_HIP_CHECK(hipMemcpyAsync(cov + done * 6, d_cov, sizeof(double) * 6 * k, hipMemcpyDeviceToHost, stream_));
     if (sigma) TE_HIP_CHECK(hipMemcpyAsync(sigma + done * 2, d_sigma, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, stream_));
-    if (ok) TE_HIP_CHECK(hipMemcpyAsync(ok + done, d_mask_, (size_t)k, hipMemcpyDeviceToHost, stream_));
+    if (ok) TE_HIP_CHECK(hipMemcpyAsync(ok + done, d_mask_.get(), (size_t)k, hipMemcpyDeviceToHost, stream_));
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
   }
 }
@@ -1855,9 +1814,9 @@ void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index) {
   flush();
   if (n_ == 0) return;
   AssocTableArgs a;
-  a.rec = records_as_stored(); a.qr = d_qr_; a.cls = n_classes_ > 1 ? d_cls_ : nullptr;
+  a.rec = records_as_stored(); a.qr = d_qr_.get(); a.cls = n_classes_ > 1 ? d_cls_.get() : nullptr;
   // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
-  a.tile_blk = d_tile_uni_ ? d_tile_blk_ : nullptr; a.tile_uni = d_tile_uni_;
+  a.tile_blk = d_tile_uni_.get() ? d_tile_blk_.get() : nullptr; a.tile_uni = d_tile_uni_.get();
   a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index;
   launch(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
@@ -1878,7 +1837,7 @@ void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scrat
   scratch.ensure(rows, M, rows * gr.chunks, M * gd.chunks);
   long off = 0;
   for (int b = 0; b < n_batches; ++b) {
-    batches[b]->assoc_table_dev(dt, scratch.table + off, b);
+    batches[b]->assoc_table_dev(dt, scratch.table.get() + off, b);
     off += batches[b]->size();
   }
   launch_assoc_match(scratch, rows, det_dev, M, gate, (int)rounds, forced_chunks, st);
@@ -1903,13 +1862,13 @@ long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& 
                             long rounds, const AssocSlotOut* out, unsigned* ids_of_det, int* batch_of_det, int* slot_of_det, double* d2_of_det,
                             long* unmatched, long* n_unmatched, int* info, hipStream_t st) {
   s.ensure_host(M);
-  if (M > 0) TE_HIP_CHECK(hipMemcpyAsync(s.det_stage, det, sizeof(double) * 7 * (size_t)M, hipMemcpyHostToDevice, st));
-  char* d = s.result_dev;
-  associate_batches(batches, n_batches, s, forced_chunks, dt, s.det_stage, M, gate, rounds, out, (int*)(d + AssocScratch::off_slot(M)),
+  if (M > 0) TE_HIP_CHECK(hipMemcpyAsync(s.det_stage.get(), det, sizeof(double) * 7 * (size_t)M, hipMemcpyHostToDevice, st));
+  char* d = s.result_dev.get();
+  associate_batches(batches, n_batches, s, forced_chunks, dt, s.det_stage.get(), M, gate, rounds, out, (int*)(d + AssocScratch::off_slot(M)),
                     (int*)(d + AssocScratch::off_batch(M)), (double*)(d + AssocScratch::off_d2(M)), (int*)(d + AssocScratch::off_info(M)), st);
-  TE_HIP_CHECK(hipMemcpyAsync(s.result_host, d, AssocScratch::result_bytes(M), hipMemcpyDeviceToHost, st));
+  TE_HIP_CHECK(hipMemcpyAsync(s.result_host.host(), d, AssocScratch::result_bytes(M), hipMemcpyDeviceToHost, st));
   TE_HIP_CHECK(hipStreamSynchronize(st));
-  const char* h = s.result_host;
+  const char* h = s.result_host.host();
   const int* hs = (const int*)(h + AssocScratch::off_slot(M));
   const int* hb = (const int*)(h + AssocScratch::off_batch(M));
   const double* hd = (const double*)(h + AssocScratch::off_d2(M));

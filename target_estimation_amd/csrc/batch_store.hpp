@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "dt_schedule.hpp"
 #include "dt_table_ring.hpp"
 #include "kf_ops.hpp"
@@ -409,7 +410,7 @@ class Batch {
   // What follows a population tick that carried an innovation stream (whose kernel has neither the fused query nor the pose
   // output) for this batch: the pose-writer launch into tick s's pose block and / or the own-time sphere query, as launches.
   void enqueue_after_innov_tick(hipStream_t st, long s, const SeqSpec& spec, bool query, const double* origin, double radius);
-  void swap_records() { std::swap(d_rec_, d_rec_alt_); }
+  void swap_records() { d_rec_.swap(d_rec_alt_); }
   // Building blocks of the manager's fused replay of all batches (Shard::stepFusedAll), and of step_fused_gated itself.  spec: the
   // call's measurements, masks, pose stream and innovation stream (ring_ticks, delta_dev and pose_dev unread: fused calls read
   // linearly and have no query).
@@ -434,7 +435,7 @@ class Batch {
     }
   };
   // (the tile arrays, the rejection runs and the slot -> row index are allocated and freed with the records: rec identifies them too)
-  DevIdentity dev_identity() const { return DevIdentity{d_rec_, d_qr_, d_tbase_, d_nmbase_, n_, ops_, d_p0tab_}; }
+  DevIdentity dev_identity() const { return DevIdentity{d_rec_.get(), d_qr_.get(), d_tbase_.get(), d_nmbase_.get(), n_, ops_, d_p0tab_.get()}; }
   void prepare() { touch(); }
   long graph_recordings() const { return graphs_.recordings(); }   // recordings made so far (what a test of the cache observes)
 
@@ -480,10 +481,36 @@ class Batch {
   std::mutex* owner_lock_ = nullptr;
   const Ops* ops_;
   hipStream_t stream_;
+  // DECLARATION ORDER MATTERS from here on: members are destroyed last to first, and every buffer must go before the streams
+  // and events it was used on.  So the owned streams and events come first (cap_stream_; the session's inside Live, ahead of
+  // its blocks), and every buffer is declared behind them.  ~Batch only ends what may still be running.
+  Stream cap_stream_;
+  static constexpr double kLiveStartTimeoutS = 2.0;
+  struct Live {
+    Event ready;
+    Stream stream;                   // the resident kernel's own stream (declared ahead of the session's blocks: see above)
+    bool active = false;
+    bool zombie = false;            // launched, never seen running, told to stop: synchronise its stream before touching records
+    PinnedBuf<char> h_block;         // host-mapped block: [0] the doorbell unless it lives behind the BAR, [64] the relay's words
+    DeviceBuf<long long> bar_bell;   // the doorbell in fine-grained DEVICE memory, written by the host through the PCIe BAR (or null)
+    long long* h_posted = nullptr;   // the doorbell as the host writes it (count | stop bit)
+    long long* d_posted = nullptr;   // the same block as the device sees it
+    int* h_done = nullptr;
+    int* d_done = nullptr;
+    DeviceBuf<char> d_block;         // device memory: [mirror word, padded to 64 B][progress words of the wavefronts]
+    double* pose_out = nullptr;      // per-tick pose output (live_set_pose_output)
+    long pose_ld = 0;
+    InnovStream gate{};              // the gate of the sessions to come (live_set_gate); !gated(): none
+    long waves = 0, cap_waves = 0;
+    long posted = 0, max_ticks = 0;
+    double dt = 0.0;
+    bool all_measured = false;
+    double share = 0.0;              // > 0 while the session is counted among the process's resident sessions (hip_check.hpp)
+  } live_;
   std::unordered_map<std::string, int> class_index_;   // raw bytes of [Q | R] -> class
   int n_classes_ = 0, qr_cap_ = 0;
-  void* d_qr_ = nullptr;           // [qr_cap_][N*N + K*K] in the batch precision
-  int* d_cls_ = nullptr;           // [cap_] class of every slot
+  DeviceBuf<char> d_qr_;           // [qr_cap_][N*N + K*K] in the batch precision
+  DeviceBuf<int> d_cls_;           // [cap_] class of every slot
   bool flip_ = false;              // the next dense tick walks the tiles backwards (zig-zag, kf_step.hpp StepArgs::reverse)
   // Zig-zag only pays when the state does not fit the Infinity Cache.  With the plain mirror b -> n - 1 - b it cost when the
   // state is L2-resident: a tile walked backwards landed on another XCD, whose L2 does not hold it (10^5 UA fp32: 4.7 ->
@@ -495,19 +522,19 @@ class Batch {
   // The records.  records(): settled -- for everything that reads or writes P words of a record and is not a dense tick of the
   // form.  records_as_stored(): as the dense ticks leave them (the linear-covariance chunks of a flagged tile unspecified) -- for
   // the dense ticks, get_state (which honours the flags) and readers of x alone (outputs, intersections).
-  char* records() { settle_tiles(); return d_rec_; }
-  char* records_as_stored() const { return d_rec_; }
+  char* records() { settle_tiles(); return d_rec_.get(); }
+  char* records_as_stored() const { return d_rec_.get(); }
   long count_uniform(long* targets_in_them);   // flagged tiles (and the targets in them); synchronises
   bool ut_on_ = true;
-  double* d_tile_blk_ = nullptr;   // [cap_ / tpw][L.lin_words], allocated with the records
-  int* d_tile_uni_ = nullptr;      // [cap_ / tpw]
+  DeviceBuf<double> d_tile_blk_;   // [cap_ / tpw][L.lin_words], allocated with the records
+  DeviceBuf<int> d_tile_uni_;      // [cap_ / tpw]
   bool ut_flagged_ = false;        // a promoting launch has run since the last settle: tiles may be flagged
   long dense_streak_ = 0;          // consecutive dense ticks since the last settle
   bool recording_ = false;
   void launch_step(const StepParams& p, hipStream_t st, int meas_rows = 7);   // ops_->step + the measured-pose rows when kept
   bool keep_meas_ = false;
   int host_meas_rows_ = 7;         // measurement rows the host SoA path transported for the tick being enqueued
-  double* d_lastmeas_ = nullptr;   // [cap_][7] doubles (measured_pose.hpp), null unless keep_meas_
+  DeviceBuf<double> d_lastmeas_;   // [cap_][7] doubles (measured_pose.hpp), null unless keep_meas_
   std::vector<std::vector<double>> class_qr_;   // [Q | R] of every class as given (doubles)
   static constexpr size_t kP0TableMax = 4096;
   std::vector<std::vector<double>> p0_tab_;
@@ -515,19 +542,19 @@ class Batch {
   std::vector<int> slot_p0_;       // slot -> row of p0_tab_
   bool p0_kept_ = true;
   int intern_p0(const double* P0);
-  char* d_rec_ = nullptr;          // the CURRENT records (A -> B ticks swap it with d_rec_alt_ after every launch)
-  char* d_rec_alt_ = nullptr;      // second record buffer of the same capacity, allocated on the first A -> B tick
+  DeviceBuf<char> d_rec_;          // the CURRENT records (A -> B ticks swap it with d_rec_alt_ after every launch)
+  DeviceBuf<char> d_rec_alt_;      // second record buffer of the same capacity, allocated on the first A -> B tick
   char* alt_records();             // null if the device has no room for it (the batch then stays in place)
   bool alt_failed_ = false;
-  TClock* d_tbase_ = nullptr;
-  int* d_nmbase_ = nullptr;
-  unsigned char* d_has_eff_ = nullptr;   // [cap_] the effective mask of a gated tick whose layout has no gated kernel (StepParams::gate_row)
+  DeviceBuf<TClock> d_tbase_;
+  DeviceBuf<int> d_nmbase_;
+  DeviceBuf<unsigned char> d_has_eff_;   // [cap_] the effective mask of a gated tick whose layout has no gated kernel (StepParams::gate_row)
   // Re-acquisition (kf_reacquire_impl.hpp): the rejection run of every slot -- library-owned, 0 at creation, follows its target
   // through erase and growth, read and written by the calls with a policy only -- and the device copies of p0_tab_ / slot_p0_.
-  unsigned char* d_run_ = nullptr;       // [cap_], allocated with the records
-  int* d_p0idx_ = nullptr;               // [cap_], allocated with the records; current behind prepare_reacquire()
+  DeviceBuf<unsigned char> d_run_;       // [cap_], allocated with the records
+  DeviceBuf<int> d_p0idx_;               // [cap_], allocated with the records; current behind prepare_reacquire()
   DirtySlots p0idx_dirty_;
-  double* d_p0tab_ = nullptr;            // [p0tab_dev_.cap][N*N]
+  DeviceBuf<double> d_p0tab_;            // [p0tab_dev_.cap][N*N]
   P0TableMirror p0tab_dev_;
   void run_move(long src, long dst);
   void fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const;   // the policy's launch parameters of tick s_call of a call
@@ -537,12 +564,12 @@ class Batch {
   // the by-id update policy: its by-entry NIS row and event row (host-mapped, sized with the staging and queue blocks; the host
   // reads them as cached host memory, never through the write-combined BAR block)
   UpdateGate pol_{};
-  char* h_pol_ = nullptr;                // nis double[pol_cap_] | event uchar[pol_cap_]
+  PinnedBuf<char> h_pol_;                // nis double[pol_cap_] | event uchar[pol_cap_]
   char* d_pol_ = nullptr;
   long pol_cap_ = 0;
   void pol_reserve(long k);
-  double* pol_nis_host() const { return reinterpret_cast<double*>(h_pol_); }
-  unsigned char* pol_event_host() const { return reinterpret_cast<unsigned char*>(h_pol_ + (size_t)pol_cap_ * sizeof(double)); }
+  double* pol_nis_host() const { return reinterpret_cast<double*>(h_pol_.host()); }
+  unsigned char* pol_event_host() const { return reinterpret_cast<unsigned char*>(h_pol_.host() + (size_t)pol_cap_ * sizeof(double)); }
   double* pol_nis_dev() const { return reinterpret_cast<double*>(d_pol_); }
   unsigned char* pol_event_dev() const { return reinterpret_cast<unsigned char*>(d_pol_ + (size_t)pol_cap_ * sizeof(double)); }
   // an indexed launch of k entries under the policy: rows reserved (unless the caller brings its own), tables current, p filled
@@ -556,19 +583,19 @@ class Batch {
   long long nm_acc_ = 0;    // batch measurement counter
   // staging for the host-array paths
   long stage_cap_ = 0;
-  int* d_idx_ = nullptr;
-  double* d_aos_ = nullptr;        // [stage_cap][19] doubles: inputs (p0|v0|a0, meas) and outputs
-  void* d_meas_ = nullptr;         // SoA [7][stage_cap] in the batch precision
-  unsigned char* d_mask_ = nullptr;
-  double* d_P0_ = nullptr;
+  DeviceBuf<int> d_idx_;
+  DeviceBuf<double> d_aos_;        // [stage_cap][19] doubles: inputs (p0|v0|a0, meas) and outputs
+  DeviceBuf<char> d_meas_;         // SoA [7][stage_cap] in the batch precision
+  DeviceBuf<unsigned char> d_mask_;
+  DeviceBuf<double> d_P0_;
   long P0_cap_ = 0;
   // convergence gates (allocated on first use)
   int gate_window_ = 0;
   long gate_cap_ = 0;
-  double* d_gate_ring_ = nullptr;
-  double* d_gate_sum_ = nullptr;
-  int* d_gate_state_ = nullptr;
-  double* d_gate_prev_ = nullptr;
+  DeviceBuf<double> d_gate_ring_;
+  DeviceBuf<double> d_gate_sum_;
+  DeviceBuf<int> d_gate_state_;
+  DeviceBuf<double> d_gate_prev_;
   void gate_reserve(int window);
   void gate_move(long src, long dst);
   void gate_reset(long first, long count);
@@ -576,7 +603,6 @@ class Batch {
   // (a recording writes into the pose and innovation buffers it was recorded with, and bakes every tick's dt into its launch)
   struct SeqKey { long n_ticks; long n; char* rec; SeqSpec spec; DtKey dt; };
   SeqGraphCache<SeqKey> graphs_{64};
-  hipStream_t cap_stream_ = nullptr;
   void drop_graphs() { graphs_.drop(); }
   // The device table of a fused call with a time-step schedule: a fresh run of a ring per call (dt_table_ring.hpp)
   DtTableRing dttab_;
@@ -590,16 +616,16 @@ class Batch {
   struct Pending { int slot; unsigned char has; double dt; double meas[7]; long out = -1; };   // out: position in the gate sink, or -1
   std::vector<Pending> pending_;
   std::vector<unsigned char> pending_mark_;
-  double* d_dtper_ = nullptr;
+  DeviceBuf<double> d_dtper_;
   // Both live in pinned, device-mapped host memory: the kernels read the queued inputs and write the
   // outputs there directly, so a flush needs no copies; when the getter table is current and the queue holds at most
   // kFusedFlushMax targets it is ONE launch -- the step kernel writes the stepped rows and then a completion flag -- and the
   // host does not synchronise the stream but spins on that flag (wait_done; tools/launch_latency.hip: launch + flag 6.7 us
   // against 13.3 us for two launches and the runtime's wait, which is what longer queues still pay).
   void pin_reserve(long k);
-  char* h_pin_ = nullptr;                    // idx int[cap] | dt double[cap] | meas T[7][cap] | has uchar[cap]
+  PinnedBuf<char> h_pin_;                    // idx int[cap] | dt double[cap] | meas T[7][cap] | has uchar[cap]
   char* d_pin_ = nullptr;                    // the same memory as the device sees it
-  char* bar_pin_ = nullptr;                  // the same sections for flushes of up to one wavefront, in fine-grained device memory behind the PCIe BAR (flush)
+  DeviceBuf<char> bar_pin_;                  // the same sections for flushes of up to one wavefront, in fine-grained device memory behind the PCIe BAR (flush)
   bool bar_pin_failed_ = false;
   long pin_cap_ = 0;
   // The getter table.  Batches up to kCacheMax build it at the first one-target getter after a change.  A larger batch
@@ -612,20 +638,20 @@ class Batch {
   long epoch_getters_ = 0;                   // one-target getters since the last change
   bool big_sweeps_ = false;                  // the last epoch of this (large) batch was a sweep
   static constexpr size_t kStateScratchKeep = 16u << 20;   // get_state's device scratch kept between calls up to this size
-  char* d_state_scratch_ = nullptr;
+  DeviceBuf<char> d_state_scratch_;
   size_t state_scratch_bytes_ = 0;
   static constexpr int kCounterDirect = 4;   // single reads of a measurement counter before all of them are copied to the host
   std::vector<int> h_nm_;
   bool nm_valid_ = false;
   int nm_reads_ = 0;
   void cache_reserve(long n);
-  double* h_cache_ = nullptr;                // [n][7] pose | [n][6] twist | [n][6] acceleration
+  PinnedBuf<double> h_cache_;                // [n][7] pose | [n][6] twist | [n][6] acceleration
   double* d_cache_ = nullptr;
   long cache_cap_ = 0;
   bool cache_valid_ = false;
-  int* h_done_ = nullptr;                    // completion flag of the last flush (host-mapped), and its device alias
+  PinnedBuf<int> h_done_;                    // completion flag of the last flush (host-mapped), and its device alias
   int* d_done_ = nullptr;
-  int* d_done_count_ = nullptr;              // device word: wavefronts of a multi-wavefront flush that have written their rows (StepArgs::done_count)
+  DeviceBuf<int> d_done_count_;              // device word: wavefronts of a multi-wavefront flush that have written their rows (StepArgs::done_count)
   static constexpr long kFusedFlushMax = 1024;   // up to this many queued targets the flush is ONE launch (flush)
   unsigned done_seq_ = 0;
   void wait_done(int seq);                   // spin on *h_done_ == seq, falling back to hipStreamSynchronize
@@ -636,28 +662,6 @@ class Batch {
     if (epoch_getters_ > 0) big_sweeps_ = epoch_getters_ > kBigDirect;   // (changes with no getter in between keep the verdict)
     epoch_getters_ = 0;
   }
-  static constexpr double kLiveStartTimeoutS = 2.0;
-  struct Live {
-    bool active = false;
-    bool zombie = false;             // launched, never seen running, told to stop: synchronise its stream before touching records
-    char* h_block = nullptr;         // host-mapped block: [0] the doorbell unless it lives behind the BAR, [64] the relay's words
-    long long* bar_bell = nullptr;   // the doorbell in fine-grained DEVICE memory, written by the host through the PCIe BAR (or null)
-    long long* h_posted = nullptr;   // the doorbell as the host writes it (count | stop bit)
-    long long* d_posted = nullptr;   // the same block as the device sees it
-    int* h_done = nullptr;
-    int* d_done = nullptr;
-    char* d_block = nullptr;         // device memory: [mirror word, padded to 64 B][progress words of the wavefronts]
-    double* pose_out = nullptr;      // per-tick pose output (live_set_pose_output)
-    long pose_ld = 0;
-    InnovStream gate{};              // the gate of the sessions to come (live_set_gate); !gated(): none
-    hipStream_t stream = nullptr;    // the resident kernel's own stream
-    hipEvent_t ready = nullptr;
-    long waves = 0, cap_waves = 0;
-    long posted = 0, max_ticks = 0;
-    double dt = 0.0;
-    bool all_measured = false;
-    double share = 0.0;              // > 0 while the session is counted among the process's resident sessions (hip_check.hpp)
-  } live_;
   void live_release();
 };
 

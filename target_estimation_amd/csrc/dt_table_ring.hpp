@@ -5,14 +5,14 @@
 // a word; the ring wraps, or grows, behind a synchronisation of the stream.  The device block goes through device_free (deferred
 // while a resident session of the process is alive); retired host blocks are kept until the owner goes.
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <vector>
 
-#include "hip_check.hpp"
+#include "dev_mem.hpp"
 
 namespace te {
 
@@ -21,43 +21,35 @@ class DtTableRing {
   DtTableRing() = default;
   DtTableRing(const DtTableRing&) = delete;
   DtTableRing& operator=(const DtTableRing&) = delete;
-  ~DtTableRing() {
-    device_free(d_);
-    if (h_) (void)hipHostFree(h_);
-    for (double* h : retired_) (void)hipHostFree(h);
-  }
   // the device address of the call's n entries, filled on `stream`
   const double* push(const double* dt_host, long n, hipStream_t stream) {
     if (n > cap_) {   // grow: nothing in flight may still read the old blocks
       const long want = (std::max<long>(std::max<long>(n, 256), cap_ * 2) + 15) / 16 * 16;
-      TE_HIP_CHECK(hipStreamSynchronize(stream));
-      double* h = nullptr;
-      double* d = nullptr;
-      TE_HIP_CHECK(hipHostMalloc((void**)&h, (size_t)want * sizeof(double), hipHostMallocDefault));
-      if (hipMalloc((void**)&d, (size_t)want * sizeof(double)) != hipSuccess) {
-        (void)hipHostFree(h);
-        throw std::runtime_error("target_estimation_amd: no device memory for the time-step table");
-      }
-      device_free(d_);   // (deferred while a resident session of the process is alive)
-      if (h_) retired_.push_back(h_);
-      d_ = d; h_ = h; cap_ = want; off_ = 0;
+      dev_mem_check(hipStreamSynchronize(stream), "DtTableRing::push: hipStreamSynchronize");
+      PinnedBuf<double> h;
+      DeviceBuf<double> d;
+      h.alloc((size_t)want);
+      if (!d.try_alloc((size_t)want)) throw std::runtime_error("target_estimation_amd: no device memory for the time-step table");
+      if (h_) retired_.push_back(std::move(h_));
+      d_ = std::move(d);   // (the old block's free is deferred while a resident session of the process is alive)
+      h_ = std::move(h); cap_ = want; off_ = 0;
     } else if (off_ + n > cap_) {   // wrap: the runs at the head of the ring may still be in flight
-      TE_HIP_CHECK(hipStreamSynchronize(stream));
+      dev_mem_check(hipStreamSynchronize(stream), "DtTableRing::push: hipStreamSynchronize");
       off_ = 0;
     }
-    double* h = h_ + off_;
-    double* d = d_ + off_;
+    double* h = h_.host() + off_;
+    double* d = d_.get() + off_;
     std::memcpy(h, dt_host, (size_t)n * sizeof(double));   // (the caller's array is read here, before the call returns)
-    TE_HIP_CHECK(hipMemcpyAsync(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+    dev_mem_check(hipMemcpyAsync(d, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream), "DtTableRing::push: hipMemcpyAsync");
     off_ += n;
     return d;
   }
 
  private:
-  double* d_ = nullptr;
-  double* h_ = nullptr;
   long cap_ = 0, off_ = 0;
-  std::vector<double*> retired_;
+  std::vector<PinnedBuf<double>> retired_;
+  PinnedBuf<double> h_;
+  DeviceBuf<double> d_;
 };
 
 }  // namespace te

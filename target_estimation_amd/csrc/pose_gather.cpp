@@ -65,20 +65,15 @@ PoseComm::PoseComm(const char id[kIdBytes], int rank, int world) : rank_(rank), 
   UniqueId uid;
   std::memcpy(uid.internal, id, kIdBytes);
   check(rccl().CommInitRank(&comm_, world, uid, rank), "ncclCommInitRank");
-  TE_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-  TE_HIP_CHECK(hipEventCreateWithFlags(&ready_, hipEventDisableTiming));
-  TE_HIP_CHECK(hipEventCreate(&start_));
-  TE_HIP_CHECK(hipEventCreate(&done_));
+  TE_HIP_CHECK(hipStreamCreateWithFlags(stream_.out(), hipStreamNonBlocking));
+  TE_HIP_CHECK(hipEventCreateWithFlags(ready_.out(), hipEventDisableTiming));
+  TE_HIP_CHECK(hipEventCreate(start_.out()));
+  TE_HIP_CHECK(hipEventCreate(done_.out()));
 }
 
 PoseComm::~PoseComm() {
-  if (in_flight_) (void)hipEventSynchronize(done_);
+  if (in_flight_) (void)hipEventSynchronize(done_.get());
   if (comm_) (void)rccl().CommDestroy(comm_);
-  if (stream_) (void)hipStreamDestroy(stream_);
-  if (ready_) (void)hipEventDestroy(ready_);
-  if (start_) (void)hipEventDestroy(start_);
-  if (done_) (void)hipEventDestroy(done_);
-  device_free(send_);
 }
 
 void PoseComm::begin(TargetManager* m, int root, const long* counts, double* recv_dev) {
@@ -87,10 +82,9 @@ void PoseComm::begin(TargetManager* m, int root, const long* counts, double* rec
   if (mine < 0) throw std::invalid_argument("target_estimation_amd: gather: negative row count");
   if (rank_ == root && !recv_dev && mine > 0) throw std::invalid_argument("target_estimation_amd: gather: the root needs a receive buffer");
   if (mine > send_cap_ && rank_ != root) {
-    if (in_flight_) TE_HIP_CHECK(hipEventSynchronize(done_));
-    device_free(send_);
-    send_ = nullptr; send_cap_ = 0;
-    TE_HIP_CHECK(hipMalloc((void**)&send_, sizeof(double) * 7 * mine));
+    if (in_flight_) TE_HIP_CHECK(hipEventSynchronize(done_.get()));
+    send_cap_ = 0;
+    send_.alloc(7 * (size_t)mine);
     send_cap_ = mine;
   }
   long offset = 0;
@@ -102,13 +96,13 @@ void PoseComm::begin(TargetManager* m, int root, const long* counts, double* rec
   m->posesForGather(mine, [&](long, hipStream_t st) -> double* {
     compute = st;
     // the previous gather reads the send buffer: the outputs kernels of this one wait for it ON THE DEVICE
-    if (in_flight_) TE_HIP_CHECK(hipStreamWaitEvent(compute, done_, 0));
+    if (in_flight_) TE_HIP_CHECK(hipStreamWaitEvent(compute, done_.get(), 0));
     // the root's own rows go straight into the receive buffer; every other rank fills its send buffer
-    return (rank_ == root) ? recv_dev + offset * 7 : send_;
+    return (rank_ == root) ? recv_dev + offset * 7 : send_.get();
   });
-  TE_HIP_CHECK(hipEventRecord(ready_, compute));
-  TE_HIP_CHECK(hipStreamWaitEvent(stream_, ready_, 0));
-  TE_HIP_CHECK(hipEventRecord(start_, stream_));
+  TE_HIP_CHECK(hipEventRecord(ready_.get(), compute));
+  TE_HIP_CHECK(hipStreamWaitEvent(stream_.get(), ready_.get(), 0));
+  TE_HIP_CHECK(hipEventRecord(start_.get(), stream_.get()));
   if (world_ > 1) {
     check(rccl().GroupStart(), "ncclGroupStart");
     int rc = 0;
@@ -117,26 +111,26 @@ void PoseComm::begin(TargetManager* m, int root, const long* counts, double* rec
       long off = 0;
       for (int r = 0; r < world_ && rc == 0; ++r) {
         if (r != root && counts[r] > 0) {
-          rc = rccl().Recv(recv_dev + off * 7, (size_t)counts[r] * 7, kNcclDouble, r, comm_, stream_);
+          rc = rccl().Recv(recv_dev + off * 7, (size_t)counts[r] * 7, kNcclDouble, r, comm_, stream_.get());
           if (rc != 0) failed = "ncclRecv";
         }
         off += counts[r];
       }
     } else if (mine > 0) {
-      rc = rccl().Send(send_, (size_t)mine * 7, kNcclDouble, root, comm_, stream_);
+      rc = rccl().Send(send_.get(), (size_t)mine * 7, kNcclDouble, root, comm_, stream_.get());
       if (rc != 0) failed = "ncclSend";
     }
     const int rc_end = rccl().GroupEnd();   // always: a failed Send / Recv must not leave the group open for the next call
     if (rc != 0) check(rc, failed);
     check(rc_end, "ncclGroupEnd");
   }
-  TE_HIP_CHECK(hipEventRecord(done_, stream_));
+  TE_HIP_CHECK(hipEventRecord(done_.get(), stream_.get()));
   in_flight_ = true;
 }
 
 void PoseComm::wait() {
   if (!in_flight_) return;
-  TE_HIP_CHECK(hipEventSynchronize(done_));
+  TE_HIP_CHECK(hipEventSynchronize(done_.get()));
   in_flight_ = false;
   timed_ = true;
 }
@@ -145,7 +139,7 @@ bool PoseComm::wait_for(double timeout_s) {
   if (!in_flight_) return true;
   const auto t_end = std::chrono::steady_clock::now() + std::chrono::duration<double>(timeout_s);
   for (;;) {
-    const hipError_t e = hipEventQuery(done_);
+    const hipError_t e = hipEventQuery(done_.get());
     if (e == hipSuccess) break;
     if (e != hipErrorNotReady) TE_HIP_CHECK(e);
     (void)hipGetLastError();   // hipErrorNotReady is not an error to keep
@@ -160,7 +154,7 @@ bool PoseComm::wait_for(double timeout_s) {
 float PoseComm::last_ms() {
   if (!timed_ || in_flight_) return 0.f;   // no finished gather yet: the events were never recorded
   float ms = 0.f;
-  TE_HIP_CHECK(hipEventElapsedTime(&ms, start_, done_));
+  TE_HIP_CHECK(hipEventElapsedTime(&ms, start_.get(), done_.get()));
   return ms;
 }
 

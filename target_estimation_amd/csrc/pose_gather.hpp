@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.hpp"
+
 namespace te {
 
 class TargetManager;
@@ -47,10 +49,10 @@ class PoseComm {
  private:
   void* comm_ = nullptr;
   int rank_, world_;
-  hipStream_t stream_ = nullptr;
-  hipEvent_t ready_ = nullptr, start_ = nullptr, done_ = nullptr;
+  Stream stream_;   // (declared ahead of the buffer used on them: it is destroyed first)
+  Event ready_, start_, done_;
   bool in_flight_ = false, timed_ = false;
-  double* send_ = nullptr;
+  DeviceBuf<double> send_;
   long send_cap_ = 0;
 };
 

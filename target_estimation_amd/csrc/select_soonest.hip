@@ -183,27 +183,17 @@ __global__ __launch_bounds__(kThreads) void soonest_merge_kernel(const SoonestAr
 }
 
 // ---------------------------------------------------------------- host side
-SoonestScratch::~SoonestScratch() {
-  device_free(lists_);
-  device_free(result_dev_);
-  if (result_host_) (void)hipHostFree(result_host_);
-}
-
 void SoonestScratch::ensure(int max_wgs) {
-  if (lists_) return;
+  if (result_host_) return;   // (allocated last: its presence stands for all three)
   max_wgs_ = max_wgs < 1 ? 1 : max_wgs > kSoonestMaxWgsLimit ? kSoonestMaxWgsLimit : max_wgs;
   // (a part with entries gets at least one workgroup: the grid may exceed the knob by the number of parts)
-  void* p = nullptr;
-  TE_HIP_CHECK(hipMalloc(&p, soonest_scratch_rows(max_wgs_ + kSoonestMaxParts) * sizeof(SoonestKey)));
-  lists_ = (SoonestKey*)p;
-  TE_HIP_CHECK(hipMalloc(&p, kResultBytes));
-  result_dev_ = (char*)p;
-  TE_HIP_CHECK(hipHostMalloc(&p, kResultBytes, hipHostMallocDefault));
-  result_host_ = (char*)p;
+  lists_.alloc(soonest_scratch_rows(max_wgs_ + kSoonestMaxParts));
+  result_dev_.alloc(kResultBytes);
+  result_host_.alloc(kResultBytes);
 }
 
 SoonestOut SoonestScratch::result_out(bool with_pose) const {
-  char* d = result_dev_;
+  char* d = result_dev_.get();
   return SoonestOut{(int*)(d + kOffBatch), (int*)(d + kOffSlot), (double*)(d + kOffDelta), with_pose ? (double*)(d + kOffPose) : nullptr,
                     (int*)(d + kOffCount)};
 }

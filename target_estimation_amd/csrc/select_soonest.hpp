@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dev_mem.hpp"
 #include "select_soonest_plan.hpp"
 
 namespace te {
@@ -46,24 +47,23 @@ struct SoonestOut {
 class SoonestScratch {
  public:
   SoonestScratch() = default;
-  ~SoonestScratch();
   SoonestScratch(const SoonestScratch&) = delete;
   SoonestScratch& operator=(const SoonestScratch&) = delete;
   void ensure(int max_wgs);            // allocates on first use, for first stages of up to max_wgs workgroups (ShardSettings::soonest_max_wgs)
   int max_wgs() const { return max_wgs_; }
-  SoonestKey* lists() const { return lists_; }
+  SoonestKey* lists() const { return lists_.get(); }
   // the device result of the host forms and its pinned mirror: batch int[K] | slot int[K] | delta double[K] | pose double[K][7] | count int
-  char* result_dev() const { return result_dev_; }
-  char* result_host() const { return result_host_; }
+  char* result_dev() const { return result_dev_.get(); }
+  char* result_host() const { return result_host_.host(); }
   static constexpr size_t kOffBatch = 0, kOffSlot = kSoonestMaxK * 4, kOffDelta = kSoonestMaxK * 8, kOffPose = kSoonestMaxK * 16,
                           kOffCount = kSoonestMaxK * 72, kResultBytes = kSoonestMaxK * 72 + 8;
   SoonestOut result_out(bool with_pose) const;
 
  private:
   int max_wgs_ = 0;
-  SoonestKey* lists_ = nullptr;
-  char* result_dev_ = nullptr;
-  char* result_host_ = nullptr;
+  DeviceBuf<SoonestKey> lists_;
+  DeviceBuf<char> result_dev_;
+  PinnedBuf<char> result_host_;
 };
 
 // Enqueue the three launches on `st`.  parts [n_parts <= kSoonestMaxParts] (host array; n_parts may be 0: an empty result).

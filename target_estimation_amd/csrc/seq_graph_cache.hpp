@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "hip_check.hpp"
 
 namespace te {
@@ -22,8 +23,8 @@ class SeqGraphCache {
  public:
   struct Entry {
     Key key;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    Graph graph;
+    GraphExec exec;   // (declared behind the graph: destroyed before it)
     unsigned long stamp = 0;
   };
 
@@ -40,10 +41,7 @@ class SeqGraphCache {
   }
   void stamp(Entry& e) { e.stamp = ++clock_; }
   long recordings() const { return recordings_; }   // recordings made so far
-  void drop() {                                     // (the owner knows that none is running)
-    for (auto& e : entries_) destroy(e);
-    entries_.clear();
-  }
+  void drop() { entries_.clear(); }                 // (the owner knows that none is running)
 
   // The returned entry stays where it is until the next record() or drop().
   template <class Body>
@@ -53,7 +51,6 @@ class SeqGraphCache {
       for (size_t k = 1; k < entries_.size(); ++k)
         if (entries_[k].stamp < entries_[victim].stamp) victim = k;
       TE_HIP_CHECK(hipStreamSynchronize(running));   // it may still be running
-      destroy(entries_[victim]);
       entries_.erase(entries_.begin() + (long)victim);
     }
     Entry e{std::move(key)};
@@ -61,16 +58,12 @@ class SeqGraphCache {
     try {
       body();
     } catch (...) {
-      hipGraph_t broken = nullptr;
-      (void)hipStreamEndCapture(capture, &broken);   // never leave the stream in capture mode
-      if (broken) (void)hipGraphDestroy(broken);
+      (void)hipStreamEndCapture(capture, e.graph.out());   // never leave the stream in capture mode
       throw;
     }
-    TE_HIP_CHECK(hipStreamEndCapture(capture, &e.graph));
-    if (hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess) {
-      (void)hipGraphDestroy(e.graph);
+    TE_HIP_CHECK(hipStreamEndCapture(capture, e.graph.out()));
+    if (hipGraphInstantiate(e.exec.out(), e.graph.get(), nullptr, nullptr, 0) != hipSuccess)
       throw std::runtime_error("target_estimation_amd: hipGraphInstantiate failed for a step sequence");
-    }
     stamp(e);
     entries_.push_back(std::move(e));
     ++recordings_;
@@ -78,7 +71,6 @@ class SeqGraphCache {
   }
 
  private:
-  static void destroy(Entry& e) { (void)hipGraphExecDestroy(e.exec); (void)hipGraphDestroy(e.graph); }
   const size_t capacity_;
   std::vector<Entry> entries_;
   unsigned long clock_ = 0;

@@ -19,48 +19,31 @@ static const double kZero6[6] = {0, 0, 0, 0, 0, 0};
 
 Shard::Shard(const ShardSettings& settings, std::mutex* owner_lock) : set_(settings), owner_lock_(owner_lock) {}
 
-Shard::~Shard() {
-  for (auto& r : rank_maps_) {
-    device_free(r.dev);
-    if (r.host) (void)hipHostFree(r.host);
-    if (r.copied) (void)hipEventDestroy(r.copied);
-  }
-  devIdsFree();
-  dropSeqGraphs();
-  for (auto st : branch_streams_) (void)hipStreamDestroy(st);
-  for (auto ev : branch_events_) (void)hipEventDestroy(ev);
-}
-
-void Shard::devIdsFree() {
-  DevIds& d = dev_ids_;
-  device_free(d.keys); device_free(d.vals); device_free(d.seen);
-  device_free(d.ids); device_free(d.loc); device_free(d.idx); device_free(d.aos); device_free(d.soa);
-  device_free(d.mask); device_free(d.found); device_free(d.out); device_free(d.counters); device_free(d.gnis); device_free(d.gev);
-  if (d.h_counters) (void)hipHostFree(d.h_counters);
-  d = DevIds();
-}
+Shard::~Shard() { dropSeqGraphs(); }   // (everything else is the members': shard.hpp on their order)
 
 void Shard::devIdsReserve(long n) {
   DevIds& d = dev_ids_;
-  if (!d.counters) {
-    TE_HIP_CHECK(hipMalloc((void**)&d.counters, sizeof(ResolveCounters)));
-    TE_HIP_CHECK(hipHostMalloc((void**)&d.h_counters, sizeof(ResolveCounters), hipHostMallocDefault));
+  if (!d.h_counters) {   // (the pinned word last: its presence stands for both)
+    d.counters.alloc(1);
+    d.h_counters.alloc(1);
   }
   if (n <= d.cap) return;
   const long want = std::max(n, d.cap * 2);
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  device_free(d.ids); device_free(d.loc); device_free(d.idx); device_free(d.aos); device_free(d.soa);
-  device_free(d.mask); device_free(d.found); device_free(d.out); device_free(d.gnis); device_free(d.gev);
-  TE_HIP_CHECK(hipMalloc((void**)&d.gnis, sizeof(double) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.gev, (size_t)want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.ids, sizeof(unsigned) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.loc, sizeof(int) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.idx, sizeof(int) * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.aos, sizeof(double) * 7 * want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.soa, (set_.dtype == F64 ? 8 : 4) * 7 * (size_t)want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.mask, (size_t)want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.found, (size_t)want));
-  TE_HIP_CHECK(hipMalloc((void**)&d.out, sizeof(double) * 19 * want));
+  // (nothing to carry over: released before the new blocks exist; a throw leaves an empty staging area)
+  d.cap = 0;
+  d.ids.reset(); d.loc.reset(); d.idx.reset(); d.aos.reset(); d.soa.reset();
+  d.mask.reset(); d.found.reset(); d.out.reset(); d.gnis.reset(); d.gev.reset();
+  d.gnis.alloc((size_t)want);
+  d.gev.alloc((size_t)want);
+  d.ids.alloc((size_t)want);
+  d.loc.alloc((size_t)want);
+  d.idx.alloc((size_t)want);
+  d.aos.alloc(7 * (size_t)want);
+  d.soa.alloc((set_.dtype == F64 ? 8 : 4) * 7 * (size_t)want);
+  d.mask.alloc((size_t)want);
+  d.found.alloc((size_t)want);
+  d.out.alloc(19 * (size_t)want);
   d.cap = want;
 }
 
@@ -72,24 +55,26 @@ void Shard::devIdsRebuild() {
   if (log2cap > 31) throw std::runtime_error("target_estimation_amd: too many targets for the device id table");
   if (log2cap != d.log2cap) {
     TE_HIP_CHECK(hipStreamSynchronize(stream_));
-    device_free(d.keys); device_free(d.vals); device_free(d.seen);
     const size_t cap = size_t(1) << log2cap;
-    TE_HIP_CHECK(hipMalloc((void**)&d.keys, sizeof(unsigned) * cap));
-    TE_HIP_CHECK(hipMalloc((void**)&d.vals, sizeof(unsigned) * cap));
-    TE_HIP_CHECK(hipMalloc((void**)&d.seen, sizeof(int) * cap));
+    DeviceBuf<unsigned> keys, vals;
+    DeviceBuf<int> seen;
+    keys.alloc(cap);
+    vals.alloc(cap);
+    seen.alloc(cap);
+    d.keys = std::move(keys); d.vals = std::move(vals); d.seen = std::move(seen);
     d.log2cap = log2cap;
   }
   const size_t cap = size_t(1) << d.log2cap;
-  TE_HIP_CHECK(hipMemsetAsync(d.vals, 0xFF, sizeof(unsigned) * cap, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(d.seen, 0, sizeof(int) * cap, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d.vals.get(), 0xFF, sizeof(unsigned) * cap, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d.seen.get(), 0, sizeof(int) * cap, stream_));
   d.epoch = 0;
   for (size_t b = 0; b < batches_.size(); ++b) {
     const long n = batches_[b]->size();
     if (!n) continue;
     devIdsReserve(n);
-    TE_HIP_CHECK(hipMemcpyAsync(d.ids, batches_[b]->slot_ids().data(), sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL(id_table_insert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.keys, d.vals, d.log2cap,
-                       d.ids, n, (unsigned)b);
+    TE_HIP_CHECK(hipMemcpyAsync(d.ids.get(), batches_[b]->slot_ids().data(), sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(id_table_insert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.keys.get(), d.vals.get(), d.log2cap,
+                       d.ids.get(), n, (unsigned)b);
     TE_HIP_CHECK(hipGetLastError());
     TE_HIP_CHECK(hipStreamSynchronize(stream_));   // d.ids is reused by the next batch; slot_ids() is pageable memory
   }
@@ -103,15 +88,15 @@ bool Shard::resolveOnDevice(const unsigned* ids, long n, ResolveCounters& out) {
   DevIds& d = dev_ids_;
   if (d.dirty) devIdsRebuild();
   devIdsReserve(n);
-  if (++d.epoch == 0x7fffffff) { TE_HIP_CHECK(hipMemsetAsync(d.seen, 0, sizeof(int) * (size_t(1) << d.log2cap), stream_)); d.epoch = 1; }
-  TE_HIP_CHECK(hipMemcpyAsync(d.ids, ids, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
-  TE_HIP_CHECK(hipMemsetAsync(d.counters, 0, sizeof(ResolveCounters), stream_));
-  hipLaunchKernelGGL(id_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.keys, d.vals, d.seen, d.log2cap,
-                     d.ids, n, d.epoch, d.loc, d.counters);
+  if (++d.epoch == 0x7fffffff) { TE_HIP_CHECK(hipMemsetAsync(d.seen.get(), 0, sizeof(int) * (size_t(1) << d.log2cap), stream_)); d.epoch = 1; }
+  TE_HIP_CHECK(hipMemcpyAsync(d.ids.get(), ids, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(d.counters.get(), 0, sizeof(ResolveCounters), stream_));
+  hipLaunchKernelGGL(id_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.keys.get(), d.vals.get(), d.seen.get(), d.log2cap,
+                     d.ids.get(), n, d.epoch, d.loc.get(), d.counters.get());
   TE_HIP_CHECK(hipGetLastError());
-  TE_HIP_CHECK(hipMemcpyAsync(d.h_counters, d.counters, sizeof(ResolveCounters), hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(d.h_counters.host(), d.counters.get(), sizeof(ResolveCounters), hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
-  out = *d.h_counters;
+  out = *d.h_counters.host();
   return true;
 }
 
@@ -568,26 +553,26 @@ long Shard::updateBatch(const unsigned* ids, long n, double dt, const double* me
     if (resolveOnDevice(ids, n, rc) && !rc.duplicate) {
       DevIds& d = dev_ids_;
       if (meas) {
-        TE_HIP_CHECK(hipMemcpyAsync(d.aos, meas, sizeof(double) * 7 * n, hipMemcpyHostToDevice, stream_));
-        batches_[0]->pack_meas_dev(d.aos, n, d.soa, n);
+        TE_HIP_CHECK(hipMemcpyAsync(d.aos.get(), meas, sizeof(double) * 7 * n, hipMemcpyHostToDevice, stream_));
+        batches_[0]->pack_meas_dev(d.aos.get(), n, d.soa.get(), n);
       }
-      if (meas && has_meas) TE_HIP_CHECK(hipMemcpyAsync(d.mask, has_meas, (size_t)n, hipMemcpyHostToDevice, stream_));
+      if (meas && has_meas) TE_HIP_CHECK(hipMemcpyAsync(d.mask.get(), has_meas, (size_t)n, hipMemcpyHostToDevice, stream_));
       long total = 0;
       bool rows = outs;   // the policy's rows by entry: for the caller, or as the kernel's NIS row alone
       for (size_t b = 0; b < nb && !rows; ++b) rows = meas && rc.found[b] > 0 && batches_[b]->update_gate().on();
-      if (rows) hipLaunchKernelGGL(gate_rows_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.gnis, d.gev, n);
+      if (rows) hipLaunchKernelGGL(gate_rows_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.gnis.get(), d.gev.get(), n);
       for (size_t b = 0; b < nb; ++b) {
         if (rc.found[b] <= 0) continue;
         total += rc.found[b];
-        hipLaunchKernelGGL(id_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.loc, n, (int)b, d.idx,
+        hipLaunchKernelGGL(id_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.loc.get(), n, (int)b, d.idx.get(),
                            (unsigned char*)nullptr);
         const bool pol = meas && batches_[b]->update_gate().on();
-        if (rows && !pol) hipLaunchKernelGGL(gate_rows_unjudged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.idx, d.gnis, n);
-        batches_[b]->step_indexed_dev(d.idx, n, dt, meas ? d.soa : nullptr, n, (meas && has_meas) ? d.mask : nullptr, rows ? d.gnis : nullptr,
-                                      rows ? d.gev : nullptr);
+        if (rows && !pol) hipLaunchKernelGGL(gate_rows_unjudged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.idx.get(), d.gnis.get(), n);
+        batches_[b]->step_indexed_dev(d.idx.get(), n, dt, meas ? d.soa.get() : nullptr, n, (meas && has_meas) ? d.mask.get() : nullptr, rows ? d.gnis.get() : nullptr,
+                                      rows ? d.gev.get() : nullptr);
       }
-      if (nis_out) TE_HIP_CHECK(hipMemcpyAsync(nis_out, d.gnis, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
-      if (event_out) TE_HIP_CHECK(hipMemcpyAsync(event_out, d.gev, (size_t)n, hipMemcpyDeviceToHost, stream_));
+      if (nis_out) TE_HIP_CHECK(hipMemcpyAsync(nis_out, d.gnis.get(), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+      if (event_out) TE_HIP_CHECK(hipMemcpyAsync(event_out, d.gev.get(), (size_t)n, hipMemcpyDeviceToHost, stream_));
       TE_HIP_CHECK(hipStreamSynchronize(stream_));   // the caller's host arrays may be reused after return
       return total;
     }
@@ -647,15 +632,15 @@ long Shard::getPoseBatch(const unsigned* ids, long n, double* pose, double* twis
     if (resolveOnDevice(ids, n, rc)) {
       DevIds& d = dev_ids_;
       long total = 0;
-      double* dp = pose ? d.out : nullptr;
-      double* dtw = twist ? d.out + 7 * n : nullptr;
-      double* da = acc ? d.out + 13 * n : nullptr;
+      double* dp = pose ? d.out.get() : nullptr;
+      double* dtw = twist ? d.out.get() + 7 * n : nullptr;
+      double* da = acc ? d.out.get() + 13 * n : nullptr;
       for (size_t b = 0; b < nb; ++b) {
         if (rc.found[b] <= 0) continue;
         total += rc.found[b];
-        hipLaunchKernelGGL(id_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.loc, n, (int)b, d.idx,
+        hipLaunchKernelGGL(id_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, d.loc.get(), n, (int)b, d.idx.get(),
                            (unsigned char*)nullptr);
-        batches_[b]->outputs_indexed_dev(d.idx, n, dp, dtw, da, at_time, t1);
+        batches_[b]->outputs_indexed_dev(d.idx.get(), n, dp, dtw, da, at_time, t1);
       }
       if (total == n) {   // every id known: straight into the caller's arrays
         if (pose) TE_HIP_CHECK(hipMemcpyAsync(pose, dp, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, stream_));
@@ -669,7 +654,7 @@ long Shard::getPoseBatch(const unsigned* ids, long n, double* pose, double* twis
         if (pose) TE_HIP_CHECK(hipMemcpyAsync(hp.data(), dp, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, stream_));
         if (twist) TE_HIP_CHECK(hipMemcpyAsync(ht.data(), dtw, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, stream_));
         if (acc) TE_HIP_CHECK(hipMemcpyAsync(ha.data(), da, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, stream_));
-        TE_HIP_CHECK(hipMemcpyAsync(hloc.data(), d.loc, sizeof(int) * n, hipMemcpyDeviceToHost, stream_));
+        TE_HIP_CHECK(hipMemcpyAsync(hloc.data(), d.loc.get(), sizeof(int) * n, hipMemcpyDeviceToHost, stream_));
         TE_HIP_CHECK(hipStreamSynchronize(stream_));
         for (long i = 0; i < n; ++i) {
           const bool ok = hloc[(size_t)i] >= 0;
@@ -905,14 +890,14 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
     });
     if (!hit) {
       if (branch_streams_.empty()) {
-        hipStream_t st; TE_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        branch_streams_.push_back(st);
+        Stream st; TE_HIP_CHECK(hipStreamCreateWithFlags(st.out(), hipStreamNonBlocking));
+        branch_streams_.push_back(std::move(st));
       }
       SeqKey key{n_ticks, DtKey(sched, dt), query, {org[0], org[1], org[2]}, radius, std::vector<Batch::SeqSpec>(specs, specs + nb), {}};
       for (size_t b = 0; b < nb; ++b) key.ident.push_back(batches_[b]->dev_identity());
       // The launches are captured on ONE stream whose dependency set is replaced at the head of every
       // batch's chain (hipStreamUpdateCaptureDependencies): the chains become the branches of the graph.
-      hipStream_t cap = branch_streams_[0];
+      hipStream_t cap = branch_streams_[0].get();
       using Nodes = std::vector<hipGraphNode_t>;
       auto set_deps = [&](Nodes& deps) {
         TE_HIP_CHECK(hipStreamUpdateCaptureDependencies(cap, deps.empty() ? nullptr : deps.data(), deps.size(), hipStreamSetCaptureDependencies));
@@ -951,7 +936,7 @@ void Shard::stepSequenceAll(long n_ticks, double dt, const Batch::SeqSpec* specs
       });
     }
     if (use_graph == 2) return;
-    TE_HIP_CHECK(hipGraphLaunch(hit->exec, stream_));
+    TE_HIP_CHECK(hipGraphLaunch(hit->exec.get(), stream_));
     for (size_t b = 0; b < nb; ++b) batches_[b]->note_replay(n_ticks);
   }
   for (size_t b = 0; b < nb; ++b) {
@@ -1104,19 +1089,18 @@ void Shard::uploadRanks(const std::vector<unsigned>& sorted_all) {
     if (r.cap < n) {   // a map that grows: the launches and the upload that still read the old buffers finish first
       const long want = std::max(n, r.cap * 2);
       TE_HIP_CHECK(hipStreamSynchronize(st));
-      device_free(r.dev);
-      if (r.host) (void)hipHostFree(r.host);
-      r.dev = nullptr; r.host = nullptr; r.cap = 0;
-      TE_HIP_CHECK(hipMalloc((void**)&r.dev, sizeof(int) * (size_t)want));
-      TE_HIP_CHECK(hipHostMalloc((void**)&r.host, sizeof(int) * (size_t)want, hipHostMallocDefault));
-      if (!r.copied) TE_HIP_CHECK(hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
+      r.cap = 0;
+      r.dev.reset(); r.host.reset();
+      r.dev.alloc((size_t)want);
+      r.host.alloc((size_t)want);
+      if (!r.copied) TE_HIP_CHECK(hipEventCreateWithFlags(r.copied.out(), hipEventDisableTiming));
       r.cap = want;
     } else {
-      TE_HIP_CHECK(hipEventSynchronize(r.copied));   // the previous upload has left the staging buffer (long since, as a rule)
+      TE_HIP_CHECK(hipEventSynchronize(r.copied.get()));   // the previous upload has left the staging buffer (long since, as a rule)
     }
-    ranks_of_slots(sorted_all, batches_[b]->slot_ids().data(), n, r.host);
-    TE_HIP_CHECK(hipMemcpyAsync(r.dev, r.host, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));   // stream-ordered, no host wait
-    TE_HIP_CHECK(hipEventRecord(r.copied, st));
+    ranks_of_slots(sorted_all, batches_[b]->slot_ids().data(), n, r.host.host());
+    TE_HIP_CHECK(hipMemcpyAsync(r.dev.get(), r.host.host(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));   // stream-ordered, no host wait
+    TE_HIP_CHECK(hipEventRecord(r.copied.get(), st));
   }
 }
 
@@ -1231,7 +1215,7 @@ long Shard::associate(double dt, const double* det, long M, double gate, long ro
 
 void Shard::launchRows(double* pose_out) {
   for (size_t b = 0; b < batches_.size(); ++b)
-    if (batches_[b]->size() > 0) batches_[b]->outputs_rows_dev(pose_out, rank_maps_[b].dev);
+    if (batches_[b]->size() > 0) batches_[b]->outputs_rows_dev(pose_out, rank_maps_[b].dev.get());
 }
 
 }  // namespace te

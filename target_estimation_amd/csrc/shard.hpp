@@ -237,8 +237,10 @@ class Shard {
     std::vector<Batch::DevIdentity> ident;
   };
   SeqGraphCache<SeqKey> seq_graphs_{8};
-  std::vector<hipStream_t> branch_streams_;   // [0]: the capture stream
-  std::vector<hipEvent_t> branch_events_;
+  // (declaration order matters from here on: the streams and events are declared ahead of the buffers used on them, so the
+  // buffers, destroyed last to first, go before them)
+  std::vector<Stream> branch_streams_;   // [0]: the capture stream
+  std::vector<Event> branch_events_;
   void dropSeqGraphs() { seq_graphs_.drop(); }
   void enqueuePopulationTick(hipStream_t st, long s, double dt, const Batch::SeqSpec* specs, bool query, const double* origin, double radius,
                              bool reverse, bool ab);
@@ -253,15 +255,15 @@ class Shard {
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call
   struct DevIds {
-    unsigned* keys = nullptr; unsigned* vals = nullptr; int* seen = nullptr;
+    DeviceBuf<unsigned> keys, vals; DeviceBuf<int> seen;
     int log2cap = 0; bool dirty = true; int epoch = 0;
     long cap = 0;                       // entries the staging holds
-    unsigned* ids = nullptr; int* loc = nullptr; int* idx = nullptr;
-    double* aos = nullptr; void* soa = nullptr; unsigned char* mask = nullptr; unsigned char* found = nullptr;
-    double* out = nullptr;              // [cap][7 + 6 + 6] getter outputs
-    double* gnis = nullptr; unsigned char* gev = nullptr;   // [cap] the update policy's rows by entry
-    ResolveCounters* counters = nullptr;
-    ResolveCounters* h_counters = nullptr;   // pinned
+    DeviceBuf<unsigned> ids; DeviceBuf<int> loc, idx;
+    DeviceBuf<double> aos; DeviceBuf<char> soa; DeviceBuf<unsigned char> mask, found;
+    DeviceBuf<double> out;              // [cap][7 + 6 + 6] getter outputs
+    DeviceBuf<double> gnis; DeviceBuf<unsigned char> gev;   // [cap] the update policy's rows by entry
+    DeviceBuf<ResolveCounters> counters;
+    PinnedBuf<ResolveCounters> h_counters;
   } dev_ids_;
   static constexpr long kDevResolveMin = 8192;   // below this the host table is faster than the extra launches
   bool smallBatchPath(long n) const;
@@ -269,10 +271,9 @@ class Shard {
   void devIdsRebuild();
   // loc[e] of every id on the device + the per-batch counts on the host; false: not applicable (too many batches)
   bool resolveOnDevice(const unsigned* ids, long n, ResolveCounters& out);
-  void devIdsFree();
 
   // per batch: rank_of_slot on the batch's device (getEstAllById), rebuilt after a change of membership
-  struct RankMap { int* dev = nullptr; int* host = nullptr; long cap = 0; hipEvent_t copied = nullptr; };   // host: pinned staging
+  struct RankMap { Event copied; DeviceBuf<int> dev; PinnedBuf<int> host; long cap = 0; };   // host: pinned staging
   std::vector<RankMap> rank_maps_;
 };
 

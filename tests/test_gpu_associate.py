@@ -352,6 +352,31 @@ def test_empty_sides_and_the_host_form():
     w.mgr.close()
 
 
+@pytest.mark.parametrize("through", ["batch", "manager"])
+def test_host_form_with_an_empty_frame_as_the_first_association(through):
+    """The FIRST association of a manager is a host-form call with no detections (a legal call: a frame in which nothing was
+    seen): the scratch's blocks exist all the same, so the result comes back -- nothing matched, settled, every slot without a
+    measurement -- and the next frame pairs as the device form does."""
+    w = World("uniform_velocity", "f64", "301", 65, seed=2)
+    b = w.init()
+    who = b if through == "batch" else w.mgr
+    r = who.associate(np.empty((0, 7)), DT, gate=GATE, rounds=4)
+    assert r.matched == 0 and list(r.info) == [0, 0, 1, 0]
+    assert r.slot_of_det.shape == (0,) and r.ids_of_det.shape == (0,) and r.d2_of_det.shape == (0,) and r.unmatched.shape == (0,)
+    has = r.has_meas if through == "batch" else r.has_meas[0]
+    assert not has.cpu().numpy().any()
+    x, P = w.cpu_state()
+    tl, ts = w.tables(x, P, DT)
+    det = _planted(w, tl, 67, 1)
+    rh = who.associate(det, DT, gate=GATE, rounds=16)
+    rd = b.associate(_cuda(det, np.float64), DT, gate=GATE, rounds=16)
+    torch.cuda.synchronize()
+    sod = rd.slot_of_det.cpu().numpy()
+    assert (sod >= 0).any() and np.array_equal(rh.slot_of_det, sod)
+    assert np.array_equal(_bits(rh.d2_of_det), _bits(rd.d2_of_det.cpu().numpy())) and rh.matched == int((sod >= 0).sum())
+    w.mgr.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- exact ties
 def _unit_world(n_pos, name="uniform_velocity", dtype="f64", mgr=None, ids=None, chunks=None):
     """targets at integer positions with S = I exactly at dt = 0: P0 = I / 2, Q = R = I / 4"""
