@@ -893,7 +893,8 @@ long target_manager_crossing_cov_batch(target_manager_c* m, const unsigned int* 
  *   ..._associate       detections from host memory; the per-detection rows come back with slots translated to ids (~0u: none);
  *                       unmatched_out [M] receives the unmatched detection indices in ascending order, *n_unmatched_out their
  *                       number.  The device outputs (meas_out_dev ...) are optional here.  Returns the matched count (or -1).
- * Not built: a spatial index (the scans are brute force over all pairs), orientation in the cost, a likelihood cost, several shards. */
+ * These four scan all pairs by brute force; the ..._associate_grid forms below pair through a uniform grid.
+ * Not built: orientation in the cost, a likelihood cost, several shards. */
 #define TARGET_ASSOC_MAX_DETECTIONS 65536
 #define TARGET_ASSOC_MAX_ROUNDS 16
 /* what one batch's slots get from a manager-level call: one per batch, in target_manager_get_batch order */
@@ -916,6 +917,47 @@ int target_manager_associate_dev(target_manager_c* m, double dt, const double* d
 long target_manager_associate(target_manager_c* m, double dt, const double* det_host, long M, double gate, int rounds,
                               const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out, int* batch_of_det_out,
                               int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out);
+/* ---- THE GRID FORM of the association: the same pairing for full frames -- up to TARGET_ASSOC_GRID_MAX_DETECTIONS detections
+ * against whatever the batch or manager holds -- through a uniform grid of cubic cells of edge `cell` (in the unit of the
+ * positions), so that the cost grows with the pairs that are near each other and not with N x M.    The argument
+ * lists are the brute-force siblings' plus `double cell` right after `rounds`; outputs, layouts, scatter, the host forms' id
+ * translation and unmatched_out are the siblings'.  The table row (zhat, W, tag), the inverse of S, d2, the rounds of mutual best,
+ * the settled rule and the tie rules -- (d2, detection) for a target's pick, (d2, batch, slot) for a detection's -- are the ones
+ * above.  TWO THINGS DIFFER.
+ * 1. THE CANDIDATE RULE GAINS THE GATE'S BOUNDING BOX: (i, j) is a candidate iff d2 <= gate AND nu_a * nu_a <= reach2_a(i) for each
+ *    axis a of x, y, z, with reach2_a = (gate * S_aa) * (1 + 2^-10), S_aa the diagonal of the very S that was inverted, in double,
+ *    nu_a the double that d2 is formed from; plain multiplies, no contraction, no square root.  In exact arithmetic the box
+ *    contains the gate ellipsoid (nu_a^2 <= d2 S_aa), so the grid form differs from the brute-force form only where rounding in
+ *    d2 exceeds one part in 10^3 of the gate -- a nearly singular S -- and it never accepts a pair that the brute-force form rejects.
+ * 2. gate MUST BE FINITE (the box is what bounds the search).
+ * CELLS.  A position's cell coordinate per axis is floor(x / cell) in double, clamped to [-2^30, 2^30].  A detection with a
+ * non-finite position is binned nowhere and is never a candidate.  A valid slot is NARROW iff reach2_a <= (cell (1 - 2^-20))^2 on
+ * all three axes (and that square is a normal double): all its candidates then lie within +-1 cell of the cell of zhat on each
+ * axis, and are found by walking 27 cells.  Any other valid slot is WIDE: its candidates are found by brute force over all
+ * detections -- correct, not fast.  info int[4] = {matched, rounds_run, settled, WIDE SLOTS}: a large info[3] says that cell is
+ * too small for the targets' uncertainty.  A slot with an invalid S is neither.  Cells hash into a power-of-two number of
+ * buckets (at least twice the entries binned, at least 1024; TE_ASSOC_GRID_BUCKETS, read when the manager is created, forces the
+ * number for tests); collisions cost time, never correctness.
+ * The result is a function of the inputs alone: two calls on the same inputs give byte-identical outputs.
+ * REFUSED, in addition to the siblings' refusals (M against TARGET_ASSOC_GRID_MAX_DETECTIONS): gate +inf or NaN; cell <= 0, NaN or
+ * inf.  ..._associate_grid_dev allocates nothing after the first call of at least that size, never waits on the host, and
+ * associate_grid -> step may be captured in the caller's hipGraph (a linear chain of kernel launches), like the sibling.
+ * Not built: orientation in the cost, a likelihood cost, several shards, per-tick association streams, the Eigen facade's form, an
+ * automatic choice of cell. */
+#define TARGET_ASSOC_GRID_MAX_DETECTIONS 1048576
+int target_batch_associate_grid_dev(target_batch_c* b, double dt, const double* det_dev, long M, double gate, int rounds, double cell,
+                                    void* meas_out_dev, long ld, unsigned char* has_meas_out_dev, int* det_of_slot_dev,
+                                    double* d2_of_slot_dev, int* slot_of_det_dev, double* d2_of_det_dev, int* info_dev);
+long target_batch_associate_grid(target_batch_c* b, double dt, const double* det_host, long M, double gate, int rounds, double cell,
+                                 void* meas_out_dev, long ld, unsigned char* has_meas_out_dev, unsigned int* ids_of_det_out,
+                                 int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out);
+int target_manager_associate_grid_dev(target_manager_c* m, double dt, const double* det_dev, long M, double gate, int rounds, double cell,
+                                      const target_assoc_out_c* per_batch, long n_batches, int* slot_of_det_dev, int* batch_of_det_dev,
+                                      double* d2_of_det_dev, int* info_dev);
+long target_manager_associate_grid(target_manager_c* m, double dt, const double* det_host, long M, double gate, int rounds, double cell,
+                                   const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out,
+                                   int* batch_of_det_out, int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out,
+                                   long* n_unmatched_out, int* info_out);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

@@ -141,6 +141,17 @@ SIGNATURES = {
     "target_manager_associate": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.POINTER(AssocOut), C.c_long,
                                             c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, C.POINTER(C.c_long),
                                             C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    # ... and its grid form: the same lists with `double cell` after rounds
+    "target_batch_associate_grid_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_int, C.c_double, C.c_void_p,
+                                                  C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_batch_associate_grid": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.c_double, C.c_void_p,
+                                               C.c_long, C.c_void_p, c_uint_p, C.POINTER(C.c_int), c_double_p, C.POINTER(C.c_long),
+                                               C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "target_manager_associate_grid_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_int, C.c_double,
+                                                    C.POINTER(AssocOut), C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "target_manager_associate_grid": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.c_double,
+                                                 C.POINTER(AssocOut), C.c_long, c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p,
+                                                 C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),
     "target_comm_unique_id": (C.c_int, [C.c_char_p]),
     "target_comm_new": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int]),

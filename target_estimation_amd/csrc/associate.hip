@@ -66,6 +66,9 @@ __global__ __launch_bounds__(64) void assoc_table_kernel(const AssocTableArgs a)
 #pragma unroll
   for (int k = 0; k < 6; ++k) row[3 + k] = W[k];
   reinterpret_cast<long long*>(row)[9] = ((long long)a.batch_index << 32) | (long long)(unsigned)slot;
+  if (a.sdiag) {   // the grid form (associate_grid.hpp): the diagonal of the S that was just inverted
+    a.sdiag[slot * 3] = S[0]; a.sdiag[slot * 3 + 1] = S[3]; a.sdiag[slot * 3 + 2] = S[5];
+  }
 }
 
 struct AssocScanArgs {

@@ -34,6 +34,7 @@ struct AssocTableArgs {
   double dt;
   AssocRow* rows;            // [size]: the batch's part of the call's table
   int batch_index;           // what the rows' tags carry
+  double* sdiag = nullptr;   // [size][3]: the diagonal of the S that was inverted, for the grid form (associate_grid.hpp); null: not written
 };
 // the launcher of a (model, precision, lanes per target, layout as LayoutInfo reports it, shared-axes form), or null
 using AssocTableLaunch = void (*)(const AssocTableArgs&, hipStream_t);
@@ -50,6 +51,8 @@ class AssocScratch {
   void ensure(long rows, long dets, long part_rows, long part_dets);
   // ... and for the host forms: the staged detections, the device result and its pinned mirror
   void ensure_host(long dets);
+  // ... and for the grid form (associate_grid.hpp): `buckets` = detection buckets + row buckets
+  void ensure_grid(long rows, long dets, long buckets);
 
   DeviceBuf<AssocRow> table;
   DeviceBuf<int> det_of_row;       // [rows]  -1: unmatched
@@ -61,6 +64,11 @@ class AssocScratch {
   DeviceBuf<double> part_dets_d2;  // [chunks][dets]
   DeviceBuf<int> part_dets_idx;
   DeviceBuf<int> state;            // {matched, rounds_run, settled, 0}
+  // grid form: S's diagonal and the box [rows][3]; the bucket of every detection, then of every row (-1: binned nowhere);
+  // per bucket (detection buckets first, then row buckets) the count, the exclusive start (+ the total) and the placement cursor;
+  // the scan's block sums; the bucket-grouped index list (detections, then narrow rows); the wide rows; {wide, matched, open, 0}
+  DeviceBuf<double> grid_sdiag, grid_reach2;
+  DeviceBuf<int> grid_bucket_of, grid_count, grid_start, grid_cursor, grid_sums, grid_order, grid_wide, grid_counters;
   // host forms: det [dets][7] | the result: slot int[dets] | batch int[dets] | d2 double[dets] | info int[4]
   DeviceBuf<double> det_stage;
   DeviceBuf<char> result_dev;
@@ -73,6 +81,7 @@ class AssocScratch {
 
  private:
   long cap_rows_ = 0, cap_dets_ = 0, cap_part_rows_ = 0, cap_part_dets_ = 0, cap_host_ = 0;
+  long cap_grid_rows_ = 0, cap_grid_dets_ = 0, cap_grid_buckets_ = 0;
 };
 
 // init + `rounds` rounds over a table of `rows` rows and det [M][7] (device); forced_chunks: TE_ASSOC_COL_CHUNKS or 0

@@ -1808,7 +1808,7 @@ void Batch::crossing_cov(const int* slots, long n, double t1, const double* orig
 }
 
 // ---------------------------------------------------------------- association of unlabelled detections (associate.hpp)
-void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index) {
+void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag) {
   const AssocTableLaunch launch = assoc_table_launcher(type_, dtype_, ops_->L.g, ops_->L.layout, shared_axes());
   if (!launch) throw std::logic_error("target_estimation_amd: associate: no kernel for this (model, precision, layout)");   // (never a fall-back)
   flush();
@@ -1817,14 +1817,14 @@ void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index) {
   a.rec = records_as_stored(); a.qr = d_qr_.get(); a.cls = n_classes_ > 1 ? d_cls_.get() : nullptr;
   // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
   a.tile_blk = d_tile_uni_.get() ? d_tile_blk_.get() : nullptr; a.tile_uni = d_tile_uni_.get();
-  a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index;
+  a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index; a.sdiag = sdiag;
   launch(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }
 
 void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det_dev, long M,
                        double gate, long rounds, const AssocSlotOut* out, int* slot_of_det, int* batch_of_det, double* d2_of_det, int* info,
-                       hipStream_t st) {
+                       hipStream_t st, double grid_cell, long forced_buckets) {
   long rows = 0;
   for (int b = 0; b < n_batches; ++b) {
     const LayoutInfo L = batches[b]->layout();
@@ -1833,39 +1833,55 @@ void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scrat
     rows += batches[b]->size();
   }
   if (rows > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: associate: more than 2^31 - 1 targets on one device");
-  const AssocGrid gr = plan_assoc_grid(rows, M, forced_chunks), gd = plan_assoc_grid(M, rows, forced_chunks);
-  scratch.ensure(rows, M, rows * gr.chunks, M * gd.chunks);
+  const bool grid = grid_cell > 0.0;
   long off = 0;
-  for (int b = 0; b < n_batches; ++b) {
-    batches[b]->assoc_table_dev(dt, scratch.table.get() + off, b);
-    off += batches[b]->size();
+  if (grid) {   // the grid form (associate_grid.hpp): one pick per row and per detection, the binning's temporaries
+    if (rows + M > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: associate_grid: more than 2^31 - 1 targets and detections");
+    const AssocGridBuckets bk = plan_assoc_grid_call(rows, M, forced_buckets);
+    scratch.ensure(rows, M, rows, M);
+    scratch.ensure_grid(rows, M, bk.total());
+    for (int b = 0; b < n_batches; ++b) {
+      batches[b]->assoc_table_dev(dt, scratch.table.get() + off, b, scratch.grid_sdiag.get() + off * 3);
+      off += batches[b]->size();
+    }
+    launch_assoc_grid_match(scratch, rows, det_dev, M, gate, grid_cell, (int)rounds, bk, st);
+  } else {
+    const AssocGrid gr = plan_assoc_grid(rows, M, forced_chunks), gd = plan_assoc_grid(M, rows, forced_chunks);
+    scratch.ensure(rows, M, rows * gr.chunks, M * gd.chunks);
+    for (int b = 0; b < n_batches; ++b) {
+      batches[b]->assoc_table_dev(dt, scratch.table.get() + off, b);
+      off += batches[b]->size();
+    }
+    launch_assoc_match(scratch, rows, det_dev, M, gate, (int)rounds, forced_chunks, st);
   }
-  launch_assoc_match(scratch, rows, det_dev, M, gate, (int)rounds, forced_chunks, st);
   off = 0;
   for (int b = 0; b < n_batches; ++b) {
     launch_assoc_scatter(batches[b]->dtype(), scratch, off, batches[b]->size(), det_dev, out[b], st);
     off += batches[b]->size();
   }
   launch_assoc_dets(scratch, M, slot_of_det, batch_of_det, d2_of_det, info, st);
+  if (grid) launch_assoc_grid_info(scratch, info, st);   // info[3]: the wide slots
   TE_HIP_CHECK(hipGetLastError());
 }
 
 void Batch::associate_dev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut& out, int* slot_of_det_dev,
-                          double* d2_of_det_dev, int* info_dev) {
-  check_assoc_args(dt, det_dev != nullptr, M, gate, rounds, out.meas != nullptr && out.has_meas != nullptr && info_dev != nullptr, out.ld, n_);
+                          double* d2_of_det_dev, int* info_dev, double grid_cell) {
+  check_assoc_args_for(grid_cell, dt, det_dev != nullptr, M, gate, rounds, out.meas != nullptr && out.has_meas != nullptr && info_dev != nullptr, out.ld, n_);
   if (!assoc_) throw std::logic_error("target_estimation_amd: associate: the batch belongs to no shard");
   Batch* self = this;
-  associate_batches(&self, 1, *assoc_, assoc_forced_chunks_, dt, det_dev, M, gate, rounds, &out, slot_of_det_dev, nullptr, d2_of_det_dev, info_dev, stream_);
+  associate_batches(&self, 1, *assoc_, assoc_forced_chunks_, dt, det_dev, M, gate, rounds, &out, slot_of_det_dev, nullptr, d2_of_det_dev, info_dev, stream_,
+                    grid_cell, assoc_forced_buckets_);
 }
 
 long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& s, int forced_chunks, double dt, const double* det, long M, double gate,
                             long rounds, const AssocSlotOut* out, unsigned* ids_of_det, int* batch_of_det, int* slot_of_det, double* d2_of_det,
-                            long* unmatched, long* n_unmatched, int* info, hipStream_t st) {
+                            long* unmatched, long* n_unmatched, int* info, hipStream_t st, double grid_cell, long forced_buckets) {
   s.ensure_host(M);
   if (M > 0) TE_HIP_CHECK(hipMemcpyAsync(s.det_stage.get(), det, sizeof(double) * 7 * (size_t)M, hipMemcpyHostToDevice, st));
   char* d = s.result_dev.get();
   associate_batches(batches, n_batches, s, forced_chunks, dt, s.det_stage.get(), M, gate, rounds, out, (int*)(d + AssocScratch::off_slot(M)),
-                    (int*)(d + AssocScratch::off_batch(M)), (double*)(d + AssocScratch::off_d2(M)), (int*)(d + AssocScratch::off_info(M)), st);
+                    (int*)(d + AssocScratch::off_batch(M)), (double*)(d + AssocScratch::off_d2(M)), (int*)(d + AssocScratch::off_info(M)), st, grid_cell,
+                    forced_buckets);
   TE_HIP_CHECK(hipMemcpyAsync(s.result_host.host(), d, AssocScratch::result_bytes(M), hipMemcpyDeviceToHost, st));
   TE_HIP_CHECK(hipStreamSynchronize(st));
   const char* h = s.result_host.host();
@@ -1887,13 +1903,13 @@ long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& 
 }
 
 long Batch::associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut& out, unsigned* ids_of_det,
-                      int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info) {
+                      int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell) {
   // (the host form's device outputs are optional: without them the call only reports the pairing)
-  check_assoc_args(dt, det != nullptr, M, gate, rounds, true, out.meas ? out.ld : n_, n_);
+  check_assoc_args_for(grid_cell, dt, det != nullptr, M, gate, rounds, true, out.meas ? out.ld : n_, n_);
   if (!assoc_) throw std::logic_error("target_estimation_amd: associate: the batch belongs to no shard");
   Batch* self = this;
   return associate_batches_host(&self, 1, *assoc_, assoc_forced_chunks_, dt, det, M, gate, rounds, &out, ids_of_det, nullptr, slot_of_det, d2_of_det,
-                                unmatched, n_unmatched, info, stream_);
+                                unmatched, n_unmatched, info, stream_, grid_cell, assoc_forced_buckets_);
 }
 
 }  // namespace te

@@ -22,6 +22,7 @@
 #include "select_soonest.hpp"
 #include "crossing_cov.hpp"
 #include "associate.hpp"
+#include "associate_grid.hpp"
 
 namespace te {
 
@@ -363,14 +364,18 @@ class Batch {
   //                      recording dropped, rejection runs and the clock are not touched; the queued one-target steps run first.
   //   associate_dev      the whole call for this batch alone (associate_batches below).
   //   associate          the host form: detections from host memory, the per-detection rows back (ids translated), one wait.
-  void set_assoc_scratch(AssocScratch* s, int forced_chunks) { assoc_ = s; assoc_forced_chunks_ = forced_chunks; }
+  //   grid_cell > 0      the grid form (associate_grid.hpp; target_batch_associate_grid[_dev]) with that cell edge;
+  //                      0: the brute-force form.  sdiag: where the table kernel also leaves S's diagonal, [size][3] (grid form).
+  void set_assoc_scratch(AssocScratch* s, int forced_chunks, long forced_buckets = 0) {
+    assoc_ = s; assoc_forced_chunks_ = forced_chunks; assoc_forced_buckets_ = forced_buckets;
+  }
   AssocScratch* assoc_scratch() const { return assoc_; }
   int assoc_forced_chunks() const { return assoc_forced_chunks_; }
-  void assoc_table_dev(double dt, AssocRow* rows, int batch_index);
+  void assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag = nullptr);
   void associate_dev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut& out, int* slot_of_det_dev,
-                     double* d2_of_det_dev, int* info_dev);
+                     double* d2_of_det_dev, int* info_dev, double grid_cell = 0.0);
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut& out, unsigned* ids_of_det,
-                 int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
+                 int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell = 0.0);
 
   // Building blocks of the manager's all-batches sequence (TargetManager::stepSequenceAll): enqueue
   // n_ticks ticks -- each optionally followed by the own-time sphere query of every slot -- on `st`
@@ -477,6 +482,7 @@ class Batch {
   SoonestScratch* soonest_ = nullptr;   // the owning shard's (set_soonest_scratch)
   AssocScratch* assoc_ = nullptr;       // the owning shard's (set_assoc_scratch)
   int assoc_forced_chunks_ = 0;
+  long assoc_forced_buckets_ = 0;       // TE_ASSOC_GRID_BUCKETS, 0 = planned (associate_grid_plan.hpp)
   int soonest_max_wgs_ = kSoonestDefaultMaxWgs;
   std::mutex* owner_lock_ = nullptr;
   const Ops* ops_;
@@ -670,14 +676,17 @@ class Batch {
 // d2_of_det [M] may be null; info [4] = {matched, rounds_run, settled, 0}.  Everything on `st` (the shard's one stream), no host
 // wait, no allocation unless the call is larger than every call before it on this scratch.  The arguments are the caller's to
 // check (check_assoc_args); nothing is enqueued before every batch has been found to have a table kernel.
+// grid_cell > 0: the grid form (associate_grid.hpp lists ITS launches; check_assoc_grid_args), info[3] = the wide slots;
+// forced_buckets: TE_ASSOC_GRID_BUCKETS or 0.
 void associate_batches(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det_dev, long M,
                        double gate, long rounds, const AssocSlotOut* out, int* slot_of_det, int* batch_of_det, double* d2_of_det, int* info,
-                       hipStream_t st);
+                       hipStream_t st, double grid_cell = 0.0, long forced_buckets = 0);
 // ... and its host form: det [M][7] in host memory is staged, the per-detection rows come back through the scratch's pinned mirror
 // (one wait), slots are translated to ids (~0u: none), unmatched [M] receives the unmatched detections in ascending order.  Any
 // output may be null.  Returns the matched count.
 long associate_batches_host(Batch* const* batches, int n_batches, AssocScratch& scratch, int forced_chunks, double dt, const double* det, long M,
                             double gate, long rounds, const AssocSlotOut* out, unsigned* ids_of_det, int* batch_of_det, int* slot_of_det,
-                            double* d2_of_det, long* unmatched, long* n_unmatched, int* info, hipStream_t st);
+                            double* d2_of_det, long* unmatched, long* n_unmatched, int* info, hipStream_t st, double grid_cell = 0.0,
+                            long forced_buckets = 0);
 
 }  // namespace te

@@ -174,7 +174,7 @@ int Shard::findOrCreateBatch(int type, const double* Q, const double* R, int lan
   // (the batch itself decides from Q and R whether it starts in the shared-axes form, and from every P0 whether it stays in it)
   batches_.emplace_back(new Batch(type, set_.dtype, lanes_code, Q, R, stream_, owner_lock_, set_.shared_axes, set_.uniform_tiles));
   batches_.back()->set_soonest_scratch(&soonest_, set_.soonest_max_wgs);
-  batches_.back()->set_assoc_scratch(&assoc_, set_.assoc_col_chunks);
+  batches_.back()->set_assoc_scratch(&assoc_, set_.assoc_col_chunks, set_.assoc_grid_buckets);
   if (set_.keep_meas) batches_.back()->set_keep_measurement(true);
   if (type >= 0 && type < 4 && set_.gate[type].on()) batches_.back()->set_update_gate(set_.gate[type]);
   cls = 0;
@@ -1192,25 +1192,25 @@ void check_assoc_outs(const std::vector<std::unique_ptr<Batch>>& batches, const 
 }  // namespace
 
 void Shard::associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
-                         int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev) {
-  check_assoc_args(dt, det_dev != nullptr, M, gate, rounds, info_dev != nullptr, 0, 0);
+                         int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev, double grid_cell) {
+  check_assoc_args_for(grid_cell, dt, det_dev != nullptr, M, gate, rounds, info_dev != nullptr, 0, 0);
   check_assoc_outs(batches_, out, n_out, true);
   std::vector<Batch*> bs;
   for (auto& b : batches_) bs.push_back(b.get());
   associate_batches(bs.data(), (int)bs.size(), assoc_, set_.assoc_col_chunks, dt, det_dev, M, gate, rounds, out, slot_of_det_dev, batch_of_det_dev,
-                    d2_of_det_dev, info_dev, stream_);
+                    d2_of_det_dev, info_dev, stream_, grid_cell, set_.assoc_grid_buckets);
 }
 
 long Shard::associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
-                      int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info) {
-  check_assoc_args(dt, det != nullptr, M, gate, rounds, true, 0, 0);
+                      int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell) {
+  check_assoc_args_for(grid_cell, dt, det != nullptr, M, gate, rounds, true, 0, 0);
   std::vector<AssocSlotOut> none(batches_.size());
   if (!out) { out = none.data(); n_out = (long)none.size(); }   // (the host form's device outputs are optional)
   check_assoc_outs(batches_, out, n_out, false);
   std::vector<Batch*> bs;
   for (auto& b : batches_) bs.push_back(b.get());
   return associate_batches_host(bs.data(), (int)bs.size(), assoc_, set_.assoc_col_chunks, dt, det, M, gate, rounds, out, ids_of_det, batch_of_det,
-                                slot_of_det, d2_of_det, unmatched, n_unmatched, info, stream_);
+                                slot_of_det, d2_of_det, unmatched, n_unmatched, info, stream_, grid_cell, set_.assoc_grid_buckets);
 }
 
 void Shard::launchRows(double* pose_out) {

@@ -53,6 +53,7 @@ struct ShardSettings {
   UpdateGate gate[4];            // TargetManager::setUpdateGate: the by-id update policy per model type; batches created later inherit it
   int soonest_max_wgs = kSoonestDefaultMaxWgs;   // TE_SELECT_SOONEST_MAX_WGS: the cap on the selection's first-stage workgroups (select_soonest.hpp)
   int assoc_col_chunks = 0;      // TE_ASSOC_COL_CHUNKS: the column chunks of the association scans, 0 = planned (associate_plan.hpp)
+  long assoc_grid_buckets = 0;    // TE_ASSOC_GRID_BUCKETS: the buckets of the grid form's hash, 0 = planned (associate_grid_plan.hpp)
 };
 
 // one batch of a manager-level selection (TargetManager::selectSoonest): the query outputs of target_batch_sequence_c and the
@@ -187,10 +188,11 @@ class Shard {
   // says what is launched, Batch::assoc_table_dev what is left alone): out [batches().size()], batch entries of batch_of_det are the
   // shard's batch indices.  associateDev: everything in device memory, no host wait.  associate: detections from host memory, the
   // per-detection rows back with ids; returns the matched count.
+  // grid_cell > 0: the grid form (associate_grid.hpp), 0: the brute-force form.
   void associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
-                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev);
+                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev, double grid_cell = 0.0);
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
-                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
+                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell = 0.0);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);

@@ -37,6 +37,8 @@ TargetManager::TargetManager(int dtype, int lanes_per_target) {
   settings_.soonest_max_wgs = soonest_max_wgs_from(std::getenv("TE_SELECT_SOONEST_MAX_WGS"));
   // TE_ASSOC_COL_CHUNKS=<n>: the column chunks of the association scans, so that small calls exercise the merge of the partials
   settings_.assoc_col_chunks = assoc_forced_chunks_from(std::getenv("TE_ASSOC_COL_CHUNKS"));
+  // TE_ASSOC_GRID_BUCKETS=<n>: the buckets of the grid form's hash (a power of two from 1 up), so that small calls live in collisions
+  settings_.assoc_grid_buckets = assoc_grid_forced_buckets_from(std::getenv("TE_ASSOC_GRID_BUCKETS"));
   const char* ld = std::getenv("TARGET_ESTIMATION_LOG_DIR");
   if (ld && ld[0]) { log_dir_ = ld; settings_.keep_meas = true; }   // batches created later inherit the measured-pose rows
   int count = 0;
@@ -806,20 +808,20 @@ long TargetManager::crossingCovBatch(const unsigned* ids, long n, double t1, con
 }
 
 void TargetManager::associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
-                                 int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev) {
+                                 int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev, double grid_cell) {
   lock_guard<mutex> lg(target_lock_);
   check_assoc_one_shard((long)shards_.size());
   DeviceGuard g(guardDev(0));
-  shards_[0]->associateDev(dt, det_dev, M, gate, rounds, out, n_out, slot_of_det_dev, batch_of_det_dev, d2_of_det_dev, info_dev);
+  shards_[0]->associateDev(dt, det_dev, M, gate, rounds, out, n_out, slot_of_det_dev, batch_of_det_dev, d2_of_det_dev, info_dev, grid_cell);
 }
 
 long TargetManager::associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
                               unsigned* ids_of_det, int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched,
-                              int* info) {
+                              int* info, double grid_cell) {
   lock_guard<mutex> lg(target_lock_);
   check_assoc_one_shard((long)shards_.size());
   DeviceGuard g(guardDev(0));
-  return shards_[0]->associate(dt, det, M, gate, rounds, out, n_out, ids_of_det, batch_of_det, slot_of_det, d2_of_det, unmatched, n_unmatched, info);
+  return shards_[0]->associate(dt, det, M, gate, rounds, out, n_out, ids_of_det, batch_of_det, slot_of_det, d2_of_det, unmatched, n_unmatched, info, grid_cell);
 }
 
 void TargetManager::synchronize() {

@@ -215,10 +215,11 @@ class TargetManager {
   // [numBatches()] in target_manager_get_batch order; a manager on one device only.  associateDev: no host wait; associate: host
   // detections in, per-detection rows with ids back, returns the matched count.  Neither settles a tile, demotes a batch, drops a
   // recording or touches a clock; the queued one-target steps run first.
+  // grid_cell > 0: the grid form (associate_grid.hpp; target_manager_associate_grid[_dev]), 0: the brute-force form.
   void associateDev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut* out, long n_out,
-                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev);
+                    int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev, double grid_cell = 0.0);
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
-                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info);
+                 int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell = 0.0);
 
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and

@@ -511,6 +511,56 @@ long target_manager_associate(target_manager_c* m, double dt, const double* det_
   });
 }
 
+// ---- the grid form (associate_grid.hpp): the same entry points with grid_cell set
+int target_batch_associate_grid_dev(target_batch_c* b, double dt, const double* det_dev, long M, double gate, int rounds, double cell,
+                                    void* meas_out_dev, long ld, unsigned char* has_meas_out_dev, int* det_of_slot_dev,
+                                    double* d2_of_slot_dev, int* slot_of_det_dev, double* d2_of_det_dev, int* info_dev) {
+  return guarded("target_batch_associate_grid_dev", [&] {
+    te::check_assoc_grid_args(dt, det_dev != nullptr, M, gate, rounds, cell, meas_out_dev != nullptr && has_meas_out_dev != nullptr && info_dev != nullptr, 0, 0);
+    BatchLock lk(B(b));
+    te::AssocSlotOut out;
+    out.meas = meas_out_dev; out.ld = ld; out.has_meas = has_meas_out_dev; out.det_of_slot = det_of_slot_dev; out.d2_of_slot = d2_of_slot_dev;
+    B(b)->associate_dev(dt, det_dev, M, gate, rounds, out, slot_of_det_dev, d2_of_det_dev, info_dev, cell);
+  });
+}
+
+long target_batch_associate_grid(target_batch_c* b, double dt, const double* det_host, long M, double gate, int rounds, double cell,
+                                 void* meas_out_dev, long ld, unsigned char* has_meas_out_dev, unsigned int* ids_of_det_out,
+                                 int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out, long* n_unmatched_out, int* info_out) {
+  return guarded_value<long>("target_batch_associate_grid", -1L, [&]() -> long {
+    te::check_assoc_grid_args(dt, det_host != nullptr, M, gate, rounds, cell, true, 0, 0);
+    BatchLock lk(B(b));
+    te::AssocSlotOut out;
+    out.meas = meas_out_dev; out.ld = ld; out.has_meas = has_meas_out_dev;
+    return B(b)->associate(dt, det_host, M, gate, rounds, out, ids_of_det_out, slot_of_det_out, d2_of_det_out, unmatched_out, n_unmatched_out, info_out,
+                           cell);
+  });
+}
+
+int target_manager_associate_grid_dev(target_manager_c* m, double dt, const double* det_dev, long M, double gate, int rounds, double cell,
+                                      const target_assoc_out_c* per_batch, long n_batches, int* slot_of_det_dev, int* batch_of_det_dev,
+                                      double* d2_of_det_dev, int* info_dev) {
+  return guarded("target_manager_associate_grid_dev", [&] {
+    te::check_assoc_grid_args(dt, det_dev != nullptr, M, gate, rounds, cell, info_dev != nullptr, 0, 0);
+    TargetManager* mgr = assoc_manager(m);
+    const std::vector<te::AssocSlotOut> outs = assoc_outs(per_batch, n_batches);
+    mgr->associateDev(dt, det_dev, M, gate, rounds, outs.data(), n_batches, slot_of_det_dev, batch_of_det_dev, d2_of_det_dev, info_dev, cell);
+  });
+}
+
+long target_manager_associate_grid(target_manager_c* m, double dt, const double* det_host, long M, double gate, int rounds, double cell,
+                                   const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out,
+                                   int* batch_of_det_out, int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out,
+                                   long* n_unmatched_out, int* info_out) {
+  return guarded_value<long>("target_manager_associate_grid", -1L, [&]() -> long {
+    te::check_assoc_grid_args(dt, det_host != nullptr, M, gate, rounds, cell, true, 0, 0);
+    TargetManager* mgr = assoc_manager(m);
+    const std::vector<te::AssocSlotOut> outs = assoc_outs(per_batch, n_batches);
+    return mgr->associate(dt, det_host, M, gate, rounds, per_batch ? outs.data() : nullptr, n_batches, ids_of_det_out, batch_of_det_out,
+                          slot_of_det_out, d2_of_det_out, unmatched_out, n_unmatched_out, info_out, cell);
+  });
+}
+
 int target_batch_intersect_sphere_dev(target_batch_c* b, double t1, const double* origin, double radius,
                                       double* delta_dev, double* pose_dev) {
   return guarded("target_batch_intersect_sphere_dev", [&] { BatchLock lk(B(b)); B(b)->intersect_dev(t1, origin, radius, delta_dev, pose_dev); });

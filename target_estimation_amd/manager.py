@@ -9,6 +9,7 @@ import numpy as np
 from . import capi
 
 ANGULAR_RATES, ANGULAR_VELOCITIES, UNIFORM_ACCELERATION, UNIFORM_VELOCITY = 0, 1, 2, 3
+TARGET_ASSOC_GRID_MAX_DETECTIONS = 1048576   # the most detections of a frame in the grid form of associate (target_batch_c.h)
 MODEL_TYPES = {"angular_rates": 0, "angular_velocities": 1, "uniform_acceleration": 2, "uniform_velocity": 3}
 MODEL_DIMS = {0: (18, 6), 1: (12, 6), 2: (9, 3), 3: (6, 3)}
 DTYPES = {"f64": 0, "f32": 1}
@@ -476,7 +477,7 @@ class Batch:
                "target_batch_crossing_cov_dev")
         return cov, sigma, ok
 
-    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None):
+    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None, cell=None):
         """Pair a frame of unlabelled detections with this batch's targets on the device (target_batch_associate[_dev]): the cost
         is the position-only Mahalanobis distance d2 against the filter's own predicted position and innovation covariance at
         dt, pairs with d2 <= gate are candidates, matching runs `rounds` rounds of mutual best (info[2] = 1: the greedy
@@ -486,7 +487,13 @@ class Batch:
         [size] int32, d2_of_slot [size], slot_of_det [M] int32, d2_of_det [M], info [4] int32 = (matched, rounds_run, settled, 0).
         out: such a namespace to write into (a call with the same tensors allocates nothing and may be captured in a graph).
         A host array: the host form.  Returns a SimpleNamespace of meas / has_meas (CUDA, as above) and NumPy arrays ids_of_det
-        [M] uint32 (0xffffffff: none), slot_of_det, d2_of_det, unmatched (ascending detection indices), info, and matched."""
+        [M] uint32 (0xffffffff: none), slot_of_det, d2_of_det, unmatched (ascending detection indices), info, and matched.
+        cell: None pairs by brute force over all (target, detection) pairs (M <= 65536).  A positive float takes the grid form
+        (target_batch_associate_grid[_dev]; M <= TARGET_ASSOC_GRID_MAX_DETECTIONS): cubic cells of that edge, in the unit of the
+        positions; gate must then be finite, a pair must also lie in the gate's bounding box, and info[3] is the number of
+        wide slots -- targets whose box exceeds a cell and that are therefore paired by brute force: cell is too small for them."""
+        grid = () if cell is None else (float(cell),)
+        sfx = "" if cell is None else "_grid"
         import torch
         from types import SimpleNamespace
         n = self.size
@@ -503,10 +510,10 @@ class Batch:
                 out.slot_of_det = torch.empty(M, dtype=torch.int32, device="cuda")
                 out.d2_of_det = torch.empty(M, dtype=torch.float64, device="cuda")
                 out.info = torch.empty(4, dtype=torch.int32, device="cuda")
-            _check(self._lib.target_batch_associate_dev(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), out.meas.data_ptr(), ld,
-                                                        out.has_meas.data_ptr(), out.det_of_slot.data_ptr(), out.d2_of_slot.data_ptr(),
-                                                        out.slot_of_det.data_ptr(), out.d2_of_det.data_ptr(), out.info.data_ptr()),
-                   "target_batch_associate_dev")
+            name = "target_batch_associate%s_dev" % sfx
+            _check(getattr(self._lib, name)(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), *grid, out.meas.data_ptr(), ld,
+                                            out.has_meas.data_ptr(), out.det_of_slot.data_ptr(), out.d2_of_slot.data_ptr(),
+                                            out.slot_of_det.data_ptr(), out.d2_of_det.data_ptr(), out.info.data_ptr()), name)
             return out
         det = np.ascontiguousarray(np.asarray(det, dtype=np.float64).reshape(-1, 7))
         M = det.shape[0]
@@ -517,10 +524,11 @@ class Batch:
         nu = C.c_long(0)
         out.info = np.zeros(4, dtype=np.int32)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
-        out.matched = _check(self._lib.target_batch_associate(
-            self._h, float(dt), _dp(det), M, float(gate), int(rounds), out.meas.data_ptr(), ld, out.has_meas.data_ptr(),
+        name = "target_batch_associate%s" % sfx
+        out.matched = _check(getattr(self._lib, name)(
+            self._h, float(dt), _dp(det), M, float(gate), int(rounds), *grid, out.meas.data_ptr(), ld, out.has_meas.data_ptr(),
             out.ids_of_det.ctypes.data_as(capi.c_uint_p), ip(out.slot_of_det), _dp(out.d2_of_det),
-            unmatched.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nu), ip(out.info)), "target_batch_associate")
+            unmatched.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nu), ip(out.info)), name)
         out.unmatched = unmatched[:nu.value].copy()
         return out
 
@@ -1166,7 +1174,7 @@ class TargetManager:
                        "target_manager_crossing_cov_batch")
         return found, cov, sigma, None if ok is None else ok.astype(bool)
 
-    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None):
+    def associate(self, det, dt, gate=float("inf"), rounds=8, out=None, cell=None):
         """Pair a frame of unlabelled detections with every target of the manager on the device (target_manager_associate[_dev];
         a manager on one device only): as Batch.associate, a detection picking among the targets of all batches by (d2, batch,
         slot).  det: [M, 7].  A CUDA double tensor: the device form, no host wait.  Returns a SimpleNamespace: meas / has_meas /
@@ -1174,9 +1182,12 @@ class TargetManager:
         one-tick form step_sequence_all(dt, r.meas, r.has_meas, n_ticks=1) reads, has_meas[i] [1, size_i]), slot_of_det /
         batch_of_det / d2_of_det [M] and info [4] CUDA tensors.  out: such a namespace to write into.
         A host array: the host form; the per-detection results come back as NumPy arrays ids_of_det, batch_of_det, slot_of_det,
-        d2_of_det, unmatched, info, and matched."""
+        d2_of_det, unmatched, info, and matched.
+        cell: None = brute force; a positive float = the grid form (target_manager_associate_grid[_dev]), as Batch.associate."""
         import torch
         from types import SimpleNamespace
+        grid = () if cell is None else (float(cell),)
+        sfx = "" if cell is None else "_grid"
         bs = self.batches()
         nb = len(bs)
         if out is None:
@@ -1197,9 +1208,10 @@ class TargetManager:
                 out.batch_of_det = torch.empty(M, dtype=torch.int32, device="cuda")
                 out.d2_of_det = torch.empty(M, dtype=torch.float64, device="cuda")
                 out.info = torch.empty(4, dtype=torch.int32, device="cuda")
-            _check(self._lib.target_manager_associate_dev(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), per, nb,
-                                                          out.slot_of_det.data_ptr(), out.batch_of_det.data_ptr(), out.d2_of_det.data_ptr(),
-                                                          out.info.data_ptr()), "target_manager_associate_dev")
+            name = "target_manager_associate%s_dev" % sfx
+            _check(getattr(self._lib, name)(self._h, float(dt), det.data_ptr(), M, float(gate), int(rounds), *grid, per, nb,
+                                            out.slot_of_det.data_ptr(), out.batch_of_det.data_ptr(), out.d2_of_det.data_ptr(),
+                                            out.info.data_ptr()), name)
             return out
         det = np.ascontiguousarray(np.asarray(det, dtype=np.float64).reshape(-1, 7))
         M = det.shape[0]
@@ -1211,10 +1223,11 @@ class TargetManager:
         nu = C.c_long(0)
         out.info = np.zeros(4, dtype=np.int32)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
-        out.matched = _check(self._lib.target_manager_associate(
-            self._h, float(dt), _dp(det), M, float(gate), int(rounds), per, nb, out.ids_of_det.ctypes.data_as(capi.c_uint_p),
+        name = "target_manager_associate%s" % sfx
+        out.matched = _check(getattr(self._lib, name)(
+            self._h, float(dt), _dp(det), M, float(gate), int(rounds), *grid, per, nb, out.ids_of_det.ctypes.data_as(capi.c_uint_p),
             ip(out.batch_of_det), ip(out.slot_of_det), _dp(out.d2_of_det), unmatched.ctypes.data_as(C.POINTER(C.c_long)), C.byref(nu),
-            ip(out.info)), "target_manager_associate")
+            ip(out.info)), name)
         out.unmatched = unmatched[:nu.value].copy()
         return out
 
