@@ -958,6 +958,61 @@ long target_manager_associate_grid(target_manager_c* m, double dt, const double*
                                    const target_assoc_out_c* per_batch, long n_batches, unsigned int* ids_of_det_out,
                                    int* batch_of_det_out, int* slot_of_det_out, double* d2_of_det_out, long* unmatched_out,
                                    long* n_unmatched_out, int* info_out);
+/* ---- TRACK LIFECYCLE: start and retire targets from an association's results, on the device.    The unlabelled
+ * path's counterpart of what target_ingest_* does for labelled measurements: a detection that matched nothing becomes a target, a
+ * target that nothing has matched for max_misses frames goes away.  Only counts, the retired slots and the new ids cross the bus.
+ * ORDER: associate -> step -> lifecycle.  Call it AFTER the tick that consumed the association: the lifecycle moves slots, so the
+ * meas_out / has_meas_out columns of that association are STALE afterwards and must not be stepped again.
+ * INPUTS, all device memory, all left untouched: det_dev [M][7] the frame; slot_of_det_dev [M] (< 0: unmatched) as
+ * target_manager_associate[_grid]_dev wrote it; has_meas_dev [n_batches] one pointer per batch in target_manager_get_batch order,
+ * the has_meas_out_dev [size] mask of the same target_assoc_out_c array (1: this slot was matched in this frame).  A caller on the
+ * labelled path who builds the masks itself may use the retirement half alone (M = 0).
+ * COUNTERS, two bytes per slot, library-owned like the rejection runs: miss = the run of consecutive lifecycle calls in which the
+ * slot's mask byte was 0 (reset by a 1, saturates at 255); hits = the calls with a 1 since creation (saturates at 255).  Both are 0
+ * at creation, however the target was created; both follow their target through every erase and through growth; only lifecycle
+ * calls write them.  target_batch_track_counts copies them out (slot order; either array may be NULL; synchronises like
+ * target_batch_rejection_runs); target_manager_get_track_counts returns 0 and one target's pair, 1 for an unknown id.
+ * RULE.  The result is a function of the inputs alone.
+ * 1. Every slot of every batch: miss and hits are updated from the mask.  A slot is STALE iff max_misses >= 1 and its new miss >=
+ *    max_misses.  max_misses = 0 retires nobody; the counters are still kept.
+ * 2. Detection j is BORN iff birth_type >= 0, slot_of_det[j] < 0, all seven words of its row are finite, and its rank among such
+ *    detections, in ascending j, is < max_births (the lowest detection indices win).
+ * 3. Retirements first: per batch the stale slots are erased as target_manager_erase_batch erases them given the ascending list
+ *    (holes below the new size are filled, in order, by the survivors at or above it).
+ * 4. Then births, appended in ascending j to the batch target_manager_init_batch_typed(birth_type, ...) would put them in (created
+ *    if need be): born target j gets the id first_id + j and, bit for bit, the record that call creates from p0 = det[j],
+ *    v0 = a0 = NULL, t0 = t_birth, dt0, Q, R, P0 with per_target_P0 = 0.  Q = R = P0 = NULL means the manager's own model
+ *    parameters, allowed only when birth_type is the manager's default model.
+ * OUTPUTS, host memory: retired_ids_out [retired_cap] the ids that went away, per batch in batch order, ascending former slot;
+ * info long[6] = {retired, born, unmatched detections not born because of the cap, unmatched detections not born because
+ * non-finite, first new id, one past the last new id}.  Returns 0, or -1 with target_manager_last_error.
+ * REFUSED, and NOTHING CHANGES on a refusal (counters, records, ids, sizes): a NULL handle, policy or info; M < 0 or
+ * M > TARGET_ASSOC_GRID_MAX_DETECTIONS; det or slot_of_det NULL with M > 0 and births on; n_batches != target_manager_num_batches; a
+ * NULL mask for a non-empty batch; max_misses outside 0..255; birth_type outside -1..3; max_births < 0; NaN t_birth or dt0; only
+ * some of Q, R, P0 given; the manager's parameters asked for a model that is not its default; a manager with several shards;
+ * retired_cap smaller than the number retired; an id of [first_id, first_id + born) already in the manager, or that range
+ * wrapping past 2^32 - 1.  What needs no handle is refused before the handle is looked at.  The plan is formed in scratch memory
+ * and read back before anything is committed, so the refusals that depend on it change nothing either.
+ * The call WAITS ON THE HOST and changes sizes: it is NOT CAPTURABLE in a hipGraph, and it does what erase and init already do to
+ * recorded sequences, uniform tiles, shared-axes batches and live sessions.  Queued one-target steps and inits run first.
+ * Not built: merging several unmatched detections of one new object; a time-based (seconds) expiry; a confirmed-only mask for the
+ * getters; several shards; the Eigen facade. */
+typedef struct target_lifecycle_c {
+  int max_misses;          /* K >= 1: retire on the K-th consecutive frame without a match; 0: retire nobody */
+  int birth_type;          /* motion model 0..3 of new targets; -1: no births */
+  unsigned int first_id;   /* born target j, in ascending detection index, gets first_id + j */
+  long max_births;         /* cap per call */
+  double dt0;              /* as target_manager_init_batch_typed */
+  double t_birth;          /* its t0 */
+  const double* Q;         /* as target_manager_init_batch_typed with per_target_P0 = 0; all three NULL: the manager's own */
+  const double* R;
+  const double* P0;
+} target_lifecycle_c;
+int target_manager_lifecycle(target_manager_c* m, const double* det_dev, const int* slot_of_det_dev, long M,
+                             const unsigned char* const* has_meas_dev, long n_batches, const target_lifecycle_c* policy,
+                             unsigned int* retired_ids_out, long retired_cap, long* info);
+int target_batch_track_counts(target_batch_c* b, unsigned char* miss_host, unsigned char* hits_host);
+int target_manager_get_track_counts(target_manager_c* m, unsigned int id, int* miss, int* hits);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

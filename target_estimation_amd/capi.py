@@ -50,6 +50,12 @@ class AssocOut(C.Structure):
                 ("d2_of_slot_dev", C.c_void_p)]
 
 
+class Lifecycle(C.Structure):
+    """target_lifecycle_c of target_batch_c.h: the policy of a track-lifecycle call"""
+    _fields_ = [("max_misses", C.c_int), ("birth_type", C.c_int), ("first_id", C.c_uint), ("max_births", C.c_long), ("dt0", C.c_double),
+                ("t_birth", C.c_double), ("Q", c_double_p), ("R", c_double_p), ("P0", c_double_p)]
+
+
 SIGNATURES = {
     # target_manager_c.h (the reference's ten symbols)
     "target_manager_new": (C.c_void_p, [C.c_char_p]),
@@ -152,6 +158,11 @@ SIGNATURES = {
     "target_manager_associate_grid": (C.c_long, [C.c_void_p, C.c_double, c_double_p, C.c_long, C.c_double, C.c_int, C.c_double,
                                                  C.POINTER(AssocOut), C.c_long, c_uint_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p,
                                                  C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    # track lifecycle: device pointers as void* (the masks: an array of them), host arrays typed
+    "target_manager_lifecycle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_void_p), C.c_long, C.POINTER(Lifecycle),
+                                           c_uint_p, C.c_long, C.POINTER(C.c_long)]),
+    "target_batch_track_counts": (C.c_int, [C.c_void_p, c_ubyte_p, c_ubyte_p]),
+    "target_manager_get_track_counts": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),
     "target_comm_unique_id": (C.c_int, [C.c_char_p]),
     "target_comm_new": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int]),

@@ -173,6 +173,10 @@ __global__ void run_moves_kernel(unsigned char* run, const int* src, const int* 
 
 void Batch::run_move(long src, long dst) {
   if (d_run_) TE_HIP_CHECK(hipMemcpyAsync(d_run_.get() + dst, d_run_.get() + src, 1, hipMemcpyDeviceToDevice, stream_));
+  if (d_miss_) {   // the track counters follow their target as the run does
+    TE_HIP_CHECK(hipMemcpyAsync(d_miss_.get() + dst, d_miss_.get() + src, 1, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(d_hits_.get() + dst, d_hits_.get() + src, 1, hipMemcpyDeviceToDevice, stream_));
+  }
   p0idx_dirty_.mark(dst, 1);
 }
 
@@ -256,6 +260,24 @@ void Batch::rejection_runs(unsigned char* out) {
   if (n_ <= 0) return;
   TE_HIP_CHECK(hipMemcpyAsync(out, d_run_.get(), (size_t)n_, hipMemcpyDeviceToHost, stream_));
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Batch::track_counts(unsigned char* miss_out, unsigned char* hits_out) {
+  flush();
+  if (n_ <= 0) return;
+  if (miss_out) TE_HIP_CHECK(hipMemcpyAsync(miss_out, d_miss_.get(), (size_t)n_, hipMemcpyDeviceToHost, stream_));
+  if (hits_out) TE_HIP_CHECK(hipMemcpyAsync(hits_out, d_hits_.get(), (size_t)n_, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+void Batch::track_count(long slot, int& miss, int& hits) {
+  flush();
+  if (slot < 0 || slot >= n_) throw std::runtime_error("target_estimation_amd: track_count: bad slot");
+  unsigned char c[2] = {0, 0};
+  TE_HIP_CHECK(hipMemcpyAsync(&c[0], d_miss_.get() + slot, 1, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipMemcpyAsync(&c[1], d_hits_.get() + slot, 1, hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  miss = (int)c[0]; hits = (int)c[1];
 }
 
 int Batch::rejection_run(long slot) {
@@ -495,7 +517,7 @@ void Batch::reserve(long n) {
   DeviceBuf<TClock> tb;
   DeviceBuf<int> nm, cl, p0idx, uni;
   DeviceBuf<double> lm, blk;
-  DeviceBuf<unsigned char> has_eff, run;
+  DeviceBuf<unsigned char> has_eff, run, miss, hits;
   rec.alloc(new_bytes);
   tb.alloc((size_t)want);
   nm.alloc((size_t)want);
@@ -503,6 +525,8 @@ void Batch::reserve(long n) {
   if (keep_meas_) lm.alloc(7 * (size_t)want);
   has_eff.alloc((size_t)want);   // (the gate's mask row is written whole by every launch that reads it: no contents to carry over)
   run.alloc((size_t)want);
+  miss.alloc((size_t)want);
+  hits.alloc((size_t)want);
   p0idx.alloc((size_t)want);
   if (tiles) { blk.alloc(tiles * (size_t)ops_->L.lin_words); uni.alloc(tiles); }
   TE_HIP_CHECK(hipMemsetAsync(rec.get(), 0, new_bytes, stream_));
@@ -520,6 +544,13 @@ void Batch::reserve(long n) {
   // the rejection runs follow their targets; the slot -> row index is uploaded again from the host's (prepare_reacquire)
   TE_HIP_CHECK(hipMemsetAsync(run.get(), 0, (size_t)want, stream_));
   if (d_run_ && n_ > 0) TE_HIP_CHECK(hipMemcpyAsync(run.get(), d_run_.get(), (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+  // ... and so do the track counters
+  TE_HIP_CHECK(hipMemsetAsync(miss.get(), 0, (size_t)want, stream_));
+  TE_HIP_CHECK(hipMemsetAsync(hits.get(), 0, (size_t)want, stream_));
+  if (d_miss_ && n_ > 0) {
+    TE_HIP_CHECK(hipMemcpyAsync(miss.get(), d_miss_.get(), (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+    TE_HIP_CHECK(hipMemcpyAsync(hits.get(), d_hits_.get(), (size_t)n_, hipMemcpyDeviceToDevice, stream_));
+  }
   TE_HIP_CHECK(hipStreamSynchronize(stream_));
   if (tiles) {
     TE_HIP_CHECK(hipMemsetAsync(blk.get(), 0, sizeof(double) * tiles * (size_t)ops_->L.lin_words, stream_));
@@ -533,6 +564,7 @@ void Batch::reserve(long n) {
   if (keep_meas_) d_lastmeas_ = std::move(lm);
   d_has_eff_ = std::move(has_eff);
   d_run_ = std::move(run);
+  d_miss_ = std::move(miss); d_hits_ = std::move(hits);
   d_p0idx_ = std::move(p0idx);
   p0idx_dirty_.clear(); p0idx_dirty_.mark(0, want);
   d_tile_blk_ = std::move(blk); d_tile_uni_ = std::move(uni);
@@ -602,7 +634,7 @@ void Batch::flush_inits() {
 // The device side of append (and, with `bookkeeping`, the host side of a multi-target append): records first .. first + count.
 long Batch::append_now(long first, long count, const unsigned* ids, double t0, const double* P0, bool per_target_P0,
                        const double* p0, const double* v0, const double* a0, int cls, const int* cls_of, const int* P0_index,
-                       long P0_count, bool bookkeeping) {
+                       long P0_count, bool bookkeeping, const double* gather_det_dev, const int* gather_rows_dev) {
   const int N = ops_->L.n;
   reserve(first + count);
   stage_reserve((cls_of || P0_index) ? 3 * count : count);   // slot list (+ per-entry class and P0 indices)
@@ -612,7 +644,8 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
   double* d_p0 = d_aos_.get();
   double* d_v0 = d_aos_.get() + 7 * count;
   double* d_a0 = d_aos_.get() + 13 * count;
-  TE_HIP_CHECK(hipMemcpyAsync(d_p0, p0, sizeof(double) * 7 * count, hipMemcpyHostToDevice, stream_));
+  if (gather_det_dev) launch_lifecycle_gather(gather_det_dev, gather_rows_dev, count, d_p0, stream_);   // (the rows never leave the device)
+  else TE_HIP_CHECK(hipMemcpyAsync(d_p0, p0, sizeof(double) * 7 * count, hipMemcpyHostToDevice, stream_));
   if (v0) TE_HIP_CHECK(hipMemcpyAsync(d_v0, v0, sizeof(double) * 6 * count, hipMemcpyHostToDevice, stream_));
   if (a0) TE_HIP_CHECK(hipMemcpyAsync(d_a0, a0, sizeof(double) * 6 * count, hipMemcpyHostToDevice, stream_));
   const long p0_words = (P0_index ? P0_count : (per_target_P0 ? count : 1)) * (long)N * N;
@@ -636,6 +669,8 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
   ops_->init(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
   TE_HIP_CHECK(hipMemsetAsync(d_run_.get() + first, 0, (size_t)count, stream_));   // a new target has no rejections behind it
+  TE_HIP_CHECK(hipMemsetAsync(d_miss_.get() + first, 0, (size_t)count, stream_));  // ... and neither misses nor hits
+  TE_HIP_CHECK(hipMemsetAsync(d_hits_.get() + first, 0, (size_t)count, stream_));
   p0idx_dirty_.mark(first, count);
   if (d_gate_ring_) { if (gate_cap_ < cap_) gate_reserve(gate_window_); gate_reset(first, count); }
   if (keep_meas_) {
@@ -661,6 +696,13 @@ long Batch::append_now(long first, long count, const unsigned* ids, double t0, c
     n_ += count;
   }
   return first;
+}
+
+long Batch::append_gathered(long count, const unsigned* ids, double t0, const double* P0, int cls, const double* det_dev, const int* rows_dev) {
+  if (count > 0 && shared_axes() && !shared_axes_p0_ok(type_, P0, 1)) demote_shared();
+  touch();
+  if (count <= 0) return n_;
+  return append_now(n_, count, ids, t0, P0, false, nullptr, nullptr, nullptr, cls, nullptr, nullptr, 0, true, det_dev, rows_dev);
 }
 
 unsigned Batch::erase_slot(long slot) {
@@ -711,6 +753,7 @@ void Batch::erase_slots(const int* slots, long k, std::vector<std::pair<unsigned
     TE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(run_moves_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream_, d_run_.get(), d_idx_.get(), d_idx_.get() + m, m);
     TE_HIP_CHECK(hipGetLastError());
+    launch_lifecycle_moves(d_miss_.get(), d_hits_.get(), d_idx_.get(), d_idx_.get() + m, m, stream_);
     for (long j = 0; j < m; ++j) {
       p0idx_dirty_.mark(dst[(size_t)j], 1);
       gate_move(src[(size_t)j], dst[(size_t)j]);

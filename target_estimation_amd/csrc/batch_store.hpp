@@ -23,6 +23,7 @@
 #include "crossing_cov.hpp"
 #include "associate.hpp"
 #include "associate_grid.hpp"
+#include "lifecycle.hpp"
 
 namespace te {
 
@@ -211,6 +212,17 @@ class Batch {
   // the rejection run of every slot (host array [size()]); synchronises
   void rejection_runs(unsigned char* out);
   int rejection_run(long slot);
+  // THE TRACK COUNTERS (lifecycle_plan.hpp; target_manager_lifecycle): per slot the run of consecutive lifecycle
+  // calls without a match (miss) and the calls with one since creation (hits), both saturating at 255.  Library-owned like the
+  // rejection runs: 0 at creation, they follow their target through erase and growth; only the lifecycle's commit writes them.
+  void track_counts(unsigned char* miss_out, unsigned char* hits_out);   // host arrays [size()]; synchronises
+  void track_count(long slot, int& miss, int& hits);
+  unsigned char* track_miss_dev() const { return d_miss_.get(); }
+  unsigned char* track_hits_dev() const { return d_hits_.get(); }
+  // `count` new targets whose poses are rows of a frame in DEVICE memory: p0 of target r = det_dev[rows_dev[r]] (seven doubles),
+  // v0 = a0 = null, one P0 and class for all -- record for record what append(count, ids, t0, P0, false, p0, null, null, cls)
+  // creates from the same rows, through the same init launcher; only the staging of p0 is a gather launch instead of a copy.
+  long append_gathered(long count, const unsigned* ids, double t0, const double* P0, int cls, const double* det_dev, const int* rows_dev);
   // RESIDENT ("live") mode for small batches: ONE launch stays on the device with the batch's state in registers and serves
   // tick after tick as the host posts them -- no per-tick dispatch (a dependent launch costs 1.5-2 us, more than the tick of a
   // 10^4-target batch itself).  Protocol:
@@ -563,6 +575,7 @@ class Batch {
   DeviceBuf<double> d_p0tab_;            // [p0tab_dev_.cap][N*N]
   P0TableMirror p0tab_dev_;
   void run_move(long src, long dst);
+  DeviceBuf<unsigned char> d_miss_, d_hits_;   // [cap_] each, allocated with the records: the track counters (track_counts)
   void fill_reacquire(StepParams& p, const InnovStream& innov, long s_call) const;   // the policy's launch parameters of tick s_call of a call
   void prepare_p0_tables();              // the body of prepare_reacquire
   void prepare_fused_reacquire(const InnovStream& innov);   // ... of a fused call (whose kernel reads no table for K = 0)
@@ -617,7 +630,8 @@ class Batch {
   struct InitQueue { std::vector<unsigned> ids; std::vector<double> p0, v0, a0, P0; double t0 = 0.0; int cls = 0; long first = 0; } initq_;
   void flush_inits();
   long append_now(long first, long count, const unsigned* ids, double t0, const double* P0, bool per_target_P0, const double* p0,
-                  const double* v0, const double* a0, int cls, const int* cls_of, const int* P0_index, long P0_count, bool bookkeeping);
+                  const double* v0, const double* a0, int cls, const int* cls_of, const int* P0_index, long P0_count, bool bookkeeping,
+                  const double* gather_det_dev = nullptr, const int* gather_rows_dev = nullptr);   // (gather: p0 from device rows, append_gathered)
   // queue of one-target steps (reference C ABI) and the cache that serves the one-target getters
   struct Pending { int slot; unsigned char has; double dt; double meas[7]; long out = -1; };   // out: position in the gate sink, or -1
   std::vector<Pending> pending_;

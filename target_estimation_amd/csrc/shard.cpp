@@ -464,6 +464,13 @@ int Shard::rejectionRun(unsigned id) {
   return -1;
 }
 
+bool Shard::trackCounts(unsigned id, int& miss, int& hits) {
+  Loc loc;
+  if (!find(id, loc)) return false;
+  batches_[(size_t)loc.batch]->track_count(loc.slot, miss, hits);
+  return true;
+}
+
 // Node-tick sizes (a few to a thousand targets per call) are a LATENCY path: staging copies and separate launches cost more than
 // the step itself (40 targets: 22 us for the dense host path below, 78 us with the getters behind it).  They go through the
 // one-target queue instead -- host table look-up per id, one indexed launch at the next read, the queue behind the PCIe BAR and the
@@ -1211,6 +1218,107 @@ long Shard::associate(double dt, const double* det, long M, double gate, long ro
   for (auto& b : batches_) bs.push_back(b.get());
   return associate_batches_host(bs.data(), (int)bs.size(), assoc_, set_.assoc_col_chunks, dt, det, M, gate, rounds, out, ids_of_det, batch_of_det,
                                 slot_of_det, d2_of_det, unmatched, n_unmatched, info, stream_, grid_cell, set_.assoc_grid_buckets);
+}
+
+// ---------------------------------------------------------------- track lifecycle (lifecycle.hpp lists the launches)
+void Shard::lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
+                      const LifecyclePolicy& p, unsigned* retired_ids_out, long retired_cap, long* info) {
+  const std::string pre = "target_estimation_amd: lifecycle: ";
+  const long nb = (long)batches_.size();
+  if (n_masks != nb) throw std::invalid_argument(pre + "n_batches " + std::to_string(n_masks) + " is not the manager's " + std::to_string(nb));
+  long rows = 0;
+  for (long b = 0; b < nb; ++b) {
+    if (batches_[(size_t)b]->size() > 0 && !has_dev[b]) throw std::invalid_argument(pre + "the mask of a non-empty batch is NULL");
+    rows += batches_[(size_t)b]->size();
+  }
+  const bool births = p.births() && M > 0;
+  for (auto& b : batches_) b->prepare();   // the queued one-target steps and inits run first
+  LifecycleScratch& s = life_;
+  s.ensure(rows, M, nb);
+
+  // THE PLAN, into the scratch alone
+  long off = 0;
+  for (long b = 0; b < nb; ++b) {
+    Batch& bt = *batches_[(size_t)b];
+    const long n = bt.size();
+    if (n > 0) launch_lifecycle_count(has_dev[b], bt.track_miss_dev(), bt.track_hits_dev(), s.new_miss.get() + off, s.new_hits.get() + off,
+                                      s.flag.get() + off, n, p.max_misses, stream_);
+    launch_lifecycle_compact(s.flag.get() + off, 1, n, s.sums.get(), s.list.get() + off, s.counts.get() + b, stream_);
+    off += n;
+  }
+  if (births) launch_lifecycle_det_flags(det_dev, slot_of_det_dev, s.flag.get() + rows, M, stream_);
+  launch_lifecycle_compact(s.flag.get() + rows, kLifecycleDetCandidate, births ? M : 0, s.sums.get(), s.list.get() + rows, s.counts.get() + nb, stream_);
+  launch_lifecycle_compact(s.flag.get() + rows, kLifecycleDetNonFinite, births ? M : 0, s.sums.get(), nullptr, s.counts.get() + nb + 1, stream_);
+  int* h = s.host.host();
+  TE_HIP_CHECK(hipMemcpyAsync(h, s.counts.get(), sizeof(int) * (size_t)(nb + 2), hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  long retired = 0;
+  std::vector<long> stale_off((size_t)nb + 1, 0);   // where batch b's list lies behind the counts in the pinned block
+  for (long b = 0; b < nb; ++b) {
+    if (h[b] < 0 || h[b] > batches_[(size_t)b]->size()) throw std::runtime_error(pre + "a stale count out of range");
+    stale_off[(size_t)b + 1] = stale_off[(size_t)b] + h[b];
+  }
+  retired = stale_off[(size_t)nb];
+  const long candidates = h[nb], nonfinite = h[nb + 1];
+  if (candidates < 0 || nonfinite < 0 || candidates + nonfinite > M) throw std::runtime_error(pre + "a detection count out of range");
+  const long born = births ? lifecycle_born(candidates, p.max_births) : 0;
+  if (retired > retired_cap)
+    throw std::invalid_argument(pre + "retired_cap " + std::to_string(retired_cap) + " < " + std::to_string(retired) + " targets to retire");
+  if (lifecycle_ids_wrap(p.first_id, born)) throw std::invalid_argument(pre + "the new ids wrap past 2^32 - 1");
+  for (long j = 0; j < born; ++j)
+    if (targets_.contains(p.first_id + (unsigned)j))
+      throw std::invalid_argument(pre + "id " + std::to_string(p.first_id + (unsigned)j) + " of the new range exists already");
+  int* lists = h + nb + 2;
+  if (retired > 0) {
+    off = 0;
+    for (long b = 0; b < nb; ++b) {
+      const long k = stale_off[(size_t)b + 1] - stale_off[(size_t)b];
+      if (k > 0) TE_HIP_CHECK(hipMemcpyAsync(lists + stale_off[(size_t)b], s.list.get() + off, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, stream_));
+      off += batches_[(size_t)b]->size();
+    }
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+  // the batch of the births, before anything is committed: a layout that is refused must leave everything as it was
+  int birth_layout = 0;
+  if (born > 0) birth_layout = chooseLayout(p.birth_type, p.Q, p.R, p.P0, 1);
+
+  // THE COMMIT: counters, then retirements, then births
+  off = 0;
+  for (long b = 0; b < nb; ++b) {
+    Batch& bt = *batches_[(size_t)b];
+    const long n = bt.size();
+    // (on the batch's own stream, ahead of its erase and append; the scratch was complete at the wait above)
+    launch_lifecycle_commit(bt.track_miss_dev(), bt.track_hits_dev(), s.new_miss.get() + off, s.new_hits.get() + off, n, bt.stream());
+    off += n;
+  }
+  std::vector<std::pair<unsigned, int>> moves;
+  long at = 0;
+  for (long b = 0; b < nb; ++b) {
+    const long k = stale_off[(size_t)b + 1] - stale_off[(size_t)b];
+    if (k <= 0) continue;
+    Batch& bt = *batches_[(size_t)b];
+    const int* slots = lists + stale_off[(size_t)b];
+    for (long j = 0; j < k; ++j) {
+      const unsigned id = bt.slot_id(slots[j]);
+      retired_ids_out[at++] = id;
+      targets_.erase(id);
+    }
+    bt.erase_slots(slots, k, moves);
+    for (auto const& mv : moves) targets_.set(mv.first, Loc{(int)b, mv.second});
+  }
+  if (retired > 0) dev_ids_.dirty = true;
+  if (born > 0) {
+    int cls = 0;
+    const int b = findOrCreateBatch(p.birth_type, p.Q, p.R, birth_layout, cls);
+    std::vector<unsigned> ids((size_t)born);
+    for (long j = 0; j < born; ++j) ids[(size_t)j] = p.first_id + (unsigned)j;
+    const long first = batches_[(size_t)b]->append_gathered(born, ids.data(), p.t_birth, p.P0, cls, det_dev, s.list.get() + rows);
+    targets_.reserve(targets_.size() + (size_t)born);
+    for (long j = 0; j < born; ++j) targets_.set(ids[(size_t)j], Loc{b, (int)(first + j)});
+    dev_ids_.dirty = true;
+  }
+  info[0] = retired; info[1] = born; info[2] = births ? candidates - born : 0; info[3] = births ? nonfinite : 0;
+  info[4] = (long)p.first_id; info[5] = (long)p.first_id + born;
 }
 
 void Shard::launchRows(double* pose_out) {

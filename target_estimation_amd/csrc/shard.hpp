@@ -115,6 +115,7 @@ class Shard {
   int state(unsigned id, double* x, double* P);
   long long numberMeasurements(unsigned id);
   int rejectionRun(unsigned id);   // the target's run of consecutive gate rejections (Batch::rejection_run), -1: unknown id
+  bool trackCounts(unsigned id, int& miss, int& hits);   // the target's track counters (Batch::track_count); false: unknown id
   double intersectTime(unsigned id, double t1, const double* origin, double radius);
   bool intersectPose(unsigned id, double t1, const double* origin, double radius, double* pose7, double* delta);
 
@@ -193,6 +194,17 @@ class Shard {
                     int* slot_of_det_dev, int* batch_of_det_dev, double* d2_of_det_dev, int* info_dev, double grid_cell = 0.0);
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
                  int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell = 0.0);
+  // THE TRACK LIFECYCLE behind a tick that consumed an association (lifecycle.hpp lists the launches; lifecycle_plan.hpp is the rule):
+  // has_dev [n_masks] the batches' masks in batch order, det_dev [M][7] / slot_of_det_dev [M] the frame and what the association
+  // wrote, all device memory and only read.  The plan -- every slot's new counters, the stale slots of every batch ascending, the
+  // born detections ascending -- is formed in the shard's scratch and read back (counts and stale slots only); every refusal that
+  // depends on it (retired_cap, the id range) is made before anything but scratch is written.  Then the counters are committed,
+  // the stale slots erased (Batch::erase_slots, the id table as eraseBatch keeps it) and the born rows appended
+  // (Batch::append_gathered) to the batch initBatch(p.birth_type, ...) would use.  p.Q / R / P0 are resolved by the manager (never
+  // null with births on).  retired_ids_out [retired_cap]: per batch in batch order, ascending former slot.  info [6]: see the C header.
+  // Waits on the host; changes sizes: what erase and append do to recordings, tiles, storage forms and sessions, it does.
+  void lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
+                 const LifecyclePolicy& p, unsigned* retired_ids_out, long retired_cap, long* info);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -253,6 +265,7 @@ class Shard {
   // released through device_free
   SoonestScratch soonest_;
   AssocScratch assoc_;   // ... and of its associations (Batch::set_assoc_scratch): grow-only
+  LifecycleScratch life_;   // ... and of its lifecycle calls: grow-only
   int soonestParts(const SoonestSpec* specs, long n_specs, int first_batch, SoonestPart* parts) const;
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call

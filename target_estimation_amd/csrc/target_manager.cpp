@@ -824,6 +824,27 @@ long TargetManager::associate(double dt, const double* det, long M, double gate,
   return shards_[0]->associate(dt, det, M, gate, rounds, out, n_out, ids_of_det, batch_of_det, slot_of_det, d2_of_det, unmatched, n_unmatched, info, grid_cell);
 }
 
+void TargetManager::lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
+                              const LifecyclePolicy& policy, unsigned* retired_ids_out, long retired_cap, long* info) {
+  lock_guard<mutex> lg(target_lock_);
+  requireOneShard("target_manager_lifecycle");
+  LifecyclePolicy p = policy;
+  if (p.births() && p.defaults()) {
+    if (!default_values_loaded_ || (int)default_type_ != p.birth_type)
+      throw std::invalid_argument("target_estimation_amd: lifecycle: Q, R and P0 may be left out only when birth_type is the manager's default model");
+    p.Q = default_Q_.data(); p.R = default_R_.data(); p.P0 = default_P_.data();
+  }
+  DeviceGuard g(guardDev(0));
+  shards_[0]->lifecycle(det_dev, slot_of_det_dev, M, has_dev, n_masks, p, retired_ids_out, retired_cap, info);
+  if (info[0] > 0 || info[1] > 0) ranks_dirty_ = true;
+  if (!log_files_.empty())
+    for (long j = 0; j < info[0]; ++j) closeLogFilesOf(retired_ids_out[j]);   // logged targets that went away close their files
+}
+
+bool TargetManager::getTrackCounts(unsigned id, int& miss, int& hits) {
+  return routeId(id, [&](Shard& s) { return s.trackCounts(id, miss, hits); });
+}
+
 void TargetManager::synchronize() {
   lock_guard<mutex> lg(target_lock_);
   for (size_t k = 0; k < shards_.size(); ++k) { DeviceGuard g(guardDev(k)); shards_[k]->synchronize(); }

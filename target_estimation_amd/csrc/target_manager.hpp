@@ -221,6 +221,15 @@ class TargetManager {
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut* out, long n_out, unsigned* ids_of_det,
                  int* batch_of_det, int* slot_of_det, double* d2_of_det, long* unmatched, long* n_unmatched, int* info, double grid_cell = 0.0);
 
+  // THE TRACK LIFECYCLE (lifecycle.hpp; target_manager_lifecycle), run after the tick that consumed an association:
+  // retires the targets that went max_misses frames without a match and creates one from every unmatched finite detection, on the
+  // device (Shard::lifecycle says how).  has_dev [n_masks] in target_manager_get_batch order; a manager on one device only.  A policy
+  // without Q, R, P0 means the manager's own model parameters and is refused unless birth_type is the manager's default model.
+  // Every refusal leaves counters, records, ids and sizes as they were.
+  void lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
+                 const LifecyclePolicy& policy, unsigned* retired_ids_out, long retired_cap, long* info);
+  bool getTrackCounts(unsigned id, int& miss, int& hits);   // false: unknown id
+
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own
   // stream so that they are resident together): BASELINE configs[3] / configs[4] put two motion models on every GPU, and
   // their per-GPU share (62 500 + 62 500 targets) is launch-bound.  specs as for stepSequenceAll (ring_ticks > 0 required).

@@ -900,6 +900,38 @@ int target_manager_get_rejection_run(target_manager_c* m, unsigned int id) {
   return rc < 0 ? rc : run;
 }
 
+// ---- track lifecycle (lifecycle.hpp).  What does not depend on the handle is refused before the handle is looked at.
+int target_manager_lifecycle(target_manager_c* m, const double* det_dev, const int* slot_of_det_dev, long M,
+                             const unsigned char* const* has_meas_dev, long n_batches, const target_lifecycle_c* policy,
+                             unsigned int* retired_ids_out, long retired_cap, long* info) {
+  return guarded("target_manager_lifecycle", [&] {
+    te::LifecyclePolicy p;
+    if (policy) {
+      p.max_misses = policy->max_misses; p.birth_type = policy->birth_type; p.first_id = policy->first_id; p.max_births = policy->max_births;
+      p.dt0 = policy->dt0; p.t_birth = policy->t_birth; p.Q = policy->Q; p.R = policy->R; p.P0 = policy->P0;
+    }
+    te::check_lifecycle_args(policy ? &p : nullptr, info != nullptr, M, det_dev != nullptr, slot_of_det_dev != nullptr, n_batches,
+                             has_meas_dev != nullptr, retired_cap, retired_ids_out != nullptr);
+    assoc_manager(m)->lifecycle(det_dev, slot_of_det_dev, M, has_meas_dev, n_batches, p, retired_ids_out, retired_cap, info);
+  });
+}
+
+int target_batch_track_counts(target_batch_c* b, unsigned char* miss_host, unsigned char* hits_host) {
+  return guarded("target_batch_track_counts", [&] {
+    BatchLock lk(B(b));
+    B(b)->track_counts(miss_host, hits_host);
+  });
+}
+
+int target_manager_get_track_counts(target_manager_c* m, unsigned int id, int* miss, int* hits) {
+  bool found = false;
+  const int rc = guarded("target_manager_get_track_counts", [&] {
+    if (!miss || !hits) throw std::invalid_argument("miss and hits must not be NULL");
+    found = M(m)->getTrackCounts(id, *miss, *hits);
+  });
+  return rc < 0 ? rc : (found ? 0 : 1);
+}
+
 // ---- the update policy of the by-id paths
 int target_manager_set_update_gate(target_manager_c* m, int type, double nis_max, int max_rejects) {
   return guarded("target_manager_set_update_gate", [&] {

@@ -190,6 +190,15 @@ class Batch:
         _check(self._lib.target_batch_rejection_runs(self._h, out.ctypes.data), "target_batch_rejection_runs")
         return out[:self.size]
 
+    def track_counts(self):
+        """(miss, hits) of every slot (uint8, slot order): the run of consecutive lifecycle calls without a match and the calls with
+        one since creation, as TargetManager.lifecycle keeps them (target_batch_track_counts); synchronises."""
+        n = self.size
+        miss, hits = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+        _check(self._lib.target_batch_track_counts(self._h, miss.ctypes.data_as(capi.c_ubyte_p), hits.ctypes.data_as(capi.c_ubyte_p)),
+               "target_batch_track_counts")
+        return miss[:n], hits[:n]
+
     def step_sequence(self, dt, meas, has_meas=None, use_graph=False, n_ticks=None, poses=None, innov=None, gate=None, reacquire=None):
         """meas: CUDA tensor [ticks, 7, ld]: one launch per tick, all enqueued by one C call.  n_ticks > ticks
         treats meas (and has_meas) as a ring: tick s reads entry s % ticks.  poses: float64 CUDA tensor
@@ -1230,6 +1239,58 @@ class TargetManager:
             ip(out.info)), name)
         out.unmatched = unmatched[:nu.value].copy()
         return out
+
+    def lifecycle(self, det, assoc_result, *, max_misses, birth_type=None, first_id, max_births=None, t_birth, dt0, Q=None, R=None, P0=None):
+        """Start and retire tracks from an association's results on the device (target_manager_lifecycle), AFTER the tick that
+        consumed the association: associate -> step_sequence_all(n_ticks=1) -> lifecycle.  det: the CUDA double tensor [M, 7] that
+        was associated (None or M = 0: the retirement half alone); assoc_result: the namespace TargetManager.associate returned for
+        it (its has_meas masks and slot_of_det are read; its meas / has_meas columns are stale afterwards: slots move).
+        max_misses = K >= 1 retires a target on its K-th consecutive frame without a match (0: nobody).  birth_type: the motion
+        model (0..3 or its name) of the targets created from the unmatched finite detections, None: no births; they get the ids
+        first_id, first_id + 1, ... in ascending detection index, at most max_births of them (None: no cap), and are initialised as
+        init_batch(ids, dt0, t_birth, det[j], type=birth_type, Q=Q, R=R, P0=P0) would; Q = R = P0 = None: the manager's own model
+        file (birth_type must be its model).  Waits on the host.  Returns a SimpleNamespace: retired_ids (uint32 array, per batch in
+        batch order, ascending former slot), born_ids (a range), retired, born, capped, non_finite."""
+        from types import SimpleNamespace
+        pol = capi.Lifecycle()
+        pol.max_misses = int(max_misses)
+        pol.birth_type = -1 if birth_type is None else _model_type(birth_type)
+        pol.first_id = int(first_id)
+        M = 0 if det is None else int(det.shape[0])
+        pol.max_births = M if max_births is None else int(max_births)
+        pol.dt0, pol.t_birth = float(dt0), float(t_birth)
+        keep = []
+        if birth_type is not None and not (Q is None and R is None and P0 is None):
+            ns, m = MODEL_DIMS[pol.birth_type]
+            for name, a, shape in (("Q", Q, (ns, ns)), ("R", R, (m, m)), ("P0", P0, (ns, ns))):
+                if a is not None:
+                    a = _d(a, shape)
+                    keep.append(a)
+                    setattr(pol, name, _dp(a))
+        if det is not None:
+            assert det.is_cuda and det.dim() == 2 and det.shape[1] == 7 and det.is_contiguous() and det.element_size() == 8
+        masks = list(assoc_result.has_meas)
+        nb = len(masks)
+        mp = (C.c_void_p * max(nb, 1))()
+        for i, h in enumerate(masks):
+            assert h.is_cuda and h.element_size() == 1
+            mp[i] = h.data_ptr()
+        sod = getattr(assoc_result, "slot_of_det", None) if M > 0 else None
+        if sod is not None:
+            assert sod.is_cuda and sod.numel() >= M and sod.element_size() == 4, "lifecycle: slot_of_det of the device form of associate"
+        cap = max(self.size(), 1)
+        retired = np.empty(cap, dtype=np.uint32)
+        info = (C.c_long * 6)()
+        _check(self._lib.target_manager_lifecycle(self._h, None if M == 0 else det.data_ptr(), None if sod is None else sod.data_ptr(), M, mp, nb,
+                                                  C.byref(pol), retired.ctypes.data_as(capi.c_uint_p), cap, info), "target_manager_lifecycle")
+        return SimpleNamespace(retired_ids=retired[:info[0]].copy(), born_ids=range(info[4], info[5]), retired=info[0], born=info[1],
+                               capped=info[2], non_finite=info[3])
+
+    def get_track_counts(self, id):
+        """(miss, hits) of one target as lifecycle keeps them (target_manager_get_track_counts), or None for an unknown id."""
+        miss, hits = C.c_int(0), C.c_int(0)
+        rc = _check(self._lib.target_manager_get_track_counts(self._h, int(id), C.byref(miss), C.byref(hits)), "target_manager_get_track_counts")
+        return (miss.value, hits.value) if rc == 0 else None
 
     def population_tick(self):
         """True if step_sequence_all steps every batch with ONE launch per tick (target_manager_population_tick)."""
