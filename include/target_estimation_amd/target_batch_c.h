@@ -995,7 +995,8 @@ long target_manager_associate_grid(target_manager_c* m, double dt, const double*
  * and read back before anything is committed, so the refusals that depend on it change nothing either.
  * The call WAITS ON THE HOST and changes sizes: it is NOT CAPTURABLE in a hipGraph, and it does what erase and init already do to
  * recorded sequences, uniform tiles, shared-axes batches and live sessions.  Queued one-target steps and inits run first.
- * Not built: merging several unmatched detections of one new object; a time-based (seconds) expiry; a confirmed-only mask for the
+ * Not built: merging several unmatched detections of one new object AT BIRTH (the duplicate tracks that follow are found and retired
+ * by target_manager_retire_duplicates below); a time-based (seconds) expiry; a confirmed-only mask for the
  * getters; several shards; the Eigen facade. */
 typedef struct target_lifecycle_c {
   int max_misses;          /* K >= 1: retire on the K-th consecutive frame without a match; 0: retire nobody */
@@ -1013,6 +1014,63 @@ int target_manager_lifecycle(target_manager_c* m, const double* det_dev, const i
                              unsigned int* retired_ids_out, long retired_cap, long* info);
 int target_batch_track_counts(target_batch_c* b, unsigned char* miss_host, unsigned char* hits_host);
 int target_manager_get_track_counts(target_manager_c* m, unsigned int id, int* miss, int* hits);
+/* ---- DUPLICATE TRACKS: find, and retire, two tracks that follow the same object, on the device.    A detector that
+ * splits one object into two detections, or clutter next to a real target, gives birth to a second track inside the first one's
+ * gate; the greedy one-to-one pairing then lets the two take turns, so neither ever reaches max_misses.  This is the self-join of
+ * the association: row against row instead of row against detection, through the same uniform grid.  A manager on ONE device.
+ * ROW.  Each slot of each batch gets one row, concatenated in target_manager_get_batch order.  zhat is exactly the association's
+ * zhat at the offset dt; Sigma = (A(dt) P A(dt)^T + Q)[0:3, 0:3], the very doubles the association forms BEFORE it adds R (the same
+ * accessors, uniform-tile words and exact zeros between separable axes).  A row is VALID iff the association's row is valid
+ * (S = Sigma + R inverts) and Sigma's six words are finite: one validity rule.
+ * ELIGIBLE.  A valid row is eligible iff its hits counter (TRACK LIFECYCLE above) is >= min_hits (0 .. 255) -- so that newborn
+ * tracks, whose P0 covers everything nearby, are not called duplicates -- and it is NARROW: reach2_a = (gate * 2 Sigma_aa) *
+ * (1 + 2^-10) <= (cell (1 - 2^-20))^2 on all three axes.  A valid row with enough hits that is not narrow is WIDE: it is EXCLUDED, not
+ * brute-forced -- a track whose box exceeds a cell is not known well enough to be merged -- and counted in info[3]; a large info[3]
+ * means that cell is too small.
+ * PAIR.  For eligible rows lo < hi (row index): C = Sigma_lo + Sigma_hi word by word in double; V = C^-1 by the association's
+ * cofactor inverse, an invalid C rejects the pair; d2 = nu^T V nu, nu = zhat_hi - zhat_lo.  The pair is a candidate iff d2 <= gate
+ * AND nu_a * nu_a <= (gate * C_aa) * (1 + 2^-10) on every axis; plain multiplies, no contraction, no square root.  The pair's box
+ * never exceeds the larger of the two rows' boxes, so a partner lies within +-1 cell and 27 cells suffice.  Both partners form the
+ * same bits because both order the pair as (lo, hi).
+ * MATCHING, in rounds of mutual best as the association's: every unmatched eligible row picks its best unmatched candidate partner
+ * by (d2, partner row), never itself; two rows that picked each other are a pair.  rounds: 1 .. TARGET_ASSOC_MAX_ROUNDS; a round is
+ * settled if every row that had a candidate at its start was matched in it; the launches of later rounds return at once.  The
+ * fixed point is sorted greedy matching by (d2, lo, hi).
+ * SURVIVOR.  Of a matched pair the WEAKER row is the duplicate: fewer hits; at equal hits, more miss; at equal both, the higher row.
+ * A chain A-B-C therefore loses one track per call; the next frame's call sees the rest.
+ * The result is a function of the inputs alone: two calls on the same inputs give byte-identical outputs.
+ *   ..._find_duplicates_dev   on the manager's stream; reads the records and counters as stored and writes only its outputs.  After
+ *                             the first call of at least that size it allocates nothing, never waits on the host and may be
+ *                             captured in the caller's hipGraph.  dup_out_dev [size] per batch is required (1 = this slot is the
+ *                             weaker of a matched pair); partner (batch, slot) and d2 (-1: none) are optional.  info int[4] =
+ *                             {pairs, rounds_run, settled, wide rows}; an empty manager gives {0, 0, 1, 0}.
+ *   ..._retire_duplicates     queued one-target work runs first; the same search into scratch memory; each batch's mask compacted
+ *                             in ascending slot order; the counts, then the lists with their partners read back; both sides
+ *                             translated to ids BEFORE anything moves; cap checked; only then are the duplicates erased as
+ *                             target_manager_erase_batch erases them.  retired_ids_out [cap] / kept_ids_out [cap]: the duplicate
+ *                             and the track that stays, per batch in batch order, ascending former slot.  info long[4] =
+ *                             {retired, rounds_run, settled, wide}.  It WAITS ON THE HOST and is NOT CAPTURABLE, and it does to
+ *                             recorded sequences, uniform tiles, shared-axes batches and live sessions what erase does.  Every
+ *                             surviving target keeps its counters, its rejection run and its record bit for bit.  Call it when
+ *                             slots are stable, for instance after the lifecycle: an earlier association's columns are STALE afterwards.
+ * REFUSED (-1, target_manager_last_error, nothing enqueued, nothing written; NOTHING CHANGES on a refusal): a NULL handle; a NULL
+ * info; a NULL dup_out_dev for a non-empty batch; n_batches != target_manager_num_batches; dt negative or NaN; gate <= 0, NaN or inf;
+ * cell <= 0, NaN or inf; rounds out of range; min_hits outside 0 .. 255; cap < 0 or smaller than the number to retire; NULL id
+ * arrays with cap > 0; a manager with several shards.  What needs no handle is refused before the handle is looked at.  (A cap
+ * smaller than the number to retire is known only after the search: the queued one-target work has run by then, as it would have
+ * on its own at the next call that reads the records; the population, records, ids and counters are untouched.)
+ * Not built: fusing the two estimates instead of dropping one; brute force for wide rows; several shards; orientation in the cost;
+ * the Eigen facade. */
+typedef struct target_dup_out_c {       /* one per batch, target_manager_get_batch order */
+  unsigned char* dup_out_dev;           /* [size] required: 1 = this slot is the weaker of a matched pair */
+  int* partner_batch_dev;               /* [size] or NULL, -1: none */
+  int* partner_slot_dev;                /* [size] or NULL, -1: none */
+  double* d2_of_slot_dev;               /* [size] or NULL, -1: none; the same bits for both partners */
+} target_dup_out_c;
+int target_manager_find_duplicates_dev(target_manager_c* m, double dt, double gate, int rounds, double cell, int min_hits,
+                                       const target_dup_out_c* per_batch, long n_batches, int* info_dev);
+int target_manager_retire_duplicates(target_manager_c* m, double dt, double gate, int rounds, double cell, int min_hits,
+                                     unsigned int* retired_ids_out, unsigned int* kept_ids_out, long cap, long* info);
 /* AoS doubles [n][7] (host layout of the reference) -> SoA [7][ld] in the batch precision, on device */
 int target_batch_pack_meas_dev(target_batch_c* b, const double* meas_aos_dev, long n, void* meas_soa_dev, long ld);
 

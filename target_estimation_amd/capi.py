@@ -50,6 +50,11 @@ class AssocOut(C.Structure):
                 ("d2_of_slot_dev", C.c_void_p)]
 
 
+class DupOut(C.Structure):
+    """target_dup_out_c of target_batch_c.h: what one batch's slots get from a duplicate search"""
+    _fields_ = [("dup_out_dev", C.c_void_p), ("partner_batch_dev", C.c_void_p), ("partner_slot_dev", C.c_void_p), ("d2_of_slot_dev", C.c_void_p)]
+
+
 class Lifecycle(C.Structure):
     """target_lifecycle_c of target_batch_c.h: the policy of a track-lifecycle call"""
     _fields_ = [("max_misses", C.c_int), ("birth_type", C.c_int), ("first_id", C.c_uint), ("max_births", C.c_long), ("dt0", C.c_double),
@@ -161,6 +166,11 @@ SIGNATURES = {
     # track lifecycle: device pointers as void* (the masks: an array of them), host arrays typed
     "target_manager_lifecycle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_void_p), C.c_long, C.POINTER(Lifecycle),
                                            c_uint_p, C.c_long, C.POINTER(C.c_long)]),
+    # duplicate tracks: device pointers as void*, host arrays typed
+    "target_manager_find_duplicates_dev": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, C.POINTER(DupOut), C.c_long,
+                                                     C.c_void_p]),
+    "target_manager_retire_duplicates": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, c_uint_p, c_uint_p, C.c_long,
+                                                   C.POINTER(C.c_long)]),
     "target_batch_track_counts": (C.c_int, [C.c_void_p, c_ubyte_p, c_ubyte_p]),
     "target_manager_get_track_counts": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "target_batch_intersect_sphere_dev": (C.c_int, [C.c_void_p, C.c_double, c_double_p, C.c_double, C.c_void_p, C.c_void_p]),

@@ -11,7 +11,8 @@ namespace te {
 // A thread per slot.  zhat = the position derive_outputs gives at the offset dt; Sigma = (A(dt) P A(dt)^T + Q)[0:3, 0:3] exactly as
 // crossing_cov_kernel forms it (crossing_predict_block per stored pair, the layout's accessors, a flagged uniform tile's words from
 // the tile's block, exact zeros between the axes of the separable layouts), in the batch's precision; S = Sigma + R[0:3, 0:3] of the
-// slot's class and W = S^-1 in double (assoc_invert_s).  An invalid S gives a NaN row: never a candidate.
+// slot's class and W = S^-1 in double (assoc_invert_s).  An invalid S gives a NaN row: never a candidate.  With a.sigma_in_w the
+// row's six W words receive Sigma itself, the doubles above before R is added (a MergeRow: track_merge_plan.hpp); validity as before.
 template <class M, typename T, int G, int LAYOUT>
 __global__ __launch_bounds__(64) void assoc_table_kernel(const AssocTableArgs a) {
 #pragma clang fp contract(off)
@@ -30,14 +31,14 @@ __global__ __launch_bounds__(64) void assoc_table_kernel(const AssocTableArgs a)
     }
     return state_get<C, T>(a.rec, slot, r, c);
   };
-  double S[6];
+  double S[6], Sg[6];   // Sg: Sigma before R is added (the track-merge row)
 #pragma unroll
   for (int r = 0, k = 0; r < 3; ++r) {
 #pragma unroll
     for (int c = r; c < 3; ++c, ++k) {
       const int rw = C::RWORD.v[r][c];
       const double Rrc = rw >= 0 ? (double)qr[rw] : 0.0;
-      if (C::SEP && r != c) { S[k] = 0.0 + Rrc; continue; }
+      if (C::SEP && r != c) { Sg[k] = 0.0; S[k] = 0.0 + Rrc; continue; }
       T B[NB][NB], Qb[NB][NB];
 #pragma unroll
       for (int i = 0; i < NB; ++i) {
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(64) void assoc_table_kernel(const AssocTableArgs a)
         }
       }
       crossing_predict_block<NB, T>(B, Qb, tau);
+      Sg[k] = (double)B[0][0];
       S[k] = (double)B[0][0] + Rrc;
     }
   }
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(64) void assoc_table_kernel(const AssocTableArgs a)
 #pragma unroll
   for (int c = 0; c < 3; ++c) row[c] = ok ? (double)pose7[c] : nan;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) row[3 + k] = W[k];
+  for (int k = 0; k < 6; ++k) row[3 + k] = a.sigma_in_w ? Sg[k] : W[k];
   reinterpret_cast<long long*>(row)[9] = ((long long)a.batch_index << 32) | (long long)(unsigned)slot;
   if (a.sdiag) {   // the grid form (associate_grid.hpp): the diagonal of the S that was just inverted
     a.sdiag[slot * 3] = S[0]; a.sdiag[slot * 3 + 1] = S[3]; a.sdiag[slot * 3 + 2] = S[5];

@@ -35,6 +35,7 @@ struct AssocTableArgs {
   AssocRow* rows;            // [size]: the batch's part of the call's table
   int batch_index;           // what the rows' tags carry
   double* sdiag = nullptr;   // [size][3]: the diagonal of the S that was inverted, for the grid form (associate_grid.hpp); null: not written
+  bool sigma_in_w = false;   // the row's six W words receive Sigma (before R is added) instead of W: a MergeRow (track_merge_plan.hpp)
 };
 // the launcher of a (model, precision, lanes per target, layout as LayoutInfo reports it, shared-axes form), or null
 using AssocTableLaunch = void (*)(const AssocTableArgs&, hipStream_t);

@@ -413,6 +413,21 @@ void launch_assoc_grid_match(const AssocScratch& s, long rows, const double* det
   }
 }
 
+long assoc_grid_scan_blocks(long buckets) { return (buckets + kScanPerBlock - 1) / kScanPerBlock; }
+
+void launch_assoc_grid_bin_rows(const int* bucket_of, int* count, int* start, int* cursor, int* sums, int* order, long rows, long buckets,
+                                hipStream_t st) {
+  AssocGridArgs a{};   // (M = 0, hd = 0: the detection part of every array is empty, the kernels are the grid form's as they are)
+  a.bucket_of = const_cast<int*>(bucket_of); a.count = count; a.start = start; a.cursor = cursor; a.sums = sums; a.order = order;
+  a.rows = rows; a.M = 0; a.hd = 0; a.hr = buckets;
+  const dim3 block(kGT);
+  const long n_blocks = assoc_grid_scan_blocks(buckets);
+  hipLaunchKernelGGL(assoc_grid_scan_blocks_kernel, dim3((unsigned)n_blocks), block, 0, st, a);
+  hipLaunchKernelGGL(assoc_grid_scan_sums_kernel, dim3(1), block, 0, st, a, n_blocks);
+  hipLaunchKernelGGL(assoc_grid_scan_add_kernel, blocks_for(buckets), block, 0, st, a);
+  hipLaunchKernelGGL(assoc_grid_place_kernel, blocks_for(rows), block, 0, st, a);
+}
+
 void launch_assoc_grid_info(const AssocScratch& s, int* info, hipStream_t st) {
   if (!info) return;
   hipLaunchKernelGGL(assoc_grid_info_kernel, dim3(1), dim3(64), 0, st, s.grid_counters.get(), info);

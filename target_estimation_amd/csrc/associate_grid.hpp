@@ -46,5 +46,11 @@ void launch_assoc_grid_match(const AssocScratch& s, long rows, const double* det
                              const AssocGridBuckets& buckets, hipStream_t st);
 // after launch_assoc_dets: info[3] = the number of wide slots
 void launch_assoc_grid_info(const AssocScratch& s, int* info, hipStream_t st);
+// The scan and place kernels above with ZERO detections, for a caller that bins rows alone (track_merge.hpp): count [buckets] the
+// entries per bucket, bucket_of [rows] (-1: binned nowhere); start [buckets + 1], cursor [buckets] and order [rows] are written,
+// sums is room for assoc_grid_scan_blocks(buckets) + 1 ints.  buckets a power of two.
+long assoc_grid_scan_blocks(long buckets);
+void launch_assoc_grid_bin_rows(const int* bucket_of, int* count, int* start, int* cursor, int* sums, int* order, long rows, long buckets,
+                                hipStream_t st);
 
 }  // namespace te

@@ -1851,7 +1851,7 @@ void Batch::crossing_cov(const int* slots, long n, double t1, const double* orig
 }
 
 // ---------------------------------------------------------------- association of unlabelled detections (associate.hpp)
-void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag) {
+void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag, bool sigma_in_w) {
   const AssocTableLaunch launch = assoc_table_launcher(type_, dtype_, ops_->L.g, ops_->L.layout, shared_axes());
   if (!launch) throw std::logic_error("target_estimation_amd: associate: no kernel for this (model, precision, layout)");   // (never a fall-back)
   flush();
@@ -1860,7 +1860,7 @@ void Batch::assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* 
   a.rec = records_as_stored(); a.qr = d_qr_.get(); a.cls = n_classes_ > 1 ? d_cls_.get() : nullptr;
   // (the flag array whenever the batch has one, flagged or not: a captured launch reads the flags of the tick it follows)
   a.tile_blk = d_tile_uni_.get() ? d_tile_blk_.get() : nullptr; a.tile_uni = d_tile_uni_.get();
-  a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index; a.sdiag = sdiag;
+  a.size = n_; a.dt = dt; a.rows = rows; a.batch_index = batch_index; a.sdiag = sdiag; a.sigma_in_w = sigma_in_w;
   launch(a, stream_);
   TE_HIP_CHECK(hipGetLastError());
 }

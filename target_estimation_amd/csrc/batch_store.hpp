@@ -383,7 +383,7 @@ class Batch {
   }
   AssocScratch* assoc_scratch() const { return assoc_; }
   int assoc_forced_chunks() const { return assoc_forced_chunks_; }
-  void assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag = nullptr);
+  void assoc_table_dev(double dt, AssocRow* rows, int batch_index, double* sdiag = nullptr, bool sigma_in_w = false);   // sigma_in_w: MergeRows (track_merge_plan.hpp)
   void associate_dev(double dt, const double* det_dev, long M, double gate, long rounds, const AssocSlotOut& out, int* slot_of_det_dev,
                      double* d2_of_det_dev, int* info_dev, double grid_cell = 0.0);
   long associate(double dt, const double* det, long M, double gate, long rounds, const AssocSlotOut& out, unsigned* ids_of_det,

@@ -1321,6 +1321,131 @@ void Shard::lifecycle(const double* det_dev, const int* slot_of_det_dev, long M,
   info[4] = (long)p.first_id; info[5] = (long)p.first_id + born;
 }
 
+// ---------------------------------------------------------------- duplicate tracks (track_merge.hpp lists the launches)
+void Shard::mergeSearch(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, int* info_dev) {
+  const int nb = (int)batches_.size();
+  long rows = 0;
+  for (auto& b : batches_) {
+    const LayoutInfo L = b->layout();
+    if (!assoc_table_launcher(b->type(), b->dtype(), L.g, L.layout, L.shared_axes != 0))
+      throw std::logic_error("target_estimation_amd: find_duplicates: no kernel for this (model, precision, layout)");   // (never a fall-back)
+    rows += b->size();
+  }
+  if (rows > 0x7fffffffL) throw std::invalid_argument("target_estimation_amd: find_duplicates: more than 2^31 - 1 targets on one device");
+  const long buckets = plan_assoc_grid_buckets(rows, set_.assoc_grid_buckets);
+  merge_.ensure(rows, buckets);
+  std::vector<MergeBatchIn> in((size_t)nb);
+  long off = 0;
+  for (int b = 0; b < nb; ++b) {
+    Batch& bt = *batches_[(size_t)b];
+    bt.assoc_table_dev(dt, merge_.table.get() + off, b, nullptr, true);
+    in[(size_t)b].size = bt.size(); in[(size_t)b].hits = bt.track_hits_dev(); in[(size_t)b].miss = bt.track_miss_dev();
+    off += bt.size();
+  }
+  launch_merge_match(merge_, rows, in.data(), nb, gate, cell, (int)rounds, min_hits, buckets, stream_);
+  off = 0;
+  for (int b = 0; b < nb; ++b) {
+    launch_merge_out(merge_, off, batches_[(size_t)b]->size(), out[b], stream_);
+    off += batches_[(size_t)b]->size();
+  }
+  launch_merge_info(merge_, info_dev, stream_);
+  TE_HIP_CHECK(hipGetLastError());
+}
+
+void Shard::findDuplicatesDev(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, long n_out, int* info_dev) {
+  const std::string pre = "target_estimation_amd: find_duplicates: ";
+  check_merge_args("find_duplicates", info_dev != nullptr, dt, gate, rounds, cell, min_hits, n_out, out != nullptr, 0, true);
+  if (n_out != (long)batches_.size())
+    throw std::invalid_argument(pre + "n_batches " + std::to_string(n_out) + " is not the manager's " + std::to_string(batches_.size()));
+  for (size_t b = 0; b < batches_.size(); ++b)
+    if (batches_[b]->size() > 0 && !out[b].dup) throw std::invalid_argument(pre + "dup_out_dev of a non-empty batch is NULL");
+  mergeSearch(dt, gate, rounds, cell, min_hits, out, info_dev);
+}
+
+void Shard::retireDuplicates(double dt, double gate, long rounds, double cell, int min_hits, unsigned* retired_ids_out, unsigned* kept_ids_out,
+                             long cap, long* info) {
+  const std::string pre = "target_estimation_amd: retire_duplicates: ";
+  check_merge_args("retire_duplicates", info != nullptr, dt, gate, rounds, cell, min_hits, 0, true, cap, retired_ids_out && kept_ids_out);
+  const long nb = (long)batches_.size();
+  long rows = 0;
+  for (auto& b : batches_) rows += b->size();
+  for (auto& b : batches_) b->prepare();   // the queued one-target steps and inits run first
+  MergeScratch& s = merge_;
+  s.ensure_retire(rows, nb);
+
+  // THE PLAN, into the scratch alone
+  std::vector<MergeSlotOut> outs((size_t)nb);
+  long off = 0;
+  for (long b = 0; b < nb; ++b) {
+    outs[(size_t)b].dup = s.dup.get() + off; outs[(size_t)b].partner_batch = s.partner_batch.get() + off;
+    outs[(size_t)b].partner_slot = s.partner_slot.get() + off;
+    off += batches_[(size_t)b]->size();
+  }
+  int* info_dev = s.counts.get() + nb;
+  mergeSearch(dt, gate, rounds, cell, min_hits, outs.data(), info_dev);
+  off = 0;
+  for (long b = 0; b < nb; ++b) {
+    const long n = batches_[(size_t)b]->size();
+    launch_lifecycle_compact(s.dup.get() + off, 1, n, s.csums.get(), s.list.get() + off, s.counts.get() + b, stream_);
+    launch_merge_gather(s, off, n, s.counts.get() + b, stream_);
+    off += n;
+  }
+  TE_HIP_CHECK(hipGetLastError());
+  int* h = s.host.host();
+  TE_HIP_CHECK(hipMemcpyAsync(h, s.counts.get(), sizeof(int) * (size_t)(nb + 4), hipMemcpyDeviceToHost, stream_));
+  TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  std::vector<long> dup_off((size_t)nb + 1, 0);   // where batch b's list lies behind the counts in the pinned block
+  for (long b = 0; b < nb; ++b) {
+    if (h[b] < 0 || h[b] > batches_[(size_t)b]->size()) throw std::runtime_error(pre + "a duplicate count out of range");
+    dup_off[(size_t)b + 1] = dup_off[(size_t)b] + h[b];
+  }
+  const long retired = dup_off[(size_t)nb];
+  const long rounds_run = h[nb + 1], settled = h[nb + 2], wide = h[nb + 3];
+  if (retired > cap) throw std::invalid_argument(pre + "cap " + std::to_string(cap) + " < " + std::to_string(retired) + " targets to retire");
+  int* lists = h + nb + 4;   // [retired] slots | [retired] partner batches | [retired] partner slots
+  int* lists_b = lists + retired;
+  int* lists_s = lists_b + retired;
+  if (retired > 0) {
+    off = 0;
+    for (long b = 0; b < nb; ++b) {
+      const long k = dup_off[(size_t)b + 1] - dup_off[(size_t)b];
+      if (k > 0) {
+        const size_t bytes = sizeof(int) * (size_t)k;
+        TE_HIP_CHECK(hipMemcpyAsync(lists + dup_off[(size_t)b], s.list.get() + off, bytes, hipMemcpyDeviceToHost, stream_));
+        TE_HIP_CHECK(hipMemcpyAsync(lists_b + dup_off[(size_t)b], s.list_batch.get() + off, bytes, hipMemcpyDeviceToHost, stream_));
+        TE_HIP_CHECK(hipMemcpyAsync(lists_s + dup_off[(size_t)b], s.list_slot.get() + off, bytes, hipMemcpyDeviceToHost, stream_));
+      }
+      off += batches_[(size_t)b]->size();
+    }
+    TE_HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+  // both sides to ids BEFORE anything moves
+  long at = 0;
+  for (long b = 0; b < nb; ++b) {
+    Batch& bt = *batches_[(size_t)b];
+    for (long k = dup_off[(size_t)b]; k < dup_off[(size_t)b + 1]; ++k, ++at) {
+      const int slot = lists[k], pb = lists_b[k], ps = lists_s[k];
+      if (slot < 0 || slot >= bt.size() || pb < 0 || pb >= nb || ps < 0 || ps >= batches_[(size_t)pb]->size())
+        throw std::runtime_error(pre + "a duplicate or its partner out of range");
+      retired_ids_out[at] = bt.slot_id(slot);
+      kept_ids_out[at] = batches_[(size_t)pb]->slot_id(ps);
+    }
+  }
+  // THE COMMIT
+  std::vector<std::pair<unsigned, int>> moves;
+  at = 0;
+  for (long b = 0; b < nb; ++b) {
+    const long k = dup_off[(size_t)b + 1] - dup_off[(size_t)b];
+    if (k <= 0) continue;
+    Batch& bt = *batches_[(size_t)b];
+    for (long j = 0; j < k; ++j) targets_.erase(retired_ids_out[at++]);
+    bt.erase_slots(lists + dup_off[(size_t)b], k, moves);
+    for (auto const& mv : moves) targets_.set(mv.first, Loc{(int)b, mv.second});
+  }
+  if (retired > 0) dev_ids_.dirty = true;
+  info[0] = retired; info[1] = rounds_run; info[2] = settled; info[3] = wide;
+}
+
 void Shard::launchRows(double* pose_out) {
   for (size_t b = 0; b < batches_.size(); ++b)
     if (batches_[b]->size() > 0) batches_[b]->outputs_rows_dev(pose_out, rank_maps_[b].dev.get());

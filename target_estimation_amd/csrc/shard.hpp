@@ -18,6 +18,7 @@
 #include "id_table.hpp"
 #include "row_split.hpp"
 #include "step_variant.hpp"
+#include "track_merge.hpp"
 
 namespace te {
 
@@ -205,6 +206,15 @@ class Shard {
   // Waits on the host; changes sizes: what erase and append do to recordings, tiles, storage forms and sessions, it does.
   void lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
                  const LifecyclePolicy& p, unsigned* retired_ids_out, long retired_cap, long* info);
+  // DUPLICATE TRACKS (track_merge.hpp lists the launches; track_merge_plan.hpp is the rule): two tracks of this shard that follow the
+  // same object.  findDuplicatesDev: out [n_out] per batch in batch order, everything in device memory, no host wait, no
+  // allocation after the first call of at least that size; reads the records and counters as stored.  retireDuplicates: the same
+  // search into the shard's scratch, each batch's mask compacted ascending (launch_lifecycle_compact), the counts, then the lists
+  // with their partners read back; both sides translated to ids BEFORE anything moves; cap checked; only then Batch::erase_slots
+  // per batch and the id table as eraseBatch keeps it.  info [4] = {retired, rounds_run, settled, wide}.  Waits on the host.
+  void findDuplicatesDev(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, long n_out, int* info_dev);
+  void retireDuplicates(double dt, double gate, long rounds, double cell, int min_hits, unsigned* retired_ids_out, unsigned* kept_ids_out,
+                        long cap, long* info);
   void liveStartAll(double dt, const Batch::SeqSpec* specs, long n_specs, long first_entry, long max_ticks, double idle_limit_s, bool query,
                     const double* origin, double radius);
   void livePostAll(long n_ticks, bool one_doorbell_per_tick);
@@ -266,6 +276,8 @@ class Shard {
   SoonestScratch soonest_;
   AssocScratch assoc_;   // ... and of its associations (Batch::set_assoc_scratch): grow-only
   LifecycleScratch life_;   // ... and of its lifecycle calls: grow-only
+  MergeScratch merge_;      // ... and of its duplicate searches: grow-only
+  void mergeSearch(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, int* info_dev);
   int soonestParts(const SoonestSpec* specs, long n_specs, int first_batch, SoonestPart* parts) const;
 
   // device-side id resolution for the array-of-ids calls (id_resolve.hpp): the table and the staging of one call

@@ -841,6 +841,25 @@ void TargetManager::lifecycle(const double* det_dev, const int* slot_of_det_dev,
     for (long j = 0; j < info[0]; ++j) closeLogFilesOf(retired_ids_out[j]);   // logged targets that went away close their files
 }
 
+void TargetManager::findDuplicatesDev(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, long n_out,
+                                      int* info_dev) {
+  lock_guard<mutex> lg(target_lock_);
+  check_merge_one_shard("find_duplicates", (long)shards_.size());
+  DeviceGuard g(guardDev(0));
+  shards_[0]->findDuplicatesDev(dt, gate, rounds, cell, min_hits, out, n_out, info_dev);
+}
+
+void TargetManager::retireDuplicates(double dt, double gate, long rounds, double cell, int min_hits, unsigned* retired_ids_out,
+                                     unsigned* kept_ids_out, long cap, long* info) {
+  lock_guard<mutex> lg(target_lock_);
+  check_merge_one_shard("retire_duplicates", (long)shards_.size());
+  DeviceGuard g(guardDev(0));
+  shards_[0]->retireDuplicates(dt, gate, rounds, cell, min_hits, retired_ids_out, kept_ids_out, cap, info);
+  if (info[0] > 0) ranks_dirty_ = true;
+  if (!log_files_.empty())
+    for (long j = 0; j < info[0]; ++j) closeLogFilesOf(retired_ids_out[j]);   // logged targets that went away close their files
+}
+
 bool TargetManager::getTrackCounts(unsigned id, int& miss, int& hits) {
   return routeId(id, [&](Shard& s) { return s.trackCounts(id, miss, hits); });
 }

@@ -228,6 +228,12 @@ class TargetManager {
   // Every refusal leaves counters, records, ids and sizes as they were.
   void lifecycle(const double* det_dev, const int* slot_of_det_dev, long M, const unsigned char* const* has_dev, long n_masks,
                  const LifecyclePolicy& policy, unsigned* retired_ids_out, long retired_cap, long* info);
+  // DUPLICATE TRACKS (track_merge.hpp; target_manager_find_duplicates_dev / target_manager_retire_duplicates): two
+  // tracks that follow the same object, found by a self-join through the association's grid (Shard::findDuplicatesDev /
+  // retireDuplicates say how); a manager on one device only.  retireDuplicates closes the log files of the targets that went away.
+  void findDuplicatesDev(double dt, double gate, long rounds, double cell, int min_hits, const MergeSlotOut* out, long n_out, int* info_dev);
+  void retireDuplicates(double dt, double gate, long rounds, double cell, int min_hits, unsigned* retired_ids_out, unsigned* kept_ids_out,
+                        long cap, long* info);
   bool getTrackCounts(unsigned id, int& miss, int& hits);   // false: unknown id
 
   // Resident ("live") mode for EVERY batch of the manager at once (Batch::live_start per batch, each kernel on its own

@@ -916,6 +916,30 @@ int target_manager_lifecycle(target_manager_c* m, const double* det_dev, const i
   });
 }
 
+// ---- duplicate tracks (track_merge.hpp).  What does not depend on the handle is refused before the handle is looked at.
+int target_manager_find_duplicates_dev(target_manager_c* m, double dt, double gate, int rounds, double cell, int min_hits,
+                                       const target_dup_out_c* per_batch, long n_batches, int* info_dev) {
+  return guarded("target_manager_find_duplicates_dev", [&] {
+    te::check_merge_args("find_duplicates", info_dev != nullptr, dt, gate, rounds, cell, min_hits, n_batches, per_batch != nullptr, 0, true);
+    TargetManager* mgr = assoc_manager(m);
+    std::vector<te::MergeSlotOut> outs((size_t)n_batches);
+    for (long i = 0; i < n_batches; ++i) {
+      outs[(size_t)i].dup = per_batch[i].dup_out_dev; outs[(size_t)i].partner_batch = per_batch[i].partner_batch_dev;
+      outs[(size_t)i].partner_slot = per_batch[i].partner_slot_dev; outs[(size_t)i].d2 = per_batch[i].d2_of_slot_dev;
+    }
+    mgr->findDuplicatesDev(dt, gate, rounds, cell, min_hits, outs.data(), n_batches, info_dev);
+  });
+}
+
+int target_manager_retire_duplicates(target_manager_c* m, double dt, double gate, int rounds, double cell, int min_hits,
+                                     unsigned int* retired_ids_out, unsigned int* kept_ids_out, long cap, long* info) {
+  return guarded("target_manager_retire_duplicates", [&] {
+    te::check_merge_args("retire_duplicates", info != nullptr, dt, gate, rounds, cell, min_hits, 0, true, cap,
+                         retired_ids_out != nullptr && kept_ids_out != nullptr);
+    assoc_manager(m)->retireDuplicates(dt, gate, rounds, cell, min_hits, retired_ids_out, kept_ids_out, cap, info);
+  });
+}
+
 int target_batch_track_counts(target_batch_c* b, unsigned char* miss_host, unsigned char* hits_host) {
   return guarded("target_batch_track_counts", [&] {
     BatchLock lk(B(b));

@@ -1286,6 +1286,47 @@ class TargetManager:
         return SimpleNamespace(retired_ids=retired[:info[0]].copy(), born_ids=range(info[4], info[5]), retired=info[0], born=info[1],
                                capped=info[2], non_finite=info[3])
 
+    def find_duplicates(self, dt, gate, cell, rounds=8, min_hits=1, out=None):
+        """Find pairs of tracks that follow the same object, on the device (target_manager_find_duplicates_dev; a manager on one
+        device only; no host wait): the association's self-join through its grid of edge `cell`, rows with fewer than min_hits
+        hits and rows whose box exceeds a cell left out.  Returns a SimpleNamespace of LISTS with one CUDA tensor per batch
+        (batches() order): dup (uint8, 1 = this slot is the weaker of a matched pair), partner_batch / partner_slot (int32, -1:
+        none), d2 (float64, -1: none), and info [4] = {pairs, rounds_run, settled, wide rows}.  out: such a namespace to write into."""
+        import torch
+        from types import SimpleNamespace
+        bs = self.batches()
+        nb = len(bs)
+        if out is None:
+            out = SimpleNamespace(dup=[torch.empty(max(b.size, 1), dtype=torch.uint8, device="cuda") for b in bs],
+                                  partner_batch=[torch.empty(max(b.size, 1), dtype=torch.int32, device="cuda") for b in bs],
+                                  partner_slot=[torch.empty(max(b.size, 1), dtype=torch.int32, device="cuda") for b in bs],
+                                  d2=[torch.empty(max(b.size, 1), dtype=torch.float64, device="cuda") for b in bs],
+                                  info=torch.empty(4, dtype=torch.int32, device="cuda"))
+        per = (capi.DupOut * max(nb, 1))()
+        for i in range(nb):
+            per[i].dup_out_dev = out.dup[i].data_ptr()
+            per[i].partner_batch_dev, per[i].partner_slot_dev = out.partner_batch[i].data_ptr(), out.partner_slot[i].data_ptr()
+            per[i].d2_of_slot_dev = out.d2[i].data_ptr()
+        _check(self._lib.target_manager_find_duplicates_dev(self._h, float(dt), float(gate), int(rounds), float(cell), int(min_hits), per, nb,
+                                                            out.info.data_ptr()), "target_manager_find_duplicates_dev")
+        return out
+
+    def retire_duplicates(self, dt, gate, cell, rounds=8, min_hits=1):
+        """Find duplicate tracks as find_duplicates does and erase the weaker track of every pair (target_manager_retire_duplicates).
+        Waits on the host; slots move, so an earlier association's columns are stale afterwards.  Returns a SimpleNamespace:
+        retired_ids / kept_ids (uint32 arrays, per batch in batch order, ascending former slot of the retired track), retired,
+        rounds_run, settled, wide."""
+        from types import SimpleNamespace
+        cap = max(self.size(), 1)
+        retired = np.empty(cap, dtype=np.uint32)
+        kept = np.empty(cap, dtype=np.uint32)
+        info = (C.c_long * 4)()
+        _check(self._lib.target_manager_retire_duplicates(self._h, float(dt), float(gate), int(rounds), float(cell), int(min_hits),
+                                                          retired.ctypes.data_as(capi.c_uint_p), kept.ctypes.data_as(capi.c_uint_p), cap, info),
+               "target_manager_retire_duplicates")
+        return SimpleNamespace(retired_ids=retired[:info[0]].copy(), kept_ids=kept[:info[0]].copy(), retired=info[0], rounds_run=info[1],
+                               settled=info[2], wide=info[3])
+
     def get_track_counts(self, id):
         """(miss, hits) of one target as lifecycle keeps them (target_manager_get_track_counts), or None for an unknown id."""
         miss, hits = C.c_int(0), C.c_int(0)
